@@ -313,37 +313,59 @@ def stream_bench(args):
     def run(i):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        first, samples, pieces = None, 0, 0
+        first, samples, pieces = None, 0, []
         for chunk in tts.tts_stream(text, conditioning_latents=(auto,), max_mel_tokens=M, use_deterministic_seed=1000 + i,
                                     stream_chunk_size=40, overlap_wav_len=1024, verbose=False):
             chunk = chunk.cpu()  # the caller plays the piece: it has to be on the host
             if first is None:
                 first = time.perf_counter() - t0
             samples += int(chunk.shape[0])
-            pieces += 1
+            pieces.append(chunk)
         return first, samples, pieces, time.perf_counter() - t0
 
     for i in range(args.warmup):
         run(i)
-    firsts, walls, samples, pieces = [], [], 0, 0
+    firsts, walls, samples, pieces = [], [], 0, []
     t0 = time.perf_counter()
     for i in range(args.steps):
         f, samples, pieces, w = run(100 + i)
         firsts.append(f)
         walls.append(w)
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # the pieces of the last timed step, end to end, and how long each one is
+        dump_outputs(args.dump_outputs, {"wav": torch.cat([p.reshape(-1) for p in pieces]),
+                                        "piece_lengths": torch.tensor([p.numel() for p in pieces], dtype=torch.float64)})
     audio_s = samples / 24000.0
     print(json.dumps({
         "metric": "rtf_stream_api_fast", "value": audio_s * args.steps / dt, "unit": "audio-s/wall-s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": args.dtype or "bf16", "data": "synthetic",
         "first_chunk_latency_s": sum(firsts) / len(firsts), "first_chunk_latency_s_max": max(firsts),
-        "wall_per_audio": dt / (audio_s * args.steps), "pieces_per_step": pieces, "audio_seconds_per_step": audio_s,
+        "wall_per_audio": dt / (audio_s * args.steps), "pieces_per_step": len(pieces), "audio_seconds_per_step": audio_s,
         "reference_claim": "README.md:34: 0.25-0.3 wall/audio on a 4 GB GPU, < 500 ms to the first chunk with streaming (other hardware; not a BASELINE number)",
         "config": {"workload": f"api_fast.tts_stream: 1 sequence x {M} mel tokens (EOS suppressed), first buffer 60 tokens then every 40, "
-                               f"HiFi-GAN re-decode of the prefix per piece, overlap 1024 samples; {pieces} pieces, {audio_s:.2f} s of 24 kHz audio",
+                               f"HiFi-GAN re-decode of the prefix per piece, overlap 1024 samples; {len(pieces)} pieces, {audio_s:.2f} s of 24 kHz audio",
                    "weights": "seeded synthetic at the reference hyper-parameters", "parallelism": "1 GPU"},
         "engine_build_s": t_build}))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last timed step, as out_dir/<name>.npy (float32, float64 kept).
+    An array over its share of the 64 MB budget is replaced by a fixed, seeded sample of its flattened elements (same indices on every
+    run with the same arguments), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def free_port():
@@ -420,7 +442,13 @@ def main():
                          "8-GPU share of 'standard'), then the full tail; the line is labelled as such (metric suffix, config.projection)")
     ap.add_argument("--no-replica", action="store_true", help="N > 1: skip the replica-throughput leg (replica_rtf)")
     ap.add_argument("--rank-check", action="store_true", help="rendezvous + the path's one all_gather on stand-in data, no engines (launcher test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (rank 0): "
+                         "wav = the utterance (utterance), the concatenated chunks (read) or the concatenated pieces (stream, plus "
+                         "piece_lengths); the inputs are seeded, so the same arguments give the same inputs on every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # nobody launched the ranks: do it here
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -503,6 +531,8 @@ def main():
     if rank == 0:  # rendered audio lives on rank 0 only
         assert abs(float(wav.shape[-1]) / 24000.0 - audio_s) < 1e-6, (wav.shape, audio_s)
         assert torch.isfinite(wav).all() and wav.abs().max() <= 1.0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"wav": wav})
 
     # N > 1: the same engines as REPLICAS - every rank renders its own complete utterance (all N candidates on its GPU, its own seed), no
     # data-path collective; N utterances per step.  This is where N GPUs pay for this pipeline (one utterance does not hold N GPUs' worth

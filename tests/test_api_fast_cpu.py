@@ -1,25 +1,16 @@
 """CPU checks of the streaming surface (tortoise_tts_amd/api_fast.py): handle_chunks against the reference's own method
-(tortoise/api_fast.py:275-309, extracted from the source file because the module itself does not import offline), and the
-class keeps the reference's signatures."""
-import ast
+(tortoise/api_fast.py:275-309, extracted from the source file because the module itself does not import offline), the pieces
+of the streaming loop against what that method makes of its decodes (tests/golden/stream_pieces.npz), and the class keeps the
+reference's signatures."""
 import inspect
 import os
 
+import numpy as np
 import pytest
 import torch
 
-from oracle import ref_shims
-
-REF = os.path.join(ref_shims.REFERENCE_ROOT, "tortoise", "api_fast.py")
-
-
-def reference_method(name):
-    tree = ast.parse(open(REF).read())
-    cls = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "TextToSpeech"][0]
-    fn = [n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == name][0]
-    ns = {"torch": torch, "MODELS_DIR": None}  # (a default-argument name of __init__)
-    exec(compile(ast.Module(body=[fn], type_ignores=[]), "api_fast_excerpt", "exec"), ns)
-    return fn, ns[name]
+from oracle import make_golden_stream as GS
+from oracle.make_golden_stream import REF, reference_decode_points, reference_method
 
 
 @pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
@@ -116,24 +107,6 @@ def test_tts_and_stream_flow_on_oracle_backed_stages(monkeypatch):
         tts.tts(text, typical_sampling=True, typical_mass=1.0)
 
 
-def reference_decode_points(n_pairs, stream_chunk_size):
-    """The reference's streaming loop (api_fast.py:399-420) restated over a generator that yields n_pairs (token, latent) pairs:
-    the number of latents handed to hifi_decoder.inference at every decode, in order."""
-    gen = iter(range(n_pairs))
-    points, all_latents, codes_, is_end, first_buffer = [], [], [], False, 60
-    while not is_end:
-        try:
-            all_latents.append(next(gen))
-            codes_.append(0)
-        except StopIteration:
-            is_end = True
-        if is_end or (stream_chunk_size > 0 and len(codes_) >= max(stream_chunk_size, first_buffer)):
-            first_buffer = 0
-            points.append(len(all_latents))
-            codes_ = []
-    return points
-
-
 @pytest.mark.parametrize("n_tokens,eos,chunk", [(70, False, 5), (64, False, 5), (61, True, 40), (60, True, 40), (100, True, 40), (99, False, 40),
                                                 (140, False, 40), (30, True, 40), (59, False, 20), (120, False, 20)])
 @torch.no_grad()
@@ -179,13 +152,22 @@ def test_stream_decode_points_follow_the_reference_loop(monkeypatch, n_tokens, e
     # the engine decodes an unchanged prefix only once and re-runs handle_chunks on it: compare piece count and decoded prefixes
     assert len(pieces) == len(want)
     assert sorted(set(want)) == sorted(set(seen))
-    # and the pieces are what the reference's handle_chunks makes of those decodes
+    # and the pieces are what the reference's handle_chunks makes of those decodes (tests/golden/stream_pieces.npz)
+    gold = np.load(GS.OUT)
+    assert sum(k.startswith(GS.key(n_tokens, chunk, "")) for k in gold.files) == len(want)
+    for i, got in enumerate(pieces):
+        assert torch.equal(torch.from_numpy(gold[GS.key(n_tokens, chunk, i)]), got)
+
+
+@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present")
+def test_stream_pieces_golden_follows_the_reference_method():
+    """tests/golden/stream_pieces.npz (oracle/make_golden_stream.py) is what the reference's own handle_chunks makes of the decodes."""
     _, ref_fn = reference_method("handle_chunks")
-    prev = over = None
-    for n, got in zip(want, pieces):
-        wav = torch.arange(n * 256, dtype=torch.float32)
-        ch, prev, over = ref_fn(None, wav, prev, over, 64)
-        assert torch.equal(ch, got)
+    want = GS.all_pieces(lambda *a: ref_fn(None, *a))
+    gold = np.load(GS.OUT)
+    assert sorted(gold.files) == sorted(want)
+    for k, v in want.items():
+        assert np.array_equal(gold[k], v), k
 
 
 @torch.no_grad()
