@@ -15,7 +15,11 @@ from tortoise_tts_amd.config import ARConfig, CLVPConfig, DiffusionConfig, Vocod
 
 VOCAB = os.path.join(ref_shims.REFERENCE_ROOT, "tortoise", "data", "tokenizer.json")
 PAT = os.path.join(ref_shims.REFERENCE_ROOT, "tortoise", "voices", "cond_latent_example", "pat.pth")
-DEFAULT_TEXT = "The expressiveness of autoregressive transformers is literally nuts! I absolutely adore them."  # do_tts.py:12
+# Pre-tokenised text ids (tts() accepts them like a str): the flow tests run without the reference's tokenizer.json.  (Some id choices
+# make the oracle-backed stand-in sample code 8192, which the oracle CLVP cannot index: these do not.)
+DEFAULT_IDS = list(range(10, 31))  # in place of do_tts.py:12's default text
+HELLO_THERE = list(range(30, 40))
+HELLO = list(range(41, 49))
 
 
 def small_setup():
@@ -42,8 +46,6 @@ def voice_latents(cfgs):
 
 @pytest.fixture()
 def tts(monkeypatch):
-    if not os.path.exists(VOCAB):
-        pytest.skip("tokenizer.json (reference data file) not present")
     fake_stages.install(monkeypatch)
     from tortoise_tts_amd.api import TextToSpeech
     sds, cfgs = small_setup()
@@ -61,19 +63,19 @@ def test_do_tts_call_sequence(tts):
     voice_samples, conditioning_latents = None, voice_latents(tts._cfgs)
     kw = dict(k=3, voice_samples=voice_samples, conditioning_latents=conditioning_latents, preset="ultra_fast",
               use_deterministic_seed=11, return_deterministic_state=True, cvvp_amount=0.0)
-    gen, dbg = tts.tts_with_preset(DEFAULT_TEXT, max_mel_tokens=48, **kw)  # do_tts.py:41-42 (+ a short decode for CPU time)
+    gen, dbg = tts.tts_with_preset(DEFAULT_IDS, max_mel_tokens=48, **kw)  # do_tts.py:41-42 (+ a short decode for CPU time)
     assert isinstance(gen, list) and len(gen) == 3  # api.py:589-592: k > 1 -> list of k clips
     for g_ in gen:
         assert g_.dim() == 3 and g_.shape[:2] == (1, 1) and g_.dtype == torch.float32 and g_.device.type == "cpu"
         assert g_.shape[-1] % 256 == 0 and g_.shape[-1] > 0 and torch.isfinite(g_).all() and g_.abs().max() <= 1.0
         assert g_.squeeze(0).cpu().shape[0] == 1  # what do_tts.py:45 hands torchaudio.save
     seed, text, vs, lat = dbg  # api.py:594-595
-    assert seed == 11 and text == DEFAULT_TEXT and vs is None and lat is conditioning_latents
+    assert seed == 11 and text == DEFAULT_IDS and vs is None and lat is conditioning_latents
     # the ranked winners are fix_autoregressive_output'ed rows padded to max_mel_tokens (api.py:425-426, 459)
     best = tts.last_best_codes
     assert best.shape == (3, 48) and best.max() < 8193
     # same seed -> same audio; k = 1 returns a bare tensor (api.py:591-592)
-    again = tts.tts_with_preset(DEFAULT_TEXT, max_mel_tokens=48, **dict(kw, k=1, return_deterministic_state=False))
+    again = tts.tts_with_preset(DEFAULT_IDS, max_mel_tokens=48, **dict(kw, k=1, return_deterministic_state=False))
     assert torch.is_tensor(again) and torch.equal(again, gen[0])
 
 
@@ -81,15 +83,13 @@ def test_do_tts_call_sequence(tts):
 def test_tts_many_equals_one_utterance_after_the_other(monkeypatch):
     """tts_many (the long-form path: read.py:66-71 renders its chunks one after the other with the same seed) batches the
     autoregressive stage over `utterance_batch` utterances; everything it returns must equal tts() called per text."""
-    if not os.path.exists(VOCAB):
-        pytest.skip("tokenizer.json (reference data file) not present")
     fake_stages.install(monkeypatch)
     from tortoise_tts_amd.api import TextToSpeech
     sds, cfgs = small_setup()
     t = TextToSpeech(models_dir="/nonexistent", tokenizer_vocab_file=VOCAB, tokenizer_basic=True, state_dicts=sds, configs=cfgs,
                      max_candidates=8, max_mel_tokens=40, candidate_sharding=False, utterance_batch=2)
     lat = voice_latents(cfgs)
-    texts = ["Once upon a time.", "There lived a girl.", list(range(10, 31))]
+    texts = [list(range(30, 40)), list(range(41, 49)), list(range(10, 31))]
     kw = dict(num_autoregressive_samples=8, diffusion_iterations=3, max_mel_tokens=32)
     one_by_one = [t.tts(x, conditioning_latents=lat, use_deterministic_seed=5, verbose=False, **kw) for x in texts]
     many = t.tts_many(texts, conditioning_latents=lat, use_deterministic_seed=5, **kw)
@@ -128,16 +128,16 @@ def test_random_voice_and_error_behaviour(tts):
     torch.manual_seed(3)
     a2, _ = tts.get_random_conditioning_latents()
     assert torch.equal(a, a2)
-    wav = tts.tts("hello there", num_autoregressive_samples=4, diffusion_iterations=4, max_mel_tokens=24, use_deterministic_seed=1)
+    wav = tts.tts(HELLO_THERE, num_autoregressive_samples=4, diffusion_iterations=4, max_mel_tokens=24, use_deterministic_seed=1)
     assert torch.is_tensor(wav) and wav.shape[:2] == (1, 1)
     with pytest.raises(ValueError, match="Too much text"):  # api.py:392
         tts.tts(list(range(1, 255)) * 2, conditioning_latents=(a, d))
     with pytest.raises(NotImplementedError, match="bracket"):
         tts.tts("[I am so sad,] hello", conditioning_latents=(a, d))
     with pytest.raises(ValueError, match="cvvp_amount"):
-        tts.tts("hello", conditioning_latents=(a, d), cvvp_amount=1.5)
+        tts.tts(HELLO, conditioning_latents=(a, d), cvvp_amount=1.5)
     with pytest.raises(ValueError, match="max_mel_tokens"):
-        tts.tts("hello", conditioning_latents=(a, d), max_mel_tokens=500)
+        tts.tts(HELLO, conditioning_latents=(a, d), max_mel_tokens=500)
 
 
 @torch.no_grad()
@@ -154,7 +154,7 @@ def test_voice_samples_path(tts):
     pairs = [(am[:, 0], dm[:, 0]), (am[:, 1], dm[:, 1])]
     a2, d2 = tts.get_conditioning_latents(pairs)
     assert torch.equal(a, a2) and torch.equal(d, d2)
-    wav = tts.tts("hello there", voice_samples=clips, num_autoregressive_samples=4, diffusion_iterations=4, max_mel_tokens=24,
+    wav = tts.tts(HELLO_THERE, voice_samples=clips, num_autoregressive_samples=4, diffusion_iterations=4, max_mel_tokens=24,
                   use_deterministic_seed=2)
     assert torch.is_tensor(wav) and wav.shape[:2] == (1, 1) and torch.isfinite(wav).all()
 
@@ -174,10 +174,10 @@ def test_cvvp_amount_blends_the_candidate_ranking(tts):
     pairs = [(torch.randn(1, 80, 64, generator=g) * 2 - 5, torch.randn(1, 100, 70, generator=g) * 2 - 5) for _ in range(2)]
     kw = dict(voice_samples=pairs, num_autoregressive_samples=8, diffusion_iterations=3, max_mel_tokens=24, use_deterministic_seed=3, k=2)
     assert tts.cvvp is None
-    tts.tts("hello there", **kw)
+    tts.tts(HELLO_THERE, **kw)
     assert tts.cvvp is None  # "only loaded if used" (api.py:234)
     clvp_best = tts.last_best_codes.clone()
-    tts.tts("hello there", cvvp_amount=1.0, **kw)
+    tts.tts(HELLO_THERE, cvvp_amount=1.0, **kw)
     assert tts.cvvp is not None and tts.cvvp.calls == 1
     cvvp_best = tts.last_best_codes.clone()
     # recompute both rankings from the candidates (same seed -> same candidates; the winners are rows of the same candidate set)
@@ -188,21 +188,32 @@ def test_cvvp_amount_blends_the_candidate_ranking(tts):
     fixed = fix_autoregressive_output(F.pad(cand, (0, 24 - cand.shape[1]), value=tts.stop_mel_token), tts.stop_mel_token)
     want = fixed[torch.topk(O.cvvp_score(tts._state_dicts["cvvp"], ccfg, auto_conds, fixed), 2).indices]
     assert torch.equal(cvvp_best, want) and not torch.equal(cvvp_best, clvp_best)
-    tts.tts("hello there", cvvp_amount=0.5, **kw)
-    text = torch.as_tensor(tts.tokenizer.encode("hello there")).reshape(1, -1)
+    tts.tts(HELLO_THERE, cvvp_amount=0.5, **kw)
+    text = torch.as_tensor(HELLO_THERE).reshape(1, -1)
     clvp = O.clvp_score(tts._state_dicts["clvp"], tts._cfgs["clvp"], F.pad(text, (0, 1)).repeat(8, 1), fixed)
     blend = O.blend_candidate_scores(clvp, O.cvvp_score(tts._state_dicts["cvvp"], ccfg, auto_conds, fixed), 0.5)
     assert torch.equal(tts.last_best_codes, fixed[torch.topk(blend, 2).indices])
     # latents only: nothing for CVVP to compare with -> CLVP's ranking (api.py:464, 473); amount 1 has nothing to rank by at all
     lat = voice_latents(tts._cfgs)
     kw2 = dict(kw, voice_samples=None, conditioning_latents=lat)
-    tts.tts("hello there", **kw2)
+    tts.tts(HELLO_THERE, **kw2)
     only_clvp = tts.last_best_codes.clone()
     n_calls = tts.cvvp.calls
-    tts.tts("hello there", cvvp_amount=0.5, **kw2)
+    tts.tts(HELLO_THERE, cvvp_amount=0.5, **kw2)
     assert torch.equal(tts.last_best_codes, only_clvp) and tts.cvvp.calls == n_calls
     with pytest.raises(ValueError, match="voice_samples"):
-        tts.tts("hello there", cvvp_amount=1.0, **kw2)
+        tts.tts(HELLO_THERE, cvvp_amount=1.0, **kw2)
+
+
+@torch.no_grad()
+def test_str_text_equals_its_token_ids(tts):
+    """A str goes through the tokenizer (api.py:390): the same audio as its ids passed pre-tokenised."""
+    if not os.path.exists(VOCAB):
+        pytest.skip("tokenizer.json (reference data file) not present")
+    kw = dict(num_autoregressive_samples=4, diffusion_iterations=4, max_mel_tokens=24, use_deterministic_seed=1)
+    from_str = tts.tts("hello there", **kw)
+    from_ids = tts.tts(tts.tokenizer.encode("hello there"), **kw)
+    assert torch.equal(from_str, from_ids)
 
 
 def test_constructor_flags(monkeypatch):

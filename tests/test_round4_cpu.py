@@ -98,8 +98,8 @@ def test_collective_init_failure_leaves_rank0_serving_under_torch_distributed_ru
 
 @torch.no_grad()
 def test_tts_many_decodes_again_when_the_fp16_autoregressive_stage_overflowed(monkeypatch):
-    """Round-4 advisor finding: with utterance_batch == 1 tts_many decodes every utterance's candidates up front and hands them to tts()
-    as '_ar_samples'; an overflowed fp16 decode (rows cut short with the stop token) was then rendered, and re-rendered after the
+    """Round-4 advisor finding: with utterance_batch == 1 tts_many decodes every utterance's candidates up front and renders them
+    afterwards; an overflowed fp16 decode (rows cut short with the stop token) was then rendered, and re-rendered after the
     demotion, from the SAME stale codes.  The guard is read right behind the decode now: the stage is rebuilt with bf16 operands and
     the texts are decoded again - same audio as an engine that ran bf16 from the start."""
     fake_stages.install(monkeypatch)

@@ -20,8 +20,11 @@ cvvp_amount > 0 (api.py:450-472; the CHANGELOG calls CVVP "removed", the call si
 first use like upstream (load_cvvp -> stages.CvvpStage, csrc/cvvp.hip) and blended into the CLVP ranking when voice_samples are given.
 Out of scope (raise, never silently fall back): wav2vec redaction of bracketed text, DeepSpeed flag.
 """
+import inspect
 import os
 import random
+import time
+import types
 
 import numpy as np
 import torch
@@ -160,7 +163,44 @@ def resolve_stage_dtypes(dtype, half):
     return {k: E.dtype_code(v) for k, v in out.items()}
 
 
-class TextToSpeech:
+class _Common:
+    """What this module's TextToSpeech and api_fast.TextToSpeech share: the lazy tokenizer, the seed, the text front-end."""
+    world = 1  # processes that share one utterance's work (TextToSpeech with candidate sharding sets its own)
+
+    @property
+    def tokenizer(self):
+        if self._tokenizer is None:
+            from .text import VoiceBpeTokenizer
+            self._tokenizer = VoiceBpeTokenizer(self.tokenizer_args[0], self.tokenizer_args[1], self.models_dir)
+        return self._tokenizer
+
+    def deterministic_state(self, seed=None):
+        """api.py:598-609."""
+        seed = int(torch.seed() % (2 ** 31)) if seed is None else int(seed)
+        if self.world > 1:
+            seed = tdist.broadcast_int(seed)  # every rank must draw the same noise and key the same Philox streams
+        torch.manual_seed(seed)
+        random.seed(seed)
+        return seed
+
+    def _text_tokens(self, text, max_mel_tokens, refuse_brackets=True):
+        """One text (str, or ids: int sequence / tensor [T]) to be spoken in max_mel_tokens -> padded int32 tokens [1, T + 1] on the device
+        (api.py:388-392).  refuse_brackets: [bracketed] text raises while enable_redaction is on (the reference redacts it from the audio)."""
+        if refuse_brackets and self.enable_redaction and isinstance(text, str) and "[" in text and "]" in text:
+            raise NotImplementedError("text with [bracketed] passages needs the wav2vec2 aligner to redact them from the audio "
+                                      "(api.py:583-587), which is outside the accelerated path; remove the brackets or construct "
+                                      "TextToSpeech(enable_redaction=False) to have them spoken")
+        ids = self.tokenizer.encode(text) if isinstance(text, str) else text
+        tokens = F.pad(torch.as_tensor(ids, dtype=torch.int32).reshape(1, -1).to(self.device), (0, 1))  # api.py:391
+        if tokens.shape[-1] >= 400:  # api.py:392
+            raise ValueError("Too much text provided. Break the text up into separate segments and re-try inference.")
+        if max_mel_tokens > self.max_mel_tokens_cap:
+            raise ValueError(f"max_mel_tokens={max_mel_tokens} exceeds the capacity this engine was built with "
+                             f"(TextToSpeech(max_mel_tokens={self.max_mel_tokens_cap}))")
+        return tokens
+
+
+class TextToSpeech(_Common):
     """Main entry point; see the module docstring.  Engine-only keyword arguments (all optional, after
     the reference's): `state_dicts` (dict of reference-layout state_dicts instead of files in
     models_dir), `dtype` (MFMA operand type: 'bf16' | 'fp16' for every stage, or a dict per stage
@@ -320,13 +360,6 @@ class TextToSpeech:
             self._build_stage(name)
 
     # ------------------------------------------------------------------ reference helpers
-    @property
-    def tokenizer(self):
-        if self._tokenizer is None:
-            from .text import VoiceBpeTokenizer
-            self._tokenizer = VoiceBpeTokenizer(self.tokenizer_args[0], self.tokenizer_args[1], self.models_dir)
-        return self._tokenizer
-
     def get_conditioning_latents(self, voice_samples, return_mels=False):
         """api.py:258-299 on the engine: ConditioningEncoder (autoregressive.py:204-228) and contextual_embedder
         (diffusion_decoder.py:186-192, 222-230) run on the device (csrc/cond.hip).  voice_samples is, as in
@@ -373,15 +406,6 @@ class TextToSpeech:
         """{'ar': 'bf16', ...}: the operand type every stage currently runs with (after any overflow demotion)."""
         return {k: E.DTYPE_NAMES[v] for k, v in self.dtypes.items()}
 
-    def deterministic_state(self, seed=None):
-        """api.py:598-609."""
-        seed = int(torch.seed() % (2 ** 31)) if seed is None else int(seed)
-        if self.world > 1:
-            seed = tdist.broadcast_int(seed)  # every rank must draw the same noise and key the same Philox streams
-        torch.manual_seed(seed)
-        random.seed(seed)
-        return seed
-
     def tts_with_preset(self, text, preset="fast", **kwargs):
         """api.py:311-332: same preset table, caller kwargs win."""
         settings = dict(BASE_SETTINGS)
@@ -400,149 +424,24 @@ class TextToSpeech:
             # diffusion generation parameters follow
             diffusion_iterations=100, cond_free=True, cond_free_k=2, diffusion_temperature=1.0,
             **hf_generate_kwargs):
-        noise = hf_generate_kwargs.pop("noise_override", None) or {}
-        top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
-        if not 0 <= cvvp_amount <= 1:
-            raise ValueError(f"cvvp_amount={cvvp_amount} must lie in [0, 1] (api.py:366-367)")
-        dev = self.device
-        if self.enable_redaction and isinstance(text, str) and "[" in text and "]" in text:
-            raise NotImplementedError("text with [bracketed] passages needs the wav2vec2 aligner to redact them from the audio "
-                                      "(api.py:583-587), which is outside the accelerated path; remove the brackets or construct "
-                                      "TextToSpeech(enable_redaction=False) to have them spoken")
+        o = self._settings(locals())  # (the arguments above, by name)
+        tokens = self._text_tokens(text, max_mel_tokens)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         ev = _StageTimer(6)
         ev.mark(0)
-
-        if isinstance(text, str):
-            text_tokens = torch.IntTensor(self.tokenizer.encode(text)).unsqueeze(0)
-        else:  # pre-tokenised ids (synthetic prompts): int sequence / tensor [T]
-            text_tokens = torch.as_tensor(text, dtype=torch.int32).reshape(1, -1)
-        text_tokens = F.pad(text_tokens.to(dev), (0, 1))  # api.py:391
-        if text_tokens.shape[-1] >= 400:  # api.py:392
-            raise ValueError("Too much text provided. Break the text up into separate segments and re-try inference.")
-        auto_conds = None  # the voice clips' mels: what CVVP compares the candidates with (api.py:393-395)
-        if voice_samples is not None:
-            auto_conditioning, diffusion_conditioning, auto_conds, _ = self.get_conditioning_latents(voice_samples, return_mels=True)
-        elif conditioning_latents is not None:
-            auto_conditioning, diffusion_conditioning = conditioning_latents
-        else:
-            auto_conditioning, diffusion_conditioning = self.get_random_conditioning_latents()
-        if cvvp_amount > 0:
-            if cvvp_amount == 1 and auto_conds is None:
+        voice = self._voice(voice_samples, conditioning_latents, mels=True)
+        if o.cvvp_amount > 0:
+            if o.cvvp_amount == 1 and voice[2] is None:
                 raise ValueError("cvvp_amount=1 ranks the candidates by CVVP alone, which compares them with the voice's conditioning clips: "
                                  "pass voice_samples (with latents only the reference has nothing to rank by, api.py:462-472)")
             self.load_cvvp()  # api.py:450-453 (loaded even when there are no clips to use it on)
-        auto_conditioning = auto_conditioning.to(dev).float()
-        diffusion_conditioning = diffusion_conditioning.to(dev).float()
-        if max_mel_tokens > self.max_mel_tokens_cap:
-            raise ValueError(f"max_mel_tokens={max_mel_tokens} exceeds the capacity this engine was built with "
-                             f"(TextToSpeech(max_mel_tokens={self.max_mel_tokens_cap}))")
-        sched = Schedule(diffusion_iterations, self.diff_cfg.trained_steps, cond_free, cond_free_k)
-
-        # ---- stage 1: this rank's share of the candidates (api.py:407-427)
-        N = int(num_autoregressive_samples)
-        lo, hi = tdist.shard_range(N, self.rank, self.world)
-        stop = self.ar_cfg.stop_mel_token
-        exp_noise = noise.get("exp_noise")
-        batches = []
-        pre = noise.get("_ar_samples")  # tts_many: this utterance's candidates were decoded in a shared batch already
-        if pre is not None:
-            batches.append(pre.to(dev).long())
-        for c0 in ([] if pre is not None else range(lo, hi, self.autoregressive_batch_size)):
-            B = min(self.autoregressive_batch_size, hi - c0)
-            self.ar.prefill(auto_conditioning, text_tokens)
-            en = exp_noise[:, c0 - lo:c0 - lo + B] if exp_noise is not None else None
-            codes, n = self.ar.generate(B, max_mel_tokens, temperature=temperature, top_p=top_p, repetition_penalty=repetition_penalty,
-                                        top_k=top_k, seed=seed, row_offset=c0, exp_noise=en, typical_mass=typical_mass)
-            batches.append(F.pad(codes, (0, max_mel_tokens - codes.shape[1]), value=stop))  # api.py:425-426
-        samples = torch.cat(batches, dim=0)
-        ev.mark(1)
-
-        # ---- CLVP ranking (api.py:447-477) + the one collective of the path
-        fixed = fix_autoregressive_output(samples, stop)
-        # api.py:462-472: CLVP unless cvvp_amount == 1; CVVP (mean over the voice's conditioning clips) when there are clips and cvvp_amount > 0
-        scores = self.clvp.score(text_tokens, fixed) if cvvp_amount != 1 else None
-        if auto_conds is not None and cvvp_amount > 0:
-            cvvp = self.cvvp.score(auto_conds, fixed)
-            scores = cvvp if cvvp_amount == 1 else cvvp * cvvp_amount + scores * (1 - cvvp_amount)
-        scores_all, codes_all = tdist.gather_candidates(scores, fixed.to(torch.int32)) if self.world > 1 else (scores, fixed.to(torch.int32))
-        best = tdist.topk_lowest_index(scores_all, k)
-        best_results = codes_all[best].long()
-        self.last_best_codes = best_results  # the k ranked winners' codes (tests, sharding checks)
-        ev.mark(2)
-
-        # ---- AR latent re-pass for the winners (api.py:516-524)
-        best_latents = self.ar.latents(auto_conditioning, text_tokens, best_results)
-        ev.mark(3)
-
-        # ---- stage 2 + 3 per winner; winners are spread round-robin over the ranks.  A single winner with
-        # conditioning_free is rendered by ranks 0 and 1 together: rank r evaluates denoiser row r of every step.
-        split = self.split_diffusion and k == 1 and bool(sched.cond_free)
-        wavs = {}
-        wav_ok = True
-        for i in range(k):
-            if split:
-                if self.rank > 1:
-                    continue
-            elif i % self.world != self.rank:
-                continue
-            codes_i = best_results[i]
-            latents = best_latents[i:i + 1]
-            latents = latents[:, :calm_trim_length(codes_i)]  # api.py:547-556
-            M = latents.shape[1]
-            S = M * 4 * 24000 // 22050  # api.py:122
-            self.diffusion.condition(latents, diffusion_conditioning, S)
-            gen = torch.Generator(device=dev).manual_seed(seed + 7919 * (i + 1))
-            x_T = noise.get("x_T")
-            x_T = (torch.randn(1, 100, S, device=dev, generator=gen) if x_T is None else x_T.to(dev)) * diffusion_temperature
-            step_noise = noise.get("step_noise")
-            if step_noise is None:
-                step_noise = torch.randn(sched.num_timesteps, 1, 100, S, device=dev, generator=gen)
-            if split:
-                mel = self.diffusion.sample_split(sched, x_T, step_noise, self.rank, tdist.exchange_rows)
-                if self.rank != 0:
-                    continue  # rank 1 only lends its GPU to the tail; rank 0 holds the same mel and runs the vocoder
-            else:
-                mel = self.diffusion.sample(sched, x_T, step_noise)
-            ev.mark(4)
-            z = noise.get("z")
-            z = torch.randn(1, self.voc_cfg.noise_dim, S + 10, device=dev, generator=gen) if z is None else z.to(dev)
-            audio = self.vocoder.inference(mel, z)
-            finite = torch.isfinite(audio).all()  # (a NaN survives the final clamp: the vocoder stage's overflow check)
-            wavs[i] = audio.cpu()
-            wav_ok = wav_ok and bool(finite)
-        if not wavs:  # this rank had no winner to render
-            ev.mark(4)
-        ev.mark(5)
-        ev.synchronize()
-        # operand-overflow guards (fp16 stages): counters the stages' own kernels kept, read after the synchronisation above
-        tripped = self._tripped_stages(wav_ok)
-        if tripped:
-            self._demote(tripped)
-            if "ar" in tripped and noise.get("_ar_samples") is not None:
-                # candidates decoded ahead of this call (tts_many) came from the stage that just overflowed: decode them again
-                noise = {k_: v_ for k_, v_ in noise.items() if k_ != "_ar_samples"}
-            return self.tts(text, voice_samples=voice_samples, conditioning_latents=conditioning_latents, k=k, verbose=verbose,
-                            use_deterministic_seed=seed, return_deterministic_state=return_deterministic_state,
-                            num_autoregressive_samples=num_autoregressive_samples, temperature=temperature, length_penalty=length_penalty,
-                            repetition_penalty=repetition_penalty, top_p=top_p, max_mel_tokens=max_mel_tokens, cvvp_amount=cvvp_amount,
-                            diffusion_iterations=diffusion_iterations, cond_free=cond_free, cond_free_k=cond_free_k,
-                            diffusion_temperature=diffusion_temperature, top_k=top_k,
-                            **({"typical_sampling": True, "typical_mass": typical_mass} if typical_mass else {}),
-                            **({"noise_override": noise} if noise else {}))
-        self.timings = {"ar_s": ev.seconds(0, 1), "clvp_s": ev.seconds(1, 2), "latents_s": ev.seconds(2, 3),
-                        "diffusion_s": ev.seconds(3, 4), "vocoder_s": ev.seconds(4, 5), "total_s": ev.seconds(0, 5)}
+        wavs = self._guarded(lambda: self._utterance(ev, tokens, voice, o, seed, k))  # (a re-render after a demotion: same seed)
+        self.timings = _event_timings(ev)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
-        if wavs is None:
-            res = None
-            return (res, (seed, text, voice_samples, conditioning_latents)) if return_deterministic_state else res
-        wav_candidates = [wavs[i] for i in range(k)]
-        res = wav_candidates if len(wav_candidates) > 1 else wav_candidates[0]
-        if return_deterministic_state:
-            return res, (seed, text, voice_samples, conditioning_latents)
-        return res
+        res = None if wavs is None else [wavs[i] for i in range(k)] if k > 1 else wavs[0]
+        return (res, (seed, text, voice_samples, conditioning_latents)) if return_deterministic_state else res
 
     @torch.no_grad()
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
@@ -555,145 +454,219 @@ class TextToSpeech:
         and UnivNet (2 ms per utterance) run per utterance as in tts().  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py)."""
         if self.world != 1:
             raise ValueError("tts_many batches utterances on one GPU: build TextToSpeech(candidate_sharding=False)")
-        settings = dict(kwargs)
-        k = int(settings.pop("k", 1))
-        if k != 1:
+        args = inspect.signature(self.tts).bind(None, **kwargs)
+        args.apply_defaults()
+        if int(args.arguments["k"]) != 1:
             raise NotImplementedError("tts_many renders the top-ranked candidate of every utterance (k = 1)")
-        if settings.pop("return_deterministic_state", False):
+        if args.arguments["return_deterministic_state"]:
             raise NotImplementedError("tts_many: return_deterministic_state is a per-call option of tts()")
-        N = int(settings.get("num_autoregressive_samples", 512))
-        max_mel_tokens = int(settings.get("max_mel_tokens", 500))
-        hf = {k_: settings[k_] for k_ in list(settings) if k_ not in (
-            "num_autoregressive_samples", "temperature", "length_penalty", "repetition_penalty", "top_p", "max_mel_tokens", "cvvp_amount",
-            "diffusion_iterations", "cond_free", "cond_free_k", "diffusion_temperature")}
-        if set(hf) - {"top_k", "typical_sampling", "typical_mass"} or settings.get("cvvp_amount", 0) != 0 or N > self.autoregressive_batch_size or N % 4 != 0:
-            # anything tts() refuses or the grouped decode cannot hold: let tts() handle (or refuse) it, one utterance at a time
-            return [self.tts(t, voice_samples=voice_samples, conditioning_latents=conditioning_latents, k=1, verbose=verbose,
-                             use_deterministic_seed=use_deterministic_seed, **settings) for t in texts]
-        top_k, typical_mass = sampler_kwargs(hf)
+        o = self._settings(args.arguments)
+        if o.noise or o.cvvp_amount != 0 or o.N > self.autoregressive_batch_size or o.N % 4 != 0:
+            # what the grouped decode cannot hold: tts() renders it, one utterance at a time
+            return [self.tts(t, voice_samples=voice_samples, conditioning_latents=conditioning_latents, verbose=verbose,
+                             use_deterministic_seed=use_deterministic_seed, **kwargs) for t in texts]
         seed = self.deterministic_state(seed=use_deterministic_seed)
-        dev = self.device
-        toks = []
-        for text in texts:
-            if self.enable_redaction and isinstance(text, str) and "[" in text and "]" in text:
-                raise NotImplementedError("text with [bracketed] passages needs the wav2vec2 aligner (api.py:583-587); see tts()")
-            t = torch.IntTensor(self.tokenizer.encode(text)).unsqueeze(0) if isinstance(text, str) else torch.as_tensor(text, dtype=torch.int32).reshape(1, -1)
-            t = F.pad(t.to(dev), (0, 1))
-            if t.shape[-1] >= 400:
-                raise ValueError("Too much text provided. Break the text up into separate segments and re-try inference.")
-            toks.append(t)
-        if voice_samples is not None:
-            conditioning_latents = self.get_conditioning_latents(voice_samples)
-        elif conditioning_latents is None:
-            conditioning_latents = self.get_random_conditioning_latents()
-        auto_conditioning = conditioning_latents[0].to(dev).float()
-        if max_mel_tokens > self.max_mel_tokens_cap:
-            raise ValueError(f"max_mel_tokens={max_mel_tokens} exceeds the capacity this engine was built with")
-        stop = self.ar_cfg.stop_mel_token
+        toks = [self._text_tokens(t, o.max_mel_tokens) for t in texts]
+        voice = self._voice(voice_samples, conditioning_latents)
         G = self.utterance_batch
-        waves = [list(range(w0, min(w0 + G, len(toks)))) for w0 in range(0, len(toks), G)]
+        waves = [toks[w0:w0 + G] for w0 in range(0, len(toks), G)]
 
-        def ar_wave(idx):
-            """One shared decode batch: the candidates of the utterances `idx` -> their code tensors [N, max_mel_tokens]."""
-            for g, j in enumerate(idx):
-                self.ar.prefill_group(g, len(idx), auto_conditioning, toks[j])
-            codes, _ = self.ar.generate(N * len(idx), max_mel_tokens, temperature=settings.get("temperature", .8), top_p=settings.get("top_p", .8),
-                                        repetition_penalty=settings.get("repetition_penalty", 2.0), top_k=top_k, seed=seed, row_offset=0,
-                                        group_seeds=[seed] * len(idx), typical_mass=typical_mass)
-            codes = F.pad(codes, (0, max_mel_tokens - codes.shape[1]), value=stop)
-            return [codes[g * N:(g + 1) * N] for g in range(len(idx))]
-
-        out, acc = [None] * len(toks), {}
         if not self.batch_diffusion:
+            # Shared decode batches, then every utterance ranked and rendered with the calls of tts().  An overflowed fp16 autoregressive
+            # stage is caught right behind the decode and decoded again: nothing renders from the codes it produced.
             ev = _StageTimer(2)
             ev.mark(0)
-            samples = [smp for idx in waves for smp in ar_wave(idx)]
-            # The candidates of every utterance are decoded up front; an overflowed fp16 autoregressive stage must be caught HERE - the
-            # per-utterance tts() calls below would otherwise render (and, after their own demotion, re-render) from codes the overflowed
-            # stage produced.  (ar.generate() synchronises, so the guard counter is current.)
-            ar_guard = getattr(self.ar, "guard", None)
-            if ar_guard is not None and ar_guard():
-                self._demote(["ar"])
-                return self.tts_many(texts, conditioning_latents=conditioning_latents, use_deterministic_seed=seed, verbose=verbose, **kwargs)
+            decoded = self._guarded(lambda: ([smp for wave in waves for smp in self._decode_wave(voice[0], wave, o, seed)], True))
             ev.mark(1)
-            for j, (t, smp) in enumerate(zip(toks, samples)):
-                out[j] = self.tts(t[0, :-1], conditioning_latents=conditioning_latents, k=1, verbose=verbose, use_deterministic_seed=seed,
-                                  noise_override={"_ar_samples": smp}, **settings)
-                for k_, v in self.timings.items():
-                    acc[k_] = acc.get(k_, 0.0) + v
+            out, acc = [], {}
+            for tokens, samples in zip(toks, decoded):
+                ev_u, ar = _StageTimer(6), self.ar
+                ev_u.mark(0)
+                # (an overflow in this utterance's latent re-pass rebuilds the stage: its codes are then decoded again, as in tts())
+                out.append(self._guarded(lambda: self._utterance(ev_u, tokens, voice, o, seed, 1, samples if self.ar is ar else None))[0])
+                for key, v in _event_timings(ev_u).items():
+                    acc[key] = acc.get(key, 0.0) + v
             ev.synchronize()
             acc["ar_s"] = acc.get("ar_s", 0.0) + ev.seconds(0, 1)
             acc["total_s"] = acc.get("total_s", 0.0) + ev.seconds(0, 1)
             self.timings = acc
             return out
 
-        diffusion_conditioning = conditioning_latents[1].to(dev).float()
-        sched = Schedule(int(settings.get("diffusion_iterations", 100)), self.diff_cfg.trained_steps, settings.get("cond_free", True),
-                         settings.get("cond_free_k", 2))
+        def lap(clock, key, t0):
+            _StageTimer.synchronize()
+            t1 = time.perf_counter()
+            clock[key] += t1 - t0
+            return t1
 
-        def prepare(t, fixed, scores):
-            """Winner + latent re-pass of one utterance (api.py:477-524) and its diffusion inputs with the noise tts() would draw."""
-            best = tdist.topk_lowest_index(scores, 1)
-            best_results = fixed.to(torch.int32)[best].long()
-            self.last_best_codes = best_results
-            best_latents = self.ar.latents(auto_conditioning, t, best_results)
-            latents = best_latents[0:1][:, :calm_trim_length(best_results[0])]
-            S = latents.shape[1] * 4 * 24000 // 22050
-            gen = torch.Generator(device=dev).manual_seed(seed + 7919)
-            x_T = torch.randn(1, 100, S, device=dev, generator=gen) * float(settings.get("diffusion_temperature", 1.0))
-            step_noise = torch.randn(sched.num_timesteps, 1, 100, S, device=dev, generator=gen)
-            z = torch.randn(1, self.voc_cfg.noise_dim, S + 10, device=dev, generator=gen)
-            return (latents, diffusion_conditioning, S, x_T, step_noise), z
+        def attempt():
+            clock = dict.fromkeys(("ar_s", "clvp_s", "latents_s", "diffusion_s", "vocoder_s"), 0.0)  # host-clock stage sums
+            t_all = time.perf_counter()
+            out, ok = [], True
+            for wave in waves:
+                t0 = time.perf_counter()
+                samples = self._decode_wave(voice[0], wave, o, seed)
+                t0 = lap(clock, "ar_s", t0)
+                # CLVP ranking of the whole wave in ONE speech-tower pass (api.py:460-477 per utterance; read.py:66-71 one call per chunk)
+                best = self._rank(wave, samples, 1, grouped=True)
+                items, zs = zip(*[self._winner_inputs(b[0], self.ar.latents(voice[0], t, b), voice[1], o, seed, 0) for t, b in zip(wave, best)])
+                t0 = lap(clock, "clvp_s", t0)
+                wavs, wave_ok = self._render_wave(o.sched, items, zs)
+                clock["diffusion_s"] += time.perf_counter() - t0
+                out += wavs
+                ok = ok and wave_ok
+            return (out, clock, t_all), ok
 
-        def render(idx, items, zs):
-            """Diffusion in shared, padded passes (neighbours in length together: least padding) + UnivNet for the utterances `idx`."""
-            order = sorted(range(len(idx)), key=lambda k_: items[k_][2])
-            mels = [None] * len(idx)
-            for w0 in range(0, len(order), G):
-                sel = order[w0:w0 + G]
-                if len(sel) == 1:
-                    lat_, dc_, S_, x_, n_ = items[sel[0]]
-                    self.diffusion.condition(lat_, dc_, S_)
-                    mels[sel[0]] = self.diffusion.sample(sched, x_, n_)
-                else:
-                    for k_, mel in zip(sel, self.diffusion.sample_many(sched, [items[k_] for k_ in sel])):
-                        mels[k_] = mel
-            for k_, j in enumerate(idx):
-                out[j] = self.vocoder.inference(mels[k_], zs[k_]).cpu()
-
-        import time as _time
-        on_gpu = torch.device(dev).type == "cuda"  # (the CPU stand-ins of the tests drive the same schedule without streams)
-
-        def sync_current():
-            if on_gpu:
-                torch.cuda.current_stream().synchronize()
-
-        t_host = {"ar_s": 0.0, "rank_s": 0.0, "render_s": 0.0}
-        t_all = _time.perf_counter()
-        for idx in waves:
-            t0 = _time.perf_counter()
-            samples = ar_wave(idx)
-            sync_current()
-            t_host["ar_s"] += _time.perf_counter() - t0
-            t0 = _time.perf_counter()
-            # CLVP ranking of the whole wave in ONE speech-tower pass (api.py:460-477 per utterance; read.py:66-71 one call per chunk)
-            fixed = [fix_autoregressive_output(smp.to(dev).long(), stop) for smp in samples]
-            scores_all = self.clvp.score_groups([toks[j] for j in idx], torch.cat(fixed, dim=0))
-            prepared = [prepare(toks[j], fx, scores_all[g * N:(g + 1) * N]) for g, (j, fx) in enumerate(zip(idx, fixed))]
-            sync_current()
-            t_host["rank_s"] += _time.perf_counter() - t0
-            t0 = _time.perf_counter()
-            render(idx, [p_[0] for p_ in prepared], [p_[1] for p_ in prepared])
-            t_host["render_s"] += _time.perf_counter() - t0
-        if on_gpu:
-            torch.cuda.synchronize()
-        tripped = self._tripped_stages(all(bool(torch.isfinite(o).all()) for o in out))
-        if tripped:  # an fp16 stage overflowed: rebuild it with bf16 operands and render the texts again (same seed)
-            self._demote(tripped)
-            return self.tts_many(texts, conditioning_latents=conditioning_latents, use_deterministic_seed=seed, verbose=verbose, **kwargs)
-        # host-clock stage sums
-        acc = {"ar_s": t_host["ar_s"], "clvp_s": t_host["rank_s"], "latents_s": 0.0, "diffusion_s": t_host["render_s"], "vocoder_s": 0.0,
-               "total_s": _time.perf_counter() - t_all}
-        self.timings = acc
+        out, clock, t_all = self._guarded(attempt)
+        self.timings = dict(clock, total_s=time.perf_counter() - t_all)
         return out
 
+    # ------------------------------------------------------------------ phases of tts() / tts_many()
+    def _settings(self, args):
+        """tts()'s generation arguments (`args`: its parameters by name), validated -> what the phases read."""
+        hf = dict(args["hf_generate_kwargs"])
+        noise = hf.pop("noise_override", None) or {}
+        top_k, typical_mass = sampler_kwargs(hf)
+        if not 0 <= args["cvvp_amount"] <= 1:
+            raise ValueError(f"cvvp_amount={args['cvvp_amount']} must lie in [0, 1] (api.py:366-367)")
+        return types.SimpleNamespace(
+            N=int(args["num_autoregressive_samples"]), max_mel_tokens=args["max_mel_tokens"], cvvp_amount=args["cvvp_amount"], noise=noise,
+            sampling=dict(temperature=args["temperature"], top_p=args["top_p"], repetition_penalty=args["repetition_penalty"], top_k=top_k,
+                          typical_mass=typical_mass),
+            sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
+            diffusion_temperature=args["diffusion_temperature"])
+
+    def _voice(self, voice_samples, conditioning_latents, mels=False):
+        """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares
+        the candidates with; None for a voice given as latents)."""
+        auto_conds = None
+        if voice_samples is None:
+            auto, diff = conditioning_latents if conditioning_latents is not None else self.get_random_conditioning_latents()
+        elif mels:
+            auto, diff, auto_conds, _ = self.get_conditioning_latents(voice_samples, return_mels=True)
+        else:
+            auto, diff = self.get_conditioning_latents(voice_samples)
+        return auto.to(self.device).float(), diff.to(self.device).float(), auto_conds
+
+    def _decode(self, auto, tokens, o, seed):
+        """This rank's share of one utterance's candidates (api.py:407-427) in autoregressive_batch_size batches -> codes [n, max_mel_tokens]."""
+        lo, hi = tdist.shard_range(o.N, self.rank, self.world)
+        exp_noise = o.noise.get("exp_noise")
+        batches = []
+        for c0 in range(lo, hi, self.autoregressive_batch_size):
+            B = min(self.autoregressive_batch_size, hi - c0)
+            self.ar.prefill(auto, tokens)
+            en = exp_noise[:, c0 - lo:c0 - lo + B] if exp_noise is not None else None
+            codes, _ = self.ar.generate(B, o.max_mel_tokens, seed=seed, row_offset=c0, exp_noise=en, **o.sampling)
+            batches.append(F.pad(codes, (0, o.max_mel_tokens - codes.shape[1]), value=self.ar_cfg.stop_mel_token))  # api.py:425-426
+        return torch.cat(batches, dim=0)
+
+    def _decode_wave(self, auto, toks, o, seed):
+        """One shared decode batch for the utterances `toks` -> their candidates' codes [N, max_mel_tokens], one tensor per utterance."""
+        for g, tokens in enumerate(toks):
+            self.ar.prefill_group(g, len(toks), auto, tokens)
+        codes, _ = self.ar.generate(o.N * len(toks), o.max_mel_tokens, seed=seed, row_offset=0, group_seeds=[seed] * len(toks), **o.sampling)
+        return list(F.pad(codes, (0, o.max_mel_tokens - codes.shape[1]), value=self.ar_cfg.stop_mel_token).split(o.N))
+
+    def _rank(self, toks, samples, k, auto_conds=None, cvvp_amount=0.0, grouped=False):
+        """api.py:447-477: every utterance's fixed candidates scored by CLVP (score() each, or ONE score_groups() pass for a wave), blended with
+        CVVP when there are clips and cvvp_amount > 0, gathered over the ranks -> the k winners' codes per utterance.  Sets last_best_codes."""
+        stop = self.ar_cfg.stop_mel_token
+        fixed = [fix_autoregressive_output(smp, stop) for smp in samples]
+        if grouped:
+            scores = self.clvp.score_groups(toks, torch.cat(fixed, dim=0)).split(fixed[0].shape[0])
+        else:  # api.py:462-472: CLVP unless cvvp_amount == 1
+            scores = [self.clvp.score(tokens, fx) if cvvp_amount != 1 else None for tokens, fx in zip(toks, fixed)]
+        best = []
+        for sc, fx in zip(scores, fixed):
+            if auto_conds is not None and cvvp_amount > 0:
+                cvvp = self.cvvp.score(auto_conds, fx)
+                sc = cvvp if cvvp_amount == 1 else cvvp * cvvp_amount + sc * (1 - cvvp_amount)
+            codes = fx.to(torch.int32)
+            if self.world > 1:
+                sc, codes = tdist.gather_candidates(sc, codes)
+            best.append(codes[tdist.topk_lowest_index(sc, k)].long())
+        self.last_best_codes = best[-1]  # the k ranked winners' codes (tests, sharding checks)
+        return best
+
+    def _winner_inputs(self, codes, latents, cond, o, seed, i):
+        """Winner i (codes [n], re-passed latents [1, n, D]) -> diffusion item (latents cut at the calm run, cond, S, x_T, step_noise) and
+        vocoder noise z, drawn in that order from seed + 7919 * (i + 1) unless noise_override supplies them (api.py:122, 547-556)."""
+        dev = self.device
+        latents = latents[:, :calm_trim_length(codes)]
+        S = latents.shape[1] * 4 * 24000 // 22050
+        gen = torch.Generator(device=dev).manual_seed(seed + 7919 * (i + 1))
+        x_T, step_noise, z = (o.noise.get(key) for key in ("x_T", "step_noise", "z"))
+        x_T = (torch.randn(1, 100, S, device=dev, generator=gen) if x_T is None else x_T.to(dev)) * o.diffusion_temperature
+        if step_noise is None:
+            step_noise = torch.randn(o.sched.num_timesteps, 1, 100, S, device=dev, generator=gen)
+        z = torch.randn(1, self.voc_cfg.noise_dim, S + 10, device=dev, generator=gen) if z is None else z.to(dev)
+        return (latents, cond, S, x_T, step_noise), z
+
+    def _diffuse(self, sched, item, split=False):
+        """Diffusion item -> mel.  split: ranks 0 and 1 evaluate denoiser row 0 / 1 of every step; rank 1 only lends its GPU and gets None."""
+        latents, cond, S, x_T, step_noise = item
+        self.diffusion.condition(latents, cond, S)
+        if not split:
+            return self.diffusion.sample(sched, x_T, step_noise)
+        mel = self.diffusion.sample_split(sched, x_T, step_noise, self.rank, tdist.exchange_rows)
+        return mel if self.rank == 0 else None
+
+    def _utterance(self, ev, tokens, voice, o, seed, k, samples=None):
+        """One utterance: this rank's candidates (decoded unless given), ranking, the winners' latent re-pass (api.py:516-524) and the winners
+        this rank renders (round-robin; a single conditioning-free winner split over ranks 0 and 1), marking `ev` 1-5 between the phases.
+        -> ({winner index: clip on the CPU}, every clip finite)."""
+        auto, diff, auto_conds = voice
+        if samples is None:
+            samples = self._decode(auto, tokens, o, seed)
+        ev.mark(1)
+        best = self._rank([tokens], [samples], k, auto_conds, o.cvvp_amount)[0]
+        ev.mark(2)
+        best_latents = self.ar.latents(auto, tokens, best)
+        ev.mark(3)
+        split = self.split_diffusion and k == 1 and bool(o.sched.cond_free)
+        wavs, ok = {}, True
+        for i in range(k):
+            if (self.rank > 1) if split else (i % self.world != self.rank):
+                continue
+            item, z = self._winner_inputs(best[i], best_latents[i:i + 1], diff, o, seed, i)
+            mel = self._diffuse(o.sched, item, split)
+            if mel is None:
+                continue
+            ev.mark(4)
+            audio = self.vocoder.inference(mel, z)
+            finite = torch.isfinite(audio).all()  # (a NaN survives the final clamp: the vocoder stage's overflow check)
+            wavs[i] = audio.cpu()
+            ok = ok and bool(finite)
+        if not wavs:  # this rank had no winner to render
+            ev.mark(4)
+        ev.mark(5)
+        return wavs, ok
+
+    def _render_wave(self, sched, items, zs):
+        """A wave's winners -> (clips on the CPU, all finite): ONE shared, padded sample_many pass in length order, UnivNet per utterance."""
+        if len(items) == 1:
+            mels = [self._diffuse(sched, items[0])]
+        else:
+            order = sorted(range(len(items)), key=lambda u: items[u][2])
+            mels = [None] * len(items)
+            for u, mel in zip(order, self.diffusion.sample_many(sched, [items[u] for u in order])):
+                mels[u] = mel
+        wavs = [self.vocoder.inference(mel, z).cpu() for mel, z in zip(mels, zs)]
+        return wavs, all(bool(torch.isfinite(w).all()) for w in wavs)
+
+    def _guarded(self, attempt):
+        """Runs attempt() -> (result, wav_ok) until no overflow guard trips, rebuilding the stage at fault with bf16 operands in between.
+        Each fp16 stage demotes once and a tripped bf16 stage raises OperandOverflow, so the loop ends."""
+        while True:
+            result, wav_ok = attempt()
+            _StageTimer.synchronize()
+            tripped = self._tripped_stages(wav_ok)
+            if not tripped:
+                return result
+            self._demote(tripped)
+
+
+def _event_timings(ev):
+    """Stage seconds of one utterance from its six _StageTimer events."""
+    return {"ar_s": ev.seconds(0, 1), "clvp_s": ev.seconds(1, 2), "latents_s": ev.seconds(2, 3), "diffusion_s": ev.seconds(3, 4),
+            "vocoder_s": ev.seconds(4, 5), "total_s": ev.seconds(0, 5)}

@@ -20,20 +20,16 @@ teacher-forced latent re-pass) and csrc/hifigan.hip.
 Sampling noise comes from the engine's Philox streams keyed by use_deterministic_seed (seeds are not portable between
 generators: parity is "same latents -> same waveform", tests/test_gpu_stages.py::test_hifigan_decoder).
 """
-import os
-import random
-
 import torch
-import torch.nn.functional as F
 
 from . import engine as E
 from . import stages
 from . import weights as W
-from .api import MODELS_DIR, _load_state_dict, _load_file, sampler_kwargs
+from .api import MODELS_DIR, _Common, _load_state_dict, _load_file, sampler_kwargs
 from .config import ARConfig, HifiganConfig
 
 
-class TextToSpeech:
+class TextToSpeech(_Common):
     """api_fast.py:180-229.  Engine-only keyword arguments as in tortoise_tts_amd.api.TextToSpeech: state_dicts
     ('autoregressive', 'hifidecoder', 'rlg_auto'), dtype, configs ('ar', 'hifigan'), max_mel_tokens."""
 
@@ -80,13 +76,6 @@ class TextToSpeech:
             return _load_file(self.models_dir, "hifidecoder.pth")
         return _load_state_dict(self.models_dir, name)
 
-    @property
-    def tokenizer(self):
-        if self._tokenizer is None:
-            from .text import VoiceBpeTokenizer
-            self._tokenizer = VoiceBpeTokenizer(self.tokenizer_args[0], self.tokenizer_args[1], self.models_dir)
-        return self._tokenizer
-
     # ------------------------------------------------------------------ conditioning (api_fast.py:230-260)
     def get_conditioning_latents(self, voice_samples, return_mels=False):
         """Only the autoregressive latent exists on this path (there is no diffusion stage).  voice_samples: 22.05 kHz clips
@@ -114,22 +103,10 @@ class TextToSpeech:
         r = torch.randn(1, ca)
         return self.rlg_auto.latents(r, r)[0]
 
-    def deterministic_state(self, seed=None):
-        seed = int(torch.seed() % (2 ** 31)) if seed is None else int(seed)
-        torch.manual_seed(seed)
-        random.seed(seed)
-        return seed
-
     def _prepare(self, text, voice_samples, conditioning_latents, max_mel_tokens):
-        if isinstance(text, str):
-            ids = self.tokenizer.encode(text)
-        else:
-            ids = [int(t) for t in text]
-        text_tokens = F.pad(torch.tensor(ids, dtype=torch.int32, device=self.device)[None], (0, 1))
-        if text_tokens.shape[-1] >= 400:
-            raise ValueError("Too much text provided. Break the text up into separate segments and re-try inference.")  # api_fast.py:371
-        if not 1 <= max_mel_tokens <= self.max_mel_tokens_cap:
-            raise ValueError(f"max_mel_tokens={max_mel_tokens} outside [1, {self.max_mel_tokens_cap}] (engine capacity)")
+        text_tokens = self._text_tokens(text, max_mel_tokens, refuse_brackets=False)  # (api_fast.py:371; no redaction on this path)
+        if max_mel_tokens < 1:
+            raise ValueError(f"max_mel_tokens={max_mel_tokens} must be at least 1")
         if voice_samples is not None:
             cond = self.get_conditioning_latents(voice_samples)
         elif conditioning_latents is not None:
@@ -138,20 +115,13 @@ class TextToSpeech:
             cond = self.get_random_conditioning_latents()
         return text_tokens, cond.to(self.device).float().reshape(1, -1)
 
-    @staticmethod
-    def _check_kwargs(k, cvvp_amount, hf_generate_kwargs):
-        """Same refusals as tortoise_tts_amd.api.TextToSpeech.tts: a sampling option the on-device sampler cannot honour raises
-        instead of being dropped.  `k` and `cvvp_amount` are accepted and unused exactly as in the reference, whose fast path always
-        decodes ONE autoregressive sample into one clip - there is no candidate ranking CLVP or CVVP could take part in
-        (api_fast.py:316, 426, 421-519).  Returns (top_k, typical_mass) (api.sampler_kwargs)."""
-        return sampler_kwargs(hf_generate_kwargs)
-
     # ------------------------------------------------------------------ non-streaming (api_fast.py:421-519)
     @torch.no_grad()
     def tts(self, text, voice_samples=None, k=1, verbose=True, use_deterministic_seed=None, conditioning_latents=None,
             num_autoregressive_samples=512, temperature=.8, length_penalty=1, repetition_penalty=2.0, top_p=.8, max_mel_tokens=500,
             cvvp_amount=.0, **hf_generate_kwargs):
-        top_k, typical_mass = self._check_kwargs(k, cvvp_amount, hf_generate_kwargs)
+        # (k and cvvp_amount are accepted and unused as in the reference: its fast path decodes ONE sample, there is nothing to rank)
+        top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
         self.ar.prefill(cond, text_tokens)
@@ -210,7 +180,7 @@ class TextToSpeech:
                    num_autoregressive_samples=512, temperature=.8, length_penalty=1, repetition_penalty=2.0, top_p=.8, max_mel_tokens=500,
                    cvvp_amount=.0, diffusion_iterations=100, cond_free=True, cond_free_k=2, diffusion_temperature=1.0,
                    **hf_generate_kwargs):
-        top_k, typical_mass = self._check_kwargs(k, cvvp_amount, hf_generate_kwargs)
+        top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
         self.ar.prefill(cond, text_tokens)
