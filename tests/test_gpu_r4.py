@@ -84,6 +84,12 @@ def test_diffusion_step_graph_is_kept_between_calls():
     assert st.stat(0) == 2 and mel_s.shape[-1] == S2 and torch.isfinite(mel_s).all()
     st.condition(latents, cond, S)
     assert torch.equal(st.sample(sched, x, noises[0]), mels[0]) and st.stat(0) == 3
+    # a rejected option value is checked before anything is dropped: the kept graph survives it
+    with pytest.raises(E.EngineError):
+        st.set_option(E.TT_DIFF_OPT_FUSED_GN, 7)
+    st.condition(latents, cond, S)
+    assert torch.equal(st.sample(sched, x, noises[0]), mels[0])
+    assert st.stat(0) == 3, f"{st.stat(0)} captures: a rejected set_option dropped the kept graph"
     assert st.guard() == 0
     st.close()
 

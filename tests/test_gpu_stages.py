@@ -487,6 +487,10 @@ def test_ar_generate_chunks_equal_one_shot_loop():
     for codes, done in st.generate_stream(6, 36, 5, first_chunk=7, seed=5):
         last, pieces = codes, pieces + 1
         assert torch.equal(codes, full[:, :codes.shape[1]])
+        if pieces == 1:
+            # the first chunk consumed the prefill logits: a one-shot generation is rejected before it touches the running stream
+            with pytest.raises(E.EngineError):
+                st.generate(6, 36, seed=5)
     assert pieces >= 2 and last.shape[1] == n and torch.equal(last, full)
     # the streaming caller runs the teacher-forced latent pass BETWEEN chunks (api_fast.tts_stream): that pass uses the handle's
     # residual-stream buffer, so a resumed chunk must rebuild its input row from the device-side state, not find it there

@@ -77,12 +77,10 @@ __global__ void even_rows_index_kernel(int* idx, int n) {
 
 }  // namespace
 
-struct tt_cond {
+struct tt_cond : EngineHandle {
   tt_cond_config cfg;
   tt_cond_weights w;
   std::vector<tt_attn_block> ar_attn, diff_attn;
-  Arena arena;
-  StreamBridge sb;
   int rows = 0, cmax = 0;
   float* mel_t = nullptr;   // [T][mel] token-major f32
   void* mel_op = nullptr;   // [T][mel_pad] T
@@ -152,7 +150,7 @@ int tt_cond_create(const tt_cond_config* cfg, const tt_cond_weights* w, tt_cond*
   e->rows = cfg->max_frames + 64;
   e->cmax = std::max(cfg->ar_dim, 2 * cfg->diff_channels);
   const size_t rows = e->rows, cm = e->cmax, melp = std::max(cfg->ar_mel_pad, cfg->diff_mel_pad);
-  int rc = e->sb.init();
+  int rc = e->open("tt_cond_create", false);
   if (!rc) rc = e->arena.alloc_t(&e->mel_t, rows * melp);
   if (!rc) rc = e->arena.alloc(&e->mel_op, rows * melp * 2);
   if (!rc) rc = e->arena.alloc_t(&e->ha, rows * cm);
@@ -183,62 +181,60 @@ int tt_cond_create(const tt_cond_config* cfg, const tt_cond_weights* w, tt_cond*
 
 void tt_cond_destroy(tt_cond* e) {
   if (!e) return;
-  (void)hipDeviceSynchronize();
-  e->arena.release();
-  e->sb.destroy();
+  e->close();
   delete e;
 }
 
 int tt_cond_ar_clip(tt_cond* e, const float* mel, int T, float* out, void* stream) {
   TT_REQUIRE(e && mel && out, "tt_cond_ar_clip: null argument");
   TT_REQUIRE(T >= 1 && T <= e->cfg.max_frames, "tt_cond_ar_clip: %d frames exceed capacity %d", T, e->cfg.max_frames);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int D = e->cfg.ar_dim, MC = e->cfg.ar_mel, MP = e->cfg.ar_mel_pad, dt = e->cfg.dtype;
-  TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));                       // [mel][T] -> [T][mel]
-  TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-  GemmArgs g = gemm_args(e->mel_op, MP, e->w.ar_w_init, MP, T, D, MP);     // conditioning_encoder.init (1x1)
-  g.bias = e->w.ar_b_init; g.out_f32 = e->ha; g.ldo32 = D;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  float* cur = e->ha;
-  float* oth = e->hb;
-  for (int i = 0; i < e->cfg.ar_blocks; ++i) {
-    TT_TRY(cond_attn_block(e, e->ar_attn[i], cur, T, D, e->cfg.ar_heads, oth, s));
-    float* t = cur; cur = oth; oth = t;
-  }
-  TT_CHECK_HIP(hipMemcpyAsync(out, cur, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, s));  // h[:, :, 0]
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int D = e->cfg.ar_dim, MC = e->cfg.ar_mel, MP = e->cfg.ar_mel_pad, dt = e->cfg.dtype;
+    TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));                       // [mel][T] -> [T][mel]
+    TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
+    GemmArgs g = gemm_args(e->mel_op, MP, e->w.ar_w_init, MP, T, D, MP);     // conditioning_encoder.init (1x1)
+    g.bias = e->w.ar_b_init; g.out_f32 = e->ha; g.ldo32 = D;
+    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    float* cur = e->ha;
+    float* oth = e->hb;
+    for (int i = 0; i < e->cfg.ar_blocks; ++i) {
+      TT_TRY(cond_attn_block(e, e->ar_attn[i], cur, T, D, e->cfg.ar_heads, oth, s));
+      float* t = cur; cur = oth; oth = t;
+    }
+    TT_CHECK_HIP(hipMemcpyAsync(out, cur, (size_t)D * sizeof(float), hipMemcpyDeviceToDevice, s));  // h[:, :, 0]
+    return 0;
+  });
 }
 
 int tt_cond_diff_clip(tt_cond* e, const float* mel, int T, float* out_sum, int* frames, void* stream) {
   TT_REQUIRE(e && mel && out_sum && frames, "tt_cond_diff_clip: null argument");
   TT_REQUIRE(e->cfg.diff_blocks > 0 && e->w.diff_w_c0 && e->w.diff_w_c1, "tt_cond_diff_clip: this handle was created without the diffusion embedder");
   TT_REQUIRE(T >= 4 && T <= e->cfg.max_frames, "tt_cond_diff_clip: %d frames outside [4, %d]", T, e->cfg.max_frames);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int C = e->cfg.diff_channels, C2 = 2 * C, MC = e->cfg.diff_mel, MP = e->cfg.diff_mel_pad, dt = e->cfg.dtype;
-  const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(k = 3, stride = 2, padding = 1): ceil(n / 2) outputs
-  TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));
-  TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-  // stride-2 convolution = stride-1 tap GEMM at every position, then the even rows
-  GemmArgs g = gemm_args(e->mel_op, MP, e->w.diff_w_c0, 3 * MP, T, C, 3 * MP);
-  g.taps = 3; g.seq_len = T; g.bias = e->w.diff_b_c0; g.out_t = e->act; g.ldot = C;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  TT_TRY(gather_rows_launch((const float*)e->act, e->even_idx, (float*)e->act2, T2, C / 2, s));  // T rows of C elements == C / 2 words
-  g = gemm_args(e->act2, C, e->w.diff_w_c1, 3 * C, T2, C2, 3 * C);
-  g.taps = 3; g.seq_len = T2; g.bias = e->w.diff_b_c1; g.out_f32 = e->ha; g.ldo32 = C2;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->hb, T3, C2, s));
-  float* cur = e->hb;
-  float* oth = e->ha;
-  for (int i = 0; i < e->cfg.diff_blocks; ++i) {
-    TT_TRY(cond_attn_block(e, e->diff_attn[i], cur, T3, C2, e->cfg.diff_heads, oth, s));
-    float* t = cur; cur = oth; oth = t;
-  }
-  colsum_kernel<<<cdiv(C2, 256), 256, 0, s>>>(cur, out_sum, T3, C2);
-  TT_CHECK_HIP(hipGetLastError());
-  *frames = T3;
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int C = e->cfg.diff_channels, C2 = 2 * C, MC = e->cfg.diff_mel, MP = e->cfg.diff_mel_pad, dt = e->cfg.dtype;
+    const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(k = 3, stride = 2, padding = 1): ceil(n / 2) outputs
+    TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));
+    TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
+    // stride-2 convolution = stride-1 tap GEMM at every position, then the even rows
+    GemmArgs g = gemm_args(e->mel_op, MP, e->w.diff_w_c0, 3 * MP, T, C, 3 * MP);
+    g.taps = 3; g.seq_len = T; g.bias = e->w.diff_b_c0; g.out_t = e->act; g.ldot = C;
+    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gather_rows_launch((const float*)e->act, e->even_idx, (float*)e->act2, T2, C / 2, s));  // T rows of C elements == C / 2 words
+    g = gemm_args(e->act2, C, e->w.diff_w_c1, 3 * C, T2, C2, 3 * C);
+    g.taps = 3; g.seq_len = T2; g.bias = e->w.diff_b_c1; g.out_f32 = e->ha; g.ldo32 = C2;
+    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->hb, T3, C2, s));
+    float* cur = e->hb;
+    float* oth = e->ha;
+    for (int i = 0; i < e->cfg.diff_blocks; ++i) {
+      TT_TRY(cond_attn_block(e, e->diff_attn[i], cur, T3, C2, e->cfg.diff_heads, oth, s));
+      float* t = cur; cur = oth; oth = t;
+    }
+    colsum_kernel<<<cdiv(C2, 256), 256, 0, s>>>(cur, out_sum, T3, C2);
+    TT_CHECK_HIP(hipGetLastError());
+    *frames = T3;
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -24,12 +24,10 @@ struct CvvpTower {
   std::vector<tt_clvp_layer> L;
 };
 
-struct tt_cvvp {
+struct tt_cvvp : EngineHandle {  // guard: bumped by the row norms / GroupNorm statistics, snapshot at the end of every tt_cvvp_score
   tt_cvvp_config cfg;
   tt_cvvp_weights w;
   CvvpTower cond, speech;
-  Arena arena;
-  StreamBridge sb;
   size_t rows = 0;
   float* x = nullptr; void* h = nullptr; void* gg = nullptr; void* attn = nullptr;
   void* q = nullptr; void* k = nullptr; void* vt = nullptr;
@@ -43,21 +41,19 @@ struct tt_cvvp {
   float* mel_t = nullptr; void* mel_op = nullptr; void* c0 = nullptr; void* c0e = nullptr;  // conditioning front: [T][mel], [T][mel_pad], [T][dim/2], [T/2][dim/2]
   int* even_idx = nullptr;
   int max_seqs = 0;
-  int* guard = nullptr;
-  int* guard_host = nullptr;
 };
 
 // e->x holds the embedded rows [B * n][dim]; leaves the tower's latent rows in latent_out [B][dim]
 static int cvvp_tower_run(tt_cvvp* e, const CvvpTower& t, int B, int n, float* latent_out, hipStream_t s) {
   const int D = e->cfg.dim, H = e->cfg.heads, dt = e->cfg.dtype;
   const int M = B * n, n_pad = round_up(n, 32);
-  XencBufs xb{e->x, e->h, e->gg, e->attn, e->q, e->k, e->vt, e->guard};
+  XencBufs xb{e->x, e->h, e->gg, e->attn, e->q, e->k, e->vt, e->guard.dev};
   TT_TRY(xenc_layers_run(dt, xb, t.L.data(), e->cfg.depth, t.w.inv_freq, D, H, D, e->cfg.rot_dim, B, n, s));
   RowNormArgs a;
   memset(&a, 0, sizeof(a));
   a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER; a.g1 = t.w.norm_g; a.b1 = t.w.norm_b; a.eps1 = 1e-5f;
   a.out_t = e->h; a.ldot = D;
-  a.guard = e->guard;
+  a.guard = e->guard.dev;
   TT_TRY(rownorm_launch(dt, a, s));
   // pre_combiner.0
   GemmArgs g = gemm_args(e->h, D, t.w.w_pre0, D, M, D, D);
@@ -67,7 +63,7 @@ static int cvvp_tower_run(tt_cvvp* e, const CvvpTower& t, int B, int n, float* l
   GroupNormArgs gn;
   memset(&gn, 0, sizeof(gn));
   gn.x = e->ha; gn.B = B; gn.S = n; gn.C = D; gn.gamma = t.w.attn.norm_g; gn.beta = t.w.attn.norm_b; gn.eps = 1e-5f; gn.act = ACT_NONE;
-  gn.out_t = e->act; gn.ldot = D; gn.partial = e->gn_partial; gn.guard = e->guard;
+  gn.out_t = e->act; gn.ldot = D; gn.partial = e->gn_partial; gn.guard = e->guard.dev;
   TT_TRY(groupnorm_launch(dt, gn, s));
   g = gemm_args(e->act, D, t.w.attn.w_qkv, D, M, 3 * D, D);
   g.bias = t.w.attn.b_qkv; g.seq_len = n; g.dmodel = D; g.heads = H; g.q = e->q; g.k = e->k; g.vt = e->vt; g.seq_pad = n_pad;
@@ -110,7 +106,7 @@ int tt_cvvp_create(const tt_cvvp_config* cfg, const tt_cvvp_weights* w, tt_cvvp*
   const size_t rows = (size_t)std::max(cfg->max_rows, cfg->max_cond_frames) + 64;
   e->rows = rows;
   e->max_seqs = cfg->max_rows / 8 + 8;  // a candidate has >= 8 codes
-  int rc = e->sb.init();
+  int rc = e->open("tt_cvvp_create", true);
   if (!rc) rc = e->arena.alloc_t(&e->x, rows * D);
   if (!rc) rc = e->arena.alloc(&e->h, rows * D * es);
   if (!rc) rc = e->arena.alloc(&e->gg, rows * D * es);
@@ -133,10 +129,7 @@ int tt_cvvp_create(const tt_cvvp_config* cfg, const tt_cvvp_weights* w, tt_cvvp*
   if (!rc) rc = e->arena.alloc(&e->c0, cf * (D / 2) * es);
   if (!rc) rc = e->arena.alloc(&e->c0e, cf * (D / 2) * es);
   if (!rc) rc = e->arena.alloc_t(&e->even_idx, cf);
-  if (!rc) rc = e->arena.alloc_t(&e->guard, 4);
-  if (!rc && hipHostMalloc((void**)&e->guard_host, 4 * sizeof(int)) != hipSuccess) { set_error("tt_cvvp_create: hipHostMalloc failed"); rc = -2; }
   if (!rc) {
-    e->guard_host[0] = 0;
     cvvp_even_rows_kernel<<<cdiv((int)cf, 256), 256>>>(e->even_idx, (int)cf);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_error("tt_cvvp_create: index fill failed"); rc = -2; }
   }
@@ -150,10 +143,7 @@ int tt_cvvp_create(const tt_cvvp_config* cfg, const tt_cvvp_weights* w, tt_cvvp*
 
 void tt_cvvp_destroy(tt_cvvp* e) {
   if (!e) return;
-  (void)hipDeviceSynchronize();
-  if (e->guard_host) (void)hipHostFree(e->guard_host);
-  e->arena.release();
-  e->sb.destroy();
+  e->close();
   delete e;
 }
 
@@ -161,42 +151,36 @@ int tt_cvvp_score(tt_cvvp* e, const float* mels, int n_clips, int T, const int* 
   TT_REQUIRE(e && mels && codes && scores, "tt_cvvp_score: null argument");
   TT_REQUIRE(n_clips >= 1 && n_clips <= 16 && T >= 29 && T <= e->cfg.max_cond_frames, "tt_cvvp_score: %d clips of %d frames (1 .. 16 clips, 29 .. %d frames)", n_clips, T, e->cfg.max_cond_frames);
   TT_REQUIRE(B >= 1 && n >= 8 && (size_t)B * n <= (size_t)e->cfg.max_rows && B <= e->max_seqs, "tt_cvvp_score: B=%d n=%d exceed capacity %d rows (n must be >= 8)", B, n, e->cfg.max_rows);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int D = e->cfg.dim, D2 = D / 2, MC = e->cfg.mel_channels, MP = e->cfg.mel_pad, dt = e->cfg.dtype;
-  const int es = dtype_bytes(dt);
-  const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(stride 2) with "same" padding: ceil(n / 2) outputs, output j = the stride-1 result at 2 j
-  for (int c = 0; c < n_clips; ++c) {
-    TT_TRY(transpose_launch(mels + (size_t)c * MC * T, e->mel_t, MC, T, s));          // [mel][T] -> [T][mel]
-    TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-    GemmArgs g = gemm_args(e->mel_op, MP, e->w.w_cond0, 5 * MP, T, D2, 5 * MP);
-    g.taps = 5; g.seq_len = T; g.bias = e->w.b_cond0; g.out_t = e->c0; g.ldot = D2;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(gather_rows_launch((const float*)e->c0, e->even_idx, (float*)e->c0e, T2, D2 * es / 4, s));  // rows of D2 elements as 4-byte words
-    g = gemm_args(e->c0e, D2, e->w.w_cond1, 3 * D2, T2, D, 3 * D2);
-    g.taps = 3; g.seq_len = T2; g.bias = e->w.b_cond1; g.out_f32 = e->ha; g.ldo32 = D;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->x, T3, D, s));
-    TT_TRY(cvvp_tower_run(e, e->cond, 1, T3, e->cond_latent + (size_t)c * D, s));
-  }
-  TT_TRY(gather_rows_launch(e->w.speech_emb, codes, e->x, B * n, D, s));
-  TT_TRY(cvvp_tower_run(e, e->speech, B, n, e->speech_latent, s));
-  for (int c = 0; c < n_clips; ++c)
-    TT_TRY(clvp_score_launch(e->cond_latent + (size_t)c * D, 1, e->speech_latent, e->w.temperature, e->clip_scores + (size_t)c * B, B, D, s));
-  TT_TRY(mean_rows_launch(e->clip_scores, scores, 1, n_clips, B, s));                   // mean over the clips (api.py:468)
-  TT_CHECK_HIP(hipMemcpyAsync(e->guard_host, e->guard, sizeof(int), hipMemcpyDeviceToHost, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int D = e->cfg.dim, D2 = D / 2, MC = e->cfg.mel_channels, MP = e->cfg.mel_pad, dt = e->cfg.dtype;
+    const int es = dtype_bytes(dt);
+    const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(stride 2) with "same" padding: ceil(n / 2) outputs, output j = the stride-1 result at 2 j
+    for (int c = 0; c < n_clips; ++c) {
+      TT_TRY(transpose_launch(mels + (size_t)c * MC * T, e->mel_t, MC, T, s));          // [mel][T] -> [T][mel]
+      TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
+      GemmArgs g = gemm_args(e->mel_op, MP, e->w.w_cond0, 5 * MP, T, D2, 5 * MP);
+      g.taps = 5; g.seq_len = T; g.bias = e->w.b_cond0; g.out_t = e->c0; g.ldot = D2;
+      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+      TT_TRY(gather_rows_launch((const float*)e->c0, e->even_idx, (float*)e->c0e, T2, D2 * es / 4, s));  // rows of D2 elements as 4-byte words
+      g = gemm_args(e->c0e, D2, e->w.w_cond1, 3 * D2, T2, D, 3 * D2);
+      g.taps = 3; g.seq_len = T2; g.bias = e->w.b_cond1; g.out_f32 = e->ha; g.ldo32 = D;
+      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+      TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->x, T3, D, s));
+      TT_TRY(cvvp_tower_run(e, e->cond, 1, T3, e->cond_latent + (size_t)c * D, s));
+    }
+    TT_TRY(gather_rows_launch(e->w.speech_emb, codes, e->x, B * n, D, s));
+    TT_TRY(cvvp_tower_run(e, e->speech, B, n, e->speech_latent, s));
+    for (int c = 0; c < n_clips; ++c)
+      TT_TRY(clvp_score_launch(e->cond_latent + (size_t)c * D, 1, e->speech_latent, e->w.temperature, e->clip_scores + (size_t)c * B, B, D, s));
+    TT_TRY(mean_rows_launch(e->clip_scores, scores, 1, n_clips, B, s));                   // mean over the clips (api.py:468)
+    return e->guard.snapshot(s);
+  });
 }
 
 int tt_cvvp_guard(tt_cvvp* e, int reset) {
   if (!e) { set_error("tt_cvvp_guard: null handle"); return -1; }
-  const int n = e->guard_host[0];
-  if (n > 0) set_error("CVVP stage: %d kernel(s) met non-finite values (operand overflow in %s)", n, e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
-  if (reset && n > 0) {
-    if (hipMemsetAsync(e->guard, 0, 4 * sizeof(int), e->sb.own) != hipSuccess || hipStreamSynchronize(e->sb.own) != hipSuccess) { set_error("tt_cvvp_guard: reset failed"); return -2; }
-    e->guard_host[0] = 0;
-  }
-  return n;
+  return e->guard.read(reset, e->sb.own, "tt_cvvp_guard", "CVVP stage: %d kernel(s) met non-finite values (operand overflow in %s)",
+                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
 }
 
 }  // extern "C"

@@ -40,15 +40,13 @@ struct DiffWork {
   int rows = 0;
 };
 
-struct tt_diff {
+struct tt_diff : EngineHandle {
   tt_diff_config cfg;
   tt_diff_weights w;
   std::vector<tt_attn_block> latent_attn, attn;
   std::vector<tt_res_block> res;
   int C, H, NR;  // NR = number of ResBlocks (3 + L + 3)
   int es = 2;    // bytes per operand element (4: the fp32 verification mode)
-  Arena arena;
-  StreamBridge sb;
   int S = 0;        // rows per sample of the current pass (a padded batch: the common padded length)
   int UB = 1;       // utterance capacity of a batched sampling run (cfg.max_batch)
   int U = 1;        // utterances of the current batch (tt_diff_batch_begin); sample index = guidance row * U + utterance
@@ -83,22 +81,16 @@ struct tt_diff {
   float* x = nullptr;          // [S][in]
   void* x_t = nullptr;         // [2][S][in_pad] T
   float* out = nullptr;        // [2][S][out]
-  // operand-overflow guard: device counter bumped by the GroupNorm / sampler kernels when they meet a non-finite value; every
-  // sampling run ends with a copy into the pinned word tt_diff_guard reads
-  int* guard = nullptr;
-  int* guard_host = nullptr;
+  // guard (EngineHandle): bumped by the GroupNorm / sampler kernels when they meet a non-finite value; every sampling run ends with
+  // a snapshot tt_diff_guard reads
   // The captured sampler step stays on the handle between calls: the caller's noise / output pointers reach the sampler kernel
   // through a device-side table (io_dev, refreshed per call), so the key is the geometry alone (utterances, lengths, guidance rows,
   // steps).  Replaces the per-call capture + instantiate of round 3 (and the destroy-right-after-the-last-launch that went with it).
   const void** io_dev = nullptr;    // [16][2]: {step_noise, mel_out} per utterance
   const void** io_host = nullptr;   // pinned staging
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  std::vector<int> step_key;
-  int captures = 0;  // sampler-step captures so far (tt_diff_stat)
+  KeptGraph step;                   // the sampler step; step.captures feeds tt_diff_stat(0)
   // split sampling: this handle evaluates one denoiser row per step
-  hipGraph_t split_graph = nullptr;
-  hipGraphExec_t split_exec = nullptr;
+  KeptGraph split;
   int split_row = -1, split_steps = 0, split_done = 0;
 };
 
@@ -112,7 +104,7 @@ static int run_gn(tt_diff* e, DiffWork& w_, const float* x, int B, int S, const 
   // per-step scale / shift rows are staged at a fixed address (e->ss_cur): no step-dependent addressing in the kernel
   a.out_t = out_t; a.ldot = ldot; a.out_f32 = out_f32; a.ldo32 = e->C;
   a.partial = w_.gn_partial;
-  a.guard = e->guard;
+  a.guard = e->guard.dev;
   if (e->masked) {
     a.vperiod = e->U;
     for (int u = 0; u < e->U; ++u) a.vlen[u] = e->Su[u];
@@ -183,7 +175,7 @@ static int run_res_block(tt_diff* e, DiffWork& w_, const tt_res_block& w, const 
     GemmGnArgs n;
     memset(&n, 0, sizeof(n));
     n.gamma = w.gn1_g; n.beta = w.gn1_b; n.gemm_part = w_.stats_part; n.part_rows = w_.stats_rows; n.S = S; n.eps = 1e-5f; n.act = ACT_SILU;
-    n.guard = e->guard;
+    n.guard = e->guard.dev;
     GemmArgs gf = g;
     gf.A = in; gf.lda = C;
     float* part = w_.stats_part == w_.gn_gemm_part ? w_.gn_gemm_part2 : w_.gn_gemm_part;
@@ -306,19 +298,8 @@ static int diff_prepare_timesteps(tt_diff* e, int n, hipStream_t s) {
   return 0;
 }
 
-static void diff_drop_step_graph(tt_diff* e) {
-  if (e->step_exec) (void)hipGraphExecDestroy(e->step_exec);
-  if (e->step_graph) (void)hipGraphDestroy(e->step_graph);
-  e->step_exec = nullptr;
-  e->step_graph = nullptr;
-  e->step_key.clear();
-}
-
 static void split_release(tt_diff* e) {
-  if (e->split_exec) (void)hipGraphExecDestroy(e->split_exec);
-  if (e->split_graph) (void)hipGraphDestroy(e->split_graph);
-  e->split_exec = nullptr;
-  e->split_graph = nullptr;
+  e->split.drop();
   e->split_row = -1;
   e->split_steps = e->split_done = 0;
 }
@@ -346,7 +327,7 @@ int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff*
   e->chunk_rows = std::max(2 * e->UB * cfg->max_seq, std::min(32768, cfg->max_steps * 2 * cfg->max_seq));
   e->rows_max = std::max(e->chunk_rows, cfg->max_codes);
   const size_t rows = (size_t)e->rows_max + 64;
-  int rc = e->sb.init();
+  int rc = e->open("tt_diff_create", true);
   if (!rc && (hipStreamCreateWithFlags(&e->pre_stream, hipStreamNonBlocking) != hipSuccess ||
               hipEventCreateWithFlags(&e->ev_pre_start, hipEventDisableTiming) != hipSuccess)) { set_error("tt_diff_create: stream / event creation failed"); rc = -2; }
   const size_t B2 = (size_t)2 * e->UB;  // samples of one denoiser pass: (conditioned, conditioning-free) x utterances
@@ -385,13 +366,8 @@ int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff*
   if (!rc) rc = e->arena.alloc_t(&e->x, (size_t)e->UB * cfg->max_seq * cfg->in_channels);
   if (!rc) rc = e->arena.alloc(&e->x_t, (B2 * cfg->max_seq + 8) * cfg->in_pad * es);
   if (!rc) rc = e->arena.alloc_t(&e->out, B2 * cfg->max_seq * cfg->out_channels);
-  if (!rc) rc = e->arena.alloc_t(&e->guard, 4);
   if (!rc) rc = e->arena.alloc_t(&e->io_dev, 32);
-  if (!rc && (hipHostMalloc((void**)&e->guard_host, 4 * sizeof(int)) != hipSuccess || hipHostMalloc((void**)&e->io_host, 32 * sizeof(void*)) != hipSuccess)) {
-    set_error("tt_diff_create: hipHostMalloc failed");
-    rc = -2;
-  }
-  if (!rc) e->guard_host[0] = 0;
+  if (!rc && hipHostMalloc((void**)&e->io_host, 32 * sizeof(void*)) != hipSuccess) { set_error("tt_diff_create: hipHostMalloc failed"); rc = -2; }
   if (rc) {
     tt_diff_destroy(e);
     return rc;
@@ -402,17 +378,14 @@ int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff*
 
 void tt_diff_destroy(tt_diff* e) {
   if (!e) return;
-  (void)hipDeviceSynchronize();
-  split_release(e);
-  diff_drop_step_graph(e);
-  if (e->guard_host) (void)hipHostFree(e->guard_host);
+  e->close();
+  e->split.drop();
+  e->step.drop();
   if (e->io_host) (void)hipHostFree((void*)e->io_host);
   for (hipEvent_t ev : e->ev_chunk)
     if (ev) (void)hipEventDestroy(ev);
   if (e->ev_pre_start) (void)hipEventDestroy(e->ev_pre_start);
   if (e->pre_stream) (void)hipStreamDestroy(e->pre_stream);
-  e->arena.release();
-  e->sb.destroy();
   delete e;
 }
 
@@ -447,68 +420,66 @@ static int diff_condition_into(tt_diff* e, const float* latents, int M, const fl
 int tt_diff_condition(tt_diff* e, const float* latents, int M, const float* cond, const int* interp_idx, int S, void* stream) {
   TT_REQUIRE(e && latents && cond && interp_idx, "tt_diff_condition: null argument");
   TT_REQUIRE(M >= 1 && M <= e->cfg.max_codes && S >= 1 && S <= e->cfg.max_seq, "tt_diff_condition: M=%d S=%d exceed capacity (%d, %d)", M, S, e->cfg.max_codes, e->cfg.max_seq);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  e->S = S;
-  e->U = 1; e->Su[0] = S; e->masked = false; e->conditioned = 1;
-  TT_TRY(diff_condition_into(e, latents, M, cond, interp_idx, S, e->code_emb, e->code_emb + (size_t)S * e->C, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    e->S = S;
+    e->U = 1; e->Su[0] = S; e->masked = false; e->conditioned = 1;
+    return diff_condition_into(e, latents, M, cond, interp_idx, S, e->code_emb, e->code_emb + (size_t)S * e->C, s);
+  });
 }
 
 int tt_diff_batch_begin(tt_diff* e, int U, int S_pad, void* stream) {
   TT_REQUIRE(e != nullptr, "tt_diff_batch_begin: null handle");
   TT_REQUIRE(U >= 1 && U <= e->UB, "tt_diff_batch_begin: %d utterances exceed this handle's capacity (%d; tt_diff_config.max_batch)", U, e->UB);
   TT_REQUIRE(S_pad >= 1 && S_pad <= e->cfg.max_seq, "tt_diff_batch_begin: padded length %d exceeds capacity %d", S_pad, e->cfg.max_seq);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  e->U = U; e->S = S_pad; e->conditioned = 0; e->masked = false;
-  for (int u = 0; u < 16; ++u) e->Su[u] = 0;
-  // rows past an utterance's own length stay zero for the whole run: they are the zero padding its convolutions read
-  TT_CHECK_HIP(hipMemsetAsync(e->code_emb, 0, (size_t)2 * U * S_pad * e->C * sizeof(float), s));
-  TT_CHECK_HIP(hipMemsetAsync(e->x_t, 0, (size_t)2 * U * S_pad * e->cfg.in_pad * e->es, s));
-  TT_CHECK_HIP(hipMemsetAsync(e->x, 0, (size_t)U * S_pad * e->cfg.in_channels * sizeof(float), s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    e->U = U; e->S = S_pad; e->conditioned = 0; e->masked = false;
+    for (int u = 0; u < 16; ++u) e->Su[u] = 0;
+    // rows past an utterance's own length stay zero for the whole run: they are the zero padding its convolutions read
+    TT_CHECK_HIP(hipMemsetAsync(e->code_emb, 0, (size_t)2 * U * S_pad * e->C * sizeof(float), s));
+    TT_CHECK_HIP(hipMemsetAsync(e->x_t, 0, (size_t)2 * U * S_pad * e->cfg.in_pad * e->es, s));
+    TT_CHECK_HIP(hipMemsetAsync(e->x, 0, (size_t)U * S_pad * e->cfg.in_channels * sizeof(float), s));
+    return 0;
+  });
 }
 
 int tt_diff_condition_slot(tt_diff* e, int u, const float* latents, int M, const float* cond, const int* interp_idx, int S, void* stream) {
   TT_REQUIRE(e && latents && cond && interp_idx, "tt_diff_condition_slot: null argument");
   TT_REQUIRE(u >= 0 && u < e->U, "tt_diff_condition_slot: utterance %d outside the batch of %d (tt_diff_batch_begin)", u, e->U);
   TT_REQUIRE(M >= 1 && M <= e->cfg.max_codes && S >= 1 && S <= e->S, "tt_diff_condition_slot: M=%d S=%d exceed capacity (%d codes, padded length %d)", M, S, e->cfg.max_codes, e->S);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const size_t slot = (size_t)e->S * e->C;
-  e->Su[u] = S;
-  e->conditioned |= 1u << u;
-  TT_TRY(diff_condition_into(e, latents, M, cond, interp_idx, S, e->code_emb + (size_t)u * slot, e->code_emb + (size_t)(e->U + u) * slot, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const size_t slot = (size_t)e->S * e->C;
+    e->Su[u] = S;
+    e->conditioned |= 1u << u;
+    return diff_condition_into(e, latents, M, cond, interp_idx, S, e->code_emb + (size_t)u * slot, e->code_emb + (size_t)(e->U + u) * slot, s);
+  });
 }
 
 int tt_diff_get_code_emb(tt_diff* e, float* dst, void* stream) {
   TT_REQUIRE(e && dst && e->S > 0, "tt_diff_get_code_emb: no conditioning");
   TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_get_code_emb: the handle holds a batch of %d utterances (tt_diff_batch_begin); call tt_diff_condition first", e->U);
-  hipStream_t us = (hipStream_t)stream;
-  TT_TRY(e->sb.enter(us));
-  TT_CHECK_HIP(hipMemcpyAsync(dst, e->code_emb, (size_t)e->S * e->C * sizeof(float), hipMemcpyDeviceToDevice, e->sb.own));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    TT_CHECK_HIP(hipMemcpyAsync(dst, e->code_emb, (size_t)e->S * e->C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  });
 }
 
 int tt_diff_forward(tt_diff* e, const float* x, int timestep, int cond_free, float* out, void* stream) {
   TT_REQUIRE(e && x && out && e->S > 0, "tt_diff_forward: call tt_diff_condition first");
   TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_forward: the handle holds a batch of %d utterances (tt_diff_batch_begin); call tt_diff_condition first", e->U);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int S = e->S, IC = e->cfg.in_channels, IP = e->cfg.in_pad;
-  TT_CHECK_HIP(hipMemcpyAsync(e->ts_dev, &timestep, sizeof(int), hipMemcpyHostToDevice, s));
-  TT_CHECK_HIP(hipStreamSynchronize(s));  // `timestep` lives on the caller's stack
-  TT_CHECK_HIP(hipMemsetAsync(e->slot, 0, sizeof(int), s));
-  TT_TRY(diff_prepare_timesteps(e, 1, s));
-  TT_TRY(cast_pad_launch(e->cfg.dtype, x, IC, e->x_t, IP, S, IC, IP, s));
-  TT_TRY(cast_pad_launch(e->cfg.dtype, x, IC, offset_t(e->x_t, (size_t)S * IP, e->es), IP, S, IC, IP, s));
-  const int B = cond_free ? 2 : 1;
-  TT_TRY(diff_integrator_all(e, 1, B, 0, s));
-  TT_TRY(diff_forward(e, B, s));
-  TT_CHECK_HIP(hipMemcpyAsync(out, e->out, (size_t)B * S * e->cfg.out_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int S = e->S, IC = e->cfg.in_channels, IP = e->cfg.in_pad;
+    TT_CHECK_HIP(hipMemcpyAsync(e->ts_dev, &timestep, sizeof(int), hipMemcpyHostToDevice, s));
+    TT_CHECK_HIP(hipStreamSynchronize(s));  // `timestep` lives on the caller's stack
+    TT_CHECK_HIP(hipMemsetAsync(e->slot, 0, sizeof(int), s));
+    TT_TRY(diff_prepare_timesteps(e, 1, s));
+    TT_TRY(cast_pad_launch(e->cfg.dtype, x, IC, e->x_t, IP, S, IC, IP, s));
+    TT_TRY(cast_pad_launch(e->cfg.dtype, x, IC, offset_t(e->x_t, (size_t)S * IP, e->es), IP, S, IC, IP, s));
+    const int B = cond_free ? 2 : 1;
+    TT_TRY(diff_integrator_all(e, 1, B, 0, s));
+    TT_TRY(diff_forward(e, B, s));
+    TT_CHECK_HIP(hipMemcpyAsync(out, e->out, (size_t)B * S * e->cfg.out_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  });
 }
 
 // p_sample_loop for the U utterances of the current batch (U = 1: the plain single-utterance run).  All of them walk the same
@@ -580,7 +551,7 @@ static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* con
     p.out = e->out + (size_t)u * S * e->cfg.out_channels;
     p.has_uncond = cond_free ? 1 : 0; p.S = e->Su[u]; p.C = IC;
     p.io = e->io_dev + 2 * u;  // {step_noise[u], mel_out[u]}: data of this call, not of the captured step
-    p.guard = e->guard;
+    p.guard = e->guard.dev;
     p.ld_rows = U * S;
     p.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
     p.mel_shift = -11.512925148010254f;
@@ -594,40 +565,14 @@ static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* con
     // everything the captured step bakes in that a later call could change
     std::vector<int> key = {U, S, R, n_steps, dt, g_prof_on ? 1 : 0};
     for (int u = 0; u < 16; ++u) key.push_back(u < U ? e->Su[u] : 0);
-    if (!e->step_exec || key != e->step_key) {
-      diff_drop_step_graph(e);
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      hipError_t ce = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-      if (ce != hipSuccess) { set_error("tt_diff_sample: capture failed: %s", hipGetErrorString(ce)); rc = -2; }
-      if (!rc) {
-        rc = one_step();
-        ce = hipStreamEndCapture(s, &graph);
-        if (!rc && ce != hipSuccess) { set_error("tt_diff_sample: capture failed: %s", hipGetErrorString(ce)); rc = -2; }
-      }
-      if (!rc) {
-        ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ce != hipSuccess) { set_error("tt_diff_sample: instantiate failed: %s", hipGetErrorString(ce)); rc = -2; }
-      }
-      if (rc) {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-      } else {
-        e->step_graph = graph;
-        e->step_exec = exec;
-        e->step_key.swap(key);
-        e->captures += 1;
-      }
-    }
+    rc = e->step.ensure(s, key.data(), key.size() * sizeof(int), "tt_diff_sample", one_step);
     for (int i = 0; i < n_steps && !rc; ++i) {
       rc = chunk_gate(i);
-      if (rc) break;
-      hipError_t ce = hipGraphLaunch(e->step_exec, s);
-      if (ce != hipSuccess) { set_error("tt_diff_sample: hipGraphLaunch: %s", hipGetErrorString(ce)); rc = -2; }
+      if (!rc) rc = e->step.launch(s, "tt_diff_sample");
     }
     if (rc) {
       (void)hipStreamSynchronize(s);
-      diff_drop_step_graph(e);
+      e->step.drop();
     }
   } else {
     for (int i = 0; i < n_steps && !rc; ++i) {
@@ -636,7 +581,7 @@ static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* con
     }
   }
   if (rc && overlap) (void)hipStreamSynchronize(ps);  // nothing of this run may still be in flight when the caller sees the error
-  if (!rc && hipMemcpyAsync(e->guard_host, e->guard, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) { set_error("tt_diff_sample: reading the guard failed"); rc = -2; }
+  if (!rc) rc = e->guard.snapshot(s);
   e->masked = false;
   return rc;
 }
@@ -646,10 +591,9 @@ int tt_diff_sample(tt_diff* e, const float* x_T, const float* step_noise, const 
   TT_REQUIRE(e && x_T && steps_host && mel_out && e->S > 0, "tt_diff_sample: call tt_diff_condition first");
   TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_sample: the handle holds a batch of %d utterances (tt_diff_sample_batch)", e->U);
   TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_sample: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  TT_TRY(diff_sample_run(e, &x_T, &step_noise, steps_host, n_steps, cond_free, &mel_out, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    return diff_sample_run(e, &x_T, &step_noise, steps_host, n_steps, cond_free, &mel_out, s);
+  });
 }
 
 int tt_diff_sample_batch(tt_diff* e, int U, const float* const* x_T, const float* const* step_noise, const tt_diff_step* steps_host, int n_steps,
@@ -658,10 +602,9 @@ int tt_diff_sample_batch(tt_diff* e, int U, const float* const* x_T, const float
   TT_REQUIRE(U == e->U && e->conditioned == (U >= 32 ? ~0u : (1u << U) - 1u), "tt_diff_sample_batch: %d utterances, but the batch has %d and conditioning mask %#x (tt_diff_batch_begin / tt_diff_condition_slot)", U, e->U, e->conditioned);
   TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_sample_batch: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
   for (int u = 0; u < U; ++u) TT_REQUIRE(x_T[u] && mel_out[u] && (step_noise[u] || n_steps == 1), "tt_diff_sample_batch: null tensor for utterance %d", u);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  TT_TRY(diff_sample_run(e, x_T, step_noise, steps_host, n_steps, cond_free, mel_out, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    return diff_sample_run(e, x_T, step_noise, steps_host, n_steps, cond_free, mel_out, s);
+  });
 }
 
 int tt_diff_split_begin(tt_diff* e, const float* x_T, const tt_diff_step* steps_host, int n_steps, int row, void* stream) {
@@ -670,76 +613,59 @@ int tt_diff_split_begin(tt_diff* e, const float* x_T, const tt_diff_step* steps_
   TT_REQUIRE(row == 0 || row == 1, "tt_diff_split_begin: row must be 0 (conditioned) or 1 (conditioning-free)");
   TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_split_begin: the handle holds a batch of %d utterances (tt_diff_batch_begin); call tt_diff_condition first", e->U);
   split_release(e);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int S = e->S, IC = e->cfg.in_channels, IP = e->cfg.in_pad, dt = e->cfg.dtype;
-  std::vector<int> ts(n_steps);
-  for (int i = 0; i < n_steps; ++i) ts[i] = steps_host[i].timestep;
-  TT_CHECK_HIP(hipMemcpyAsync(e->ts_dev, ts.data(), n_steps * sizeof(int), hipMemcpyHostToDevice, s));
-  TT_CHECK_HIP(hipMemcpyAsync(e->steps_dev, steps_host, n_steps * sizeof(tt_diff_step), hipMemcpyHostToDevice, s));
-  TT_CHECK_HIP(hipStreamSynchronize(s));  // host staging buffers may go away
-  TT_CHECK_HIP(hipMemsetAsync(e->slot, 0, sizeof(int), s));
-  TT_TRY(diff_prepare_timesteps(e, n_steps, s));
-  TT_TRY(transpose_launch(x_T, e->x, IC, S, s));  // [C][S] -> [S][C]
-  TT_TRY(cast_pad_launch(dt, e->x, IC, e->x_t, IP, S, IC, IP, s));
-  TT_TRY(cast_pad_launch(dt, e->x, IC, offset_t(e->x_t, (size_t)S * IP, e->es), IP, S, IC, IP, s));
-  TT_TRY(diff_integrator_all(e, n_steps, 1, row, s));
-  int rc = 0;
-  if (graphs_enabled()) {
-    TT_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    rc = diff_forward(e, 1, s);
-    hipError_t ce = hipStreamEndCapture(s, &e->split_graph);
-    if (!rc && ce != hipSuccess) { set_error("tt_diff_split_begin: capture failed: %s", hipGetErrorString(ce)); rc = -2; }
-    if (!rc) {
-      ce = hipGraphInstantiate(&e->split_exec, e->split_graph, nullptr, nullptr, 0);
-      if (ce != hipSuccess) { set_error("tt_diff_split_begin: instantiate failed: %s", hipGetErrorString(ce)); rc = -2; }
-    }
-    if (rc) split_release(e);
-  }
-  TT_TRY(rc);
-  e->split_row = row;
-  e->split_steps = n_steps;
-  e->split_done = 0;
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int S = e->S, IC = e->cfg.in_channels, IP = e->cfg.in_pad, dt = e->cfg.dtype;
+    std::vector<int> ts(n_steps);
+    for (int i = 0; i < n_steps; ++i) ts[i] = steps_host[i].timestep;
+    TT_CHECK_HIP(hipMemcpyAsync(e->ts_dev, ts.data(), n_steps * sizeof(int), hipMemcpyHostToDevice, s));
+    TT_CHECK_HIP(hipMemcpyAsync(e->steps_dev, steps_host, n_steps * sizeof(tt_diff_step), hipMemcpyHostToDevice, s));
+    TT_CHECK_HIP(hipStreamSynchronize(s));  // host staging buffers may go away
+    TT_CHECK_HIP(hipMemsetAsync(e->slot, 0, sizeof(int), s));
+    TT_TRY(diff_prepare_timesteps(e, n_steps, s));
+    TT_TRY(transpose_launch(x_T, e->x, IC, S, s));  // [C][S] -> [S][C]
+    TT_TRY(cast_pad_launch(dt, e->x, IC, e->x_t, IP, S, IC, IP, s));
+    TT_TRY(cast_pad_launch(dt, e->x, IC, offset_t(e->x_t, (size_t)S * IP, e->es), IP, S, IC, IP, s));
+    TT_TRY(diff_integrator_all(e, n_steps, 1, row, s));
+    if (graphs_enabled()) TT_TRY(e->split.capture(s, "tt_diff_split_begin", [&]() -> int { return diff_forward(e, 1, s); }));
+    e->split_row = row;
+    e->split_steps = n_steps;
+    e->split_done = 0;
+    return 0;
+  });
 }
 
 int tt_diff_split_forward(tt_diff* e, float* out_row, void* stream) {
   TT_REQUIRE(e && out_row && e->split_row >= 0, "tt_diff_split_forward: call tt_diff_split_begin first");
   TT_REQUIRE(e->split_done < e->split_steps, "tt_diff_split_forward: all %d steps already ran", e->split_steps);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  if (e->split_exec) {
-    hipError_t ce = hipGraphLaunch(e->split_exec, s);
-    if (ce != hipSuccess) { set_error("tt_diff_split_forward: hipGraphLaunch: %s", hipGetErrorString(ce)); return -2; }
-  } else {
-    TT_TRY(diff_forward(e, 1, s));
-  }
-  TT_CHECK_HIP(hipMemcpyAsync(out_row, e->out, (size_t)e->S * e->cfg.out_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    TT_TRY(e->split.exec ? e->split.launch(s, "tt_diff_split_forward") : diff_forward(e, 1, s));
+    TT_CHECK_HIP(hipMemcpyAsync(out_row, e->out, (size_t)e->S * e->cfg.out_channels * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  });
 }
 
 int tt_diff_split_update(tt_diff* e, const float* rows, const float* step_noise, float* mel_out, void* stream) {
   TT_REQUIRE(e && rows && mel_out && e->split_row >= 0, "tt_diff_split_update: call tt_diff_split_begin first");
   TT_REQUIRE(e->split_done < e->split_steps, "tt_diff_split_update: all %d steps already ran", e->split_steps);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  PSampleArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.steps = e->steps_dev; pa.slot = e->slot; pa.x = e->x; pa.x_t = e->x_t; pa.cpad = e->cfg.in_pad; pa.out = rows;
-  pa.has_uncond = 1; pa.noise = step_noise; pa.S = e->S; pa.C = e->cfg.in_channels;
-  pa.mel_out = mel_out;
-  pa.guard = e->guard;
-  pa.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
-  pa.mel_shift = -11.512925148010254f;
-  TT_TRY(psample_launch(e->cfg.dtype, pa, s));
-  TT_TRY(slot_advance_launch(e->slot, e->ss_all, e->ss_cur, e->NR * 2 * e->C, e->n_steps_cur - 1, s));
-  e->split_done += 1;
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    PSampleArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.steps = e->steps_dev; pa.slot = e->slot; pa.x = e->x; pa.x_t = e->x_t; pa.cpad = e->cfg.in_pad; pa.out = rows;
+    pa.has_uncond = 1; pa.noise = step_noise; pa.S = e->S; pa.C = e->cfg.in_channels;
+    pa.mel_out = mel_out;
+    pa.guard = e->guard.dev;
+    pa.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
+    pa.mel_shift = -11.512925148010254f;
+    TT_TRY(psample_launch(e->cfg.dtype, pa, s));
+    TT_TRY(slot_advance_launch(e->slot, e->ss_all, e->ss_cur, e->NR * 2 * e->C, e->n_steps_cur - 1, s));
+    e->split_done += 1;
+    return 0;
+  });
 }
 
 int tt_diff_split_end(tt_diff* e) {
   TT_REQUIRE(e != nullptr, "tt_diff_split_end: null handle");
-  TT_CHECK_HIP(hipMemcpyAsync(e->guard_host, e->guard, sizeof(int), hipMemcpyDeviceToHost, e->sb.own));
+  TT_TRY(e->guard.snapshot(e->sb.own));
   TT_CHECK_HIP(hipStreamSynchronize(e->sb.own));
   split_release(e);
   return 0;
@@ -747,7 +673,7 @@ int tt_diff_split_end(tt_diff* e) {
 
 int tt_diff_stat(tt_diff* e, int which) {  // 0: sampler-step graph captures so far (tests: the kept graph is reused)
   if (!e) { set_error("tt_diff_stat: null handle"); return -1; }
-  return which == 0 ? e->captures : -1;
+  return which == 0 ? e->step.captures : -1;
 }
 
 // TT_DIFF_OPT_OVERLAP_PREPASS [1]: the conditioning-integrator pre-pass runs chunk by chunk on its own stream while the sampler loop
@@ -756,8 +682,8 @@ int tt_diff_set_option(tt_diff* e, int option, int value) {
   TT_REQUIRE(e != nullptr, "tt_diff_set_option: null handle");
   TT_REQUIRE(option == TT_DIFF_OPT_OVERLAP_PREPASS || option == TT_DIFF_OPT_FUSED_GN, "tt_diff_set_option: unknown option %d", option);
   if (option == TT_DIFF_OPT_FUSED_GN) {
-    if (value != e->fuse_gn) diff_drop_step_graph(e);  // the kept sampler step was captured with the other launch sequence
     TT_REQUIRE(value == 0 || value == 1, "tt_diff_set_option: TT_DIFF_OPT_FUSED_GN takes 0 (stand-alone applies) or 1 (default: ResBlock in_layers fused), got %d", value);
+    if (value != e->fuse_gn) e->step.drop();  // the kept sampler step was captured with the other launch sequence
     e->fuse_gn = value;
     return 0;
   }
@@ -769,13 +695,8 @@ int tt_diff_set_option(tt_diff* e, int option, int value) {
 // the last reset, as of the end of the last finished tt_diff_sample / tt_diff_sample_batch / tt_diff_split_end.  reset != 0 clears it.
 int tt_diff_guard(tt_diff* e, int reset) {
   if (!e) { set_error("tt_diff_guard: null handle"); return -1; }
-  const int n = e->guard_host[0];
-  if (n > 0) set_error("diffusion stage: %d kernel(s) met non-finite values (operand overflow in %s)", n, e->cfg.dtype == DT_F16 ? "fp16: re-run this stage with bf16 operands" : "bf16");
-  if (reset && n > 0) {  // (a clean counter needs no device work: this sits at the end of every utterance)
-    if (hipMemsetAsync(e->guard, 0, 4 * sizeof(int), e->sb.own) != hipSuccess || hipStreamSynchronize(e->sb.own) != hipSuccess) { set_error("tt_diff_guard: reset failed"); return -2; }
-    e->guard_host[0] = 0;
-  }
-  return n;
+  return e->guard.read(reset, e->sb.own, "tt_diff_guard", "diffusion stage: %d kernel(s) met non-finite values (operand overflow in %s)",
+                       e->cfg.dtype == DT_F16 ? "fp16: re-run this stage with bf16 operands" : "bf16");
 }
 
 }  // extern "C"

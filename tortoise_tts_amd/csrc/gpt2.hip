@@ -24,7 +24,7 @@ struct ArParams {
   int pad[3];
 };
 
-struct tt_ar {
+struct tt_ar : EngineHandle {
   tt_ar_config cfg;
   tt_ar_weights w;
   std::vector<tt_gpt_layer> L;
@@ -33,8 +33,6 @@ struct tt_ar {
   int Vp = 0;               // vocabulary padded to a multiple of 4: row stride of the logits and rows of the padded head copy
   void* w_head_p = nullptr; // [Vp][D] T  lm_head weight with zero rows appended (8194 -> 8196: every epilogue access of the head GEMM
   float* b_head_p = nullptr;//            is a whole aligned quad - the run-time-ragged generic kernel cost 24 us per step instead of ~12)
-  Arena arena;
-  StreamBridge sb;
   // shared prefix cache [layers][H][P1][64] (row-major) and per-sequence cache
   void* kp = nullptr; void* vp = nullptr;
   void* kc = nullptr; void* vc = nullptr;
@@ -53,8 +51,8 @@ struct tt_ar {
   float* typ_logits = nullptr;  // [max_batch][Vp]: the rows the sampler reads under typical sampling (tt_sampling.typical_mass)
   int* state = nullptr; unsigned* seen = nullptr; int* unfinished = nullptr; int* unfinished_count = nullptr;
   int* next_tok = nullptr;
-  int* guard = nullptr;    // [4] device counters: [0] rows with a non-finite value seen by the row norms / the sampler (tt_ar_guard)
-  int* guard_host = nullptr;  // pinned copy, refreshed at the end of every generation / latent pass
+  // guard (EngineHandle): rows with a non-finite value seen by the row norms / the sampler, snapshot at the end of every generation /
+  // latent pass (tt_ar_guard)
   int max_rows = 0;
   int P1 = 0;      // current prefix length (incl. start token); with several groups the longest one
   int G = 1;       // utterances (groups) of the current batch, each with its own prefix: kp / vp are [group][layer][H][max_prefix][64]
@@ -71,13 +69,11 @@ struct tt_ar {
   int gen_done = 0;    // tokens sampled by the running generation (tt_ar_generate / tt_ar_generate_chunk)
   bool gen_finished = false;
   // The captured decode step is kept between calls: everything a call can change is either device data (token / slot counters, the
-  // Philox keys below, the prefix caches) or part of step_key - the bytes of the sampler's argument block plus the batch / group /
-  // prefix-length values the launchers bake into the graph.  A call with the same key replays step_exec; any other key re-captures.
+  // Philox keys below, the prefix caches) or part of step.key - the bytes of the sampler's argument block plus the batch / group /
+  // prefix-length values the launchers bake into the graph.  A call with the same key replays the graph; any other key re-captures.
   ArParams* par_dev = nullptr;    // Philox key per utterance group (group 0 alone without groups) + row_offset of the call
   ArParams* par_host = nullptr;   // pinned staging of the same
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  std::vector<unsigned char> step_key;
+  KeptGraph step;                 // the decode step; step.captures feeds tt_ar_stat(0)
   // The sampler writes into a code buffer the HANDLE owns ([max_batch][tmax], stop-filled at the start of a generation) and the
   // finished columns are copied to the caller's buffer at the end of a call: the caller's pointer is not part of the kept graph.
   int* codes_own = nullptr;
@@ -91,20 +87,11 @@ struct tt_ar {
   // Handles that decode at most 4 sequences (the streaming engine of api_fast.py: max_batch = 1): the decode step's GEMMs run GEMV-shaped
   // (gemv.hip) - a property of the HANDLE, not of a call's batch, so a handle's kernels never change between calls
   int gemv = 0;  // 0 | 1 GEMV launches | 2 GEMV launches that also do the layer norm in front of them (five launches per layer)
-  int captures = 0;   // decode-step captures so far (tt_ar_stat: tests assert the kept graph is reused)
   int drains = 0;     // host-side queue drains the launch loop fell back to (0 when the progress words arrive)
   bool typical = false;  // the last generation ran the typical-sampling mask ahead of the sampler (one more launch per step)
 };
 
 namespace tt { int g_ar_gemv = 2; }  // ttx_kernel_variant(TTX_AR_GEMV), read at tt_ar_create: handles of <= 4 sequences run 0 = the MFMA decode GEMMs | 1 = GEMV launches | 2 = GEMVs with the layer norms inside
-
-static void ar_drop_step_graph(tt_ar* e) {
-  if (e->step_exec) (void)hipGraphExecDestroy(e->step_exec);
-  if (e->step_graph) (void)hipGraphDestroy(e->step_graph);
-  e->step_exec = nullptr;
-  e->step_graph = nullptr;
-  e->step_key.clear();
-}
 
 static const int MAX_SPLIT = 8;
 
@@ -126,7 +113,7 @@ static int ar_rownorm_rows(tt_ar* e, float* x, void* h_out, int M, const float* 
   a.g1 = g1; a.b1 = b1; a.eps1 = 1e-5f;
   a.out_t = h_out; a.ldot = e->D;
   a.row_blocks = 1;
-  a.guard = e->guard;
+  a.guard = e->guard.dev;
   return rownorm_launch(e->cfg.dtype, a, s);
 }
 static int ar_rownorm(tt_ar* e, float* x, int M, const float* g1, const float* b1, const float* g2, const float* b2,
@@ -202,7 +189,7 @@ static int ar_head_norm(tt_ar* e, float* x, void* h_out, int M, const float* add
   a.g2 = e->w.final_norm_g; a.b2 = e->w.final_norm_b; a.eps2 = 1e-5f;
   a.out_t = h_out; a.ldot = e->D;
   a.row_blocks = 1;
-  a.guard = e->guard;
+  a.guard = e->guard.dev;
   if (e->lat && lat_index != -2 && M <= e->lat_batch) {
     a.out_f32 = e->lat; a.ldo32 = e->D;
     a.f32_slot_stride = (size_t)e->lat_batch * e->D;
@@ -248,7 +235,7 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
       v.A = e->h; v.lda = D; v.W = w.w_qkv; v.ldw = D; v.M = nb; v.N = 3 * D; v.K = D; v.bias = w.b_qkv; v.epi = GEMV_QKV;
       v.step = e->state + 1; v.qbuf = e->q; v.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es); v.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
       v.heads = H; v.tmax = e->tmax; v.dmodel = D; v.q_scale = 0.125f;
-      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln1_g; v.ln_b = w.ln1_b; v.ln_eps = 1e-5f; v.guard = e->guard; }
+      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln1_g; v.ln_b = w.ln1_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
       TT_TRY(gemv_launch(dt, v, s));
       DecodeAttnArgs a;
       memset(&a, 0, sizeof(a));
@@ -263,7 +250,7 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
       TT_TRY(gemv_launch(dt, v, s));
       if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln2_g, w.ln2_b, nullptr, slabs, 0, nb, s));
       memset(&v, 0, sizeof(v));
-      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln2_g; v.ln_b = w.ln2_b; v.ln_eps = 1e-5f; v.guard = e->guard; }
+      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln2_g; v.ln_b = w.ln2_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
       v.A = e->h; v.lda = D; v.W = w.w_fc; v.ldw = D; v.M = nb; v.N = 4 * D; v.K = D; v.bias = w.b_fc; v.epi = GEMV_GELU_T; v.out_t = e->ff; v.ldot = 4 * D;
       TT_TRY(gemv_launch(dt, v, s));
       memset(&v, 0, sizeof(v));
@@ -338,29 +325,6 @@ static int decode_step_enqueue(tt_ar* e, hipStream_t s, bool embedded = false) {
   return ar_head_gemm(e, B, s);
 }
 
-// Capture fn() on stream s into a new graph + executable.
-template <typename F>
-static int ar_capture(hipStream_t s, F&& fn, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  TT_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  const int rc = fn();
-  hipError_t ce = hipStreamEndCapture(s, &graph);
-  if (rc) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
-  }
-  if (ce == hipSuccess) ce = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  if (ce != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    set_error("tt_ar_generate: graph capture / instantiate failed: %s", hipGetErrorString(ce));
-    return -2;
-  }
-  *graph_out = graph;
-  *exec_out = exec;
-  return 0;
-}
-
 extern "C" {
 
 int tt_ar_create(const tt_ar_config* cfg, const tt_ar_weights* w, tt_ar** out) {
@@ -390,7 +354,7 @@ int tt_ar_create(const tt_ar_config* cfg, const tt_ar_weights* w, tt_ar** out) {
   e->tmax = round_up(cfg->max_new_tokens, 8);
 #endif
   const int D = e->D, H = e->H;
-  int rc = e->sb.init();
+  int rc = e->open("tt_ar_create", true);
   e->max_rows = std::max(std::max(cfg->max_prefix, cfg->max_full_rows), cfg->max_batch);
   const size_t rows = (size_t)e->max_rows + 64;
   e->prefix_layer_elems = (size_t)H * cfg->max_prefix * 64;
@@ -427,16 +391,13 @@ int tt_ar_create(const tt_ar_config* cfg, const tt_ar_weights* w, tt_ar** out) {
   }
   if (!rc) rc = e->arena.alloc_t(&e->par_dev, 1);
   if (!rc) rc = e->arena.alloc_t(&e->codes_own, (size_t)cfg->max_batch * e->tmax);
-  if (!rc) rc = e->arena.alloc_t(&e->guard, 4);
   if (!rc && (hipHostMalloc((void**)&e->par_host, sizeof(ArParams)) != hipSuccess ||
               hipHostMalloc((void**)&e->progress_host, 4 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-              hipHostMalloc((void**)&e->guard_host, 4 * sizeof(int)) != hipSuccess ||
               hipHostGetDevicePointer((void**)&e->progress_dev, e->progress_host, 0) != hipSuccess)) {
     set_error("tt_ar_create: hipHostMalloc failed");
     rc = -2;
   }
   if (!rc) {
-    e->guard_host[0] = 0;
     e->progress_host[0] = 0; e->progress_host[1] = -1; e->progress_host[2] = e->progress_host[3] = 0;
   }
   // GEMV-shaped decode step: <= 4 sequences per handle, 16-bit operands, the trunk's K in {1024, 2048, 4096} (gemv.hip)
@@ -451,13 +412,10 @@ int tt_ar_create(const tt_ar_config* cfg, const tt_ar_weights* w, tt_ar** out) {
 
 void tt_ar_destroy(tt_ar* e) {
   if (!e) return;
-  (void)hipDeviceSynchronize();
-  ar_drop_step_graph(e);
+  e->close();
+  e->step.drop();
   if (e->par_host) (void)hipHostFree(e->par_host);
   if (e->progress_host) (void)hipHostFree(e->progress_host);
-  if (e->guard_host) (void)hipHostFree(e->guard_host);
-  e->arena.release();
-  e->sb.destroy();
   delete e;
 }
 
@@ -465,61 +423,60 @@ int tt_ar_prefill_group(tt_ar* e, int group, int n_groups, const float* prefix_e
   TT_REQUIRE(e && prefix_emb, "tt_ar_prefill: null argument");
   TT_REQUIRE(n_groups >= 1 && n_groups <= e->cfg.max_groups && group >= 0 && group < n_groups, "tt_ar_prefill_group: group %d of %d (capacity %d groups)", group, n_groups, e->cfg.max_groups);
   TT_REQUIRE(P >= 1 && P + 1 <= e->cfg.max_prefix, "tt_ar_prefill: prefix of %d rows exceeds capacity %d", P + 1, e->cfg.max_prefix);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int D = e->D;
-  if (n_groups != e->G || group == 0) {  // a new batch starts with its group 0
-    e->G = n_groups;
-    e->prefilled = 0;
-  }
-  const int P1 = P + 1;
-  e->P1g[group] = P1;
-  e->prefilled |= 1u << group;
-  e->P1 = 0;
-  for (int gi = 0; gi < n_groups; ++gi)
-    if ((e->prefilled >> gi) & 1u) e->P1 = std::max(e->P1, e->P1g[gi]);
-  // per-layer stride of the prefix cache = its capacity (H * max_prefix * 64): group g, layer l at (g * layers + l) strides
-  TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // start-token row: mel_embedding[start] + mel_pos_embedding[0]  (autoregressive.py:137-141)
-  {
-    RowNormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = e->x + (size_t)P * D; a.ldx = D; a.M = 1; a.D = D;
-    a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * D; a.ldxin = D;
-    a.add_bias = e->w.mel_pos;  // row 0
-    a.write_x = 1; a.mode = NORM_NONE;
-    TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
-  }
-  TT_TRY(gpt_trunk_full(e, 1, P1, true, s, group));
-  const int B_saved = e->B;
-  e->B = 1;
-  int rc = ar_head(e, e->x + (size_t)P * D, 1, nullptr, 0, s, group == 0 ? 0 : -2, group);  // logits row `group`
-  e->B = B_saved;
-  TT_TRY(rc);
-  e->logits_from_prefill = e->prefilled == (n_groups >= 32 ? ~0u : (1u << n_groups) - 1u);
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int D = e->D;
+    if (n_groups != e->G || group == 0) {  // a new batch starts with its group 0
+      e->G = n_groups;
+      e->prefilled = 0;
+    }
+    const int P1 = P + 1;
+    e->P1g[group] = P1;
+    e->prefilled |= 1u << group;
+    e->P1 = 0;
+    for (int gi = 0; gi < n_groups; ++gi)
+      if ((e->prefilled >> gi) & 1u) e->P1 = std::max(e->P1, e->P1g[gi]);
+    // per-layer stride of the prefix cache = its capacity (H * max_prefix * 64): group g, layer l at (g * layers + l) strides
+    TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // start-token row: mel_embedding[start] + mel_pos_embedding[0]  (autoregressive.py:137-141)
+    {
+      RowNormArgs a;
+      memset(&a, 0, sizeof(a));
+      a.x = e->x + (size_t)P * D; a.ldx = D; a.M = 1; a.D = D;
+      a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * D; a.ldxin = D;
+      a.add_bias = e->w.mel_pos;  // row 0
+      a.write_x = 1; a.mode = NORM_NONE;
+      TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
+    }
+    TT_TRY(gpt_trunk_full(e, 1, P1, true, s, group));
+    const int B_saved = e->B;
+    e->B = 1;
+    int rc = ar_head(e, e->x + (size_t)P * D, 1, nullptr, 0, s, group == 0 ? 0 : -2, group);  // logits row `group`
+    e->B = B_saved;
+    TT_TRY(rc);
+    e->logits_from_prefill = e->prefilled == (n_groups >= 32 ? ~0u : (1u << n_groups) - 1u);
+    return 0;
+  });
 }
 
 int tt_ar_prefill(tt_ar* e, const float* prefix_emb, int P, void* stream) { return tt_ar_prefill_group(e, 0, 1, prefix_emb, P, stream); }
 
 int tt_ar_get_logits(tt_ar* e, float* dst, int rows, void* stream) {
   TT_REQUIRE(e && dst && rows >= 1 && rows <= e->logits_rows, "tt_ar_get_logits: %d rows requested, %d available", rows, e ? e->logits_rows : 0);
-  hipStream_t us = (hipStream_t)stream;
-  TT_TRY(e->sb.enter(us));
-  TT_CHECK_HIP(hipMemcpy2DAsync(dst, (size_t)e->V * sizeof(float), e->logits, (size_t)e->Vp * sizeof(float), (size_t)e->V * sizeof(float), (size_t)rows,
-                                hipMemcpyDeviceToDevice, e->sb.own));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    TT_CHECK_HIP(hipMemcpy2DAsync(dst, (size_t)e->V * sizeof(float), e->logits, (size_t)e->Vp * sizeof(float), (size_t)e->V * sizeof(float), (size_t)rows,
+                                  hipMemcpyDeviceToDevice, s));
+    return 0;
+  });
 }
 
 int tt_ar_begin(tt_ar* e, int B, void* stream) {
   TT_REQUIRE(e && B >= 1 && B <= e->cfg.max_batch, "tt_ar_begin: batch %d exceeds capacity", B);
   TT_REQUIRE(e->P1 > 0, "tt_ar_begin: call tt_ar_prefill first");
-  hipStream_t us = (hipStream_t)stream;
-  TT_TRY(e->sb.enter(us));
-  e->B = B;
-  e->host_slot = -1;
-  TT_TRY(ar_begin_launch(e->state, e->seen, e->unfinished, e->unfinished_count, B, e->V, e->tmax + 8, e->cfg.start_mel_token, e->sb.own));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    e->B = B;
+    e->host_slot = -1;
+    return ar_begin_launch(e->state, e->seen, e->unfinished, e->unfinished_count, B, e->V, e->tmax + 8, e->cfg.start_mel_token, s);
+  });
 }
 
 int tt_ar_decode_step(tt_ar* e, const int* tokens, void* stream) {
@@ -527,14 +484,23 @@ int tt_ar_decode_step(tt_ar* e, const int* tokens, void* stream) {
   // the step about to run writes KV slot host_slot + 1 and reads mel position row host_slot + 1 + mel_pos_offset
   TT_REQUIRE(e->host_slot + 1 < e->tmax, "tt_ar_decode_step: all %d KV slots of this handle are used", e->tmax);
   TT_REQUIRE(e->host_slot + 1 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_decode_step: step %d is beyond the mel position table (%d rows)", e->host_slot + 1, e->cfg.mel_pos_len);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  TT_CHECK_HIP(hipMemcpyAsync(e->next_tok, tokens, (size_t)e->B * sizeof(int), hipMemcpyDeviceToDevice, s));
-  TT_TRY(ar_state_advance_launch(e->state, nullptr, nullptr, s));  // state[1] = slot of the token being fed
-  e->host_slot += 1;
-  e->logits_from_prefill = false;
-  TT_TRY(decode_step_enqueue(e, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    TT_CHECK_HIP(hipMemcpyAsync(e->next_tok, tokens, (size_t)e->B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    TT_TRY(ar_state_advance_launch(e->state, nullptr, nullptr, s));  // state[1] = slot of the token being fed
+    e->host_slot += 1;
+    e->logits_from_prefill = false;
+    return decode_step_enqueue(e, s);
+  });
+}
+
+// The checks of a generation that depend on the sampling arguments and the handle's state: they run before anything of a running
+// generation is touched, so a rejected call leaves it resumable.
+static int ar_generate_check(const tt_ar* e, int B, bool fresh, const tt_sampling* sp) {
+  TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
+             (double)sp->typical_mass);
+  TT_REQUIRE(e->G <= 1 || (B % e->G == 0 && (B / e->G) % 4 == 0), "tt_ar_generate: %d sequences do not split into %d groups of a multiple of 4", B, e->G);
+  TT_REQUIRE(!fresh || e->logits_from_prefill, "tt_ar_generate: the logits buffer does not hold the prefill logits of all %d group(s); call tt_ar_prefill / tt_ar_prefill_group first", e->G);
+  return 0;
 }
 
 // Sampling loop shared by tt_ar_generate (fresh = true: the whole utterance) and tt_ar_generate_chunk (streaming: the loop
@@ -542,8 +508,6 @@ int tt_ar_decode_step(tt_ar* e, const int* tokens, void* stream) {
 // replaying the step graph again).  Tokens [e->gen_done, target) are produced; codes is the caller's [B][ldcodes] buffer.
 static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes, const tt_sampling* sp, int* codes, int* n_steps_host,
                            int* finished_host, hipStream_t s) {
-  TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
-             (double)sp->typical_mass);
   SampleArgs sa;
   memset(&sa, 0, sizeof(sa));
   sa.B = B; sa.V = e->V; sa.seen = e->seen;
@@ -553,7 +517,7 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
   sa.codes = e->codes_own; sa.ldcodes = e->tmax; sa.next_tok = e->next_tok; sa.unfinished_count = e->unfinished_count;
   sa.embed_x = e->x; sa.tok_emb = e->w.mel_emb; sa.pos_emb = e->w.mel_pos; sa.D = e->D; sa.pos_offset = e->cfg.mel_pos_offset;
   sa.pos_len = e->cfg.mel_pos_len;
-  sa.guard = e->guard;
+  sa.guard = e->guard.dev;
   sa.typical_mass = sp->typical_mass; sa.typical_out = e->typ_logits;
   e->typical = sp->typical_mass != 0.f;
   // the Philox keys and the row offset go through device memory (sa.seed / sa.group_seeds / sa.row_offset stay zero): neither the
@@ -565,7 +529,6 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
   for (int gi = 0; gi < 16; ++gi) e->par_host->keys[gi] = sp->seed;
   e->par_host->row_offset = sp->row_offset;
   if (e->G > 1) {
-    TT_REQUIRE(B % e->G == 0 && (B / e->G) % 4 == 0, "tt_ar_generate: %d sequences do not split into %d groups of a multiple of 4", B, e->G);
     sa.ngroups = e->G; sa.group_size = B / e->G;
     for (int gi = 0; gi < e->G; ++gi) e->par_host->keys[gi] = sp->group_seeds ? sp->group_seeds[gi] : sp->seed;
   }
@@ -583,7 +546,6 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->codes_own, e->cfg.stop_mel_token, (size_t)B * e->tmax, s));
     // token 0: every row samples from the shared prefill logits
     sa.logits = e->logits; sa.ldl = 0; sa.ldg = e->Vp;
-    TT_REQUIRE(e->logits_from_prefill, "tt_ar_generate: the logits buffer does not hold the prefill logits of all %d group(s); call tt_ar_prefill / tt_ar_prefill_group first", e->G);
     e->logits_from_prefill = false;
     TT_TRY(sample_launch(sa, s));
     TT_TRY(ar_state_advance_launch(e->state, e->unfinished_count, e->progress_dev, s));
@@ -613,19 +575,10 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     int geo[24] = {B, e->G, e->P1, g_prof_on ? 1 : 0};
     for (int gi = 0; gi < 16; ++gi) geo[4 + gi] = gi < e->G ? e->P1g[gi] : 0;
     memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
-    if (e->step_exec == nullptr || key != e->step_key) {
-      ar_drop_step_graph(e);
-      rc = ar_capture(s, [&]() -> int {
-        TT_TRY(decode_step_enqueue(e, s, true));
-        return tail_enqueue(s);
-      }, &e->step_graph, &e->step_exec);
-      if (rc) {
-        ar_drop_step_graph(e);
-        return rc;
-      }
-      e->step_key.swap(key);
-      e->captures += 1;
-    }
+    TT_TRY(e->step.ensure(s, key.data(), key.size(), "tt_ar_generate", [&]() -> int {
+      TT_TRY(decode_step_enqueue(e, s, true));
+      return tail_enqueue(s);
+    }));
   }
   const int first_step = e->gen_done;
   int steps_done = e->gen_done;
@@ -651,16 +604,14 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     }
     if (rc) break;
     if (prog[1] >= 0) { stop_seen = true; break; }
-    hipError_t le = hipSuccess;
     if (use_graph) {
-      le = hipGraphLaunch(e->step_exec, s);
+      rc = e->step.launch(s, "tt_ar_generate");
     } else {
       e->host_slot = step - 1;
       rc = decode_step_enqueue(e, s, true);
       if (!rc) rc = tail_enqueue(s);
-      if (rc) break;
     }
-    if (le != hipSuccess) { set_error("tt_ar_generate: step launch: %s", hipGetErrorString(le)); rc = -2; break; }
+    if (rc) break;
     steps_done = step + 1;
   }
   (void)stop_seen;
@@ -668,13 +619,13 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     // the finished columns go to the caller's buffer; one host-visible completion point per call
     hipError_t ce = hipMemcpy2DAsync(codes, (size_t)ldcodes * sizeof(int), e->codes_own, (size_t)e->tmax * sizeof(int),
                                      (size_t)steps_done * sizeof(int), (size_t)B, hipMemcpyDeviceToDevice, s);
-    if (ce == hipSuccess) ce = hipMemcpyAsync(e->guard_host, e->guard, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(s);
     if (ce != hipSuccess) { set_error("tt_ar_generate: %s", hipGetErrorString(ce)); rc = -2; }
+    if (!rc) rc = e->guard.snapshot(s);
+    if (!rc && (ce = hipStreamSynchronize(s)) != hipSuccess) { set_error("tt_ar_generate: %s", hipGetErrorString(ce)); rc = -2; }
   }
   if (rc) {
     (void)hipStreamSynchronize(s);
-    ar_drop_step_graph(e);  // a failed replay leaves nothing to trust
+    e->step.drop();  // a failed replay leaves nothing to trust
   }
   TT_TRY(rc);
   const int first_zero = prog[1];
@@ -693,10 +644,10 @@ int tt_ar_generate(tt_ar* e, int B, int max_new, const tt_sampling* sp, int* cod
   TT_REQUIRE(max_new >= 1 && max_new <= e->tmax, "tt_ar_generate: max_new %d exceeds capacity %d", max_new, e->tmax);
   TT_REQUIRE(max_new - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate: max_new %d exceeds the mel position table", max_new);
   TT_REQUIRE(e->P1 > 0, "tt_ar_generate: call tt_ar_prefill first");
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  TT_TRY(ar_generate_run(e, B, true, max_new, max_new, sp, codes, n_steps_host, nullptr, s));
-  return e->sb.leave(us);
+  TT_TRY(ar_generate_check(e, B, true, sp));
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    return ar_generate_run(e, B, true, max_new, max_new, sp, codes, n_steps_host, nullptr, s);
+  });
 }
 
 int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, const tt_sampling* sp, int* codes, int* n_total_host,
@@ -709,53 +660,53 @@ int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, co
   const int target = done + n_more;
   TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "tt_ar_generate_chunk: %d + %d tokens exceed capacity (%d code columns, %d KV slots)", done, n_more, ldcodes, e->tmax);
   TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate_chunk: %d tokens exceed the mel position table", target);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  if (!first && e->gen_finished) {  // every row already stopped
-    *n_total_host = e->gen_done;
-    *finished_host = 1;
-    return e->sb.leave(us);
-  }
-  TT_TRY(ar_generate_run(e, B, first != 0, target, ldcodes, sp, codes, n_total_host, finished_host, s));
-  return e->sb.leave(us);
+  const bool stopped = !first && e->gen_finished;  // every row already stopped
+  if (!stopped) TT_TRY(ar_generate_check(e, B, first != 0, sp));
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    if (stopped) {
+      *n_total_host = e->gen_done;
+      *finished_host = 1;
+      return 0;
+    }
+    return ar_generate_run(e, B, first != 0, target, ldcodes, sp, codes, n_total_host, finished_host, s);
+  });
 }
 
 int tt_ar_stream_latents(tt_ar* e, int B, int n, float* out, void* stream) {
   TT_REQUIRE(e && out, "tt_ar_stream_latents: null argument");
   TT_REQUIRE(e->lat != nullptr, "tt_ar_stream_latents: this handle was created with max_batch %d > 8 (no per-step latent capture)", e->cfg.max_batch);
   TT_REQUIRE(B >= 1 && B <= e->lat_batch && B == e->B && n >= 1 && n <= e->gen_done, "tt_ar_stream_latents: %d x %d latents requested, generation holds %d x %d", B, n, e->B, e->gen_done);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const size_t row = (size_t)e->D * sizeof(float);
-  for (int b = 0; b < B; ++b) {
-    float* dst = out + (size_t)b * n * e->D;
-    // latent 0 is the start-token row of the shared prefill (one copy for every sequence)
-    TT_CHECK_HIP(hipMemcpyAsync(dst, e->lat, row, hipMemcpyDeviceToDevice, s));
-    if (n > 1)
-      TT_CHECK_HIP(hipMemcpy2DAsync(dst + e->D, row, e->lat + ((size_t)e->lat_batch + b) * e->D, (size_t)e->lat_batch * row, row, (size_t)(n - 1),
-                                    hipMemcpyDeviceToDevice, s));
-  }
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const size_t row = (size_t)e->D * sizeof(float);
+    for (int b = 0; b < B; ++b) {
+      float* dst = out + (size_t)b * n * e->D;
+      // latent 0 is the start-token row of the shared prefill (one copy for every sequence)
+      TT_CHECK_HIP(hipMemcpyAsync(dst, e->lat, row, hipMemcpyDeviceToDevice, s));
+      if (n > 1)
+        TT_CHECK_HIP(hipMemcpy2DAsync(dst + e->D, row, e->lat + ((size_t)e->lat_batch + b) * e->D, (size_t)e->lat_batch * row, row, (size_t)(n - 1),
+                                      hipMemcpyDeviceToDevice, s));
+    }
+    return 0;
+  });
 }
 
 int tt_ar_latents(tt_ar* e, const float* emb, int k, int n, float* out, void* stream) {
   TT_REQUIRE(e && emb && out && k >= 1 && n >= 1, "tt_ar_latents: bad arguments");
   TT_REQUIRE(k * n <= e->max_rows && k <= e->cfg.max_batch, "tt_ar_latents: %d x %d rows exceed capacity %d", k, n, e->max_rows);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const int D = e->D, M = k * n;
-  TT_CHECK_HIP(hipMemcpyAsync(e->x, emb, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-  TT_TRY(gpt_trunk_full(e, k, n, false, s));
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER;
-  a.g1 = e->w.lnf_g; a.b1 = e->w.lnf_b; a.eps1 = 1e-5f;
-  a.g2 = e->w.final_norm_g; a.b2 = e->w.final_norm_b; a.eps2 = 1e-5f;
-  a.out_f32 = out; a.ldo32 = D;
-  a.guard = e->guard;
-  TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
-  TT_CHECK_HIP(hipMemcpyAsync(e->guard_host, e->guard, sizeof(int), hipMemcpyDeviceToHost, s));
-  return e->sb.leave(us);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const int D = e->D, M = k * n;
+    TT_CHECK_HIP(hipMemcpyAsync(e->x, emb, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    TT_TRY(gpt_trunk_full(e, k, n, false, s));
+    RowNormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER;
+    a.g1 = e->w.lnf_g; a.b1 = e->w.lnf_b; a.eps1 = 1e-5f;
+    a.g2 = e->w.final_norm_g; a.b2 = e->w.final_norm_b; a.eps2 = 1e-5f;
+    a.out_f32 = out; a.ldo32 = D;
+    a.guard = e->guard.dev;
+    TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
+    return e->guard.snapshot(s);
+  });
 }
 
 // Operand-overflow guard (fp16 operands saturate at 65504): row norms / sampler launches that met a non-finite value since the
@@ -763,13 +714,8 @@ int tt_ar_latents(tt_ar* e, const float* emb, int k, int n, float* out, void* st
 // synchronised its stream).  reset != 0 clears the counter.  Returns the count (>= 0) or a negative error.
 int tt_ar_guard(tt_ar* e, int reset) {
   if (!e) { set_error("tt_ar_guard: null handle"); return -1; }
-  const int n = e->guard_host[0];
-  if (n > 0) set_error("autoregressive stage: %d kernel(s) met non-finite values (operand overflow in %s)", n, e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
-  if (reset && n > 0) {  // (a clean counter needs no device work: this sits at the end of every utterance)
-    if (hipMemsetAsync(e->guard, 0, 4 * sizeof(int), e->sb.own) != hipSuccess || hipStreamSynchronize(e->sb.own) != hipSuccess) { set_error("tt_ar_guard: reset failed"); return -2; }
-    e->guard_host[0] = 0;
-  }
-  return n;
+  return e->guard.read(reset, e->sb.own, "tt_ar_guard", "autoregressive stage: %d kernel(s) met non-finite values (operand overflow in %s)",
+                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
 }
 
 // Counters for tests / diagnostics: 0 = decode-step graph captures so far, 1 = queue drains of the launch loop (expected 0),
@@ -777,7 +723,7 @@ int tt_ar_guard(tt_ar* e, int reset) {
 int tt_ar_stat(tt_ar* e, int which) {
   if (!e) { set_error("tt_ar_stat: null handle"); return -1; }
   const int per_step = 7 * e->cfg.layers + 4 + (e->typical ? 1 : 0);
-  return which == 0 ? e->captures : which == 1 ? e->drains : which == 2 ? per_step : -1;
+  return which == 0 ? e->step.captures : which == 1 ? e->drains : which == 2 ? per_step : -1;
 }
 
 // Engine options of a handle (defaults in brackets):

@@ -48,12 +48,10 @@ __global__ void mrf_combine_kernel(const float* __restrict__ z0, const float* __
 
 }  // namespace
 
-struct tt_hifi {
+struct tt_hifi : EngineHandle {
   tt_hifi_config cfg;
   tt_hifi_weights w;
   std::vector<tt_hifi_resblock> res;
-  Arena arena;
-  StreamBridge sb;
   int cw[TT_HIFI_MAX_STAGES + 1];   // real channel width per level (level 0 = after conv_pre)
   int cp[TT_HIFI_MAX_STAGES + 1];   // padded to a multiple of 64
   float* lat1 = nullptr;   // [4 T][in] first interpolation
@@ -94,6 +92,8 @@ int tt_hifi_create(const tt_hifi_config* cfg, const tt_hifi_weights* w, tt_hifi*
   TT_REQUIRE(cfg->num_stages >= 1 && cfg->num_stages <= TT_HIFI_MAX_STAGES && cfg->num_kernels >= 1 && cfg->num_kernels <= 3 &&
              cfg->num_dilations >= 1 && cfg->num_dilations <= 3, "tt_hifi_create: %d stages / %d kernels / %d dilations unsupported", cfg->num_stages, cfg->num_kernels, cfg->num_dilations);
   TT_REQUIRE(cfg->in_channels % 64 == 0 && cfg->cond_channels % 64 == 0 && cfg->initial_channel % 64 == 0 && cfg->max_latents >= 1, "tt_hifi_create: widths must be multiples of 64");
+  for (int i = 0; i < cfg->num_stages; ++i)
+    TT_REQUIRE(cfg->up_factor[i] >= 2 && cfg->up_factor[i] % 2 == 0 && (cfg->initial_channel >> (i + 1)) >= 4, "tt_hifi_create: stage %d (factor %d, %d channels) unsupported", i, cfg->up_factor[i], cfg->initial_channel >> (i + 1));
   tt_hifi* e = new tt_hifi();
   e->cfg = *cfg;
   e->w = *w;
@@ -102,13 +102,11 @@ int tt_hifi_create(const tt_hifi_config* cfg, const tt_hifi_weights* w, tt_hifi*
     e->cw[i] = cfg->initial_channel >> i;
     e->cp[i] = std::max(64, round_up(e->cw[i], 64));
   }
-  for (int i = 0; i < cfg->num_stages; ++i)
-    TT_REQUIRE(cfg->up_factor[i] >= 2 && cfg->up_factor[i] % 2 == 0 && e->cw[i + 1] >= 4, "tt_hifi_create: stage %d (factor %d, %d channels) unsupported", i, cfg->up_factor[i], e->cw[i + 1]);
   const int T2max = tt_hifi_output_frames(cfg->max_latents);
   size_t need = 0;
   hifi_elems(e, T2max, &need);
   e->cap_elems = need + 4096;
-  int rc = e->sb.init();
+  int rc = e->open("tt_hifi_create", false);
   if (!rc) rc = e->arena.alloc_t(&e->lat1, (size_t)(4 * cfg->max_latents + 8) * cfg->in_channels);
   if (!rc) rc = e->arena.alloc(&e->lat2, (size_t)(T2max + 8) * cfg->in_channels * 2);
   if (!rc) rc = e->arena.alloc(&e->g_t, (size_t)cfg->cond_channels * 2 + 256);
@@ -131,83 +129,81 @@ int tt_hifi_create(const tt_hifi_config* cfg, const tt_hifi_weights* w, tt_hifi*
 
 void tt_hifi_destroy(tt_hifi* e) {
   if (!e) return;
-  (void)hipDeviceSynchronize();
-  e->arena.release();
-  e->sb.destroy();
+  e->close();
   delete e;
 }
 
 int tt_hifi_run(tt_hifi* e, const float* latents, int T, const float* g, float* wav, int* n_samples, void* stream) {
   TT_REQUIRE(e && latents && g && wav && n_samples, "tt_hifi_run: null argument");
   TT_REQUIRE(T >= 1 && T <= e->cfg.max_latents, "tt_hifi_run: %d latents exceed capacity %d", T, e->cfg.max_latents);
-  hipStream_t us = (hipStream_t)stream, s = e->sb.own;
-  TT_TRY(e->sb.enter(us));
-  const tt_hifi_config& c = e->cfg;
-  const int dt = c.dtype, IN = c.in_channels, C0 = c.initial_channel;
   const int T1 = (int)floor((double)T * 4.0), T2 = tt_hifi_output_frames(T);
   TT_REQUIRE(T2 >= 1, "tt_hifi_run: no output frames");
-  // latents -> x4 -> x24000/22050 (linear), operand type
-  interp_rows_kernel<float><<<T1, 256, 0, s>>>(latents, e->lat1, T, T1, IN, (float)(1.0 / (1024.0 / 256.0)));
-  if (dt == DT_BF16) interp_rows_kernel<bf16><<<T2, 256, 0, s>>>(e->lat1, (bf16*)e->lat2, T1, T2, IN, (float)(1.0 / (24000.0 / 22050.0)));
-  else interp_rows_kernel<f16><<<T2, 256, 0, s>>>(e->lat1, (f16*)e->lat2, T1, T2, IN, (float)(1.0 / (24000.0 / 22050.0)));
-  TT_CHECK_HIP(hipGetLastError());
-  // conv_pre bias + cond_layer(g): one M = 1 GEMM, the conv_pre bias rides as the residual
-  TT_TRY(cast_pad_launch(dt, g, c.cond_channels, e->g_t, c.cond_channels, 1, c.cond_channels, c.cond_channels, s));
-  GemmArgs gm = gemm_args(e->g_t, c.cond_channels, e->w.w_cond, c.cond_channels, 1, C0, c.cond_channels);
-  gm.bias = e->w.b_cond; gm.res = e->w.b_pre; gm.ldres = C0; gm.out_f32 = e->bias0; gm.ldo32 = C0;
-  TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-  // conv_pre (k7) -> lrelu(0.1) -> operand of the first transposed conv ([T2 + 1][C0], last row zero)
-  gm = gemm_args(e->lat2, IN, e->w.w_pre, 7 * IN, T2, C0, 7 * IN);
-  gm.taps = 7; gm.seq_len = T2; gm.bias = e->bias0; gm.act = ACT_LRELU; gm.slope = c.lrelu_slope; gm.out_t = e->a_in; gm.ldot = e->cp[0];
-  TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-  int rows = T2;
-  for (int i = 0; i < c.num_stages; ++i) {
-    const int u = c.up_factor[i], Cin = e->cp[i], C = e->cp[i + 1], p = u / 2;
-    const int R = rows * u;  // samples after this stage
-    TT_CHECK_HIP(hipMemsetAsync(offset_t(e->a_in, (size_t)rows * Cin), 0, (size_t)Cin * 2, s));  // x[rows] = 0
-    // ConvTranspose1d as a 2-tap GEMM over rows + 1 input rows: flat output row t + p
-    gm = gemm_args(e->a_in, Cin, e->w.w_up[i], 2 * Cin, rows + 1, u * C, 2 * Cin);
-    gm.taps = 2; gm.seq_len = rows + 1; gm.bias = e->w.b_up[i]; gm.out_f32 = e->o32; gm.ldo32 = u * C; gm.out_t = e->o_t; gm.ldot = u * C;
-    gm.act_t = ACT_LRELU; gm.slope_t = c.lrelu_slope;
-    TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-    const float* o32 = e->o32 + (size_t)p * C;
-    const void* o_t = offset_t(e->o_t, (size_t)p * C);
-    for (int j = 0; j < c.num_kernels; ++j) {
-      const tt_hifi_resblock& rb = e->res[i * c.num_kernels + j];
-      const int ks = c.kernel_size[j];
-      const float* x32 = o32;
-      const void* xop = o_t;
-      for (int d = 0; d < c.num_dilations; ++d) {
-        const bool last = d == c.num_dilations - 1;
-        gm = gemm_args(xop, C, rb.w1[d], ks * C, R, C, ks * C);   // convs1[d]: dilated, LeakyReLU on the output
-        gm.taps = ks; gm.dilation = c.dilation[d]; gm.seq_len = R; gm.bias = rb.b1[d]; gm.act = ACT_LRELU; gm.slope = c.lrelu_slope;
-        gm.out_t = e->t1; gm.ldot = C;
-        TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-        float* xn = last ? e->z[j] : (d & 1 ? e->xb : e->xa);
-        gm = gemm_args(e->t1, C, rb.w2[d], ks * C, R, C, ks * C);  // convs2[d] + skip; next dilation's activated operand
-        gm.taps = ks; gm.seq_len = R; gm.bias = rb.b2[d]; gm.res = x32; gm.ldres = C; gm.out_f32 = xn; gm.ldo32 = C;
-        if (!last) { gm.out_t = e->xt; gm.ldot = C; gm.act_t = ACT_LRELU; gm.slope_t = c.lrelu_slope; }
-        TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-        x32 = xn;
-        xop = e->xt;
-      }
-    }
-    // mean of the ResBlocks -> LeakyReLU (0.1 between stages, 0.01 = F.leaky_relu default before conv_post) -> operand type
-    const bool final_stage = i == c.num_stages - 1;
-    const size_t n4 = (size_t)R * C / 4;
-    const int blocks = (int)std::min<size_t>((n4 + 255) / 256, 8192);
-    const float slope = final_stage ? 0.01f : c.lrelu_slope;
-    if (dt == DT_BF16) mrf_combine_kernel<bf16><<<blocks, 256, 0, s>>>(e->z[0], e->z[1], e->z[2], c.num_kernels, (bf16*)e->a_in, n4, slope);
-    else mrf_combine_kernel<f16><<<blocks, 256, 0, s>>>(e->z[0], e->z[1], e->z[2], c.num_kernels, (f16*)e->a_in, n4, slope);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    const tt_hifi_config& c = e->cfg;
+    const int dt = c.dtype, IN = c.in_channels, C0 = c.initial_channel;
+    // latents -> x4 -> x24000/22050 (linear), operand type
+    interp_rows_kernel<float><<<T1, 256, 0, s>>>(latents, e->lat1, T, T1, IN, (float)(1.0 / (1024.0 / 256.0)));
+    if (dt == DT_BF16) interp_rows_kernel<bf16><<<T2, 256, 0, s>>>(e->lat1, (bf16*)e->lat2, T1, T2, IN, (float)(1.0 / (24000.0 / 22050.0)));
+    else interp_rows_kernel<f16><<<T2, 256, 0, s>>>(e->lat1, (f16*)e->lat2, T1, T2, IN, (float)(1.0 / (24000.0 / 22050.0)));
     TT_CHECK_HIP(hipGetLastError());
-    rows = R;
-  }
-  const int CL = e->cp[c.num_stages];
-  gm = gemm_args(e->a_in, CL, e->w.w_post, 7 * CL, rows, 1, 7 * CL);  // conv_post (k7) -> tanh
-  gm.taps = 7; gm.seq_len = rows; gm.bias = e->w.b_post; gm.act = ACT_TANH; gm.out_f32 = wav; gm.ldo32 = 1;
-  TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
-  *n_samples = rows;
-  return e->sb.leave(us);
+    // conv_pre bias + cond_layer(g): one M = 1 GEMM, the conv_pre bias rides as the residual
+    TT_TRY(cast_pad_launch(dt, g, c.cond_channels, e->g_t, c.cond_channels, 1, c.cond_channels, c.cond_channels, s));
+    GemmArgs gm = gemm_args(e->g_t, c.cond_channels, e->w.w_cond, c.cond_channels, 1, C0, c.cond_channels);
+    gm.bias = e->w.b_cond; gm.res = e->w.b_pre; gm.ldres = C0; gm.out_f32 = e->bias0; gm.ldo32 = C0;
+    TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+    // conv_pre (k7) -> lrelu(0.1) -> operand of the first transposed conv ([T2 + 1][C0], last row zero)
+    gm = gemm_args(e->lat2, IN, e->w.w_pre, 7 * IN, T2, C0, 7 * IN);
+    gm.taps = 7; gm.seq_len = T2; gm.bias = e->bias0; gm.act = ACT_LRELU; gm.slope = c.lrelu_slope; gm.out_t = e->a_in; gm.ldot = e->cp[0];
+    TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+    int rows = T2;
+    for (int i = 0; i < c.num_stages; ++i) {
+      const int u = c.up_factor[i], Cin = e->cp[i], C = e->cp[i + 1], p = u / 2;
+      const int R = rows * u;  // samples after this stage
+      TT_CHECK_HIP(hipMemsetAsync(offset_t(e->a_in, (size_t)rows * Cin), 0, (size_t)Cin * 2, s));  // x[rows] = 0
+      // ConvTranspose1d as a 2-tap GEMM over rows + 1 input rows: flat output row t + p
+      gm = gemm_args(e->a_in, Cin, e->w.w_up[i], 2 * Cin, rows + 1, u * C, 2 * Cin);
+      gm.taps = 2; gm.seq_len = rows + 1; gm.bias = e->w.b_up[i]; gm.out_f32 = e->o32; gm.ldo32 = u * C; gm.out_t = e->o_t; gm.ldot = u * C;
+      gm.act_t = ACT_LRELU; gm.slope_t = c.lrelu_slope;
+      TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+      const float* o32 = e->o32 + (size_t)p * C;
+      const void* o_t = offset_t(e->o_t, (size_t)p * C);
+      for (int j = 0; j < c.num_kernels; ++j) {
+        const tt_hifi_resblock& rb = e->res[i * c.num_kernels + j];
+        const int ks = c.kernel_size[j];
+        const float* x32 = o32;
+        const void* xop = o_t;
+        for (int d = 0; d < c.num_dilations; ++d) {
+          const bool last = d == c.num_dilations - 1;
+          gm = gemm_args(xop, C, rb.w1[d], ks * C, R, C, ks * C);   // convs1[d]: dilated, LeakyReLU on the output
+          gm.taps = ks; gm.dilation = c.dilation[d]; gm.seq_len = R; gm.bias = rb.b1[d]; gm.act = ACT_LRELU; gm.slope = c.lrelu_slope;
+          gm.out_t = e->t1; gm.ldot = C;
+          TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+          float* xn = last ? e->z[j] : (d & 1 ? e->xb : e->xa);
+          gm = gemm_args(e->t1, C, rb.w2[d], ks * C, R, C, ks * C);  // convs2[d] + skip; next dilation's activated operand
+          gm.taps = ks; gm.seq_len = R; gm.bias = rb.b2[d]; gm.res = x32; gm.ldres = C; gm.out_f32 = xn; gm.ldo32 = C;
+          if (!last) { gm.out_t = e->xt; gm.ldot = C; gm.act_t = ACT_LRELU; gm.slope_t = c.lrelu_slope; }
+          TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+          x32 = xn;
+          xop = e->xt;
+        }
+      }
+      // mean of the ResBlocks -> LeakyReLU (0.1 between stages, 0.01 = F.leaky_relu default before conv_post) -> operand type
+      const bool final_stage = i == c.num_stages - 1;
+      const size_t n4 = (size_t)R * C / 4;
+      const int blocks = (int)std::min<size_t>((n4 + 255) / 256, 8192);
+      const float slope = final_stage ? 0.01f : c.lrelu_slope;
+      if (dt == DT_BF16) mrf_combine_kernel<bf16><<<blocks, 256, 0, s>>>(e->z[0], e->z[1], e->z[2], c.num_kernels, (bf16*)e->a_in, n4, slope);
+      else mrf_combine_kernel<f16><<<blocks, 256, 0, s>>>(e->z[0], e->z[1], e->z[2], c.num_kernels, (f16*)e->a_in, n4, slope);
+      TT_CHECK_HIP(hipGetLastError());
+      rows = R;
+    }
+    const int CL = e->cp[c.num_stages];
+    gm = gemm_args(e->a_in, CL, e->w.w_post, 7 * CL, rows, 1, 7 * CL);  // conv_post (k7) -> tanh
+    gm.taps = 7; gm.seq_len = rows; gm.bias = e->w.b_post; gm.act = ACT_TANH; gm.out_f32 = wav; gm.ldo32 = 1;
+    TT_TRY(gemm_launch(dt, EPI_STD, gm, s));
+    *n_samples = rows;
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -40,8 +40,46 @@ def latent_pass_embeddings(text_emb_w, text_pos_w, mel_emb_w, mel_pos_w, cfg, co
     return torch.cat([cond[:, None, :], text_emb, mel_emb], dim=1).contiguous(), m.shape[1]
 
 
-class ArStage:
+class _Handle:
+    """A stage that owns one engine handle `h`: made by <api>_create, destroyed by close() or when the stage is collected.
+    `api` is the prefix of the stage's C entry points (tt_ar, tt_clvp, ...)."""
+
+    api = None
+
+    def _create(self, *args):
+        self.h = E.vp()
+        E.check(self._fn("_create")(*args, C.byref(self.h)))
+
+    def _fn(self, suffix):
+        return getattr(self.lib, self.api + suffix)
+
+    def close(self):
+        if self.h:
+            self._fn("_destroy")(self.h)
+            self.h = E.vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _GuardedHandle(_Handle):
+    """A stage whose kernels count the non-finite values they meet (operand-overflow guard).  Stages without one have no guard()
+    at all: TextToSpeech looks for the attribute."""
+
+    def guard(self, reset=True):
+        """Non-finite values this stage's kernels met since the last reset (norms / sampler of the AR and CLVP / CVVP stages, GroupNorm
+        statistics / sampler inputs of the diffusion stage, predicted LVC kernels of the vocoder), as of its last finished run: read it
+        after a synchronisation (e.g. reading the result)."""
+        return E.guard_count(self._fn("_guard")(self.h, int(reset)))
+
+
+class ArStage(_GuardedHandle):
     """UnifiedVoice hot path: prefill + sampling loop + latent re-pass (autoregressive.py:454-563)."""
+
+    api = "tt_ar"
 
     def __init__(self, sd, cfg: ARConfig = ARConfig(), device="cuda", dtype=E.TT_BF16, max_batch=256, max_text=402,
                  max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1):
@@ -68,8 +106,7 @@ class ArStage:
         self.max_groups = max_groups
         self.max_latent_candidates = max_latent_candidates
         self.ccfg = c
-        self.h = E.vp()
-        E.check(self.lib.tt_ar_create(C.byref(c), C.byref(self.w.weights), C.byref(self.h)))
+        self._create(C.byref(c), C.byref(self.w.weights))
         # A/B switches of the measurement scripts (scripts/ab_stage.py); the product default is what tt_ar_create sets
         for env, opt in (("TT_AR_LOOKAHEAD", E.TT_AR_OPT_LOOKAHEAD),):
             if os.environ.get(env):
@@ -82,21 +119,6 @@ class ArStage:
     def stat(self, which):
         """tt_ar_stat: 0 decode-step graph captures, 1 queue drains of the launch loop, 2 launches per decode step."""
         return self.lib.tt_ar_stat(self.h, int(which))
-
-    def guard(self, reset=True):
-        """Non-finite values met by this stage's norms / sampler since the last reset (operand-overflow guard)."""
-        return E.guard_count(self.lib.tt_ar_guard(self.h, int(reset)))
-
-    def close(self):
-        if self.h:
-            self.lib.tt_ar_destroy(self.h)
-            self.h = E.vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- prefix (autoregressive.py:538-544)
     def prefix_embedding(self, cond_latent, text_tokens):
@@ -207,8 +229,10 @@ class ArStage:
         return out[:, -mel_rows:][:, :-2]
 
 
-class ClvpStage:
+class ClvpStage(_GuardedHandle):
     """CLVP.forward(return_loss=False) (clvp.py:99-135)."""
+
+    api = "tt_clvp"
 
     def __init__(self, sd, cfg: CLVPConfig = CLVPConfig(), device="cuda", dtype=E.TT_BF16, max_rows=256 * 500):
         self.lib = E.init()
@@ -219,23 +243,7 @@ class ClvpStage:
         c.dtype, c.dim, c.latent_dim, c.depth, c.heads = dtype, cfg.dim, cfg.dim_latent, cfg.depth, cfg.heads
         c.ff_inner, c.rot_dim, c.max_rows = cfg.dim * cfg.ff_mult, cfg.rotary_dim, max_rows
         self.max_rows = max_rows
-        self.h = E.vp()
-        E.check(self.lib.tt_clvp_create(C.byref(c), C.byref(self.w.text), C.byref(self.w.speech), E.ptr(self.w.temperature),
-                                        C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.lib.tt_clvp_destroy(self.h)
-            self.h = E.vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def guard(self, reset=True):
-        return E.guard_count(self.lib.tt_clvp_guard(self.h, int(reset)))
+        self._create(C.byref(c), C.byref(self.w.text), C.byref(self.w.speech), E.ptr(self.w.temperature))
 
     def score(self, text_tokens, codes):
         """text_tokens int [1 or B, T] (rows identical), codes int [B, n] -> f32 [B]."""
@@ -281,8 +289,10 @@ def nearest_interp_index(m, s):
     return np.minimum(idx, m - 1).astype(np.int32)
 
 
-class CvvpStage:
+class CvvpStage(_GuardedHandle):
     """The CVVP term of the candidate ranking, tts(cvvp_amount > 0) (cvvp.py:107-131 as api.py:464-468 drives it)."""
+
+    api = "tt_cvvp"
 
     def __init__(self, sd, cfg: CVVPConfig = CVVPConfig(), device="cuda", dtype=E.TT_F16, max_rows=256 * 500, max_cond_frames=520):
         self.lib = E.init()
@@ -293,22 +303,7 @@ class CvvpStage:
         c.dtype, c.dim, c.heads, c.depth, c.rot_dim = dtype, cfg.model_dim, cfg.heads, cfg.depth, cfg.rotary_dim
         c.mel_channels, c.mel_pad, c.max_rows, c.max_cond_frames = cfg.mel_channels, self.w.mel_pad, max_rows, max_cond_frames
         self.max_rows, self.max_cond_frames = max_rows, max_cond_frames
-        self.h = E.vp()
-        E.check(self.lib.tt_cvvp_create(C.byref(c), C.byref(self.w.weights), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.lib.tt_cvvp_destroy(self.h)
-            self.h = E.vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def guard(self, reset=True):
-        return E.guard_count(self.lib.tt_cvvp_guard(self.h, int(reset)))
+        self._create(C.byref(c), C.byref(self.w.weights))
 
     def score(self, auto_conds, codes):
         """auto_conds f32 [1, n_clips, 80, T] (the voice's conditioning clips, api.py:262-276), codes int [B, n] -> f32 [B]: the mean over
@@ -328,8 +323,10 @@ class CvvpStage:
         return torch.cat(outs)
 
 
-class DiffusionStage:
+class DiffusionStage(_GuardedHandle):
     """DiffusionTts + SpacedDiffusion.p_sample_loop (api.py:117-130)."""
+
+    api = "tt_diff"
 
     def __init__(self, sd, cfg: DiffusionConfig = DiffusionConfig(), device="cuda", dtype=E.TT_BF16, max_seq=2304, max_codes=512,
                  max_steps=512, max_batch=1):
@@ -343,8 +340,7 @@ class DiffusionStage:
         c.latent_channels, c.max_seq, c.max_codes, c.max_steps = cfg.in_latent_channels, max_seq, max_codes, max_steps
         c.max_batch = max_batch  # utterances one sample_many() pass may hold
         self.max_batch = max_batch
-        self.h = E.vp()
-        E.check(self.lib.tt_diff_create(C.byref(c), C.byref(self.w.weights), C.byref(self.h)))
+        self._create(C.byref(c), C.byref(self.w.weights))
         self.S = 0
         if os.environ.get("TT_DIFF_OVERLAP_PREPASS"):  # A/B switch of the measurement scripts
             self.set_option(E.TT_DIFF_OPT_OVERLAP_PREPASS, int(os.environ["TT_DIFF_OVERLAP_PREPASS"]))
@@ -354,24 +350,8 @@ class DiffusionStage:
     def set_option(self, option, value):
         E.check(self.lib.tt_diff_set_option(self.h, int(option), int(value)))
 
-    def close(self):
-        if self.h:
-            self.lib.tt_diff_destroy(self.h)
-            self.h = E.vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def stat(self, which):
         return self.lib.tt_diff_stat(self.h, int(which))
-
-    def guard(self, reset=True):
-        """Non-finite GroupNorm statistics / sampler inputs since the last reset, as of the last finished sampling run (the caller
-        has synchronised, e.g. by reading the result)."""
-        return E.guard_count(self.lib.tt_diff_guard(self.h, int(reset)))
 
     def condition(self, latents, cond_latent, S):
         """latents f32 [1, M, latent]; cond_latent f32 [1, 2C] (diffusion_decoder.py:232-260)."""
@@ -499,11 +479,13 @@ class DiffusionStage:
         return self.split_end()
 
 
-class ConditioningStage:
+class ConditioningStage(_Handle):
     """Conditioning encoders of the voice_samples path on the device (csrc/cond.hip):
     UnifiedVoice.get_conditioning (ConditioningEncoder, autoregressive.py:204-228, 444-452) and
     DiffusionTts.get_conditioning (contextual_embedder, diffusion_decoder.py:186-192, 222-230).  Inputs are the mel
     spectrograms api.py:271-289 builds from the clips; the per-clip results are combined exactly as the reference does."""
+
+    api = "tt_cond"
 
     def __init__(self, sd_ar, sd_diff, ar_cfg, diff_cfg, device="cuda", dtype=E.TT_BF16, max_frames=1024):
         self.lib = E.init()
@@ -519,19 +501,7 @@ class ConditioningStage:
         c.diff_mel, c.diff_mel_pad = sh["diff_mel"], sh["mel_pad"]
         c.max_frames = max_frames
         self.cfg = c
-        self.handle = C.c_void_p()
-        E.check(self.lib.tt_cond_create(C.byref(c), C.byref(self.w.weights), C.byref(self.handle)))
-
-    def close(self):
-        if self.handle:
-            self.lib.tt_cond_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.byref(c), C.byref(self.w.weights))
 
     def _clips(self, mels, n_mel):
         """Accepts [1, n_clips, n_mel, T] (the reference's stacked tensor) or a list of [1, n_mel, T] / [n_mel, T] clips."""
@@ -554,7 +524,7 @@ class ConditioningStage:
         acc = torch.zeros(self.cfg.ar_dim, device=self.device, dtype=torch.float32)
         out = torch.empty(self.cfg.ar_dim, device=self.device, dtype=torch.float32)
         for m in clips:
-            E.check(self.lib.tt_cond_ar_clip(self.handle, E.ptr(m), m.shape[1], E.ptr(out), E.stream_ptr()))
+            E.check(self.lib.tt_cond_ar_clip(self.h, E.ptr(m), m.shape[1], E.ptr(out), E.stream_ptr()))
             acc += out
         return (acc / len(clips))[None]
 
@@ -568,7 +538,7 @@ class ConditioningStage:
         total = 0
         for m in clips:
             frames = C.c_int(0)
-            E.check(self.lib.tt_cond_diff_clip(self.handle, E.ptr(m), m.shape[1], E.ptr(out), C.byref(frames), E.stream_ptr()))
+            E.check(self.lib.tt_cond_diff_clip(self.h, E.ptr(m), m.shape[1], E.ptr(out), C.byref(frames), E.stream_ptr()))
             acc += out
             total += frames.value
         return (acc / total)[None]
@@ -612,9 +582,11 @@ class RandomLatentStage:
         return self._run(self.nets[0], r_auto), self._run(self.nets[1], r_diffuser)
 
 
-class HifiganStage:
+class HifiganStage(_Handle):
     """HiFi-GAN decoder of the streaming path (csrc/hifigan.hip): hifi_decoder.inference(gpt_latents,
     auto_conditioning) of api_fast.py:420 / 517 (hifigan_decoder.py:259-289)."""
+
+    api = "tt_hifi"
 
     def __init__(self, sd_folded, cfg, device="cuda", dtype=E.TT_BF16, max_latents=512):
         self.lib = E.init()
@@ -636,19 +608,7 @@ class HifiganStage:
         c.lrelu_slope = cfg.lrelu_slope
         c.max_latents = max_latents
         self.c = c
-        self.handle = C.c_void_p()
-        E.check(self.lib.tt_hifi_create(C.byref(c), C.byref(self.w.weights), C.byref(self.handle)))
-
-    def close(self):
-        if self.handle:
-            self.lib.tt_hifi_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.byref(c), C.byref(self.w.weights))
 
     def inference(self, latents, g):
         """latents f32 [1, T, in_channels], g f32 [1, cond_channels] -> wav f32 [1, 1, frames * hop] (on the device)."""
@@ -658,13 +618,15 @@ class HifiganStage:
         n = self.lib.tt_hifi_output_frames(T) * self.cfg.hop
         wav = torch.empty(n, device=self.device, dtype=torch.float32)
         ns = C.c_int(0)
-        E.check(self.lib.tt_hifi_run(self.handle, E.ptr(lat), T, E.ptr(gv), E.ptr(wav), C.byref(ns), E.stream_ptr()))
+        E.check(self.lib.tt_hifi_run(self.h, E.ptr(lat), T, E.ptr(gv), E.ptr(wav), C.byref(ns), E.stream_ptr()))
         assert ns.value == n, (ns.value, n)
         return wav[None, None]
 
 
-class VocoderStage:
+class VocoderStage(_GuardedHandle):
     """UnivNetGenerator.inference (vocoder.py:300-312)."""
+
+    api = "tt_voc"
 
     def __init__(self, sd_folded, cfg: VocoderConfig = VocoderConfig(), device="cuda", dtype=E.TT_BF16, max_frames=2304):
         self.lib = E.init()
@@ -673,23 +635,7 @@ class VocoderStage:
         self.w = pack.pack_vocoder(sd_folded, cfg, self.device, dtype)
         c = E.VocConfig()
         c.dtype, c.max_frames, c.mel_channels, c.mel_pad = dtype, max_frames, cfg.n_mel_channels, self.w.mel_pad
-        self.h = E.vp()
-        E.check(self.lib.tt_voc_create(C.byref(c), C.byref(self.w.weights), C.byref(self.h)))
-
-    def close(self):
-        if self.h:
-            self.lib.tt_voc_destroy(self.h)
-            self.h = E.vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def guard(self, reset=True):
-        """Workgroups that met non-finite predicted LVC kernels since the last reset (operand-overflow guard; read after a synchronisation)."""
-        return E.guard_count(self.lib.tt_voc_guard(self.h, int(reset)))
+        self._create(C.byref(c), C.byref(self.w.weights))
 
     def inference(self, mel, z):
         """mel f32 [1, 100, S]; z f32 [1, 64, S+10] -> audio [1, 1, S*256]."""
