@@ -141,6 +141,32 @@ int tt_ar_stream_latents(tt_ar* h, int B, int n, float* out, void* stream);
  *   TT_AR_OPT_LOOKAHEAD  [6]  decode steps the host may launch ahead of the device (the loop is paced by progress words the
  *                             last kernel of a step publishes to pinned memory; no queue drain inside the loop) */
 #define TT_AR_OPT_LOOKAHEAD 4
+/*   TT_AR_OPT_SESSIONS   [0]  value 1 makes the handle a SESSION handle: each of its S = max_batch rows (S <= 4) serves one streaming
+ *                             session with its own prefix, token count, Philox key, repetition mask and stop state, all in device
+ *                             memory, so that sessions start and end independently while every step of every running row replays
+ *                             ONE kept step graph (admitting or retiring a session never re-captures: tt_ar_stat(h, 0) holds).
+ *                             Allowed only on a fresh handle (before the first prefill) with max_batch <= 4, 16-bit operands and
+ *                             max_groups >= max_batch, and a prefix capacity whose keys and values fit the decode attention's 160 KB
+ *                             of LDS next to the scores (max_prefix <= about 600 at max_new_tokens = 500; the exact bound is
+ *                             8 KB per 64 prefix rows + 1 KB per 8 + 4 bytes per prefix row and KV slot); selects the GEMV-shaped
+ *                             decode step for the handle's whole life.  A session's
+ *                             codes and latents are bit-identical to the same session alone on a max_batch = 1 handle, whatever the
+ *                             other rows do and whichever slot it sits in.  On a session handle:
+ *                               tt_ar_prefill_group(h, slot, S, prefix, P, stream) admits a session into a free slot (the running
+ *                                 rows are untouched); an occupied slot or a prefix beyond max_prefix is refused before anything changes;
+ *                               tt_ar_generate_chunk(h, S, first (ignored), n_more, ldcodes, s, codes, n_total_host[S],
+ *                                 finished_host[S], stream) advances every running row by up to n_more tokens (a row stops at its
+ *                                 stop token, which it counts) into codes int32 [S][ldcodes], row = slot, each row from column 0;
+ *                                 s->group_seeds[slot] (or s->seed) is a session's Philox key, taken at its first step.  The scalars
+ *                                 temperature / top_p / repetition_penalty / top_k / typical_mass belong to the handle while a session
+ *                                 that has sampled runs: other values are refused; exp_noise is refused;
+ *                               tt_ar_stream_latents(h, S, n, out, stream) returns out f32 [S][n][D], row r's latents 0 .. n - 1
+ *                                 (latent 0 from its admission); rows holding fewer than n carry undefined tails;
+ *                               tt_ar_generate, tt_ar_begin and tt_ar_decode_step are refused.
+ *   TT_AR_OPT_SESSION_CLOSE   retires the session in slot `value` of a session handle (finished or not); the slot is free for the
+ *                             next admission. */
+#define TT_AR_OPT_SESSIONS 5
+#define TT_AR_OPT_SESSION_CLOSE 6
 int tt_ar_set_option(tt_ar* h, int option, int value);
 /* Operand-overflow guard: the row norms and the sampler count launches that met a non-finite value (an fp16 operand beyond 65504
  * upstream).  Returns the count as of the last finished tt_ar_generate[_chunk] / tt_ar_latents (>= 0; tt_last_error() then names

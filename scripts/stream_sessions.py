@@ -1,0 +1,96 @@
+"""Several streaming sessions in one decode batch (TT_AR_OPT_SESSIONS): per-token step time with 1 .. 4 running sessions, aggregate
+tokens per second, and the first-piece latency of a session admitted while three others run.
+
+    python scripts/stream_sessions.py [--dtype bf16] [--tokens 120] [--out profiles/r07_stream_sessions.json]
+
+Full-size synthetic weights with the stop token suppressed (every session runs its whole length).  Warm-up steps are excluded from
+every timing; the single-stream figure is the max_batch = 1 handle of api_fast.tts_stream on the same weights."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--tokens", type=int, default=120)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    from oracle import make_golden_full as GF
+    from tortoise_tts_amd import engine as E
+    from tortoise_tts_amd import stages
+    from tortoise_tts_amd import weights as W
+    from tortoise_tts_amd.api_fast import TextToSpeech
+    from tortoise_tts_amd.config import ARConfig, HifiganConfig
+    cfg = ARConfig()
+    dt = E.dtype_code(args.dtype)
+    sd = W.suppress_stop_token(W.synthetic_state_dict(W.ar_manifest(cfg), 1234), cfg)
+    text, auto, _ = GF.prompt()
+    N, warm = args.tokens, 20
+    res = {"dtype": args.dtype, "timed_tokens": N, "warmup_tokens": warm, "device": torch.cuda.get_device_name(0)}
+
+    single = stages.ArStage(sd, cfg, dtype=dt, max_batch=1, max_text=80, max_new_tokens=warm + N + 8, max_latent_candidates=1)
+    single.prefill(auto, text)
+    for c, _ in single.generate_stream(1, warm + N, warm, first_chunk=warm, seed=1):
+        if c.shape[1] == warm:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+    torch.cuda.synchronize()
+    res["single_handle_step_ms"] = (time.perf_counter() - t0) / N * 1e3
+    single.close()
+
+    st = stages.ArStage(sd, cfg, dtype=dt, max_batch=4, max_text=80, max_new_tokens=warm + N + 8, max_latent_candidates=1, sessions=True)
+    res["sessions"] = {}
+    for k in range(1, 5):
+        for r in range(k):
+            st.admit(r, auto, text, 10 + r)
+        st.advance(warm)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n, _ = st.advance(N)
+        torch.cuda.synchronize()
+        dt_s = time.perf_counter() - t0
+        assert n[:k] == [warm + N] * k, n
+        res["sessions"][k] = {"step_ms": dt_s / N * 1e3, "tokens_per_s": k * N / dt_s}
+        for r in range(k):
+            st.close(r)
+    res["graph_captures"] = st.stat(0)
+    st.close()
+    one = res["sessions"][1]
+    res["speedup_4_vs_1_tokens_per_s"] = res["sessions"][4]["tokens_per_s"] / one["tokens_per_s"]
+    res["step_4_vs_single_handle"] = res["sessions"][4]["step_ms"] / res["single_handle_step_ms"]
+
+    h_cfg = HifiganConfig()
+    sds = {"autoregressive": sd, "hifidecoder": W.synthetic_state_dict(W.hifigan_manifest(h_cfg), 1238)}
+    tts = TextToSpeech(state_dicts=sds, dtype=args.dtype, max_mel_tokens=200, kv_cache=True, max_streams=4)
+    lat = []
+    for trial in range(3):
+        for i in range(3):
+            tts.open_stream(text, conditioning_latents=(auto,), max_mel_tokens=200, use_deterministic_seed=i + 10 * trial)
+        pieces = tts.stream_pieces()
+        next(pieces)  # the three running sessions are past their first buffer
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sid = tts.open_stream(text, conditioning_latents=(auto,), max_mel_tokens=200, use_deterministic_seed=99 + trial)
+        for s, wav, _ in pieces:
+            if s == sid:
+                wav.cpu()
+                lat.append(time.perf_counter() - t0)
+                break
+        for _ in pieces:
+            pass
+    res["first_piece_latency_ms_with_three_running"] = [x * 1e3 for x in lat]
+    print(json.dumps(res, indent=1))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

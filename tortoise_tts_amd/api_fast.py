@@ -16,10 +16,18 @@ teacher-forced latent re-pass) and csrc/hifigan.hip.
                             0, 2, 3, ... with kv_cache=True (autoregressive.py:134-149; oracle.ar_latents(stream_positions=True),
                             pinned live against the reference's sample_stream) - which the tests use as the check.
   * handle_chunks           api_fast.py:275-309, restated (host-side tensor slicing / cross-fade).
+  * max_streams = 2 .. 4    (engine-only) several streaming sessions share one decode batch: open_stream() admits a session at any
+                            time, stream_pieces() yields (session id, wav_chunk, done) with every session on exactly the piece schedule
+                            of tts_stream, tts_stream_many() wraps the two.  The AR handle is a session handle (TT_AR_OPT_SESSIONS):
+                            one row per session, each with its own state on the device, all advanced by one captured decode step.
 
 Sampling noise comes from the engine's Philox streams keyed by use_deterministic_seed (seeds are not portable between
 generators: parity is "same latents -> same waveform", tests/test_gpu_stages.py::test_hifigan_decoder).
 """
+import inspect
+from dataclasses import dataclass
+from typing import Any
+
 import torch
 
 from . import engine as E
@@ -29,13 +37,34 @@ from .api import MODELS_DIR, _Common, _load_state_dict, _load_file, sampler_kwar
 from .config import ARConfig, HifiganConfig
 
 
+@dataclass
+class _Session:
+    """One streaming session of a max_streams > 1 instance: its row on the AR handle and the state of tts_stream's loop."""
+    sid: int
+    slot: int
+    cond: Any
+    text_tokens: Any
+    max_mel_tokens: int
+    chunk: int
+    stream_chunk_size: int
+    overlap: int
+    target: int           # token count at which the next piece is due
+    n: int = 0            # tokens sampled so far
+    emitted: int = 0
+    threshold: int = 0
+    wav_gen_prev: Any = None
+    wav_overlap: Any = None
+
+
 class TextToSpeech(_Common):
     """api_fast.py:180-229.  Engine-only keyword arguments as in tortoise_tts_amd.api.TextToSpeech: state_dicts
-    ('autoregressive', 'hifidecoder', 'rlg_auto'), dtype, configs ('ar', 'hifigan'), max_mel_tokens."""
+    ('autoregressive', 'hifidecoder', 'rlg_auto'), dtype, configs ('ar', 'hifigan'), max_mel_tokens, and max_streams (1 .. 4):
+    streaming sessions served from one shared decode batch (open_stream / stream_pieces / tts_stream_many); 1 keeps the
+    single-sequence engine of tts() / tts_stream()."""
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
-                 state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402):
+                 state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1):
         self.models_dir = models_dir
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option")
@@ -56,8 +85,19 @@ class TextToSpeech(_Common):
         self.tokenizer_args = (tokenizer_vocab_file, tokenizer_basic)
         self._tokenizer = None
         self.max_mel_tokens_cap = max_mel_tokens
-        self.ar = stages.ArStage(self._sd("autoregressive"), self.ar_cfg, self.device, self.dtype, max_batch=1, max_text=max_text_tokens,
-                                 max_new_tokens=max_mel_tokens, max_latent_candidates=1, kv_cache=self.kv_cache)
+        if not 1 <= int(max_streams) <= 4:
+            raise ValueError(f"max_streams={max_streams} outside 1 .. 4 (the sessions of one decode batch)")
+        self.max_streams = int(max_streams)
+        if self.max_streams == 1:
+            self.ar = stages.ArStage(self._sd("autoregressive"), self.ar_cfg, self.device, self.dtype, max_batch=1, max_text=max_text_tokens,
+                                     max_new_tokens=max_mel_tokens, max_latent_candidates=1, kv_cache=self.kv_cache)
+        else:
+            self.ar = stages.ArStage(self._sd("autoregressive"), self.ar_cfg, self.device, self.dtype, max_batch=self.max_streams,
+                                     max_text=max_text_tokens, max_new_tokens=max_mel_tokens, max_latent_candidates=1, kv_cache=self.kv_cache,
+                                     sessions=True)
+        self._sessions = {}      # slot -> _Session
+        self._session_settings = None
+        self._next_sid = 0
         hsd = self._sd("hifidecoder")
         if any(k.endswith("weight_v") for k in hsd):
             hsd = W.fold_weight_norm(hsd)
@@ -121,6 +161,7 @@ class TextToSpeech(_Common):
             num_autoregressive_samples=512, temperature=.8, length_penalty=1, repetition_penalty=2.0, top_p=.8, max_mel_tokens=500,
             cvvp_amount=.0, **hf_generate_kwargs):
         # (k and cvvp_amount are accepted and unused as in the reference: its fast path decodes ONE sample, there is nothing to rank)
+        self._single("tts")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -180,6 +221,7 @@ class TextToSpeech(_Common):
                    num_autoregressive_samples=512, temperature=.8, length_penalty=1, repetition_penalty=2.0, top_p=.8, max_mel_tokens=500,
                    cvvp_amount=.0, diffusion_iterations=100, cond_free=True, cond_free_k=2, diffusion_temperature=1.0,
                    **hf_generate_kwargs):
+        self._single("tts_stream")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -211,3 +253,134 @@ class TextToSpeech(_Common):
                 break
             emitted = codes.shape[1]
             threshold = chunk
+
+    # ------------------------------------------------------------------ several streams in one decode batch (max_streams > 1)
+    def _single(self, name):
+        if getattr(self, "max_streams", 1) != 1:
+            raise NotImplementedError(f"{name}: this instance serves streaming sessions (max_streams={self.max_streams}); use open_stream / "
+                                      f"stream_pieces / tts_stream_many, or an instance with max_streams=1")
+
+    @torch.no_grad()
+    def open_stream(self, text, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
+        """Admit one streaming session (max_streams > 1) and return its id.  Takes tts_stream's arguments; the session's pieces come out
+        of stream_pieces() on exactly tts_stream's schedule.  May be called at any time, also between pieces of other sessions.  Raises
+        when every slot is busy or when the sampling settings differ from those of the running sessions (they share one sampler)."""
+        if self.max_streams == 1:
+            raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
+        if "exp_noise" in kwargs:
+            raise ValueError("open_stream: injected exp_noise is not available for streaming sessions (they draw from their Philox streams)")
+        bound = inspect.signature(TextToSpeech.tts_stream).bind(self, text, **kwargs)
+        bound.apply_defaults()
+        a = bound.arguments
+        top_k, typical_mass = sampler_kwargs(a["hf_generate_kwargs"])
+        settings = (float(a["temperature"]), float(a["top_p"]), float(a["repetition_penalty"]), int(top_k), float(typical_mass))
+        free = [r for r in range(self.max_streams) if r not in self._sessions]
+        if not free:
+            raise RuntimeError(f"open_stream: all {self.max_streams} streaming slots are busy")
+        if self._sessions and settings != self._session_settings:
+            raise ValueError(f"open_stream: sampling settings {settings} differ from those of the running sessions {self._session_settings} "
+                             f"(temperature, top_p, repetition_penalty, top_k, typical_mass)")
+        max_mel_tokens = a["max_mel_tokens"]
+        seed = self.deterministic_state(seed=use_deterministic_seed)
+        text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
+        slot = free[0]
+        self.ar.admit(slot, cond, text_tokens, seed)
+        size = a["stream_chunk_size"]
+        chunk = size if size > 0 else max_mel_tokens
+        first = max(chunk, 60) if size > 0 else max_mel_tokens  # first_buffer = 60 (api_fast.py:401, 412)
+        sess = _Session(self._next_sid, slot, cond, text_tokens, max_mel_tokens, chunk, size, a["overlap_wav_len"], min(first, max_mel_tokens),
+                        threshold=first)
+        self._next_sid += 1
+        self._sessions[slot] = sess
+        self._session_settings = settings
+        return sess.sid
+
+    def close_stream(self, sid):
+        """Retire session `sid` before it ends (a client that went away): its row stops decoding and is free for the next open_stream.
+        The other sessions are untouched.  Raises KeyError for an id that is not open."""
+        for slot, sess in self._sessions.items():
+            if sess.sid == sid:
+                del self._sessions[slot]
+                self.ar.close(slot)
+                return
+        raise KeyError(f"close_stream: no open session {sid}")
+
+    def _session_piece(self, sess, n, finished):
+        """tts_stream's loop body for one session whose token count reached its piece boundary (or its end): the wav chunks it yields."""
+        codes = self.ar.session_codes(sess.slot)[:, :n]
+        done = finished or n >= sess.max_mel_tokens
+        if done and codes.shape[1] > 0 and int(codes[0, -1]) == self.stop_mel_token:
+            codes = codes[:, :-1]
+        if codes.shape[1] == 0:  # (tts_stream yields nothing at all; the session still reports its end)
+            return [(torch.zeros(0, device=self.device), True)]
+        self.last_codes = codes
+        if self.stream_latents_from == "steps":
+            latents = self.ar.session_latents(sess.slot, codes.shape[1])
+        else:
+            latents = self.ar.latents(sess.cond, sess.text_tokens, codes, stream_positions=self.kv_cache)
+        wav_gen = self.hifi_decoder.inference(latents, sess.cond).reshape(-1)
+        wav_chunk, sess.wav_gen_prev, sess.wav_overlap = self.handle_chunks(wav_gen, sess.wav_gen_prev, sess.wav_overlap, sess.overlap)
+        if not done:
+            sess.emitted, sess.threshold = codes.shape[1], sess.chunk
+            sess.target = min(n + sess.chunk, sess.max_mel_tokens)
+            return [(wav_chunk, False)]
+        if sess.stream_chunk_size > 0 and codes.shape[1] - sess.emitted == sess.threshold:  # the extra piece (see tts_stream)
+            last, sess.wav_gen_prev, sess.wav_overlap = self.handle_chunks(wav_gen, sess.wav_gen_prev, sess.wav_overlap, sess.overlap)
+            return [(wav_chunk, False), (last, True)]
+        return [(wav_chunk, True)]
+
+    @torch.no_grad()
+    def stream_pieces(self):
+        """Generator of (session id, wav_chunk, done) over every open session until none is left.  All running sessions advance in one
+        decode batch, by the smallest distance of any of them to its next piece boundary (or its own max_mel_tokens), so none overshoots;
+        each session's pieces equal what tts_stream would have yielded for it.  Sessions opened between pieces join the batch."""
+        if self.max_streams == 1:
+            raise NotImplementedError("stream_pieces: create the instance with max_streams=2 .. 4")
+        while self._sessions:
+            step = min(sess.target - sess.n for sess in self._sessions.values())
+            temperature, top_p, repetition_penalty, top_k, typical_mass = self._session_settings
+            n_total, finished = self.ar.advance(max(step, 1), temperature=temperature, top_p=top_p, repetition_penalty=repetition_penalty,
+                                                top_k=top_k, typical_mass=typical_mass)
+            batch = sorted(self._sessions.items())  # the sessions this advance served (open_stream / close_stream may run between pieces)
+            for slot, sess in batch:
+                if self._sessions.get(slot) is not sess:  # closed while an earlier piece of this round was out
+                    continue
+                sess.n = n_total[slot]
+                if not (finished[slot] or n_total[slot] >= sess.target):
+                    continue
+                pieces = self._session_piece(sess, n_total[slot], finished[slot])
+                if pieces[-1][1]:  # the session is over: its row is free for the next admission
+                    del self._sessions[slot]
+                    self.ar.close(slot)
+                for wav_chunk, done in pieces:
+                    yield sess.sid, wav_chunk, done
+
+    def tts_stream_many(self, texts, **kwargs):
+        """Stream several texts at once (max_streams > 1): a generator of (index into texts, wav_chunk, done).  kwargs are tts_stream's,
+        shared by all texts; use_deterministic_seed may be a list with one seed per text.  Texts beyond the free slots are admitted as
+        earlier sessions end."""
+        seeds = kwargs.pop("use_deterministic_seed", None)
+        if not isinstance(seeds, (list, tuple)):
+            seeds = [seeds] * len(texts)
+        pending = list(range(len(texts)))
+        index = {}
+
+        def admit():
+            while pending and len(self._sessions) < self.max_streams:
+                i = pending.pop(0)
+                index[self.open_stream(texts[i], use_deterministic_seed=seeds[i], **kwargs)] = i
+
+        admit()
+        pieces = self.stream_pieces()
+        while True:
+            try:
+                sid, wav_chunk, done = next(pieces)
+            except StopIteration:
+                if not pending:
+                    return
+                admit()
+                pieces = self.stream_pieces()
+                continue
+            yield index[sid], wav_chunk, done
+            if done:
+                admit()

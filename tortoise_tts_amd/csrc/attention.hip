@@ -1035,12 +1035,22 @@ __global__ __launch_bounds__(NSEQ * 64, 4) void decode_attn_lds_kernel(DecodeAtt
   TT_ASTAMP(0);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tgen = *a.step + 1;       // generated keys 0..*step (read first: a scalar load, nothing in front of it to drain)
   const int h = (int)blockIdx.x;      // grid = (heads, sequence groups)
   const int b_raw = (int)blockIdx.y * NSEQ + wave;
   const int b = min(b_raw, a.B - 1);  // surplus waves of the last group repeat its last sequence (never stored)
-  int P1 = a.P1;
+  // generated keys 0..*step (read first: a scalar load, nothing in front of it to drain); a session handle's row (NSEQ == 1: one
+  // sequence per workgroup) reads its own newest slot, prefix length and prefix cache - a row that does not decode leaves at once
+  int tgen, P1 = a.P1;
   size_t goff = 0;
+  if (NSEQ == 1 && a.row_slot) {
+    const int sl = a.row_slot[b];
+    if (sl < 0) return;
+    tgen = sl + 1;
+    P1 = a.row_p1[b];
+    goff = (size_t)b * a.prefix_group_stride;
+  } else {
+    tgen = *a.step + 1;
+  }
   if (a.ngroups > 1) {  // several utterances in one batch: this workgroup's sequences all belong to one of them (group_size % NSEQ == 0)
     const int grp = ((int)blockIdx.y * NSEQ) / a.group_size;
     P1 = a.p1_tab[grp];
@@ -1245,6 +1255,10 @@ extern "C" int ttx_attn_stamps(unsigned long long* out, int nwg) {
 namespace tt {
 #endif
 
+size_t decode_attention_session_lds(int p1_cap, int tmax) {
+  return (size_t)((p1_cap + 63) >> 6) * 8 * 1024 + (size_t)((p1_cap + 7) >> 3) * 1024 + (size_t)(p1_cap + tmax) * sizeof(float);
+}
+
 int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stream) {
   if (dtype == DT_F32) return decode_attn_f32_launch(a, stream);  // verification mode (attention_f32.hip)
   TT_REQUIRE(a.B > 0 && a.heads > 0 && a.P1 >= 0 && a.tmax > 0, "decode_attention: bad shape");
@@ -1255,6 +1269,10 @@ int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stre
   // shared-prefix kernel with 4 sequences per workgroup (measured 2 % ahead of 16 at 256 candidates and 40 % ahead at 32:
   // more, smaller workgroups); the per-wave kernel only when the staged prefix + score rows do not fit the LDS (very long prompts)
   int nseq = a.variant == 1 ? 0 : a.variant == 2 ? 16 : 4;
+  if (a.row_slot) {  // session handle: one row per workgroup, the LDS sized for the prefix capacity a.P1
+    TT_REQUIRE(a.row_p1 && a.prefix_group_stride && a.ngroups <= 1 && a.P1 >= 1, "decode_attention: per-row sessions need row_p1, a prefix stride and a prefix capacity");
+    nseq = 1;
+  }
   if (a.ngroups > 1) {
     TT_REQUIRE(a.ngroups <= 16 && a.group_size > 0 && a.group_size % 4 == 0 && a.B == a.ngroups * a.group_size,
                "decode_attention: %d groups of %d sequences (a multiple of 4) do not make %d sequences", a.ngroups, a.group_size, a.B);
@@ -1262,6 +1280,8 @@ int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stre
   }
   const int kl_bytes = ((a.P1 + 63) >> 6) * 8 * 1024, vl_bytes = ((a.P1 + 7) >> 3) * 1024;
   if (a.P1 < 1) nseq = 0;
+  TT_REQUIRE(!a.row_slot || decode_attention_session_lds(a.P1, a.tmax) <= DECODE_LDS_CAP,
+             "decode_attention: a session row's prefix capacity %d does not fit the LDS", a.P1);
   if (nseq && (size_t)kl_bytes + vl_bytes + (size_t)nseq * ctx_cap * sizeof(float) > 160 * 1024) nseq = nseq == 16 ? 4 : 0;
   if (nseq && (size_t)kl_bytes + vl_bytes + (size_t)nseq * ctx_cap * sizeof(float) > 160 * 1024) nseq = 0;
   if (nseq) {
@@ -1276,8 +1296,8 @@ int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stre
       }                                                                                                                              \
       launch_timed(ps, decode_attn_lds_kernel<T, NS>, blocks, dim3(NS * 64), smem, stream, a, ctx_cap, kl_bytes, vl_bytes);          \
     } while (0)
-    if (dtype == DT_BF16) { if (nseq == 16) TT_DEC(bf16, 16); else TT_DEC(bf16, 4); }
-    else { if (nseq == 16) TT_DEC(f16, 16); else TT_DEC(f16, 4); }
+    if (dtype == DT_BF16) { if (nseq == 16) TT_DEC(bf16, 16); else if (nseq == 1) TT_DEC(bf16, 1); else TT_DEC(bf16, 4); }
+    else { if (nseq == 16) TT_DEC(f16, 16); else if (nseq == 1) TT_DEC(f16, 1); else TT_DEC(f16, 4); }
 #undef TT_DEC
     TT_CHECK_HIP(hipGetLastError());
     return 0;

@@ -150,6 +150,21 @@ int tt_op_decode_attention(int dtype, const void* q, const void* kp, const void*
   return 0;
 }
 
+int tt_op_decode_attention_rows(int dtype, const void* q, const void* kp, const void* vp, long long prefix_stride, const int* p1_rows, int p1_cap,
+                                const void* kc, const void* vc, int tmax, const int* slot_rows, void* out, int B, int heads, void* stream) {
+  TT_REQUIRE(q && kp && vp && p1_rows && kc && vc && slot_rows && out && prefix_stride > 0 && p1_cap >= 1 && B >= 1 && heads >= 1 && tmax >= 1,
+             "tt_op_decode_attention_rows: bad arguments");
+  TT_REQUIRE(dtype == DT_BF16 || dtype == DT_F16, "tt_op_decode_attention_rows: 16-bit operands only");
+  DecodeAttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = q; a.kp = kp; a.vp = vp; a.P1 = p1_cap; a.kc = kc; a.vc = vc; a.tmax = tmax;
+  a.out = out; a.B = B; a.heads = heads;
+  a.row_slot = slot_rows; a.row_p1 = p1_rows; a.prefix_group_stride = (size_t)prefix_stride;
+  TT_TRY(decode_attention_launch(dtype, a, (hipStream_t)stream));
+  TT_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+  return 0;
+}
+
 // One sampling step on caller-provided state (seen bitmask, unfinished flags); `step` indexes codes / exp_noise.
 int tt_op_sample(const float* logits, int ldl, int B, int V, unsigned* seen, const tt_sampling* sp, int step, int* unfinished,
                  int stop_token, int* codes, int ldcodes, void* stream) {

@@ -34,7 +34,8 @@ __device__ __forceinline__ float gv_dot8(Vec<f16>::x8 a, Vec<f16>::x8 b, float a
 }
 
 // EPI: GEMV_F32 out_f32 = acc + bias (lm_head) | GEMV_RES x += acc + bias in place (projections) | GEMV_GELU_T out_t = gelu_tanh(acc + bias) (c_fc)
-//      | GEMV_QKV q * scale -> qbuf, K / V appended to the per-sequence cache at the device-side step (EpiQkvDecode's layout)
+//      | GEMV_QKV q * scale -> qbuf, K / V appended to the per-sequence cache at the device-side step (EpiQkvDecode's layout) - on a session
+//        handle at every row's own slot (row_slot)
 // LN: the activation rows are LayerNorm(ln_x rows) computed here (K == 1024: a lane's sixteen channels of each f32 residual row, two-pass variance
 //     over the wave, affine, rounded to T like the row-norm kernel's output) while the weight rows are in flight - every workgroup repeats the
 //     4 KB row's norm instead of a launch of its own doing it once.
@@ -104,7 +105,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
   float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (a.bias) bv = *(const float4*)(a.bias + n0);
   int t = 0;
-  if (EPI == GEMV_QKV) t = *a.step;
+  int trow[MR];  // session handle: every row's own slot, requested with the bias (off the tail of the stores); < 0: that row stores nothing
+  if (EPI == GEMV_QKV && !a.row_slot) t = *a.step;
+#pragma unroll
+  for (int r = 0; r < MR; ++r) trow[r] = (EPI == GEMV_QKV && a.row_slot) ? a.row_slot[min(r, a.M - 1)] : t;
 #pragma unroll
   for (int r = 0; r < MR; ++r) {
     float v[4];
@@ -126,6 +130,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs a) {
     } else if (EPI == GEMV_GELU_T) {
       *(typename Vec<T>::x4*)((T*)a.out_t + (size_t)r * a.ldot + n0) = pack4<T>(gelu_tanh(v[0]), gelu_tanh(v[1]), gelu_tanh(v[2]), gelu_tanh(v[3]));
     } else {  // GEMV_QKV: column n0 = part * dmodel + h * 64 + d, d a multiple of 4 (gemm_impl.h EpiQkvDecode::store)
+      t = trow[r];
+      if (a.row_slot && t < 0) continue;
       const int part = n0 / a.dmodel, cc = n0 - part * a.dmodel;
       const int h = cc >> 6, d = cc & 63;
       const size_t bh = (size_t)r * a.heads + h;
@@ -146,7 +152,7 @@ bool gemv_supported(int dtype, const GemvArgs& a) {
                               : (a.A && (a.lda & 7) == 0 && ((size_t)a.A & 15) == 0);
   return (dtype == DT_BF16 || dtype == DT_F16) && a.M >= 1 && a.M <= 4 && (a.K == 1024 || a.K == 2048 || a.K == 4096) && (a.N & 3) == 0 && rows_ok &&
          (a.ldw & 7) == 0 && ((size_t)a.W & 15) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) &&
-         (a.epi == GEMV_QKV ? (a.step && a.qbuf && a.kc && a.vc && a.dmodel % 64 == 0 && a.N == 3 * a.dmodel && a.heads * 64 == a.dmodel)
+         (a.epi == GEMV_QKV ? ((a.step || a.row_slot) && a.qbuf && a.kc && a.vc && a.dmodel % 64 == 0 && a.N == 3 * a.dmodel && a.heads * 64 == a.dmodel)
           : a.epi == GEMV_GELU_T ? (a.out_t && ((size_t)a.out_t & 7) == 0 && (a.ldot & 3) == 0)
                                  : (a.out_f32 && ((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0));
 }

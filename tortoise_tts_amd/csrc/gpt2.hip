@@ -89,6 +89,17 @@ struct tt_ar : EngineHandle {
   int gemv = 0;  // 0 | 1 GEMV launches | 2 GEMV launches that also do the layer norm in front of them (five launches per layer)
   int drains = 0;     // host-side queue drains the launch loop fell back to (0 when the progress words arrive)
   bool typical = false;  // the last generation ran the typical-sampling mask ahead of the sampler (one more launch per step)
+  // Session handles (TT_AR_OPT_SESSIONS): every row is one streaming session with its own state in device memory (sess: int[4][max_batch],
+  // SessPlane) - admitted (tt_ar_prefill_group into its slot), advanced (tt_ar_generate_chunk) and retired (TT_AR_OPT_SESSION_CLOSE)
+  // independently of the others, all through ONE captured step graph.  Its prefix lives in prefix-cache group `slot`; its first token
+  // is drawn from pre_logits[slot], the logits of its admission.  The host mirror below is refreshed at the end of every call.
+  int sessions = 0;
+  int* sess = nullptr;
+  int* sess_host = nullptr;       // pinned copy of sess, read back at the end of a chunk
+  float* pre_logits = nullptr;    // [max_batch][Vp]
+  int s_n[16] = {0}, s_run[16] = {0};
+  bool s_key_pending[16] = {false};
+  tt_sampling s_scalars;          // the sampling scalars of the running sessions (exp_noise / seeds / group_seeds unused)
 };
 
 namespace tt { int g_ar_gemv = 2; }  // ttx_kernel_variant(TTX_AR_GEMV), read at tt_ar_create: handles of <= 4 sequences run 0 = the MFMA decode GEMMs | 1 = GEMV launches | 2 = GEMVs with the layer norms inside
@@ -176,7 +187,7 @@ static int pick_split(int B, int N, int K) {
 // lat_index: >= 0 files the normalised row(s) as that latent (prefill: 0); -1: under the device-side step counter (decode step
 // feeding token i - 1 produces latent i); -2: no capture
 static int ar_head_norm(tt_ar* e, float* x, void* h_out, int M, const float* add_bias, const float* slabs, int nslab, int slab_rows,
-                        hipStream_t s, int lat_index = -2) {
+                        hipStream_t s, int lat_index = -2, int lat_row = 0) {
   RowNormArgs a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.ldx = e->D; a.M = M; a.D = e->D;
@@ -193,12 +204,20 @@ static int ar_head_norm(tt_ar* e, float* x, void* h_out, int M, const float* add
   if (e->lat && lat_index != -2 && M <= e->lat_batch) {
     a.out_f32 = e->lat; a.ldo32 = e->D;
     a.f32_slot_stride = (size_t)e->lat_batch * e->D;
-    if (lat_index >= 0) a.out_f32 += (size_t)lat_index * a.f32_slot_stride;
+    if (lat_index >= 0) a.out_f32 += (size_t)lat_index * a.f32_slot_stride + (size_t)lat_row * e->D;
+    else if (e->sessions) { a.f32_row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; a.f32_slot_base = 1; }  // every row its own index
     else { a.f32_slot = e->state + 1; a.f32_slot_base = 1; }
   }
   return rownorm_launch(e->cfg.dtype, a, s);
 }
-static int ar_head_gemm(tt_ar* e, int M, hipStream_t s, int logits_row0 = 0) {
+static int ar_head_gemm(tt_ar* e, int M, hipStream_t s, int logits_row0 = 0, float* out = nullptr) {
+  if (out) {  // (a session's admission: its own logits row, outside the decode step's rows)
+    GemvArgs v;
+    memset(&v, 0, sizeof(v));
+    v.A = e->h; v.lda = e->D; v.W = e->w_head_p; v.ldw = e->D; v.M = M; v.N = e->Vp; v.K = e->D; v.bias = e->b_head_p; v.epi = GEMV_F32;
+    v.out_f32 = out; v.ldo32 = e->Vp;
+    return gemv_launch(e->cfg.dtype, v, s);
+  }
   if (e->gemv && M <= 4) {
     GemvArgs v;
     memset(&v, 0, sizeof(v));
@@ -235,6 +254,7 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
       v.A = e->h; v.lda = D; v.W = w.w_qkv; v.ldw = D; v.M = nb; v.N = 3 * D; v.K = D; v.bias = w.b_qkv; v.epi = GEMV_QKV;
       v.step = e->state + 1; v.qbuf = e->q; v.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es); v.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
       v.heads = H; v.tmax = e->tmax; v.dmodel = D; v.q_scale = 0.125f;
+      if (e->sessions) { v.step = nullptr; v.row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; }
       if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln1_g; v.ln_b = w.ln1_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
       TT_TRY(gemv_launch(dt, v, s));
       DecodeAttnArgs a;
@@ -244,6 +264,11 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
       a.vp = offset_t(e->vp, (size_t)l * e->prefix_layer_elems, e->es);
       a.P1 = e->P1; a.kc = v.kc; a.vc = v.vc; a.tmax = e->tmax; a.step = e->state + 1;
       a.out = e->attn; a.B = nb; a.heads = H; a.host_tgen = e->host_slot + 1;
+      if (e->sessions) {  // every row its own prefix group, prefix length and newest slot - all device data; P1 = the capacity
+        a.P1 = e->cfg.max_prefix; a.step = nullptr; a.host_tgen = 0;
+        a.row_slot = v.row_slot; a.row_p1 = e->sess + SESS_P1 * e->cfg.max_batch;
+        a.prefix_group_stride = (size_t)e->cfg.layers * e->prefix_layer_elems;
+      }
       TT_TRY(decode_attention_launch(dt, a, s));
       memset(&v, 0, sizeof(v));
       v.A = e->attn; v.lda = D; v.W = w.w_proj; v.ldw = D; v.M = nb; v.N = D; v.K = D; v.bias = w.b_proj; v.epi = GEMV_RES; v.out_f32 = x; v.ldo32 = D;
@@ -416,11 +441,42 @@ void tt_ar_destroy(tt_ar* e) {
   e->step.drop();
   if (e->par_host) (void)hipHostFree(e->par_host);
   if (e->progress_host) (void)hipHostFree(e->progress_host);
+  if (e->sess_host) (void)hipHostFree(e->sess_host);
   delete e;
+}
+
+// Session handles: admit a session into slot `slot` of the S = max_batch rows.  The running rows are untouched: the prefix goes to
+// prefix-cache group `slot`, its logits to pre_logits[slot], its start-token latent to latent 0 of row `slot`.
+static int ar_admit(tt_ar* e, int slot, int S, const float* prefix_emb, int P, hipStream_t stream) {
+  TT_REQUIRE(S == e->cfg.max_batch && slot >= 0 && slot < S, "tt_ar_prefill_group: slot %d of %d (a session handle has %d slots)", slot, S, e->cfg.max_batch);
+  TT_REQUIRE(P >= 1 && P + 1 <= e->cfg.max_prefix, "tt_ar_prefill: prefix of %d rows exceeds capacity %d", P + 1, e->cfg.max_prefix);
+  TT_REQUIRE(e->s_run[slot] == SESS_FREE, "tt_ar_prefill_group: slot %d holds a session (close it with TT_AR_OPT_SESSION_CLOSE first)", slot);
+  return e->sb.run(stream, [&](hipStream_t s) -> int {
+    const int D = e->D, P1 = P + 1;
+    TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RowNormArgs a;  // start-token row, as tt_ar_prefill_group
+    memset(&a, 0, sizeof(a));
+    a.x = e->x + (size_t)P * D; a.ldx = D; a.M = 1; a.D = D;
+    a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * D; a.ldxin = D;
+    a.add_bias = e->w.mel_pos;
+    a.write_x = 1; a.mode = NORM_NONE;
+    TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
+    TT_TRY(gpt_trunk_full(e, 1, P1, true, s, slot));
+    TT_TRY(ar_head_norm(e, e->x + (size_t)P * D, e->h, 1, nullptr, e->slabs, 0, 1, s, 0, slot));
+    TT_TRY(ar_head_gemm(e, 1, s, 0, e->pre_logits + (size_t)slot * e->Vp));
+    TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->codes_own + (size_t)slot * e->tmax), e->cfg.stop_mel_token, (size_t)e->tmax, s));
+    TT_TRY(ar_sess_admit_launch(e->sess, S, slot, P1, e->seen, e->unfinished, e->V, e->cfg.start_mel_token, s));
+    e->P1g[slot] = P1;
+    e->s_n[slot] = 0;
+    e->s_run[slot] = SESS_RUNNING;
+    e->s_key_pending[slot] = true;
+    return 0;
+  });
 }
 
 int tt_ar_prefill_group(tt_ar* e, int group, int n_groups, const float* prefix_emb, int P, void* stream) {
   TT_REQUIRE(e && prefix_emb, "tt_ar_prefill: null argument");
+  if (e->sessions) return ar_admit(e, group, n_groups, prefix_emb, P, (hipStream_t)stream);
   TT_REQUIRE(n_groups >= 1 && n_groups <= e->cfg.max_groups && group >= 0 && group < n_groups, "tt_ar_prefill_group: group %d of %d (capacity %d groups)", group, n_groups, e->cfg.max_groups);
   TT_REQUIRE(P >= 1 && P + 1 <= e->cfg.max_prefix, "tt_ar_prefill: prefix of %d rows exceeds capacity %d", P + 1, e->cfg.max_prefix);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
@@ -471,6 +527,7 @@ int tt_ar_get_logits(tt_ar* e, float* dst, int rows, void* stream) {
 
 int tt_ar_begin(tt_ar* e, int B, void* stream) {
   TT_REQUIRE(e && B >= 1 && B <= e->cfg.max_batch, "tt_ar_begin: batch %d exceeds capacity", B);
+  TT_REQUIRE(!e->sessions, "tt_ar_begin: a session handle decodes with tt_ar_generate_chunk");
   TT_REQUIRE(e->P1 > 0, "tt_ar_begin: call tt_ar_prefill first");
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
     e->B = B;
@@ -480,7 +537,7 @@ int tt_ar_begin(tt_ar* e, int B, void* stream) {
 }
 
 int tt_ar_decode_step(tt_ar* e, const int* tokens, void* stream) {
-  TT_REQUIRE(e && tokens && e->B > 0, "tt_ar_decode_step: call tt_ar_begin first");
+  TT_REQUIRE(e && tokens && e->B > 0 && !e->sessions, "tt_ar_decode_step: call tt_ar_begin first");
   // the step about to run writes KV slot host_slot + 1 and reads mel position row host_slot + 1 + mel_pos_offset
   TT_REQUIRE(e->host_slot + 1 < e->tmax, "tt_ar_decode_step: all %d KV slots of this handle are used", e->tmax);
   TT_REQUIRE(e->host_slot + 1 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_decode_step: step %d is beyond the mel position table (%d rows)", e->host_slot + 1, e->cfg.mel_pos_len);
@@ -643,6 +700,7 @@ int tt_ar_generate(tt_ar* e, int B, int max_new, const tt_sampling* sp, int* cod
   TT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "tt_ar_generate: batch %d exceeds capacity %d", B, e->cfg.max_batch);
   TT_REQUIRE(max_new >= 1 && max_new <= e->tmax, "tt_ar_generate: max_new %d exceeds capacity %d", max_new, e->tmax);
   TT_REQUIRE(max_new - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate: max_new %d exceeds the mel position table", max_new);
+  TT_REQUIRE(!e->sessions, "tt_ar_generate: a session handle decodes with tt_ar_generate_chunk");
   TT_REQUIRE(e->P1 > 0, "tt_ar_generate: call tt_ar_prefill first");
   TT_TRY(ar_generate_check(e, B, true, sp));
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
@@ -650,9 +708,131 @@ int tt_ar_generate(tt_ar* e, int B, int max_new, const tt_sampling* sp, int* cod
   });
 }
 
+static bool same_scalars(const tt_sampling& a, const tt_sampling& b) {
+  return a.temperature == b.temperature && a.top_p == b.top_p && a.repetition_penalty == b.repetition_penalty && a.top_k == b.top_k &&
+         a.typical_mass == b.typical_mass;
+}
+
+// Session handles: every running row advances by up to n_more tokens through the one kept step graph.  A row stops advancing at its
+// stop token; the loop ends early once no row runs.  codes [S][ldcodes]; n_total_host / finished_host [S].
+static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_sampling* sp, int* codes, int* n_total_host, int* finished_host,
+                             hipStream_t stream) {
+  TT_REQUIRE(S == e->cfg.max_batch, "tt_ar_generate_chunk: a session handle advances all %d slots (got %d)", e->cfg.max_batch, S);
+  TT_REQUIRE(sp->exp_noise == nullptr, "tt_ar_generate_chunk: injected exp_noise is not available on a session handle");
+  TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
+             (double)sp->typical_mass);
+  TT_REQUIRE(sp->temperature > 0.f && sp->top_p > 0.f && sp->repetition_penalty > 0.f, "tt_ar_generate_chunk: bad sampling parameters");
+  bool running = false, others = false;
+  for (int r = 0; r < S; ++r) {
+    if (e->s_run[r] != SESS_RUNNING) continue;
+    running = true;
+    others = others || !e->s_key_pending[r];
+    const int target = e->s_n[r] + n_more;
+    TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "tt_ar_generate_chunk: slot %d: %d + %d tokens exceed capacity (%d code columns, %d KV slots)", r,
+               e->s_n[r], n_more, ldcodes, e->tmax);
+    TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate_chunk: slot %d: %d tokens exceed the mel position table", r, target);
+  }
+  // the sampling scalars belong to the handle while a session that already sampled runs
+  TT_REQUIRE(!others || same_scalars(*sp, e->s_scalars), "tt_ar_generate_chunk: sampling settings differ from those of the running sessions");
+  return e->sb.run(stream, [&](hipStream_t s) -> int {
+    if (running) {
+      e->s_scalars = *sp;
+      SampleArgs sa;
+      memset(&sa, 0, sizeof(sa));
+      sa.B = S; sa.V = e->V; sa.seen = e->seen;
+      sa.rep_penalty = sp->repetition_penalty; sa.temperature = sp->temperature; sa.top_p = sp->top_p; sa.top_k = sp->top_k;
+      sa.state = e->state; sa.unfinished = e->unfinished; sa.stop_token = e->cfg.stop_mel_token;
+      sa.codes = e->codes_own; sa.ldcodes = e->tmax; sa.next_tok = e->next_tok; sa.unfinished_count = e->unfinished_count;
+      sa.embed_x = e->x; sa.tok_emb = e->w.mel_emb; sa.pos_emb = e->w.mel_pos; sa.D = e->D; sa.pos_offset = e->cfg.mel_pos_offset;
+      sa.pos_len = e->cfg.mel_pos_len;
+      sa.guard = e->guard.dev;
+      sa.typical_mass = sp->typical_mass; sa.typical_out = e->typ_logits;
+      sa.keys_dev = e->par_dev->keys;
+      sa.row_offset_dev = &e->par_dev->row_offset;
+      sa.sess = e->sess; sa.pre_logits = e->pre_logits;
+      sa.logits = e->logits; sa.ldl = e->Vp; sa.ldg = e->Vp;
+      e->typical = sp->typical_mass != 0.f;
+      // a session's key is taken at its first step; the others keep theirs
+      for (int r = 0; r < S; ++r)
+        if (e->s_run[r] == SESS_RUNNING && e->s_key_pending[r]) e->par_host->keys[r] = sp->group_seeds ? sp->group_seeds[r] : sp->seed;
+      e->par_host->row_offset = 0;
+      TT_CHECK_HIP(hipMemcpyAsync(e->par_dev, e->par_host, sizeof(ArParams), hipMemcpyHostToDevice, s));
+      // the counters of this call: state[0] = its steps so far, state[2] = the step after which no row ran (-1: none yet)
+      TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->state, 0, 1, s));
+      TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->state + 1), -1, 2, s));
+      TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->unfinished_count, 0, (size_t)e->tmax + 8, s));
+      // the input rows of the next step (a prefill / latent pass since the last chunk used e->x as its residual stream)
+      TT_TRY(ar_embed_rows_launch(e->next_tok, e->sess + SESS_SLOT * S, e->w.mel_emb, e->w.mel_pos, e->x, S, e->D, e->cfg.mel_pos_offset, s));
+      volatile int* prog = e->progress_host;
+      prog[0] = 0;
+      prog[1] = -1;
+      auto step_enqueue = [&](hipStream_t st) -> int {
+        TT_TRY(decode_layers_enqueue(e, st));
+        TT_TRY(ar_head_gemm(e, S, st));
+        TT_TRY(sample_launch(sa, st));
+        return ar_sess_advance_launch(e->state, e->sess, S, e->unfinished, e->unfinished_count, e->progress_dev, st);
+      };
+      const bool use_graph = graphs_enabled();
+      if (use_graph) {
+        // baked in: the sampler's argument block and the profiler switch - no batch, prefix length or step of any row
+        std::vector<unsigned char> key(sizeof(sa) + 4 * sizeof(int));
+        memcpy(key.data(), &sa, sizeof(sa));
+        int geo[4] = {S, -1, e->cfg.max_prefix, g_prof_on ? 1 : 0};
+        memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
+        TT_TRY(e->step.ensure(s, key.data(), key.size(), "tt_ar_generate_chunk", [&]() -> int { return step_enqueue(s); }));
+      }
+      int rc = 0;
+      for (int step = 0; step < n_more; ++step) {
+        const auto wait0 = std::chrono::steady_clock::now();
+        while (step - prog[0] >= e->lookahead && prog[1] < 0) {
+          if (std::chrono::steady_clock::now() - wait0 > std::chrono::milliseconds(200)) {  // (as ar_generate_run)
+            int st3[3] = {0, 0, -1};
+            hipError_t ce = hipStreamSynchronize(s);
+            if (ce == hipSuccess) ce = hipMemcpy(st3, e->state, sizeof(st3), hipMemcpyDeviceToHost);
+            if (ce != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; break; }
+            prog[0] = st3[0];
+            if (st3[2] >= 0) prog[1] = st3[2];
+            e->drains += 1;
+            break;
+          }
+          usleep(50);
+        }
+        if (rc || prog[1] >= 0) break;
+        rc = use_graph ? e->step.launch(s, "tt_ar_generate_chunk") : step_enqueue(s);
+        if (rc) break;
+      }
+      if (!rc) {
+        const int cols = std::min(ldcodes, e->tmax);
+        hipError_t ce = hipMemcpy2DAsync(codes, (size_t)ldcodes * sizeof(int), e->codes_own, (size_t)e->tmax * sizeof(int), (size_t)cols * sizeof(int),
+                                         (size_t)S, hipMemcpyDeviceToDevice, s);
+        if (ce == hipSuccess) ce = hipMemcpyAsync(e->sess_host, e->sess, (size_t)4 * S * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (ce != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; }
+        if (!rc) rc = e->guard.snapshot(s);
+        if (!rc && (ce = hipStreamSynchronize(s)) != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; }
+      }
+      if (rc) {
+        (void)hipStreamSynchronize(s);
+        e->step.drop();
+        return rc;
+      }
+      for (int r = 0; r < S; ++r) {
+        if (e->s_run[r] == SESS_RUNNING) e->s_key_pending[r] = false;
+        e->s_n[r] = e->sess_host[SESS_N * S + r];
+        e->s_run[r] = e->sess_host[SESS_RUN * S + r];
+      }
+    }
+    for (int r = 0; r < S; ++r) {
+      n_total_host[r] = e->s_n[r];
+      finished_host[r] = e->s_run[r] == SESS_FINISHED ? 1 : 0;
+    }
+    return 0;
+  });
+}
+
 int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, const tt_sampling* sp, int* codes, int* n_total_host,
                          int* finished_host, void* stream) {
   TT_REQUIRE(e && sp && codes && n_total_host && finished_host, "tt_ar_generate_chunk: null argument");
+  if (e->sessions) return ar_sessions_chunk(e, B, n_more, ldcodes, sp, codes, n_total_host, finished_host, (hipStream_t)stream);
   TT_REQUIRE(B >= 1 && B <= e->cfg.max_batch, "tt_ar_generate_chunk: batch %d exceeds capacity %d", B, e->cfg.max_batch);
   TT_REQUIRE(e->P1 > 0, "tt_ar_generate_chunk: call tt_ar_prefill first");
   TT_REQUIRE(first || (e->gen_done >= 1 && e->B == B), "tt_ar_generate_chunk: no generation of %d rows to resume", B);
@@ -675,6 +855,18 @@ int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, co
 int tt_ar_stream_latents(tt_ar* e, int B, int n, float* out, void* stream) {
   TT_REQUIRE(e && out, "tt_ar_stream_latents: null argument");
   TT_REQUIRE(e->lat != nullptr, "tt_ar_stream_latents: this handle was created with max_batch %d > 8 (no per-step latent capture)", e->cfg.max_batch);
+  if (e->sessions) {  // [S][n][D]: row r's latents 0 .. n - 1, each row counted from its own admission
+    int most = 0;
+    for (int r = 0; r < e->cfg.max_batch; ++r) most = std::max(most, e->s_n[r]);
+    TT_REQUIRE(B == e->cfg.max_batch && n >= 1 && n <= std::max(most, 1), "tt_ar_stream_latents: %d x %d latents requested, the sessions hold %d x at most %d", B, n,
+               e->cfg.max_batch, most);
+    return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+      const size_t row = (size_t)e->D * sizeof(float);
+      for (int r = 0; r < B; ++r)
+        TT_CHECK_HIP(hipMemcpy2DAsync(out + (size_t)r * n * e->D, row, e->lat + (size_t)r * e->D, (size_t)B * row, row, (size_t)n, hipMemcpyDeviceToDevice, s));
+      return 0;
+    });
+  }
   TT_REQUIRE(B >= 1 && B <= e->lat_batch && B == e->B && n >= 1 && n <= e->gen_done, "tt_ar_stream_latents: %d x %d latents requested, generation holds %d x %d", B, n, e->B, e->gen_done);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
     const size_t row = (size_t)e->D * sizeof(float);
@@ -727,13 +919,52 @@ int tt_ar_stat(tt_ar* e, int which) {
 }
 
 // Engine options of a handle (defaults in brackets):
-//   TT_AR_OPT_LOOKAHEAD   [6]  decode steps the host may run ahead of the device (>= 1)
+//   TT_AR_OPT_LOOKAHEAD      [6]  decode steps the host may run ahead of the device (>= 1)
+//   TT_AR_OPT_SESSIONS       [0]  1: the handle serves streaming sessions, one per row (fresh handles of <= 4 rows, 16-bit, max_groups >= max_batch)
+//   TT_AR_OPT_SESSION_CLOSE       retire the session in slot `value` of a session handle
 int tt_ar_set_option(tt_ar* e, int option, int value) {
   TT_REQUIRE(e != nullptr, "tt_ar_set_option: null handle");
   switch (option) {
     case TT_AR_OPT_LOOKAHEAD:
       TT_REQUIRE(value >= 1 && value <= 64, "tt_ar_set_option: lookahead %d outside 1 .. 64", value);
       e->lookahead = value;
+      break;
+    case TT_AR_OPT_SESSIONS: {
+      const tt_ar_config& c = e->cfg;
+      TT_REQUIRE(value == 1 && !e->sessions, "tt_ar_set_option: sessions are switched on once, with value 1 (got %d)", value);
+      TT_REQUIRE(c.max_batch <= 4 && c.dtype != DT_F32 && c.max_groups >= c.max_batch && e->D == 1024,
+                 "tt_ar_set_option: sessions need max_batch <= 4, 16-bit operands, max_groups >= max_batch and model_dim 1024 (max_batch %d, dtype %d, max_groups %d)",
+                 c.max_batch, c.dtype, c.max_groups);
+      TT_REQUIRE(e->P1 == 0 && e->step.captures == 0 && !e->step.exec, "tt_ar_set_option: sessions must be switched on before the first prefill");
+      // a session row stages its whole prefix capacity in the decode attention's LDS (about 600 prefix rows at 500 tokens)
+      TT_REQUIRE(decode_attention_session_lds(c.max_prefix, e->tmax) <= DECODE_LDS_CAP,
+                 "tt_ar_set_option: sessions need the prefix capacity in the attention's LDS: max_prefix %d with %d KV slots needs %zu bytes, %zu available",
+                 c.max_prefix, e->tmax, decode_attention_session_lds(c.max_prefix, e->tmax), DECODE_LDS_CAP);
+      int rc = e->arena.alloc_t(&e->sess, (size_t)4 * c.max_batch);
+      if (!rc) rc = e->arena.alloc_t(&e->pre_logits, (size_t)c.max_batch * e->Vp);
+      if (!rc && hipHostMalloc((void**)&e->sess_host, (size_t)4 * c.max_batch * sizeof(int)) != hipSuccess) {
+        set_error("tt_ar_set_option: hipHostMalloc failed");
+        rc = -2;
+      }
+      TT_TRY(rc);
+      // (arena memory is zeroed: every row starts SESS_FREE.  The slot plane of a free row must read -1)
+      TT_CHECK_HIP(hipMemset(e->sess + SESS_SLOT * c.max_batch, 0xff, (size_t)c.max_batch * sizeof(int)));
+      TT_CHECK_HIP(hipDeviceSynchronize());
+      // the GEMV-shaped step of a <= 4-sequence handle, for the whole life of the handle (its level as tt_ar_create picks it)
+      e->gemv = tt::g_ar_gemv ? tt::g_ar_gemv : 2;
+      e->sessions = 1;
+      e->B = c.max_batch;
+      memset(e->s_n, 0, sizeof(e->s_n));
+      memset(e->s_run, 0, sizeof(e->s_run));
+      break;
+    }
+    case TT_AR_OPT_SESSION_CLOSE:
+      TT_REQUIRE(e->sessions, "tt_ar_set_option: TT_AR_OPT_SESSION_CLOSE needs a session handle (TT_AR_OPT_SESSIONS)");
+      TT_REQUIRE(value >= 0 && value < e->cfg.max_batch && e->s_run[value] != SESS_FREE, "tt_ar_set_option: slot %d holds no session to close", value);
+      TT_TRY(ar_sess_close_launch(e->sess, e->cfg.max_batch, value, e->sb.own));
+      e->s_run[value] = SESS_FREE;
+      e->s_n[value] = 0;
+      e->s_key_pending[value] = false;
       break;
     default: TT_REQUIRE(false, "tt_ar_set_option: unknown option %d", option);
   }

@@ -52,6 +52,10 @@ __global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
 
   float* o32 = a.out_f32;
   if (o32 && a.f32_slot) o32 += (size_t)(*a.f32_slot + a.f32_slot_base) * a.f32_slot_stride;
+  if (o32 && a.f32_row_slot) {  // (block-uniform: one row per block)
+    const int sl = a.f32_row_slot[row];
+    o32 = sl < 0 ? nullptr : o32 + (size_t)(sl + a.f32_slot_base) * a.f32_slot_stride;
+  }
   auto emit = [&](const float4* y) {
 #pragma unroll
     for (int j = 0; j < J; ++j) {
@@ -188,7 +192,7 @@ static void rownorm_narrow_dispatch(const ProfScope& ps, const RowNormArgs& a, h
 
 template <typename T>
 static bool rownorm_narrow_launch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
-  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr) return false;
+  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr || a.f32_row_slot != nullptr) return false;
   switch (a.nslab) {
     case 0: rownorm_narrow_dispatch<T, 0>(ps, a, stream); return true;
     case 1: rownorm_narrow_dispatch<T, 1>(ps, a, stream); return true;

@@ -36,6 +36,9 @@ struct RowNormArgs {
   const int* f32_slot;
   int f32_slot_base;
   size_t f32_slot_stride;
+  // optional, session handles (generic kernel only): row r files its f32 copy under its own counter f32_row_slot[r] (+ f32_slot_base);
+  // a negative counter files nothing for that row
+  const int* f32_row_slot;
   int row_blocks;      // 1: always one workgroup per row (the decode step: a row's arithmetic order must not depend on how many rows the batch has)
   int* guard;          // optional device counter: += 1 per workgroup / wave that saw a non-finite input value (operand-overflow guard)
 };
@@ -108,8 +111,16 @@ struct DecodeAttnArgs {
   int ngroups, group_size;
   size_t prefix_group_stride;
   int p1_tab[16];
+  // session handles (row_slot != null): every sequence is its own utterance with its own state in device memory.  Row b attends its
+  // prefix (prefix_group_stride * b elements in, row_p1[b] rows) and its own keys 0 .. row_slot[b]; a negative slot skips the row.
+  // P1 is then the prefix CAPACITY (LDS sizing); nothing per row is baked into the launch.
+  const int* row_slot;
+  const int* row_p1;
 };
 int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stream);
+// LDS bytes of the session-row decode attention for a prefix capacity p1_cap and tmax own keys (it must stay <= DECODE_LDS_CAP)
+size_t decode_attention_session_lds(int p1_cap, int tmax);
+constexpr size_t DECODE_LDS_CAP = 160 * 1024;
 int decode_attn_f32_launch(const DecodeAttnArgs& a, hipStream_t stream);  // fp32 verification mode (attention_f32.hip)
 
 // ------------------------------------------------------------------------------ GEMV-shaped decode GEMMs (gemv.hip): M <= 4 rows
@@ -133,6 +144,7 @@ struct GemvArgs {
   void* vc;
   int heads, tmax, dmodel;
   float q_scale;
+  const int* row_slot;  // optional (session handles): row r appends at its own slot row_slot[r] instead of *step; negative: no store
   // fused LayerNorm (GEMV_QKV / GEMV_GELU_T, K == 1024): when ln_x is set the activation rows are LayerNorm(ln_x[M][ldx] f32; ln_g, ln_b, ln_eps) and A is unused
   const float* ln_x;
   int ldx;
@@ -182,7 +194,16 @@ struct SampleArgs {
   // like `logits`: same ldl / ldg), and the sampler reads those rows instead; 0 = off
   float typical_mass;
   float* typical_out;
+  // session handles (sess != null): every row is its own utterance, with its state in sess = int[4][B] (SessRow planes).  A row
+  // samples only while sess[SESS_RUN][b] == 1, at its own step sess[SESS_N][b] (Philox counter, codes column, mel position) with
+  // Philox key keys_dev[b] and candidate index 0; its first token is drawn from pre_logits + b * ldl (its admission prefill), later
+  // ones from `logits`.  state[0] counts the steps of the call (unfinished_count index).  Rows that do not sample zero their embed_x row.
+  int* sess;
+  const float* pre_logits;
 };
+// planes of the per-row session state (tt_ar session handles): int[4][max_batch]
+enum SessPlane { SESS_N = 0, SESS_SLOT = 1, SESS_RUN = 2, SESS_P1 = 3 };
+enum SessRun { SESS_FREE = 0, SESS_RUNNING = 1, SESS_FINISHED = 2 };
 int sample_launch(const SampleArgs& a, hipStream_t stream);
 // the typical-sampling mask alone: rows of a.logits -> a.typical_out (sample_launch runs it ahead of the sampler when a.typical_mass != 0)
 int typical_mask_launch(const SampleArgs& a, hipStream_t stream);
@@ -191,10 +212,21 @@ int typical_mask_launch(const SampleArgs& a, hipStream_t stream);
 int ar_state_advance_launch(int* state, const int* unfinished_count, int* progress, hipStream_t stream);
 int ar_begin_launch(int* state, unsigned* seen, int* unfinished, int* unfinished_count, int B, int V, int max_steps,
                     int start_token, hipStream_t stream);
+// session handles: the step counter of every running row advances (SESS_SLOT = index of the token just sampled, SESS_N += 1); a row
+// whose token was the stop token becomes SESS_FINISHED (slot -1: it neither decodes nor samples again).  state[0] / state[2] and the
+// progress words count the steps of the call as ar_state_advance_launch does.
+int ar_sess_advance_launch(int* state, int* sess, int B, const int* unfinished, const int* unfinished_count, int* progress, hipStream_t stream);
+// session handles: row `row` starts a new session with a prefix of P1 rows (seen mask and unfinished flag as ar_begin_launch sets them)
+int ar_sess_admit_launch(int* sess, int B, int row, int P1, unsigned* seen, int* unfinished, int V, int start_token, hipStream_t stream);
+// session handles: row `row` is freed
+int ar_sess_close_launch(int* sess, int B, int row, hipStream_t stream);
 
 // x[b][:] = tok_emb[tok[b]][:] + pos_emb[state[1] + pos_offset][:]   (pos_offset 2: kv_cache=True rule, 1: kv_cache=False rule)
 int ar_embed_launch(const int* tok, const int* state, const float* tok_emb, const float* pos_emb, float* x, int B, int D, int pos_offset,
                     hipStream_t stream);
+// session handles: the same per row at its own slot row_slot[b]; rows with a negative slot get a zero row
+int ar_embed_rows_launch(const int* tok, const int* row_slot, const float* tok_emb, const float* pos_emb, float* x, int B, int D, int pos_offset,
+                         hipStream_t stream);
 
 // ------------------------------------------------------------------------------ small fused ops
 // (GEGLU is formed in the projection GEMM's epilogue: gemm.h EPI_GEGLU)

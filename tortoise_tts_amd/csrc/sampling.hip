@@ -70,7 +70,7 @@ __device__ __forceinline__ int sample_commit(const SampleArgs& a, int b, int ste
   a.codes[(size_t)b * a.ldcodes + step] = tok;
   a.next_tok[b] = tok;
   atomicOr(&seen[tok >> 5], 1u << (tok & 31));
-  if (still) atomicAdd(&a.unfinished_count[step], 1);
+  if (still) atomicAdd(&a.unfinished_count[a.sess ? a.state[0] : step], 1);  // (session handles: the step of the call)
   return tok;
 }
 // whole block: next decode step's input row, mel_embedding[tok] + mel_pos_embedding[index of this token + offset].  The token
@@ -86,6 +86,30 @@ __device__ __forceinline__ void sample_embed(const SampleArgs& a, int b, int ste
       *(float4*)(a.embed_x + (size_t)b * a.D + c) = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
     }
   }
+}
+
+// Session handles (a.sess): whether row b samples this step; a row that does not (free, or finished) zeroes its input row of the next
+// step instead, so that the rows the batch carries along stay finite
+__device__ __forceinline__ bool sess_idle(const SampleArgs& a, int b, int tid, int nthreads) {
+  if (!a.sess || a.sess[SESS_RUN * a.B + b] == SESS_RUNNING) return false;
+  if (a.embed_x)
+    for (int c = tid * 4; c < a.D; c += nthreads * 4) *(float4*)(a.embed_x + (size_t)b * a.D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  return true;
+}
+// the row's step (Philox counter, codes column), logits row, Philox key and candidate index (block-uniform)
+__device__ __forceinline__ int sample_step(const SampleArgs& a, int b) { return a.sess ? a.sess[SESS_N * a.B + b] : a.state[0]; }
+__device__ __forceinline__ const float* sample_logits(const SampleArgs& a, int b, int grp, int step) {
+  if (a.sess) return (step == 0 && a.pre_logits ? a.pre_logits : a.logits) + (size_t)b * a.ldl;  // token 0: the row's admission prefill
+  return a.logits + (a.ldl ? (size_t)b * a.ldl : (size_t)grp * (a.ldg ? a.ldg : a.V));
+}
+__device__ __forceinline__ unsigned long long sample_key(const SampleArgs& a, int b, int grp) {
+  // from device memory when the caller replays a cached step graph (the seed of a call is then data, not a baked-in kernel argument),
+  // else from the argument block; a session row has its own key
+  return a.keys_dev ? a.keys_dev[a.sess ? b : grp] : (a.ngroups > 1 ? a.group_seeds[grp] : a.seed);
+}
+__device__ __forceinline__ int sample_cand(const SampleArgs& a, int b, int grp, int row_offset) {
+  // global index of the candidate: within its utterance (the draw does not depend on the batching); a session row is candidate 0
+  return a.sess ? 0 : row_offset + (a.ngroups > 1 ? b - grp * a.group_size : b);
 }
 
 // PER: vocabulary entries per thread (V <= 256 PER): 33 covers the model's 8194 mel codes, 40 anything up to 10240 - every unrolled loop below is PER long
@@ -108,13 +132,12 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x;
   TT_STAMP(0);
   const int V = a.V;
-  const int step = a.state[0];
+  if (sess_idle(a, b, tid, 256)) return;
+  const int step = sample_step(a, b);
   const int grp = a.ngroups > 1 ? b / a.group_size : 0;  // utterance of this row (block-uniform)
-  // Philox key of this row's utterance: from device memory when the caller replays a cached step graph (the seed of a call is then
-  // data, not a baked-in kernel argument), else from the argument block; block-uniform, read once
-  const unsigned long long philox_key = a.keys_dev ? a.keys_dev[grp] : (a.ngroups > 1 ? a.group_seeds[grp] : a.seed);
+  const unsigned long long philox_key = sample_key(a, b, grp);  // Philox key of this row's utterance (block-uniform, read once)
   const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;  // (block-uniform scalar load)
-  const float* lg = a.logits + (a.ldl ? (size_t)b * a.ldl : (size_t)grp * (a.ldg ? a.ldg : V));
+  const float* lg = sample_logits(a, b, grp, step);
   unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
   float val[PER];
   bool bad = false;  // NaN / +inf logits: an operand overflowed somewhere upstream (-inf is legitimate: a suppressed token)
@@ -408,8 +431,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         } else {
           unsigned r[4];
           const unsigned long long key = philox_key;
-          const int cand = a.ngroups > 1 ? b - grp * a.group_size : b;  // index within the utterance: the draw does not depend on the batching
-          philox4x32_10((unsigned)id, (unsigned)step, (unsigned)(row_offset + cand), 0u, (unsigned)key, (unsigned)(key >> 32), r);
+          const int cand = sample_cand(a, b, grp, row_offset);  // index within the utterance: the draw does not depend on the batching
+          philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)key, (unsigned)(key >> 32), r);
           const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
           q = -__logf(u);
         }
@@ -493,8 +516,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       } else {
         unsigned r[4];
         const unsigned long long key = philox_key;
-        const int cand = a.ngroups > 1 ? b - grp * a.group_size : b;  // index within the utterance: the draw does not depend on the batching
-        philox4x32_10((unsigned)id, (unsigned)step, (unsigned)(row_offset + cand), 0u, (unsigned)key, (unsigned)(key >> 32), r);
+        const int cand = sample_cand(a, b, grp, row_offset);  // index within the utterance: the draw does not depend on the batching
+        philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)key, (unsigned)(key >> 32), r);
         const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
         q = -__logf(u);
       }
@@ -559,13 +582,12 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   __shared__ int red_i[16];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int V = a.V;
-  const int step = a.state[0];
+  if (sess_idle(a, b, tid, 1024)) return;
+  const int step = sample_step(a, b);
   const int grp = a.ngroups > 1 ? b / a.group_size : 0;
-  // Philox key of this row's utterance: from device memory when the caller replays a cached step graph (the seed of a call is then
-  // data, not a baked-in kernel argument), else from the argument block; block-uniform, read once
-  const unsigned long long philox_key = a.keys_dev ? a.keys_dev[grp] : (a.ngroups > 1 ? a.group_seeds[grp] : a.seed);
+  const unsigned long long philox_key = sample_key(a, b, grp);
   const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;
-  const float* lg = a.logits + (a.ldl ? (size_t)b * a.ldl : (size_t)grp * (a.ldg ? a.ldg : V));
+  const float* lg = sample_logits(a, b, grp, step);
   unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
   for (int t = tid; t < WIDE_N; t += 1024) {
     unsigned kk = 0u;  // padding slots sort behind every real score (f2key(-inf) = 0x007FFFFF > 0)
@@ -640,8 +662,8 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
     } else {
       unsigned r[4];
       const unsigned long long pk = philox_key;
-      const int cand = a.ngroups > 1 ? b - grp * a.group_size : b;
-      philox4x32_10((unsigned)id, (unsigned)step, (unsigned)(row_offset + cand), 0u, (unsigned)pk, (unsigned)(pk >> 32), r);
+      const int cand = sample_cand(a, b, grp, row_offset);
+      philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)pk, (unsigned)(pk >> 32), r);
       const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
       q = -__logf(u);
     }
@@ -709,7 +731,8 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
   // the ids seen so far are then the same for all its candidates (the fake prefix ids): the first one's mask is read
   const size_t row_off = a.ldl ? (size_t)r * a.ldl : (size_t)r * (a.ldg ? a.ldg : V);
   const int seen_row = a.ldl ? r : (a.ngroups > 1 ? r * a.group_size : 0);
-  const float* lg = a.logits + row_off;
+  if (a.sess && a.sess[SESS_RUN * a.B + r] != SESS_RUNNING) return;  // (session handles: a row that does not sample)
+  const float* lg = a.sess ? sample_logits(a, r, 0, sample_step(a, r)) : a.logits + row_off;
   float* out = a.typical_out + row_off;
   const unsigned* seen = a.seen + (size_t)seen_row * ((V + 31) / 32);
   float raw[TYP_PER], s[TYP_PER];
@@ -788,9 +811,11 @@ int sample_launch(const SampleArgs& a_in, hipStream_t stream) {
   TT_REQUIRE(a.B > 0 && a.V > 0 && a.V <= WIDE_V, "sample: V=%d unsupported (<= %d)", a.V, WIDE_V);
   TT_REQUIRE(a.ngroups <= 1 || (a.ngroups <= 16 && a.group_size > 0 && a.B == a.ngroups * a.group_size), "sample: %d groups of %d rows do not make %d rows", a.ngroups, a.group_size, a.B);
   TT_REQUIRE(a.temperature > 0.f && a.top_p > 0.f && a.rep_penalty > 0.f, "sample: bad sampling parameters");
+  TT_REQUIRE(!a.sess || (a.ldl > 0 && a.ngroups <= 1 && !a.exp_noise && a.keys_dev), "sample: session rows need per-row logits, device keys and no injected noise");
   if (a.typical_mass != 0.f) {
     TT_TRY(typical_mask_launch(a, stream));
     a.logits = a.typical_out;
+    a.pre_logits = nullptr;  // (the masked rows already came from the right source)
   }
   ProfScope ps(PROF_SAMPLE, stream, 0.0, (double)a.B * a.V * 4.0, true);
   if (a.top_k >= 1 && a.top_k <= 256) {
@@ -841,6 +866,74 @@ int ar_state_advance_launch(int* state, const int* unfinished_count, int* progre
   return 0;
 }
 
+// Session handles: the same bookkeeping per row (one thread walks the <= 4 rows).  A running row's newest token (index SESS_N) becomes
+// its slot; a row whose token was the stop token is finished - its count includes the stop token, as a single generation's does.
+__global__ void ar_sess_advance_kernel(int* state, int* sess, int B, const int* unfinished, const int* unfinished_count, int* progress) {
+  if (threadIdx.x == 0) {
+    for (int r = 0; r < B; ++r) {
+      if (sess[SESS_RUN * B + r] != SESS_RUNNING) continue;
+      const int n = sess[SESS_N * B + r];
+      sess[SESS_N * B + r] = n + 1;
+      if (unfinished[r]) {
+        sess[SESS_SLOT * B + r] = n;
+      } else {
+        sess[SESS_SLOT * B + r] = -1;
+        sess[SESS_RUN * B + r] = SESS_FINISHED;
+      }
+    }
+    const int step = state[0];
+    state[0] = step + 1;
+    state[1] = step;
+    if (progress) {
+      if (unfinished_count[step] == 0 && state[2] < 0) {
+        state[2] = step;
+        __hip_atomic_store(progress + 1, step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      __hip_atomic_store(progress, step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+int ar_sess_advance_launch(int* state, int* sess, int B, const int* unfinished, const int* unfinished_count, int* progress, hipStream_t stream) {
+  ar_sess_advance_kernel<<<1, 64, 0, stream>>>(state, sess, B, unfinished, unfinished_count, progress);
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ void ar_sess_admit_kernel(int* sess, int B, int row, int P1, unsigned* seen, int* unfinished, int V, int start_token) {
+  const int words = (V + 31) / 32;
+  for (int w = threadIdx.x; w < words; w += blockDim.x) {
+    unsigned v = 0u;
+    if (w == 0) v |= 1u << 1;  // fake_inputs = [1] * P + [start_mel_token], as ar_begin_kernel
+    if (w == (start_token >> 5)) v |= 1u << (start_token & 31);
+    seen[(size_t)row * words + w] = v;
+  }
+  if (threadIdx.x == 0) {
+    unfinished[row] = 1;
+    sess[SESS_N * B + row] = 0;
+    sess[SESS_SLOT * B + row] = -1;  // token 0 comes from the admission's logits: nothing to decode yet
+    sess[SESS_RUN * B + row] = SESS_RUNNING;
+    sess[SESS_P1 * B + row] = P1;
+  }
+}
+int ar_sess_admit_launch(int* sess, int B, int row, int P1, unsigned* seen, int* unfinished, int V, int start_token, hipStream_t stream) {
+  ar_sess_admit_kernel<<<1, 256, 0, stream>>>(sess, B, row, P1, seen, unfinished, V, start_token);
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+__global__ void ar_sess_close_kernel(int* sess, int B, int row) {
+  if (threadIdx.x == 0) {
+    sess[SESS_N * B + row] = 0;
+    sess[SESS_SLOT * B + row] = -1;
+    sess[SESS_RUN * B + row] = SESS_FREE;
+  }
+}
+int ar_sess_close_launch(int* sess, int B, int row, hipStream_t stream) {
+  ar_sess_close_kernel<<<1, 64, 0, stream>>>(sess, B, row);
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 __global__ void ar_begin_kernel(int* state, unsigned* seen, int* unfinished, int* unfinished_count, int B, int V, int max_steps,
                                 int start_token) {
   const int words = (V + 31) / 32;
@@ -879,6 +972,28 @@ __global__ __launch_bounds__(256) void ar_embed_kernel(const int* tok, const int
     *(float4*)(x + (size_t)b * D + c) = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
   }
 }
+__global__ __launch_bounds__(256) void ar_embed_rows_kernel(const int* tok, const int* row_slot, const float* tok_emb, const float* pos_emb,
+                                                            float* x, int D, int pos_offset) {
+  const int b = blockIdx.x;
+  const int sl = row_slot[b];
+  for (int c = threadIdx.x * 4; c < D; c += 1024) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (sl >= 0) {
+      const float4 e = *(const float4*)(tok_emb + (size_t)tok[b] * D + c);
+      const float4 p = *(const float4*)(pos_emb + (size_t)(sl + pos_offset) * D + c);
+      v = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
+    }
+    *(float4*)(x + (size_t)b * D + c) = v;
+  }
+}
+int ar_embed_rows_launch(const int* tok, const int* row_slot, const float* tok_emb, const float* pos_emb, float* x, int B, int D, int pos_offset,
+                         hipStream_t stream) {
+  TT_REQUIRE(D % 4 == 0, "ar_embed: D must be a multiple of 4");
+  ar_embed_rows_kernel<<<B, 256, 0, stream>>>(tok, row_slot, tok_emb, pos_emb, x, D, pos_offset);
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int ar_embed_launch(const int* tok, const int* state, const float* tok_emb, const float* pos_emb, float* x, int B, int D, int pos_offset,
                     hipStream_t stream) {
   TT_REQUIRE(D % 4 == 0, "ar_embed: D must be a multiple of 4");

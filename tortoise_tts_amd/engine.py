@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("TORTOISE_MI355X_LIB") or os.path.join(HERE, "lib", "l
 TT_BF16, TT_F16, TT_F32 = 0, 1, 2  # TT_F32: the slow fp32-operand VERIFICATION mode of the AR / CLVP / diffusion / vocoder stages (tests)
 DTYPE_NAMES = {TT_BF16: "bf16", TT_F16: "fp16", TT_F32: "fp32"}
 TT_AR_OPT_LOOKAHEAD = 4
+TT_AR_OPT_SESSIONS = 5
+TT_AR_OPT_SESSION_CLOSE = 6
 TT_DIFF_OPT_OVERLAP_PREPASS = 1
 TT_DIFF_OPT_FUSED_GN = 2
 TTX_FLASH32, TTX_GEMM_P8, TTX_VOC_MFMA, TTX_GEMM_SKINNY, TTX_AR_GEMV = 0, 1, 2, 3, 4  # ttx_kernel_variant families (include/tortoise_mi355x_test.h)
@@ -230,6 +232,7 @@ _TEST_PROTOS = {
     "tt_op_gn_gemm_workspace": (_sz, [_i, _i]),
     "tt_op_flash_attention": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp]),
     "tt_op_decode_attention": (_i, [_i, vp, vp, vp, _i, vp, vp, _i, _i, vp, _i, _i, _i, vp]),
+    "tt_op_decode_attention_rows": (_i, [_i, vp, vp, vp, C.c_longlong, vp, _i, vp, vp, _i, vp, vp, _i, _i, vp]),
     "tt_op_gemv": (_i, [_i, vp, vp, _i, _i, _i, vp, _i, vp, vp, vp]),
     "tt_op_gemv_ln": (_i, [_i, vp, vp, vp, _f, vp, _i, _i, vp, vp, vp]),
     "tt_op_sample": (_i, [vp, _i, _i, _i, vp, C.POINTER(Sampling), _i, vp, _i, vp, _i, vp]),

@@ -82,8 +82,12 @@ class ArStage(_GuardedHandle):
     api = "tt_ar"
 
     def __init__(self, sd, cfg: ARConfig = ARConfig(), device="cuda", dtype=E.TT_BF16, max_batch=256, max_text=402,
-                 max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1):
+                 max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1, sessions=False):
+        """sessions=True: a session handle (TT_AR_OPT_SESSIONS) - each of its max_batch <= 4 rows serves one streaming session, admitted,
+        advanced and retired on its own (admit / advance / session_codes / session_latents / close(slot))."""
         self.lib = E.init()
+        if sessions:
+            max_groups = max(max_groups, max_batch)
         self.cfg = cfg
         self.device = torch.device(device)
         self.dtype = dtype
@@ -107,6 +111,15 @@ class ArStage(_GuardedHandle):
         self.max_latent_candidates = max_latent_candidates
         self.ccfg = c
         self._create(C.byref(c), C.byref(self.w.weights))
+        self.sessions = bool(sessions)
+        if self.sessions:
+            self.set_option(E.TT_AR_OPT_SESSIONS, 1)
+            self.max_batch = max_batch
+            self.max_new = max_new_tokens
+            self._seeds = [0] * max_batch
+            self._n = [0] * max_batch
+            self._finished = [False] * max_batch
+            self._codes = self._codes_buffer(max_batch, max_new_tokens)
         # A/B switches of the measurement scripts (scripts/ab_stage.py); the product default is what tt_ar_create sets
         for env, opt in (("TT_AR_LOOKAHEAD", E.TT_AR_OPT_LOOKAHEAD),):
             if os.environ.get(env):
@@ -209,6 +222,47 @@ class ArStage(_GuardedHandle):
         out = torch.empty(B, n, self.cfg.model_dim, device=self.device, dtype=torch.float32)
         E.check(self.lib.tt_ar_stream_latents(self.h, B, n, E.ptr(out), E.stream_ptr()))
         return out
+
+    # -- session handles (sessions=True): one streaming session per row
+    def admit(self, slot, cond_latent, text_tokens, seed):
+        """Start a session in free row `slot`: its prefix is evaluated now, its first token is drawn at the next advance() with Philox
+        key `seed`.  The running sessions are untouched."""
+        emb = self.prefix_embedding(cond_latent[:1], text_tokens[:1])[0].contiguous()
+        E.check(self.lib.tt_ar_prefill_group(self.h, int(slot), self.max_batch, E.ptr(emb), emb.shape[0], E.stream_ptr()))
+        self._seeds[slot] = int(seed)
+        self._n[slot], self._finished[slot] = 0, False
+
+    def advance(self, n, temperature=0.8, top_p=0.8, repetition_penalty=2.0, top_k=50, typical_mass=0.0):
+        """Every running session samples up to n more tokens (a session stops at its stop token).  Returns (n_total, finished), lists
+        over the slots.  The sampling settings belong to the handle while a session that has sampled runs."""
+        S = self.max_batch
+        s = E.Sampling()
+        s.temperature, s.top_p, s.repetition_penalty, s.top_k = temperature, top_p, repetition_penalty, top_k
+        s.typical_mass = float(typical_mass)
+        s.seed, s.row_offset, s.exp_noise = 0, 0, None
+        gs = (C.c_ulonglong * S)(*self._seeds)
+        s.group_seeds = C.cast(gs, C.POINTER(C.c_ulonglong))
+        n_total, fin = (C.c_int * S)(), (C.c_int * S)()
+        E.check(self.lib.tt_ar_generate_chunk(self.h, S, 0, int(n), self.max_new, C.byref(s), E.ptr(self._codes), n_total, fin, E.stream_ptr()))
+        self._n, self._finished = list(n_total), [bool(v) for v in fin]
+        return list(self._n), list(self._finished)
+
+    def session_codes(self, slot):
+        """int64 [1, n]: the tokens session `slot` has sampled (its stop token included once it has finished)."""
+        return self._codes[slot:slot + 1, :self._n[slot]].long()
+
+    def session_latents(self, slot, n):
+        """f32 [1, n, D]: latents 0 .. n - 1 of session `slot`, as stream_latents files them for a single generation."""
+        out = torch.empty(self.max_batch, n, self.cfg.model_dim, device=self.device, dtype=torch.float32)
+        E.check(self.lib.tt_ar_stream_latents(self.h, self.max_batch, n, E.ptr(out), E.stream_ptr()))
+        return out[slot:slot + 1]
+
+    def close(self, slot=None):
+        """close(slot): retire the session in row `slot` (its row is free for the next admit).  close(): release the handle."""
+        if slot is None:
+            return super().close()
+        self.set_option(E.TT_AR_OPT_SESSION_CLOSE, int(slot))
+        self._n[slot], self._finished[slot] = 0, False
 
     # -- latent re-pass (autoregressive.py:454-506 as api.py:521-524 calls it)
     def latents(self, cond_latent, text_tokens, codes, stream_positions=False):
