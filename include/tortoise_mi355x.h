@@ -159,14 +159,28 @@ int tt_ar_stream_latents(tt_ar* h, int B, int n, float* out, void* stream);
  *                                 stop token, which it counts) into codes int32 [S][ldcodes], row = slot, each row from column 0;
  *                                 s->group_seeds[slot] (or s->seed) is a session's Philox key, taken at its first step.  The scalars
  *                                 temperature / top_p / repetition_penalty / top_k / typical_mass belong to the handle while a session
- *                                 that has sampled runs: other values are refused; exp_noise is refused;
+ *                                 that has sampled runs: other values are refused (unless TT_AR_OPT_SESSION_SAMPLING is on, below);
+ *                                 exp_noise is refused;
  *                               tt_ar_stream_latents(h, S, n, out, stream) returns out f32 [S][n][D], row r's latents 0 .. n - 1
  *                                 (latent 0 from its admission); rows holding fewer than n carry undefined tails;
  *                               tt_ar_generate, tt_ar_begin and tt_ar_decode_step are refused.
  *   TT_AR_OPT_SESSION_CLOSE   retires the session in slot `value` of a session handle (finished or not); the slot is free for the
- *                             next admission. */
+ *                             next admission.
+ *   TT_AR_OPT_SESSION_SAMPLING [0]  value 1 gives every session its own sampling settings.  Allowed once, on a session handle, before
+ *                             its first admission.  tt_ar_generate_chunk's `s` then points at S tt_sampling structs, one per slot:
+ *                             s[r] holds slot r's temperature / top_p / repetition_penalty / top_k / typical_mass and its Philox key
+ *                             (s[r].seed), taken at the session's first step and fixed from then on.  Entries of free and finished
+ *                             slots are not read.  Refused before anything changes: an entry of a running slot whose values differ from
+ *                             those its session started with (the message names the slot), and in any entry a running or pending row
+ *                             uses, temperature / top_p / repetition_penalty <= 0, typical_mass outside {0} and (0, 1), or a non-null
+ *                             exp_noise or group_seeds.  Each session computes exactly what it computes alone on a max_batch = 1 handle
+ *                             with its own settings.  The settings are device data on every session handle: the kept step graphs
+ *                             differ only in the optional launches the running rows need - the full-sort sampler (a top_k outside
+ *                             1 .. 256) and the typical mask (typical_mass != 0) - at most four graphs, each captured once
+ *                             (tt_ar_stat(h, 0) counts them); default settings replay the same launches as without the option. */
 #define TT_AR_OPT_SESSIONS 5
 #define TT_AR_OPT_SESSION_CLOSE 6
+#define TT_AR_OPT_SESSION_SAMPLING 7
 int tt_ar_set_option(tt_ar* h, int option, int value);
 /* Operand-overflow guard: the row norms and the sampler count launches that met a non-finite value (an fp16 operand beyond 65504
  * upstream).  Returns the count as of the last finished tt_ar_generate[_chunk] / tt_ar_latents (>= 0; tt_last_error() then names

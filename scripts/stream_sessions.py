@@ -2,6 +2,11 @@
 tokens per second, and the first-piece latency of a session admitted while three others run.
 
     python scripts/stream_sessions.py [--dtype bf16] [--tokens 120] [--out profiles/r07_stream_sessions.json]
+    python scripts/stream_sessions.py --per-session [--rounds 3] [--only typical_and_full_sort] [--out ...]
+
+--per-session: four sessions on a handle with per-session sampling (TT_AR_OPT_SESSION_SAMPLING), per-token step time for four sessions
+with the default settings, four different fast-path settings, and a mix with one typical and one full-sort row; the configurations
+alternate for --rounds rounds, so each one's spread is measured against the same drift.  --only runs one of them (e.g. under a tracer).
 
 Full-size synthetic weights with the stop token suppressed (every session runs its whole length).  Warm-up steps are excluded from
 every timing; the single-stream figure is the max_batch = 1 handle of api_fast.tts_stream on the same weights."""
@@ -21,7 +26,12 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--tokens", type=int, default=120)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--per-session", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--only", default=None)
     args = ap.parse_args()
+    if args.per_session:
+        return per_session(args)
     from oracle import make_golden_full as GF
     from tortoise_tts_amd import engine as E
     from tortoise_tts_amd import stages
@@ -86,6 +96,52 @@ def main():
         for _ in pieces:
             pass
     res["first_piece_latency_ms_with_three_running"] = [x * 1e3 for x in lat]
+    print(json.dumps(res, indent=1))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+PER_SESSION = {
+    "default4": [{}, {}, {}, {}],
+    "fast4": [{}, dict(temperature=0.5, top_p=0.95, repetition_penalty=1.0), dict(top_k=1, repetition_penalty=1.3),
+              dict(temperature=1.0, top_p=1.0, top_k=100)],
+    "typical_and_full_sort": [{}, dict(typical_mass=0.9), dict(top_k=0), {}],
+}
+
+
+def per_session(args):
+    from oracle import make_golden_full as GF
+    from tortoise_tts_amd import engine as E
+    from tortoise_tts_amd import stages
+    from tortoise_tts_amd import weights as W
+    from tortoise_tts_amd.config import ARConfig
+    cfg = ARConfig()
+    dt = E.dtype_code(args.dtype)
+    sd = W.suppress_stop_token(W.synthetic_state_dict(W.ar_manifest(cfg), 1234), cfg)
+    text, auto, _ = GF.prompt()
+    N, warm = args.tokens, 20
+    names = [args.only] if args.only else list(PER_SESSION)
+    res = {"dtype": args.dtype, "timed_tokens": N, "warmup_tokens": warm, "device": torch.cuda.get_device_name(0), "settings": PER_SESSION,
+           "step_ms": {k: [] for k in names}}
+    st = stages.ArStage(sd, cfg, dtype=dt, max_batch=4, max_text=80, max_new_tokens=warm + N + 8, max_latent_candidates=1, sessions=True,
+                        per_session_sampling=True)
+    for _ in range(args.rounds):
+        for name in names:
+            for r, own in enumerate(PER_SESSION[name]):
+                st.admit(r, auto, text, 10 + r, **own)
+            st.advance(warm)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n, _ = st.advance(N)
+            torch.cuda.synchronize()
+            assert n == [warm + N] * 4, n
+            res["step_ms"][name].append((time.perf_counter() - t0) / N * 1e3)
+            res.setdefault("launches_per_step", {})[name] = st.stat(2)
+            for r in range(4):
+                st.close(r)
+    res["graph_captures"] = st.stat(0)
+    st.close()
     print(json.dumps(res, indent=1))
     if args.out:
         with open(args.out, "w") as f:

@@ -20,6 +20,7 @@ teacher-forced latent re-pass) and csrc/hifigan.hip.
                             time, stream_pieces() yields (session id, wav_chunk, done) with every session on exactly the piece schedule
                             of tts_stream, tts_stream_many() wraps the two.  The AR handle is a session handle (TT_AR_OPT_SESSIONS):
                             one row per session, each with its own state on the device, all advanced by one captured decode step.
+                            per_session_sampling=True lets every session keep its own sampling settings (TT_AR_OPT_SESSION_SAMPLING).
 
 Sampling noise comes from the engine's Philox streams keyed by use_deterministic_seed (seeds are not portable between
 generators: parity is "same latents -> same waveform", tests/test_gpu_stages.py::test_hifigan_decoder).
@@ -60,11 +61,13 @@ class TextToSpeech(_Common):
     """api_fast.py:180-229.  Engine-only keyword arguments as in tortoise_tts_amd.api.TextToSpeech: state_dicts
     ('autoregressive', 'hifidecoder', 'rlg_auto'), dtype, configs ('ar', 'hifigan'), max_mel_tokens, and max_streams (1 .. 4):
     streaming sessions served from one shared decode batch (open_stream / stream_pieces / tts_stream_many); 1 keeps the
-    single-sequence engine of tts() / tts_stream()."""
+    single-sequence engine of tts() / tts_stream().  per_session_sampling=True (max_streams > 1): each session samples with the
+    settings it was opened with, whatever the other sessions use (else they must all match)."""
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
-                 state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1):
+                 state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1,
+                 per_session_sampling=False):
         self.models_dir = models_dir
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option")
@@ -88,13 +91,17 @@ class TextToSpeech(_Common):
         if not 1 <= int(max_streams) <= 4:
             raise ValueError(f"max_streams={max_streams} outside 1 .. 4 (the sessions of one decode batch)")
         self.max_streams = int(max_streams)
+        self.per_session_sampling = bool(per_session_sampling)
+        if self.per_session_sampling and self.max_streams == 1:
+            raise ValueError("per_session_sampling=True needs max_streams=2 .. 4 (a single stream has its settings per call)")
         if self.max_streams == 1:
             self.ar = stages.ArStage(self._sd("autoregressive"), self.ar_cfg, self.device, self.dtype, max_batch=1, max_text=max_text_tokens,
                                      max_new_tokens=max_mel_tokens, max_latent_candidates=1, kv_cache=self.kv_cache)
         else:
+            own = {"per_session_sampling": True} if self.per_session_sampling else {}
             self.ar = stages.ArStage(self._sd("autoregressive"), self.ar_cfg, self.device, self.dtype, max_batch=self.max_streams,
                                      max_text=max_text_tokens, max_new_tokens=max_mel_tokens, max_latent_candidates=1, kv_cache=self.kv_cache,
-                                     sessions=True)
+                                     sessions=True, **own)
         self._sessions = {}      # slot -> _Session
         self._session_settings = None
         self._next_sid = 0
@@ -264,7 +271,8 @@ class TextToSpeech(_Common):
     def open_stream(self, text, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Admit one streaming session (max_streams > 1) and return its id.  Takes tts_stream's arguments; the session's pieces come out
         of stream_pieces() on exactly tts_stream's schedule.  May be called at any time, also between pieces of other sessions.  Raises
-        when every slot is busy or when the sampling settings differ from those of the running sessions (they share one sampler)."""
+        when every slot is busy or when the sampling settings differ from those of the running sessions (they share one sampler) -
+        with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken."""
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -274,17 +282,25 @@ class TextToSpeech(_Common):
         a = bound.arguments
         top_k, typical_mass = sampler_kwargs(a["hf_generate_kwargs"])
         settings = (float(a["temperature"]), float(a["top_p"]), float(a["repetition_penalty"]), int(top_k), float(typical_mass))
+        if self.per_session_sampling:
+            try:
+                stages.session_sampling(*settings)
+            except ValueError as err:
+                raise ValueError(f"open_stream: {err}") from None
         free = [r for r in range(self.max_streams) if r not in self._sessions]
         if not free:
             raise RuntimeError(f"open_stream: all {self.max_streams} streaming slots are busy")
-        if self._sessions and settings != self._session_settings:
+        if not self.per_session_sampling and self._sessions and settings != self._session_settings:
             raise ValueError(f"open_stream: sampling settings {settings} differ from those of the running sessions {self._session_settings} "
                              f"(temperature, top_p, repetition_penalty, top_k, typical_mass)")
         max_mel_tokens = a["max_mel_tokens"]
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
         slot = free[0]
-        self.ar.admit(slot, cond, text_tokens, seed)
+        if self.per_session_sampling:
+            self.ar.admit(slot, cond, text_tokens, seed, **dict(zip(("temperature", "top_p", "repetition_penalty", "top_k", "typical_mass"), settings)))
+        else:
+            self.ar.admit(slot, cond, text_tokens, seed)
         size = a["stream_chunk_size"]
         chunk = size if size > 0 else max_mel_tokens
         first = max(chunk, 60) if size > 0 else max_mel_tokens  # first_buffer = 60 (api_fast.py:401, 412)
@@ -338,9 +354,12 @@ class TextToSpeech(_Common):
             raise NotImplementedError("stream_pieces: create the instance with max_streams=2 .. 4")
         while self._sessions:
             step = min(sess.target - sess.n for sess in self._sessions.values())
-            temperature, top_p, repetition_penalty, top_k, typical_mass = self._session_settings
-            n_total, finished = self.ar.advance(max(step, 1), temperature=temperature, top_p=top_p, repetition_penalty=repetition_penalty,
-                                                top_k=top_k, typical_mass=typical_mass)
+            if self.per_session_sampling:  # (every session with the settings it was opened with)
+                n_total, finished = self.ar.advance(max(step, 1))
+            else:
+                temperature, top_p, repetition_penalty, top_k, typical_mass = self._session_settings
+                n_total, finished = self.ar.advance(max(step, 1), temperature=temperature, top_p=top_p, repetition_penalty=repetition_penalty,
+                                                    top_k=top_k, typical_mass=typical_mass)
             batch = sorted(self._sessions.items())  # the sessions this advance served (open_stream / close_stream may run between pieces)
             for slot, sess in batch:
                 if self._sessions.get(slot) is not sess:  # closed while an earlier piece of this round was out
@@ -357,18 +376,28 @@ class TextToSpeech(_Common):
 
     def tts_stream_many(self, texts, **kwargs):
         """Stream several texts at once (max_streams > 1): a generator of (index into texts, wav_chunk, done).  kwargs are tts_stream's,
-        shared by all texts; use_deterministic_seed may be a list with one seed per text.  Texts beyond the free slots are admitted as
-        earlier sessions end."""
+        shared by all texts; use_deterministic_seed may be a list with one seed per text, and so may temperature, top_p,
+        repetition_penalty, top_k, typical_sampling and typical_mass on an instance with per_session_sampling.  Texts beyond the free
+        slots are admitted as earlier sessions end."""
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):
             seeds = [seeds] * len(texts)
+        per_text = {}
+        for name in ("temperature", "top_p", "repetition_penalty", "top_k", "typical_sampling", "typical_mass"):
+            if isinstance(kwargs.get(name), (list, tuple)):
+                if not self.per_session_sampling:
+                    raise ValueError(f"tts_stream_many: a list of {name} values needs an instance with per_session_sampling=True")
+                if len(kwargs[name]) != len(texts):
+                    raise ValueError(f"tts_stream_many: {len(kwargs[name])} {name} values for {len(texts)} texts")
+                per_text[name] = kwargs.pop(name)
         pending = list(range(len(texts)))
         index = {}
 
         def admit():
             while pending and len(self._sessions) < self.max_streams:
                 i = pending.pop(0)
-                index[self.open_stream(texts[i], use_deterministic_seed=seeds[i], **kwargs)] = i
+                own = {name: values[i] for name, values in per_text.items()}
+                index[self.open_stream(texts[i], use_deterministic_seed=seeds[i], **kwargs, **own)] = i
 
         admit()
         pieces = self.stream_pieces()

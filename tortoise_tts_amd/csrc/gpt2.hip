@@ -22,6 +22,7 @@ struct ArParams {
   unsigned long long keys[16];
   int row_offset;
   int pad[3];
+  SampleScalars rows[4];  // session handles: each row's sampling scalars (SampleArgs.rows), taken at its session's first step
 };
 
 struct tt_ar : EngineHandle {
@@ -100,6 +101,14 @@ struct tt_ar : EngineHandle {
   int s_n[16] = {0}, s_run[16] = {0};
   bool s_key_pending[16] = {false};
   tt_sampling s_scalars;          // the sampling scalars of the running sessions (exp_noise / seeds / group_seeds unused)
+  // The scalars of every row are device data (par_dev->rows): the step graph bakes in only which optional sampler launches the running
+  // rows need (SampleRowLaunch bits), one kept graph per combination - step for none (default settings), sess_steps[c - 1] for c.
+  KeptGraph sess_steps[3];
+  int sess_launch = 0;            // the combination of the last chunk (tt_ar_stat(2))
+  // TT_AR_OPT_SESSION_SAMPLING: tt_ar_generate_chunk takes one tt_sampling per slot; s_rows[r] = what slot r's session started with
+  int sess_sampling = 0;
+  int admissions = 0;
+  tt_sampling s_rows[4];
 };
 
 namespace tt { int g_ar_gemv = 2; }  // ttx_kernel_variant(TTX_AR_GEMV), read at tt_ar_create: handles of <= 4 sequences run 0 = the MFMA decode GEMMs | 1 = GEMV launches | 2 = GEMVs with the layer norms inside
@@ -439,6 +448,7 @@ void tt_ar_destroy(tt_ar* e) {
   if (!e) return;
   e->close();
   e->step.drop();
+  for (KeptGraph& g : e->sess_steps) g.drop();
   if (e->par_host) (void)hipHostFree(e->par_host);
   if (e->progress_host) (void)hipHostFree(e->progress_host);
   if (e->sess_host) (void)hipHostFree(e->sess_host);
@@ -470,6 +480,7 @@ static int ar_admit(tt_ar* e, int slot, int S, const float* prefix_emb, int P, h
     e->s_n[slot] = 0;
     e->s_run[slot] = SESS_RUNNING;
     e->s_key_pending[slot] = true;
+    e->admissions += 1;
     return 0;
   });
 }
@@ -713,15 +724,22 @@ static bool same_scalars(const tt_sampling& a, const tt_sampling& b) {
          a.typical_mass == b.typical_mass;
 }
 
-// Session handles: every running row advances by up to n_more tokens through the one kept step graph.  A row stops advancing at its
-// stop token; the loop ends early once no row runs.  codes [S][ldcodes]; n_total_host / finished_host [S].
+static bool valid_scalars(const tt_sampling& q) {
+  return q.temperature > 0.f && q.top_p > 0.f && q.repetition_penalty > 0.f && (q.typical_mass == 0.f || (q.typical_mass > 0.f && q.typical_mass < 1.f));
+}
+
+// Session handles: every running row advances by up to n_more tokens through the kept step graph of the optional sampler launches its
+// rows need.  A row stops advancing at its stop token; the loop ends early once no row runs.  codes [S][ldcodes]; n_total_host /
+// finished_host [S].  sp: one tt_sampling for every row, or with TT_AR_OPT_SESSION_SAMPLING one per slot (sp[S]).
 static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_sampling* sp, int* codes, int* n_total_host, int* finished_host,
                              hipStream_t stream) {
   TT_REQUIRE(S == e->cfg.max_batch, "tt_ar_generate_chunk: a session handle advances all %d slots (got %d)", e->cfg.max_batch, S);
-  TT_REQUIRE(sp->exp_noise == nullptr, "tt_ar_generate_chunk: injected exp_noise is not available on a session handle");
-  TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
-             (double)sp->typical_mass);
-  TT_REQUIRE(sp->temperature > 0.f && sp->top_p > 0.f && sp->repetition_penalty > 0.f, "tt_ar_generate_chunk: bad sampling parameters");
+  if (!e->sess_sampling) {
+    TT_REQUIRE(sp->exp_noise == nullptr, "tt_ar_generate_chunk: injected exp_noise is not available on a session handle");
+    TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
+               (double)sp->typical_mass);
+    TT_REQUIRE(sp->temperature > 0.f && sp->top_p > 0.f && sp->repetition_penalty > 0.f, "tt_ar_generate_chunk: bad sampling parameters");
+  }
   bool running = false, others = false;
   for (int r = 0; r < S; ++r) {
     if (e->s_run[r] != SESS_RUNNING) continue;
@@ -731,31 +749,55 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
     TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "tt_ar_generate_chunk: slot %d: %d + %d tokens exceed capacity (%d code columns, %d KV slots)", r,
                e->s_n[r], n_more, ldcodes, e->tmax);
     TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate_chunk: slot %d: %d tokens exceed the mel position table", r, target);
+    if (e->sess_sampling) {  // (entries of free and finished slots are not read)
+      const tt_sampling& q = sp[r];
+      TT_REQUIRE(q.exp_noise == nullptr && q.group_seeds == nullptr, "tt_ar_generate_chunk: slot %d: exp_noise and group_seeds are not available with per-session sampling (seed is the key)", r);
+      TT_REQUIRE(valid_scalars(q), "tt_ar_generate_chunk: slot %d: bad sampling parameters (temperature %g, top_p %g, repetition_penalty %g, typical_mass %g)", r,
+                 (double)q.temperature, (double)q.top_p, (double)q.repetition_penalty, (double)q.typical_mass);
+      TT_REQUIRE(e->s_key_pending[r] || (same_scalars(q, e->s_rows[r]) && q.seed == e->s_rows[r].seed),
+                 "tt_ar_generate_chunk: slot %d: sampling settings differ from those its session started with", r);
+    }
   }
-  // the sampling scalars belong to the handle while a session that already sampled runs
-  TT_REQUIRE(!others || same_scalars(*sp, e->s_scalars), "tt_ar_generate_chunk: sampling settings differ from those of the running sessions");
+  // the sampling scalars belong to the handle while a session that already sampled runs (unless each session has its own)
+  TT_REQUIRE(e->sess_sampling || !others || same_scalars(*sp, e->s_scalars), "tt_ar_generate_chunk: sampling settings differ from those of the running sessions");
   return e->sb.run(stream, [&](hipStream_t s) -> int {
     if (running) {
-      e->s_scalars = *sp;
+      if (!e->sess_sampling) e->s_scalars = *sp;
+      // a session's key and scalars are taken at its first step; the others keep theirs
+      int launch = 0;
+      for (int r = 0; r < S; ++r) {
+        if (e->s_run[r] != SESS_RUNNING) continue;
+        if (e->s_key_pending[r]) {
+          const tt_sampling& q = e->sess_sampling ? sp[r] : *sp;
+          e->par_host->keys[r] = e->sess_sampling ? q.seed : (sp->group_seeds ? sp->group_seeds[r] : sp->seed);
+          SampleScalars& sc = e->par_host->rows[r];
+          sc.rep_penalty = q.repetition_penalty; sc.temperature = q.temperature; sc.top_p = q.top_p; sc.top_k = q.top_k; sc.typical_mass = q.typical_mass;
+          e->s_rows[r] = q;
+          e->s_rows[r].exp_noise = nullptr;
+          e->s_rows[r].group_seeds = nullptr;
+          e->s_rows[r].seed = e->par_host->keys[r];
+        }
+        const SampleScalars& sc = e->par_host->rows[r];
+        if (!sample_fast_k(sc.top_k)) launch |= SAMPLE_ROWS_WIDE;
+        if (sc.typical_mass != 0.f) launch |= SAMPLE_ROWS_TYPICAL;
+      }
+      e->par_host->row_offset = 0;
       SampleArgs sa;
       memset(&sa, 0, sizeof(sa));
       sa.B = S; sa.V = e->V; sa.seen = e->seen;
-      sa.rep_penalty = sp->repetition_penalty; sa.temperature = sp->temperature; sa.top_p = sp->top_p; sa.top_k = sp->top_k;
+      sa.rows = e->par_dev->rows; sa.row_launch = launch;  // (the five scalars of the argument block stay zero: every row reads its own)
       sa.state = e->state; sa.unfinished = e->unfinished; sa.stop_token = e->cfg.stop_mel_token;
       sa.codes = e->codes_own; sa.ldcodes = e->tmax; sa.next_tok = e->next_tok; sa.unfinished_count = e->unfinished_count;
       sa.embed_x = e->x; sa.tok_emb = e->w.mel_emb; sa.pos_emb = e->w.mel_pos; sa.D = e->D; sa.pos_offset = e->cfg.mel_pos_offset;
       sa.pos_len = e->cfg.mel_pos_len;
       sa.guard = e->guard.dev;
-      sa.typical_mass = sp->typical_mass; sa.typical_out = e->typ_logits;
+      sa.typical_out = e->typ_logits;
       sa.keys_dev = e->par_dev->keys;
       sa.row_offset_dev = &e->par_dev->row_offset;
       sa.sess = e->sess; sa.pre_logits = e->pre_logits;
       sa.logits = e->logits; sa.ldl = e->Vp; sa.ldg = e->Vp;
-      e->typical = sp->typical_mass != 0.f;
-      // a session's key is taken at its first step; the others keep theirs
-      for (int r = 0; r < S; ++r)
-        if (e->s_run[r] == SESS_RUNNING && e->s_key_pending[r]) e->par_host->keys[r] = sp->group_seeds ? sp->group_seeds[r] : sp->seed;
-      e->par_host->row_offset = 0;
+      e->typical = (launch & SAMPLE_ROWS_TYPICAL) != 0;
+      e->sess_launch = launch;
       TT_CHECK_HIP(hipMemcpyAsync(e->par_dev, e->par_host, sizeof(ArParams), hipMemcpyHostToDevice, s));
       // the counters of this call: state[0] = its steps so far, state[2] = the step after which no row ran (-1: none yet)
       TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->state, 0, 1, s));
@@ -772,14 +814,16 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
         TT_TRY(sample_launch(sa, st));
         return ar_sess_advance_launch(e->state, e->sess, S, e->unfinished, e->unfinished_count, e->progress_dev, st);
       };
+      KeptGraph& graph = launch ? e->sess_steps[launch - 1] : e->step;
       const bool use_graph = graphs_enabled();
       if (use_graph) {
-        // baked in: the sampler's argument block and the profiler switch - no batch, prefix length or step of any row
+        // baked in: the sampler's argument block (pointers and the combination of optional launches) and the profiler switch - no
+        // batch, prefix length, step or sampling scalar of any row
         std::vector<unsigned char> key(sizeof(sa) + 4 * sizeof(int));
         memcpy(key.data(), &sa, sizeof(sa));
         int geo[4] = {S, -1, e->cfg.max_prefix, g_prof_on ? 1 : 0};
         memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
-        TT_TRY(e->step.ensure(s, key.data(), key.size(), "tt_ar_generate_chunk", [&]() -> int { return step_enqueue(s); }));
+        TT_TRY(graph.ensure(s, key.data(), key.size(), "tt_ar_generate_chunk", [&]() -> int { return step_enqueue(s); }));
       }
       int rc = 0;
       for (int step = 0; step < n_more; ++step) {
@@ -798,7 +842,7 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
           usleep(50);
         }
         if (rc || prog[1] >= 0) break;
-        rc = use_graph ? e->step.launch(s, "tt_ar_generate_chunk") : step_enqueue(s);
+        rc = use_graph ? graph.launch(s, "tt_ar_generate_chunk") : step_enqueue(s);
         if (rc) break;
       }
       if (!rc) {
@@ -812,7 +856,7 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
       }
       if (rc) {
         (void)hipStreamSynchronize(s);
-        e->step.drop();
+        graph.drop();
         return rc;
       }
       for (int r = 0; r < S; ++r) {
@@ -914,14 +958,17 @@ int tt_ar_guard(tt_ar* e, int reset) {
 // 2 = kernel launches of one decode step (layers + head + sampler + step counter).
 int tt_ar_stat(tt_ar* e, int which) {
   if (!e) { set_error("tt_ar_stat: null handle"); return -1; }
-  const int per_step = 7 * e->cfg.layers + 4 + (e->typical ? 1 : 0);
-  return which == 0 ? e->step.captures : which == 1 ? e->drains : which == 2 ? per_step : -1;
+  const int per_step = 7 * e->cfg.layers + 4 + (e->typical ? 1 : 0) + (e->sessions && (e->sess_launch & SAMPLE_ROWS_WIDE) ? 1 : 0);
+  int captures = e->step.captures;
+  for (const KeptGraph& g : e->sess_steps) captures += g.captures;
+  return which == 0 ? captures : which == 1 ? e->drains : which == 2 ? per_step : -1;
 }
 
 // Engine options of a handle (defaults in brackets):
 //   TT_AR_OPT_LOOKAHEAD      [6]  decode steps the host may run ahead of the device (>= 1)
 //   TT_AR_OPT_SESSIONS       [0]  1: the handle serves streaming sessions, one per row (fresh handles of <= 4 rows, 16-bit, max_groups >= max_batch)
 //   TT_AR_OPT_SESSION_CLOSE       retire the session in slot `value` of a session handle
+//   TT_AR_OPT_SESSION_SAMPLING [0] 1: tt_ar_generate_chunk takes one tt_sampling per slot (session handles, before the first admission)
 int tt_ar_set_option(tt_ar* e, int option, int value) {
   TT_REQUIRE(e != nullptr, "tt_ar_set_option: null handle");
   switch (option) {
@@ -958,6 +1005,12 @@ int tt_ar_set_option(tt_ar* e, int option, int value) {
       memset(e->s_run, 0, sizeof(e->s_run));
       break;
     }
+    case TT_AR_OPT_SESSION_SAMPLING:
+      TT_REQUIRE(e->sessions, "tt_ar_set_option: TT_AR_OPT_SESSION_SAMPLING needs a session handle (TT_AR_OPT_SESSIONS)");
+      TT_REQUIRE(value == 1 && !e->sess_sampling, "tt_ar_set_option: per-session sampling is switched on once, with value 1 (got %d)", value);
+      TT_REQUIRE(e->admissions == 0, "tt_ar_set_option: per-session sampling must be switched on before the first admission");
+      e->sess_sampling = 1;
+      break;
     case TT_AR_OPT_SESSION_CLOSE:
       TT_REQUIRE(e->sessions, "tt_ar_set_option: TT_AR_OPT_SESSION_CLOSE needs a session handle (TT_AR_OPT_SESSIONS)");
       TT_REQUIRE(value >= 0 && value < e->cfg.max_batch && e->s_run[value] != SESS_FREE, "tt_ar_set_option: slot %d holds no session to close", value);

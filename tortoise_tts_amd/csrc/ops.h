@@ -157,6 +157,12 @@ bool gemv_supported(int dtype, const GemvArgs& a);
 int gemv_launch(int dtype, const GemvArgs& a, hipStream_t stream);
 
 // ------------------------------------------------------------------------------ AR sampling
+// one row's sampling scalars (session handles keep them in device memory, one entry per row: SampleArgs.rows)
+struct SampleScalars {
+  float rep_penalty, temperature, top_p;
+  int top_k;
+  float typical_mass;
+};
 struct SampleArgs {
   const float* logits;  // [B][ldl]; ldl == 0 broadcasts one row per utterance group (the shared-prefix prefill logits), ldg apart
   int ldl, ldg;
@@ -200,7 +206,16 @@ struct SampleArgs {
   // ones from `logits`.  state[0] counts the steps of the call (unfinished_count index).  Rows that do not sample zero their embed_x row.
   int* sess;
   const float* pre_logits;
+  // per-row sampling scalars (session handles; rows != null): row b samples with rows[b] (block-uniform, read once) instead of the five
+  // scalars above, which are then unused.  Each launch covers all B rows and a row is served by the launch that owns it: the fast
+  // sampler (top_k 1 .. 256; it also zeroes the rows that do not sample), the full-sort sampler (any other top_k) and, for rows with
+  // typical_mass != 0, the typical mask ahead of both.  row_launch (SampleRowLaunch bits) says which of the two optional launches run.
+  const SampleScalars* rows;
+  int row_launch;
 };
+enum SampleRowLaunch { SAMPLE_ROWS_WIDE = 1, SAMPLE_ROWS_TYPICAL = 2 };
+// which sampler serves a row with this top_k (the fast one: 1 .. 256)
+static inline __host__ __device__ bool sample_fast_k(int top_k) { return top_k >= 1 && top_k <= 256; }
 // planes of the per-row session state (tt_ar session handles): int[4][max_batch]
 enum SessPlane { SESS_N = 0, SESS_SLOT = 1, SESS_RUN = 2, SESS_P1 = 3 };
 enum SessRun { SESS_FREE = 0, SESS_RUNNING = 1, SESS_FINISHED = 2 };

@@ -107,6 +107,19 @@ __device__ __forceinline__ unsigned long long sample_key(const SampleArgs& a, in
   // else from the argument block; a session row has its own key
   return a.keys_dev ? a.keys_dev[a.sess ? b : grp] : (a.ngroups > 1 ? a.group_seeds[grp] : a.seed);
 }
+// the row's sampling scalars: its own entry on a session handle with per-row scalars (block-uniform, read once), else the argument block
+__device__ __forceinline__ SampleScalars sample_scalars(const SampleArgs& a, int b) {
+  if (a.rows) return a.rows[b];
+  SampleScalars sc;
+  sc.rep_penalty = a.rep_penalty; sc.temperature = a.temperature; sc.top_p = a.top_p; sc.top_k = a.top_k; sc.typical_mass = a.typical_mass;
+  return sc;
+}
+// per-row scalars: a typical row reads the mask's output row, the others their own source (sample_launch switches `logits` for the
+// whole launch otherwise)
+__device__ __forceinline__ const float* sample_row_logits(const SampleArgs& a, const SampleScalars& sc, int b, int grp, int step) {
+  if (a.rows && sc.typical_mass != 0.f) return a.typical_out + (size_t)b * a.ldl;
+  return sample_logits(a, b, grp, step);
+}
 __device__ __forceinline__ int sample_cand(const SampleArgs& a, int b, int grp, int row_offset) {
   // global index of the candidate: within its utterance (the draw does not depend on the batching); a session row is candidate 0
   return a.sess ? 0 : row_offset + (a.ngroups > 1 ? b - grp * a.group_size : b);
@@ -133,11 +146,13 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   TT_STAMP(0);
   const int V = a.V;
   if (sess_idle(a, b, tid, 256)) return;
+  const SampleScalars sc = sample_scalars(a, b);
+  if (a.rows && !sample_fast_k(sc.top_k)) return;  // (a row of the full-sort sampler)
   const int step = sample_step(a, b);
   const int grp = a.ngroups > 1 ? b / a.group_size : 0;  // utterance of this row (block-uniform)
   const unsigned long long philox_key = sample_key(a, b, grp);  // Philox key of this row's utterance (block-uniform, read once)
   const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;  // (block-uniform scalar load)
-  const float* lg = sample_logits(a, b, grp, step);
+  const float* lg = sample_row_logits(a, sc, b, grp, step);
   unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
   float val[PER];
   bool bad = false;  // NaN / +inf logits: an operand overflowed somewhere upstream (-inf is legitimate: a suppressed token)
@@ -159,8 +174,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       float s = raw[j];
       const bool live = t < V;
       bad = bad || (live && (s != s || s == INFINITY));
-      if (a.rep_penalty != 1.0f && ((sw[j] >> (t & 31)) & 1u)) s = s < 0.f ? s * a.rep_penalty : s / a.rep_penalty;
-      if (a.temperature != 1.0f) s = s / a.temperature;
+      if (sc.rep_penalty != 1.0f && ((sw[j] >> (t & 31)) & 1u)) s = s < 0.f ? s * sc.rep_penalty : s / sc.rep_penalty;
+      if (sc.temperature != 1.0f) s = s / sc.temperature;
       if (__float_as_uint(s) == 0x80000000u) s = 0.f;  // -0.0 ties with +0.0 in the reference's float comparisons: one zero, so that key order == float order
       val[j] = live ? s : -INFINITY;
     }
@@ -181,7 +196,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   // A plateau of equal scores that overflows the candidate buffer, or k beyond the populated threads, takes the generic path: a
   // counting search over all register-resident keys, 16 rounds.  (Round 3's radix select put ~8 000 LDS atomicAdds on three or
   // four bins in its first pass: logits share their sign / exponent byte.)
-  const int k = a.top_k < V ? a.top_k : V;
+  const int k = sc.top_k < V ? sc.top_k : V;
   const int lane = tid & 63;
   unsigned key[PER];
   unsigned tmax = 0u;
@@ -401,11 +416,11 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       TT_STAMP(6);
       TT_STAMP(7);
       int keep = n;
-      if (a.top_p < 1.0f) {
+      if (sc.top_p < 1.0f) {
         // ascending cumulative probability of element r == sum of the probabilities of elements n-1 .. r; the partial sums never decrease,
         // so "the first r (from the top) whose sum exceeds 1 - top_p" is 1 + the number of r in [1, n) whose sum does
         const int pb = __builtin_bit_cast(int, e / total);
-        const float thr = 1.0f - a.top_p;
+        const float thr = 1.0f - sc.top_p;
         float tail = 0.f;
         int over = 0;
 #pragma unroll
@@ -474,10 +489,10 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     if (tid < 64) {  // wave 0, every lane redundantly: the same sequential arithmetic as one thread walking the arrays
       const float* pr = (const float*)si;
       int keep = n;
-      if (a.top_p < 1.0f) {
+      if (sc.top_p < 1.0f) {
         float tail = 0.f;
         keep = 1;
-        const float thr = 1.0f - a.top_p;
+        const float thr = 1.0f - sc.top_p;
         // ascending cumulative probability of element r == sum of probabilities of elements r..n-1
         bool done = false;
         for (int hi = n - 1; hi >= 1 && !done; hi -= 64) {  // elements hi, hi - 1, ... in chunks of 64 (lane j holds element hi - j)
@@ -582,19 +597,25 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   __shared__ int red_i[16];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int V = a.V;
-  if (sess_idle(a, b, tid, 1024)) return;
+  const SampleScalars sc = sample_scalars(a, b);
+  if (a.rows) {
+    // per-row scalars: only the running rows of this sampler; the fast sampler zeroes the rows that do not sample (once per row)
+    if (a.sess[SESS_RUN * a.B + b] != SESS_RUNNING || sample_fast_k(sc.top_k)) return;
+  } else if (sess_idle(a, b, tid, 1024)) {
+    return;
+  }
   const int step = sample_step(a, b);
   const int grp = a.ngroups > 1 ? b / a.group_size : 0;
   const unsigned long long philox_key = sample_key(a, b, grp);
   const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;
-  const float* lg = sample_logits(a, b, grp, step);
+  const float* lg = sample_row_logits(a, sc, b, grp, step);
   unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
   for (int t = tid; t < WIDE_N; t += 1024) {
     unsigned kk = 0u;  // padding slots sort behind every real score (f2key(-inf) = 0x007FFFFF > 0)
     if (t < V) {
       float s = lg[t];
-      if (a.rep_penalty != 1.0f && ((seen[t >> 5] >> (t & 31)) & 1u)) s = s < 0.f ? s * a.rep_penalty : s / a.rep_penalty;
-      if (a.temperature != 1.0f) s = s / a.temperature;
+      if (sc.rep_penalty != 1.0f && ((seen[t >> 5] >> (t & 31)) & 1u)) s = s < 0.f ? s * sc.rep_penalty : s / sc.rep_penalty;
+      if (sc.temperature != 1.0f) s = s / sc.temperature;
       kk = f2key(s);
     }
     key[t] = kk;
@@ -619,7 +640,7 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   }
   __syncthreads();
   // survivors of top-k: everything >= the k-th score (ties kept, like TopKLogitsWarper's `scores < kth` removal)
-  const int k_eff = (a.top_k <= 0 || a.top_k > V) ? V : a.top_k;
+  const int k_eff = (sc.top_k <= 0 || sc.top_k > V) ? V : sc.top_k;
   const unsigned kth = key[k_eff - 1];
   for (int t = tid; t < V; t += 1024)
     if (key[t] >= kth && (t + 1 == V || key[t + 1] < kth)) n_s = t + 1;
@@ -632,10 +653,10 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
     float total = 0.f;
     for (int i = 0; i < n; ++i) total += ef[i];
     int keep = n;
-    if (a.top_p < 1.0f) {
+    if (sc.top_p < 1.0f) {
       float tail = 0.f;
       keep = 1;
-      const float thr = 1.0f - a.top_p;
+      const float thr = 1.0f - sc.top_p;
       for (int r = n - 1; r >= 1; --r) {
         tail += ef[r] / total;
         if (tail > thr) {
@@ -732,6 +753,8 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
   const size_t row_off = a.ldl ? (size_t)r * a.ldl : (size_t)r * (a.ldg ? a.ldg : V);
   const int seen_row = a.ldl ? r : (a.ngroups > 1 ? r * a.group_size : 0);
   if (a.sess && a.sess[SESS_RUN * a.B + r] != SESS_RUNNING) return;  // (session handles: a row that does not sample)
+  const SampleScalars sc = sample_scalars(a, r);
+  if (a.rows && sc.typical_mass == 0.f) return;  // (per-row scalars: a row without typical sampling)
   const float* lg = a.sess ? sample_logits(a, r, 0, sample_step(a, r)) : a.logits + row_off;
   float* out = a.typical_out + row_off;
   const unsigned* seen = a.seen + (size_t)seen_row * ((V + 31) / 32);
@@ -743,7 +766,7 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
     const int tc = min(t, V - 1);
     raw[j] = lg[tc];
     float x = raw[j];
-    if (a.rep_penalty != 1.0f && ((seen[tc >> 5] >> (tc & 31)) & 1u)) x = x < 0.f ? x * a.rep_penalty : x / a.rep_penalty;
+    if (sc.rep_penalty != 1.0f && ((seen[tc >> 5] >> (tc & 31)) & 1u)) x = x < 0.f ? x * sc.rep_penalty : x / sc.rep_penalty;
     s[j] = t < V ? x : -INFINITY;
     m = fmaxf(m, s[j]);
   }
@@ -787,7 +810,7 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
 #pragma unroll
     for (int j = 0; j < TYP_PER; ++j) part += key[j] < c ? (double)pc[j] : 0.0;
     const float below = (float)typ_block_sum(part, red_d[2 + (bit & 1)], tid);  // two slot sets: one barrier per round
-    tau = below < a.typical_mass ? c : tau;  // (block-uniform: every thread adds the same 16 partials in the same order)
+    tau = below < sc.typical_mass ? c : tau;  // (block-uniform: every thread adds the same 16 partials in the same order)
   }
 #pragma unroll
   for (int j = 0; j < TYP_PER; ++j) {
@@ -798,20 +821,56 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
 
 int typical_mask_launch(const SampleArgs& a, hipStream_t stream) {
   TT_REQUIRE(a.B > 0 && a.V > 0 && a.V <= WIDE_V, "typical mask: V=%d unsupported (<= %d)", a.V, WIDE_V);
-  TT_REQUIRE(a.typical_mass > 0.f && a.typical_mass < 1.f, "sample: typical_mass %g outside (0, 1)", (double)a.typical_mass);
-  TT_REQUIRE(a.typical_out != nullptr && a.rep_penalty > 0.f, "sample: typical sampling needs a row buffer and a positive repetition penalty");
+  if (a.rows) {  // (per-row scalars: the engine validated every row's mass and penalty; rows with mass 0 return at once)
+    TT_REQUIRE(a.typical_out != nullptr && a.sess && a.ldl > 0, "sample: per-row typical sampling needs a session handle's row buffer");
+  } else {
+    TT_REQUIRE(a.typical_mass > 0.f && a.typical_mass < 1.f, "sample: typical_mass %g outside (0, 1)", (double)a.typical_mass);
+    TT_REQUIRE(a.typical_out != nullptr && a.rep_penalty > 0.f, "sample: typical sampling needs a row buffer and a positive repetition penalty");
+  }
   const int rows = a.ldl ? a.B : (a.ngroups > 1 ? a.ngroups : 1);
   hipLaunchKernelGGL(typical_mask_kernel, dim3(rows), dim3(1024), 0, stream, a);
   TT_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
+static int sample_wide_launch(const ProfScope& ps, const SampleArgs& a, hipStream_t stream) {
+  constexpr size_t smem = (size_t)WIDE_N * 6 + (size_t)WIDE_V * 4;
+  static bool attr_done = false;
+  if (!attr_done) {
+    TT_CHECK_HIP(hipFuncSetAttribute((const void*)sample_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    attr_done = true;
+  }
+  launch_timed(ps, sample_wide_kernel, dim3(a.B), dim3(1024), smem, stream, a);
+  return 0;
+}
+
+static void sample_fast_launch(const ProfScope& ps, const SampleArgs& a, hipStream_t stream) {
+  if (a.V <= 33 * 256) launch_timed(ps, sample_kernel<33>, dim3(a.B), dim3(256), 0, stream, a);
+  else launch_timed(ps, sample_kernel<40>, dim3(a.B), dim3(256), 0, stream, a);
+}
+
 int sample_launch(const SampleArgs& a_in, hipStream_t stream) {
   SampleArgs a = a_in;
   TT_REQUIRE(a.B > 0 && a.V > 0 && a.V <= WIDE_V, "sample: V=%d unsupported (<= %d)", a.V, WIDE_V);
   TT_REQUIRE(a.ngroups <= 1 || (a.ngroups <= 16 && a.group_size > 0 && a.B == a.ngroups * a.group_size), "sample: %d groups of %d rows do not make %d rows", a.ngroups, a.group_size, a.B);
-  TT_REQUIRE(a.temperature > 0.f && a.top_p > 0.f && a.rep_penalty > 0.f, "sample: bad sampling parameters");
+  TT_REQUIRE(a.rows || (a.temperature > 0.f && a.top_p > 0.f && a.rep_penalty > 0.f), "sample: bad sampling parameters");
   TT_REQUIRE(!a.sess || (a.ldl > 0 && a.ngroups <= 1 && !a.exp_noise && a.keys_dev), "sample: session rows need per-row logits, device keys and no injected noise");
+  if (a.rows) {
+    // per-row scalars (session handles): the typical mask when a row needs it, the fast sampler always (it owns the rows that do not
+    // sample), the full-sort sampler when a row needs it - each launch over all rows, each row served by its own
+    TT_REQUIRE(a.sess != nullptr, "sample: per-row sampling scalars need a session handle");
+    if (a.row_launch & SAMPLE_ROWS_TYPICAL) TT_TRY(typical_mask_launch(a, stream));
+    {
+      ProfScope ps(PROF_SAMPLE, stream, 0.0, (double)a.B * a.V * 4.0, true);
+      sample_fast_launch(ps, a, stream);
+    }
+    if (a.row_launch & SAMPLE_ROWS_WIDE) {
+      ProfScope ps(PROF_SAMPLE, stream, 0.0, (double)a.B * a.V * 4.0, true);
+      TT_TRY(sample_wide_launch(ps, a, stream));
+    }
+    TT_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   if (a.typical_mass != 0.f) {
     TT_TRY(typical_mask_launch(a, stream));
     a.logits = a.typical_out;
@@ -819,16 +878,9 @@ int sample_launch(const SampleArgs& a_in, hipStream_t stream) {
   }
   ProfScope ps(PROF_SAMPLE, stream, 0.0, (double)a.B * a.V * 4.0, true);
   if (a.top_k >= 1 && a.top_k <= 256) {
-    if (a.V <= 33 * 256) launch_timed(ps, sample_kernel<33>, dim3(a.B), dim3(256), 0, stream, a);
-    else launch_timed(ps, sample_kernel<40>, dim3(a.B), dim3(256), 0, stream, a);
+    sample_fast_launch(ps, a, stream);
   } else {  // top_k == 0 (HF: no top-k warper), > 256, or beyond the vocabulary: the full-sort kernel
-    constexpr size_t smem = (size_t)WIDE_N * 6 + (size_t)WIDE_V * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-      TT_CHECK_HIP(hipFuncSetAttribute((const void*)sample_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-      attr_done = true;
-    }
-    launch_timed(ps, sample_wide_kernel, dim3(a.B), dim3(1024), smem, stream, a);
+    TT_TRY(sample_wide_launch(ps, a, stream));
   }
   TT_CHECK_HIP(hipGetLastError());
   return 0;

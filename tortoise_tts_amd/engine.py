@@ -14,6 +14,7 @@ DTYPE_NAMES = {TT_BF16: "bf16", TT_F16: "fp16", TT_F32: "fp32"}
 TT_AR_OPT_LOOKAHEAD = 4
 TT_AR_OPT_SESSIONS = 5
 TT_AR_OPT_SESSION_CLOSE = 6
+TT_AR_OPT_SESSION_SAMPLING = 7
 TT_DIFF_OPT_OVERLAP_PREPASS = 1
 TT_DIFF_OPT_FUSED_GN = 2
 TTX_FLASH32, TTX_GEMM_P8, TTX_VOC_MFMA, TTX_GEMM_SKINNY, TTX_AR_GEMV = 0, 1, 2, 3, 4  # ttx_kernel_variant families (include/tortoise_mi355x_test.h)

@@ -16,6 +16,17 @@ from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderCo
 from .schedule import Schedule
 
 
+def session_sampling(temperature=0.8, top_p=0.8, repetition_penalty=2.0, top_k=50, typical_mass=0.0):
+    """One session's sampling settings as the engine takes them: (temperature, top_p, repetition_penalty, top_k, typical_mass), checked
+    as tt_ar_generate_chunk checks them (ValueError).  typical_mass 0 = off."""
+    v = (float(temperature), float(top_p), float(repetition_penalty), int(top_k), float(typical_mass))
+    if not (v[0] > 0 and v[1] > 0 and v[2] > 0):
+        raise ValueError(f"temperature={temperature}, top_p={top_p} and repetition_penalty={repetition_penalty} must be positive")
+    if not (v[4] == 0.0 or 0.0 < v[4] < 1.0):
+        raise ValueError(f"typical_mass={typical_mass} must be 0 (off) or lie in (0, 1)")
+    return v
+
+
 def _i32(t, device):
     return t.to(device=device, dtype=torch.int32).contiguous()
 
@@ -82,9 +93,13 @@ class ArStage(_GuardedHandle):
     api = "tt_ar"
 
     def __init__(self, sd, cfg: ARConfig = ARConfig(), device="cuda", dtype=E.TT_BF16, max_batch=256, max_text=402,
-                 max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1, sessions=False):
+                 max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1, sessions=False,
+                 per_session_sampling=False):
         """sessions=True: a session handle (TT_AR_OPT_SESSIONS) - each of its max_batch <= 4 rows serves one streaming session, admitted,
-        advanced and retired on its own (admit / advance / session_codes / session_latents / close(slot))."""
+        advanced and retired on its own (admit / advance / session_codes / session_latents / close(slot)).  per_session_sampling=True
+        (TT_AR_OPT_SESSION_SAMPLING): every session keeps the sampling settings it was admitted with (admit(..., temperature=...))."""
+        if per_session_sampling and not sessions:
+            raise ValueError("per_session_sampling=True needs sessions=True")
         self.lib = E.init()
         if sessions:
             max_groups = max(max_groups, max_batch)
@@ -114,6 +129,10 @@ class ArStage(_GuardedHandle):
         self.sessions = bool(sessions)
         if self.sessions:
             self.set_option(E.TT_AR_OPT_SESSIONS, 1)
+            self.per_session_sampling = bool(per_session_sampling)
+            if self.per_session_sampling:
+                self.set_option(E.TT_AR_OPT_SESSION_SAMPLING, 1)
+                self._settings = [session_sampling()] * max_batch
             self.max_batch = max_batch
             self.max_new = max_new_tokens
             self._seeds = [0] * max_batch
@@ -224,28 +243,53 @@ class ArStage(_GuardedHandle):
         return out
 
     # -- session handles (sessions=True): one streaming session per row
-    def admit(self, slot, cond_latent, text_tokens, seed):
+    def admit(self, slot, cond_latent, text_tokens, seed, **settings):
         """Start a session in free row `slot`: its prefix is evaluated now, its first token is drawn at the next advance() with Philox
-        key `seed`.  The running sessions are untouched."""
+        key `seed`.  The running sessions are untouched.  With per_session_sampling, `settings` are the session's own (temperature,
+        top_p, repetition_penalty, top_k, typical_mass; session_sampling's defaults), validated before the row is taken."""
+        if self.per_session_sampling:
+            own = session_sampling(**settings)
+        elif settings:
+            raise TypeError("admit: sampling settings belong to advance() unless the stage was made with per_session_sampling=True")
         emb = self.prefix_embedding(cond_latent[:1], text_tokens[:1])[0].contiguous()
         E.check(self.lib.tt_ar_prefill_group(self.h, int(slot), self.max_batch, E.ptr(emb), emb.shape[0], E.stream_ptr()))
         self._seeds[slot] = int(seed)
         self._n[slot], self._finished[slot] = 0, False
+        if self.per_session_sampling:
+            self._settings[slot] = own
 
-    def advance(self, n, temperature=0.8, top_p=0.8, repetition_penalty=2.0, top_k=50, typical_mass=0.0):
+    def advance(self, n, *args, **scalars):
         """Every running session samples up to n more tokens (a session stops at its stop token).  Returns (n_total, finished), lists
-        over the slots.  The sampling settings belong to the handle while a session that has sampled runs."""
+        over the slots.  scalars: temperature=0.8, top_p=0.8, repetition_penalty=2.0, top_k=50, typical_mass=0.0 - they belong to the
+        handle while a session that has sampled runs.  With per_session_sampling every session samples with its own settings (admit)
+        and passing scalars here is a TypeError."""
         S = self.max_batch
+        if self.per_session_sampling:
+            if args or scalars:
+                raise TypeError(f"advance: per-session sampling takes each session's settings at admit(), not {list(args) + sorted(scalars)}")
+            s = (E.Sampling * S)()
+            for r in range(S):
+                v = self._settings[r]
+                s[r].temperature, s[r].top_p, s[r].repetition_penalty, s[r].top_k, s[r].typical_mass = v
+                s[r].seed, s[r].row_offset, s[r].exp_noise, s[r].group_seeds = self._seeds[r], 0, None, None
+            sp = s
+        else:
+            s, gs = self._shared_sampling(*args, **scalars)
+            sp = C.byref(s)
+        n_total, fin = (C.c_int * S)(), (C.c_int * S)()
+        E.check(self.lib.tt_ar_generate_chunk(self.h, S, 0, int(n), self.max_new, sp, E.ptr(self._codes), n_total, fin, E.stream_ptr()))
+        self._n, self._finished = list(n_total), [bool(v) for v in fin]
+        return list(self._n), list(self._finished)
+
+    def _shared_sampling(self, temperature=0.8, top_p=0.8, repetition_penalty=2.0, top_k=50, typical_mass=0.0):
+        """The one tt_sampling of a handle without per-session sampling (and the seed array it points to)."""
         s = E.Sampling()
         s.temperature, s.top_p, s.repetition_penalty, s.top_k = temperature, top_p, repetition_penalty, top_k
         s.typical_mass = float(typical_mass)
         s.seed, s.row_offset, s.exp_noise = 0, 0, None
-        gs = (C.c_ulonglong * S)(*self._seeds)
+        gs = (C.c_ulonglong * self.max_batch)(*self._seeds)
         s.group_seeds = C.cast(gs, C.POINTER(C.c_ulonglong))
-        n_total, fin = (C.c_int * S)(), (C.c_int * S)()
-        E.check(self.lib.tt_ar_generate_chunk(self.h, S, 0, int(n), self.max_new, C.byref(s), E.ptr(self._codes), n_total, fin, E.stream_ptr()))
-        self._n, self._finished = list(n_total), [bool(v) for v in fin]
-        return list(self._n), list(self._finished)
+        return s, gs
 
     def session_codes(self, slot):
         """int64 [1, n]: the tokens session `slot` has sampled (its stop token included once it has finished)."""
