@@ -77,6 +77,21 @@ int tt_op_convt1d(const float* x, const float* w, const float* bias, float* y, i
 int tt_op_lvc(int dtype, const float* x_in, const void* kernels, int ldk, int koff, const float* bias, int ldb, int boff, float* x, int L,
               int hop, void* stream);
 
+/* wav2vec2 aligner front (csrc/align.hip, include/tortoise_mi355x_align.h).  Resampler: y f32 [ceil(2 S / 3)] = torchaudio's 24 -> 16 kHz
+ * resample of x f32 [S] with taps f32 [2][23]; stats f32 [2] = {mean, 1 / sqrt(unbiased var + 1e-7)} of y; workspace of
+ * tt_op_w2v_resample_workspace(S) bytes. */
+size_t tt_op_w2v_resample_workspace(int S);
+int tt_op_w2v_resample(const float* x, int S, const float* taps, float* y, float* stats, void* workspace, void* stream);
+/* feature-encoder layer 0: out [frames][512] = GELU(LayerNorm(Conv1d(1, 512, k, stride)((y - stats[0]) * stats[1]) + b; g, beta, 1e-5));
+ * w f32 [512][k] (k = 10); out_t in the operand type `dtype`, out_f32 optional */
+int tt_op_w2v_conv0(int dtype, const float* y, const float* stats, int frames, int k, int stride, const float* w, const float* b, const float* g,
+                    const float* beta, void* out_t, float* out_f32, void* stream);
+/* row LayerNorm followed by an activation (ACT_* code) in one launch: out = act(LayerNorm(x[M][D]; g, b, eps)) */
+int tt_op_layernorm_act(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int act, void* out_t, float* out_f32,
+                        void* stream);
+/* ids int32 [T] = per-row argmax of logits f32 [T][ld] over the first V columns (ties: lowest index); out (optional) f32 [T][V] gets the rows */
+int tt_op_w2v_argmax(const float* logits, int ld, int T, int V, int* ids, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

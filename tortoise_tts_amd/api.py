@@ -15,10 +15,12 @@ Constructor flags of the reference and what they mean here:
                0,1,2,...; kv_cache=True: rows 0,2,3,...; autoregressive.py:134-149);
   * half       True selects fp16 MFMA operands (the reference's fp16 autocast), False the engine default (bf16) unless
                the engine-only `dtype=` says otherwise;
-  * enable_redaction  bracketed text needs the wav2vec2 aligner (out of scope): such text raises, other text is unaffected.
+  * enable_redaction  [bracketed] text is spoken and then cut out of every returned clip by the wav2vec2 CTC aligner, as
+               wav2vec_alignment.py does (align.py + stages.AlignerStage, csrc/align.hip; built on first use from the HF-format files
+               under models_dir or the HF hub cache, or the engine-only `aligner=`); text without '[' is unaffected.
 cvvp_amount > 0 (api.py:450-472; the CHANGELOG calls CVVP "removed", the call sites and cvvp.pth remain): the CVVP model is built on
 first use like upstream (load_cvvp -> stages.CvvpStage, csrc/cvvp.hip) and blended into the CLVP ranking when voice_samples are given.
-Out of scope (raise, never silently fall back): wav2vec redaction of bracketed text, DeepSpeed flag.
+Out of scope (raise, never silently fall back): DeepSpeed flag.
 """
 import inspect
 import os
@@ -30,6 +32,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import align
 from . import dist as tdist
 from . import engine as E
 from . import stages
@@ -183,13 +186,9 @@ class _Common:
         random.seed(seed)
         return seed
 
-    def _text_tokens(self, text, max_mel_tokens, refuse_brackets=True):
+    def _text_tokens(self, text, max_mel_tokens):
         """One text (str, or ids: int sequence / tensor [T]) to be spoken in max_mel_tokens -> padded int32 tokens [1, T + 1] on the device
-        (api.py:388-392).  refuse_brackets: [bracketed] text raises while enable_redaction is on (the reference redacts it from the audio)."""
-        if refuse_brackets and self.enable_redaction and isinstance(text, str) and "[" in text and "]" in text:
-            raise NotImplementedError("text with [bracketed] passages needs the wav2vec2 aligner to redact them from the audio "
-                                      "(api.py:583-587), which is outside the accelerated path; remove the brackets or construct "
-                                      "TextToSpeech(enable_redaction=False) to have them spoken")
+        (api.py:388-392)."""
         ids = self.tokenizer.encode(text) if isinstance(text, str) else text
         tokens = F.pad(torch.as_tensor(ids, dtype=torch.int32).reshape(1, -1).to(self.device), (0, 1))  # api.py:391
         if tokens.shape[-1] >= 400:  # api.py:392
@@ -205,19 +204,23 @@ class TextToSpeech(_Common):
     the reference's): `state_dicts` (dict of reference-layout state_dicts instead of files in
     models_dir), `dtype` (MFMA operand type: 'bf16' | 'fp16' for every stage, or a dict per stage
     {'ar', 'clvp', 'diffusion', 'vocoder'}; see resolve_stage_dtypes for the defaults), `max_candidates`
-    (per-GPU decode batch capacity), `configs` (ARConfig/CLVPConfig/DiffusionConfig/VocoderConfig overrides for tests)."""
+    (per-GPU decode batch capacity), `configs` (ARConfig/CLVPConfig/DiffusionConfig/VocoderConfig overrides for tests), `aligner` ((config
+    dict, state_dict, vocab dict, tokenizer config dict) of the wav2vec2 redaction aligner instead of its files)."""
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, max_candidates=256, configs=None, max_mel_tokens=500, max_text_tokens=402,
-                 candidate_sharding=True, utterance_batch=1):
+                 candidate_sharding=True, utterance_batch=1, aligner=None):
         self.models_dir = models_dir
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option; the MI355X engine "
                                       "always runs its own fused HIP path")
-        # wav2vec2 redaction is outside the hot path (SURVEY.md §2 row 15).  The flag is kept (reference default True): text
-        # without [brackets] is unaffected by it in the reference too; bracketed text raises in tts() instead of being spoken.
+        # enable_redaction (reference default True): every clip of a text with '[' loses its [bracketed] passages (api.py:583-587); the
+        # wav2vec2 aligner that finds them is built on first use (load_aligner)
         self.enable_redaction = bool(enable_redaction)
+        self._aligner_source = aligner
+        self.aligner = None
+        self.aligner_dtype = E.TT_F16  # (bf16 after an overflow; not one of the four dtype_names() stages)
         self.kv_cache = bool(kv_cache)
         self.half = bool(half)
         # candidate_sharding=False: this instance renders whole utterances on its own GPU even inside a multi-rank job (the
@@ -329,6 +332,65 @@ class TextToSpeech(_Common):
                                          max_rows=max(c["cap"], 8) * c["max_mel_tokens"])
         return self.cvvp
 
+    def load_aligner(self):
+        """wav2vec_alignment.py:51-58: the wav2vec2 CTC aligner of the redaction path as a device stage, from `aligner=` or the files find_aligner
+        locates.  NotImplementedError when there are none (bracketed text cannot be redacted without them)."""
+        if self.aligner is None:
+            src = self._aligner_source if self._aligner_source is not None else align.find_aligner(self.models_dir)
+            if src is None:
+                raise NotImplementedError("text with [bracketed] passages is redacted from the audio by the wav2vec2 aligner (api.py:583-587), "
+                                          "whose files were not found: " + align.where_to_put_files(self.models_dir) +
+                                          "; or construct TextToSpeech(enable_redaction=False) to have the brackets spoken")
+            self._aligner_source = src
+            self.aligner = stages.AlignerStage(src, self.device, self.aligner_dtype, max_samples=self._caps["max_S"] * 256 + 256)
+        return self.aligner
+
+    def _redaction_text(self, text):
+        """text when its clips are to be redacted (enable_redaction and a str with '['), else None.  Checked before anything renders: an
+        unpaired '[' or a text with nothing outside brackets raises ValueError, missing aligner files NotImplementedError."""
+        if not (self.enable_redaction and isinstance(text, str) and "[" in text):
+            return None
+        align.redaction_plan(text)
+        self.load_aligner()
+        return text
+
+    def _redact(self, audio, text):
+        """wav2vec_alignment.py redact on one rendered clip [1, 1, n] (any device) -> the clip without the [bracketed] passages, same device.
+        An fp16 overflow rebuilds the aligner with bf16 operands and aligns the same clip again (the audio is not rendered again)."""
+        t0 = time.perf_counter()
+        clip = audio.reshape(1, -1)
+        while True:
+            al = self.load_aligner()
+            ids = al.frame_ids(clip)
+            if not al.guard():
+                break
+            if al.dtype != E.TT_F16:
+                raise E.OperandOverflow("the aligner stage produced non-finite values with bf16 operands (non-finite weights or audio?)")
+            import warnings
+            warnings.warn("tortoise_tts_amd: the aligner stage overflowed fp16 operands; rebuilding it with bf16 operands")
+            al.close()
+            self.aligner, self.aligner_dtype = None, E.TT_BF16
+        out = align.redact(clip, text, lambda _: ids, al.tokenizer).reshape(1, 1, -1)
+        self._redact_s += time.perf_counter() - t0
+        return out
+
+    def _redact_clips(self, wavs, text):
+        """{winner index: clip} this rank rendered -> the same clips redacted, on the CPU.  Runs after _guarded has accepted the utterance (a
+        clip that a demotion is about to re-render is never aligned).  Alignment can fail on the data (RuntimeError / ValueError): with
+        several ranks the outcome is agreed over them first, so that every rank raises together and none is left waiting in a collective."""
+        out, err = {}, None
+        try:
+            for i, w in wavs.items():
+                out[i] = self._redact(w, text).cpu()
+        except Exception as ex:  # (any failure: the other ranks must hear of it before this one leaves)
+            err = ex
+        failed = tdist.any_over_ranks([err is not None])[0] if self.world > 1 else err is not None
+        if err is not None:
+            raise err
+        if failed:
+            raise RuntimeError("redaction failed on another rank of this job (its own error says why)")
+        return out
+
     def _tripped_stages(self, wav_ok=True):
         """Stages whose operand-overflow guard counted non-finite values during the utterance that just finished (the caller has
         synchronised); agreed over the ranks so that every rank takes the same decision.  Resets the counters."""
@@ -425,6 +487,7 @@ class TextToSpeech(_Common):
             diffusion_iterations=100, cond_free=True, cond_free_k=2, diffusion_temperature=1.0,
             **hf_generate_kwargs):
         o = self._settings(locals())  # (the arguments above, by name)
+        redact = self._redaction_text(text)
         tokens = self._text_tokens(text, max_mel_tokens)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         ev = _StageTimer(6)
@@ -435,8 +498,12 @@ class TextToSpeech(_Common):
                 raise ValueError("cvvp_amount=1 ranks the candidates by CVVP alone, which compares them with the voice's conditioning clips: "
                                  "pass voice_samples (with latents only the reference has nothing to rank by, api.py:462-472)")
             self.load_cvvp()  # api.py:450-453 (loaded even when there are no clips to use it on)
-        wavs = self._guarded(lambda: self._utterance(ev, tokens, voice, o, seed, k))  # (a re-render after a demotion: same seed)
+        wavs = self._guarded(lambda: self._utterance(ev, tokens, voice, o, seed, k, keep_on_device=redact is not None))  # (a re-render after a demotion: same seed)
         self.timings = _event_timings(ev)
+        if redact is not None:
+            self._redact_s = 0.0
+            wavs = self._redact_clips(wavs, redact)
+            self.timings["redact_s"] = self._redact_s
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -465,8 +532,10 @@ class TextToSpeech(_Common):
             # what the grouped decode cannot hold: tts() renders it, one utterance at a time
             return [self.tts(t, voice_samples=voice_samples, conditioning_latents=conditioning_latents, verbose=verbose,
                              use_deterministic_seed=use_deterministic_seed, **kwargs) for t in texts]
+        redacts = [self._redaction_text(t) for t in texts]
         seed = self.deterministic_state(seed=use_deterministic_seed)
         toks = [self._text_tokens(t, o.max_mel_tokens) for t in texts]
+        self._redact_s = 0.0
         voice = self._voice(voice_samples, conditioning_latents)
         G = self.utterance_batch
         waves = [toks[w0:w0 + G] for w0 in range(0, len(toks), G)]
@@ -479,16 +548,20 @@ class TextToSpeech(_Common):
             decoded = self._guarded(lambda: ([smp for wave in waves for smp in self._decode_wave(voice[0], wave, o, seed)], True))
             ev.mark(1)
             out, acc = [], {}
-            for tokens, samples in zip(toks, decoded):
+            for tokens, samples, redact in zip(toks, decoded, redacts):
                 ev_u, ar = _StageTimer(6), self.ar
                 ev_u.mark(0)
                 # (an overflow in this utterance's latent re-pass rebuilds the stage: its codes are then decoded again, as in tts())
-                out.append(self._guarded(lambda: self._utterance(ev_u, tokens, voice, o, seed, 1, samples if self.ar is ar else None))[0])
+                clip = self._guarded(lambda: self._utterance(ev_u, tokens, voice, o, seed, 1, samples if self.ar is ar else None,
+                                                             keep_on_device=redact is not None))[0]
+                out.append(clip if redact is None else self._redact_clips({0: clip}, redact)[0])
                 for key, v in _event_timings(ev_u).items():
                     acc[key] = acc.get(key, 0.0) + v
             ev.synchronize()
             acc["ar_s"] = acc.get("ar_s", 0.0) + ev.seconds(0, 1)
             acc["total_s"] = acc.get("total_s", 0.0) + ev.seconds(0, 1)
+            if any(r is not None for r in redacts):
+                acc["redact_s"] = self._redact_s
             self.timings = acc
             return out
 
@@ -517,7 +590,10 @@ class TextToSpeech(_Common):
             return (out, clock, t_all), ok
 
         out, clock, t_all = self._guarded(attempt)
+        out = [w if r is None else self._redact_clips({0: w}, r)[0] for w, r in zip(out, redacts)]  # (after the guards accepted the waves)
         self.timings = dict(clock, total_s=time.perf_counter() - t_all)
+        if any(r is not None for r in redacts):
+            self.timings["redact_s"] = self._redact_s
         return out
 
     # ------------------------------------------------------------------ phases of tts() / tts_many()
@@ -611,10 +687,11 @@ class TextToSpeech(_Common):
         mel = self.diffusion.sample_split(sched, x_T, step_noise, self.rank, tdist.exchange_rows)
         return mel if self.rank == 0 else None
 
-    def _utterance(self, ev, tokens, voice, o, seed, k, samples=None):
+    def _utterance(self, ev, tokens, voice, o, seed, k, samples=None, keep_on_device=False):
         """One utterance: this rank's candidates (decoded unless given), ranking, the winners' latent re-pass (api.py:516-524) and the winners
         this rank renders (round-robin; a single conditioning-free winner split over ranks 0 and 1), marking `ev` 1-5 between the phases.
-        -> ({winner index: clip on the CPU}, every clip finite)."""
+        keep_on_device: the clips stay on the device (tts() redacts them there once the utterance is accepted, api.py:583-587).
+        -> ({winner index: clip on the CPU (or the device)}, every clip finite)."""
         auto, diff, auto_conds = voice
         if samples is None:
             samples = self._decode(auto, tokens, o, seed)
@@ -635,7 +712,7 @@ class TextToSpeech(_Common):
             ev.mark(4)
             audio = self.vocoder.inference(mel, z)
             finite = torch.isfinite(audio).all()  # (a NaN survives the final clamp: the vocoder stage's overflow check)
-            wavs[i] = audio.cpu()
+            wavs[i] = audio if keep_on_device else audio.cpu()
             ok = ok and bool(finite)
         if not wavs:  # this rank had no winner to render
             ev.mark(4)

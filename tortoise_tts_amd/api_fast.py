@@ -151,7 +151,7 @@ class TextToSpeech(_Common):
         return self.rlg_auto.latents(r, r)[0]
 
     def _prepare(self, text, voice_samples, conditioning_latents, max_mel_tokens):
-        text_tokens = self._text_tokens(text, max_mel_tokens, refuse_brackets=False)  # (api_fast.py:371; no redaction on this path)
+        text_tokens = self._text_tokens(text, max_mel_tokens)  # (api_fast.py:371; no redaction on this path)
         if max_mel_tokens < 1:
             raise ValueError(f"max_mel_tokens={max_mel_tokens} must be at least 1")
         if voice_samples is not None:

@@ -127,6 +127,11 @@ __global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
       }
     }
   }
+  if (a.act != ACT_NONE) {
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      v[j] = make_float4(apply_act(v[j].x, a.act, 0.f), apply_act(v[j].y, a.act, 0.f), apply_act(v[j].z, a.act, 0.f), apply_act(v[j].w, a.act, 0.f));
+  }
   emit(v);
 }
 
@@ -192,7 +197,7 @@ static void rownorm_narrow_dispatch(const ProfScope& ps, const RowNormArgs& a, h
 
 template <typename T>
 static bool rownorm_narrow_launch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
-  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr || a.f32_row_slot != nullptr) return false;
+  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr || a.f32_row_slot != nullptr || a.act != ACT_NONE) return false;
   switch (a.nslab) {
     case 0: rownorm_narrow_dispatch<T, 0>(ps, a, stream); return true;
     case 1: rownorm_narrow_dispatch<T, 1>(ps, a, stream); return true;
@@ -289,6 +294,11 @@ __global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
         }
       }
     }
+    if (a.act != ACT_NONE) {
+#pragma unroll
+      for (int j = 0; j < J; ++j)
+        v[j] = make_float4(apply_act(v[j].x, a.act, 0.f), apply_act(v[j].y, a.act, 0.f), apply_act(v[j].z, a.act, 0.f), apply_act(v[j].w, a.act, 0.f));
+    }
   }
 #pragma unroll
   for (int j = 0; j < J; ++j) {
@@ -303,6 +313,7 @@ __global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
 int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream) {
   TT_REQUIRE(a.M > 0 && a.D > 0 && a.D % 4 == 0 && a.D <= 4096, "rownorm: bad shape M=%d D=%d", a.M, a.D);
   TT_REQUIRE(a.ldx % 4 == 0, "rownorm: ldx must be a multiple of 4");
+  TT_REQUIRE(a.act == ACT_NONE || a.mode == NORM_LAYER, "rownorm: a post-norm activation needs the LayerNorm mode");
   ProfScope ps(PROF_ROWNORM, stream, 0.0, (double)a.M * a.D * (4.0 * (1 + a.nslab + (a.write_x ? 1 : 0)) + (a.out_t ? 2.0 : 0.0) + (a.out_f32 ? 4.0 : 0.0)), true);
   // few rows (decode): one block per row keeps 4x more loads in flight; many rows: wave per row, no barriers
   if (a.D <= 1024 && a.M >= 1024 && !a.row_blocks) {

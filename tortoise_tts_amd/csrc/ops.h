@@ -41,6 +41,8 @@ struct RowNormArgs {
   const int* f32_row_slot;
   int row_blocks;      // 1: always one workgroup per row (the decode step: a row's arithmetic order must not depend on how many rows the batch has)
   int* guard;          // optional device counter: += 1 per workgroup / wave that saw a non-finite input value (operand-overflow guard)
+  int act;             // activation applied to the normalised row before it is emitted (ACT_NONE; LayerNorm only: the wav2vec2
+                       // feature encoder's LayerNorm + GELU, csrc/align.hip)
 };
 int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream);
 

@@ -1,4 +1,5 @@
-"""ctypes binding of include/tortoise_mi355x.h (the drop-in boundary) and include/tortoise_mi355x_test.h (operator-level test entries).
+"""ctypes binding of include/tortoise_mi355x.h (the drop-in boundary), include/tortoise_mi355x_align.h (the redaction aligner) and
+include/tortoise_mi355x_test.h (operator-level test entries).
 
 The library is the product: there is no PyTorch/CPU fallback.  If the shared object is missing
 or the device is not gfx950, loading fails loudly.
@@ -154,6 +155,25 @@ class HifiWeights(C.Structure):
                 ("res_host", C.POINTER(HifiResBlock)), ("w_post", vp), ("b_post", vp)]
 
 
+W2V_CONV_LAYERS = 7
+
+
+class W2vConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dtype", "dim", "heads", "layers", "ff_dim", "conv_dim")] + [
+        ("conv_kernel", C.c_int * W2V_CONV_LAYERS), ("conv_stride", C.c_int * W2V_CONV_LAYERS)] + [
+        (n, C.c_int) for n in ("pos_kernel", "pos_groups", "vocab", "vocab_pad", "max_samples")] + [("eps", C.c_float)]
+
+
+class W2vWeights(C.Structure):
+    _fields_ = [("resample_taps", vp), ("w_conv0", vp), ("b_conv0", vp), ("w_conv", vp * W2V_CONV_LAYERS), ("b_conv", vp * W2V_CONV_LAYERS),
+                ("ln_conv_g", vp * W2V_CONV_LAYERS), ("ln_conv_b", vp * W2V_CONV_LAYERS), ("fp_ln_g", vp), ("fp_ln_b", vp), ("w_fp", vp),
+                ("b_fp", vp), ("w_pos", vp), ("b_pos", vp), ("layers_host", C.POINTER(GptLayer)), ("lnf_g", vp), ("lnf_b", vp),
+                ("w_head", vp), ("b_head", vp)]
+
+
+# include/tortoise_mi355x_align.h, order == tt_align_struct_size(which)
+ALIGN_STRUCTS = [W2vConfig, W2vWeights]
+
 # order == tt_struct_size(which)
 BOUNDARY_STRUCTS = [GptLayer, ArConfig, ArWeights, Sampling, ClvpLayer, ClvpTower, ClvpConfig, AttnBlock, ResBlock, DiffConfig,
                     DiffWeights, DiffStep, VocBlock, VocConfig, VocWeights, CondConfig, CondWeights, HifiResBlock, HifiConfig, HifiWeights,
@@ -222,6 +242,16 @@ _PROTOS = {
     "tt_prof_class_name": (C.c_char_p, [_i]),
     "tt_prof_read": (_i, [_i, C.POINTER(C.c_double)]),
 }
+# include/tortoise_mi355x_align.h: the wav2vec2 aligner of the redaction path (its own header and version, same library)
+_ALIGN_PROTOS = {
+    "tt_align_abi_version": (_i, []),
+    "tt_align_struct_size": (_sz, [_i]),
+    "tt_w2v_create": (_i, [C.POINTER(W2vConfig), C.POINTER(W2vWeights), C.POINTER(vp)]),
+    "tt_w2v_destroy": (None, [vp]),
+    "tt_w2v_frames": (_i, [vp, _i]),
+    "tt_w2v_run": (_i, [vp, vp, _i, vp, vp, vp]),
+    "tt_w2v_guard": (_i, [vp, _i]),
+}
 # include/tortoise_mi355x_test.h: operator-level TEST entries + the A/B switch (not part of the boundary a maintainer binds)
 _TEST_PROTOS = {
     "ttx_kernel_variant": (_i, [_i, _i]),
@@ -241,6 +271,11 @@ _TEST_PROTOS = {
     "tt_op_conv1d": (_i, [vp, vp, vp, vp, _i, _i, _i, _i, _i, _i, _f, _i, _f, vp]),
     "tt_op_convt1d": (_i, [vp, vp, vp, vp, _i, _i, _i, _f, vp]),
     "tt_op_lvc": (_i, [_i, vp, vp, _i, _i, vp, _i, _i, vp, _i, _i, vp]),
+    "tt_op_w2v_resample_workspace": (_sz, [_i]),
+    "tt_op_w2v_resample": (_i, [vp, _i, vp, vp, vp, vp, vp]),
+    "tt_op_w2v_conv0": (_i, [_i, vp, vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_op_layernorm_act": (_i, [_i, vp, _i, _i, vp, vp, _f, _i, vp, vp, vp]),
+    "tt_op_w2v_argmax": (_i, [vp, _i, _i, _i, vp, vp, vp]),
 }
 
 _lib = None
@@ -259,12 +294,16 @@ def load_library():
     # both have to bind to the ONE HIP runtime that torch ships (libamdhip64.so.7, resolved by SONAME).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()):
+    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     for i, st in enumerate(BOUNDARY_STRUCTS):
         want = lib.tt_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(ALIGN_STRUCTS):
+        want = lib.tt_align_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     _lib = lib

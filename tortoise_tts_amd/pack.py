@@ -442,3 +442,63 @@ def pack_vocoder(sd_folded, cfg: VocoderConfig, device, dtype, mel_pad=128):
     h.weights = w
     h.mel_pad = mel_pad
     return h
+
+
+# ----------------------------------------------------------------------------------------- wav2vec2 aligner (redaction)
+def pack_w2v(sd, fields, device, dtype):
+    """Wav2Vec2ForCTC state_dict (the reference's jbetker/wav2vec2-large-robust-ft-libritts-voxpopuli, HF layout) -> tt_w2v_weights.
+    fields: align.check_config(config).  q / k / v stacked into one [3D][D] projection, convolutions [out][tap][in], the positional
+    conv's weight norm folded, lm_head padded to a multiple of 64 rows."""
+    from .align import fold_pos_conv, resample_taps
+    h = Holder(device, dtype)
+    wop = h.op
+    D, V = fields["dim"], fields["vocab"]
+    w = E.W2vWeights()
+    w.resample_taps = _p(h.f32(resample_taps()))
+    fe = "wav2vec2.feature_extractor.conv_layers"
+    for i in range(E.W2V_CONV_LAYERS):
+        cw = sd[f"{fe}.{i}.conv.weight"].float()
+        if i == 0:
+            w.w_conv0 = _p(h.f32(cw.reshape(cw.shape[0], -1)))
+            w.b_conv0 = _p(h.f32(sd[f"{fe}.{i}.conv.bias"]))
+        else:
+            w.w_conv[i] = _p(h.conv(cw))
+        w.b_conv[i] = _p(h.f32(sd[f"{fe}.{i}.conv.bias"]))
+        w.ln_conv_g[i] = _p(h.f32(sd[f"{fe}.{i}.layer_norm.weight"]))
+        w.ln_conv_b[i] = _p(h.f32(sd[f"{fe}.{i}.layer_norm.bias"]))
+    fp = "wav2vec2.feature_projection"
+    w.fp_ln_g = _p(h.f32(sd[f"{fp}.layer_norm.weight"]))
+    w.fp_ln_b = _p(h.f32(sd[f"{fp}.layer_norm.bias"]))
+    w.w_fp = _p(wop(sd[f"{fp}.projection.weight"]))
+    w.b_fp = _p(h.f32(sd[f"{fp}.projection.bias"]))
+    w.w_pos = _p(h.conv(fold_pos_conv(sd)))  # [D][pos_kernel][D / groups]: group g = rows g * D / groups ..
+    w.b_pos = _p(h.f32(sd["wav2vec2.encoder.pos_conv_embed.conv.bias"]))
+    layers = (E.GptLayer * fields["layers"])()
+    for l in range(fields["layers"]):
+        p = f"wav2vec2.encoder.layers.{l}"
+        L = layers[l]
+        L.ln1_g = _p(h.f32(sd[f"{p}.layer_norm.weight"]))
+        L.ln1_b = _p(h.f32(sd[f"{p}.layer_norm.bias"]))
+        L.w_qkv = _p(wop(torch.cat([sd[f"{p}.attention.{n}_proj.weight"].float() for n in "qkv"], dim=0)))
+        L.b_qkv = _p(h.f32(torch.cat([sd[f"{p}.attention.{n}_proj.bias"].float() for n in "qkv"], dim=0)))
+        L.w_proj = _p(wop(sd[f"{p}.attention.out_proj.weight"]))
+        L.b_proj = _p(h.f32(sd[f"{p}.attention.out_proj.bias"]))
+        L.ln2_g = _p(h.f32(sd[f"{p}.final_layer_norm.weight"]))
+        L.ln2_b = _p(h.f32(sd[f"{p}.final_layer_norm.bias"]))
+        L.w_fc = _p(wop(sd[f"{p}.feed_forward.intermediate_dense.weight"]))
+        L.b_fc = _p(h.f32(sd[f"{p}.feed_forward.intermediate_dense.bias"]))
+        L.w_proj2 = _p(wop(sd[f"{p}.feed_forward.output_dense.weight"]))
+        L.b_proj2 = _p(h.f32(sd[f"{p}.feed_forward.output_dense.bias"]))
+    w.layers_host = layers
+    w.lnf_g = _p(h.f32(sd["wav2vec2.encoder.layer_norm.weight"]))
+    w.lnf_b = _p(h.f32(sd["wav2vec2.encoder.layer_norm.bias"]))
+    h.vocab_pad = (V + 63) // 64 * 64
+    head = torch.zeros(h.vocab_pad, D)
+    head[:V] = sd["lm_head.weight"].float()
+    bias = torch.zeros(h.vocab_pad)
+    bias[:V] = sd["lm_head.bias"].float()
+    w.w_head = _p(wop(head))
+    w.b_head = _p(h.f32(bias))
+    h.layers = layers
+    h.weights = w
+    return h

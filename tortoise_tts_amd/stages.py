@@ -421,6 +421,54 @@ class CvvpStage(_GuardedHandle):
         return torch.cat(outs)
 
 
+class AlignerStage(_GuardedHandle):
+    """The wav2vec2 CTC model of the redaction path (wav2vec_alignment.py:63-72 Wav2VecAlignment.align up to the logits): a 24 kHz clip ->
+    the argmax id of every frame.  source = (config dict, state_dict, vocab dict, tokenizer config dict) as align.find_aligner reads them."""
+
+    api = "tt_w2v"
+
+    def __init__(self, source, device="cuda", dtype=E.TT_F16, max_samples=24000 * 30):
+        from . import align
+        cfg, sd, vocab, tok_cfg = source
+        fields = align.check_config(cfg)  # (before the library: a config the stage does not implement is refused on any machine)
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self.source = source
+        self.tokenizer = align.CtcTokenizer(vocab, tok_cfg)
+        self.fields = fields
+        self.w = pack.pack_w2v(sd, fields, self.device, dtype)
+        c = E.W2vConfig()
+        c.dtype, c.dim, c.heads, c.layers, c.ff_dim, c.conv_dim = dtype, fields["dim"], fields["heads"], fields["layers"], fields["ff_dim"], 512
+        for i in range(E.W2V_CONV_LAYERS):
+            c.conv_kernel[i], c.conv_stride[i] = fields["conv_kernel"][i], fields["conv_stride"][i]
+        c.pos_kernel, c.pos_groups, c.vocab, c.vocab_pad = fields["pos_kernel"], fields["pos_groups"], fields["vocab"], self.w.vocab_pad
+        c.max_samples, c.eps = int(max_samples), fields["eps"]
+        self.max_samples = int(max_samples)
+        self._create(C.byref(c), C.byref(self.w.weights))
+
+    def frames(self, samples):
+        return self.lib.tt_w2v_frames(self.h, int(samples))
+
+    def run(self, audio, logits=False):
+        """audio f32 [S] or [1, S] at 24 kHz -> frame ids int32 [T] on the device (and the logits f32 [T, vocab] with logits=True)."""
+        x = audio.reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+        S = x.shape[0]
+        if S > self.max_samples:
+            raise ValueError(f"a clip of {S} samples exceeds the aligner's capacity ({self.max_samples})")
+        T = self.frames(S)
+        if T < 1:
+            raise ValueError(f"a clip of {S} samples is shorter than the aligner's receptive field")
+        ids = torch.empty(T, device=self.device, dtype=torch.int32)
+        lg = torch.empty(T, self.fields["vocab"], device=self.device, dtype=torch.float32) if logits else None
+        E.check(self.lib.tt_w2v_run(self.h, E.ptr(x), S, E.ptr(ids), E.ptr(lg), E.stream_ptr()))
+        return (ids, lg) if logits else ids
+
+    def frame_ids(self, audio):
+        """-> the frame ids as a host list (synchronises: the overflow guard can be read afterwards)."""
+        return self.run(audio).cpu().tolist()
+
+
 class DiffusionStage(_GuardedHandle):
     """DiffusionTts + SpacedDiffusion.p_sample_loop (api.py:117-130)."""
 
