@@ -92,6 +92,21 @@ int tt_op_layernorm_act(int dtype, const float* x, int M, int D, const float* g,
 /* ids int32 [T] = per-row argmax of logits f32 [T][ld] over the first V columns (ties: lowest index); out (optional) f32 [T][V] gets the rows */
 int tt_op_w2v_argmax(const float* logits, int ld, int T, int V, int* ids, float* out, void* stream);
 
+/* Tortoise detector kernels (csrc/classify.hip, include/tortoise_mi355x_classify.h).  Statistics partials: `part` workspaces of
+ * tt_op_cls_workspace(L) bytes, [block][16][2] sum / sum of squares in double.  init: out f32 [n][32] = Conv1d(1, 32, 3, pad 1)(x f32 [n]),
+ * w f32 [32][3]; stats: f32 [16][2] = {mean, 1 / sqrt(var + 1e-5)} of the 16 groups of a [L][C] tensor from the partials of `nblocks`
+ * workgroups; conv: out f32 [Lout][cout] = Conv1d(cin, cout, 5, stride, pad 2)(stride 1: SiLU(GroupNorm16(x; stats, gamma, beta)), stride 4: x)
+ * + b (+ res), w in the operand type [cout][5][cin], partials of out when part != NULL (cout <= 64); attention: out [nq][512] (operand
+ * type) = QKVAttentionLegacy(4 heads of 128) of qkv f32 [n][1536] for the first nq queries; head: logits f32 [2] = w f32 [2][512] x[0] + b,
+ * emb (optional) f32 [512] = x[0] */
+size_t tt_op_cls_workspace(int L);
+int tt_op_cls_init(const float* x, int n, const float* w, const float* b, float* out, void* part, void* stream);
+int tt_op_cls_stats(const void* part, int nblocks, int L, int C, float* stats, void* stream);
+int tt_op_cls_conv(int dtype, int cin, int cout, int stride, const float* x, int Lin, const float* stats, const float* gamma, const float* beta,
+                   const void* w, const float* b, const float* res, float* out, void* part, void* stream);
+int tt_op_cls_attention(int dtype, const float* qkv, int n, int nq, void* out, void* stream);
+int tt_op_cls_head(const float* x, const float* w, const float* b, float* logits, float* emb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,8 @@ Constructor flags of the reference and what they mean here:
                under models_dir or the HF hub cache, or the engine-only `aligner=`); text without '[' is unaffected.
 cvvp_amount > 0 (api.py:450-472; the CHANGELOG calls CVVP "removed", the call sites and cvvp.pth remain): the CVVP model is built on
 first use like upstream (load_cvvp -> stages.CvvpStage, csrc/cvvp.hip) and blended into the CLVP ranking when voice_samples are given.
+classify_audio_clip(clip) (api.py; is_this_from_tortoise.py) runs the Tortoise detector on the device (stages.ClassifierStage,
+csrc/classify.hip), with classifier.pth read and packed once per (models_dir, device).
 Out of scope (raise, never silently fall back): DeepSpeed flag.
 """
 import inspect
@@ -125,6 +127,42 @@ def _load_file(models_dir, filename):
         raise FileNotFoundError(f"{path} not found. Put the reference checkpoints in models_dir (or $TORTOISE_MODELS_DIR), or pass "
                                 f"state_dicts= to TextToSpeech; there is no network access to download them.")
     return torch.load(path, map_location="cpu")
+
+
+_CLASSIFIERS = {}  # (models_dir, device) -> ClassifierStage: classifier.pth is read and packed once per process
+
+
+def classify_audio_clip(clip, *, models_dir=MODELS_DIR):
+    """api.py classify_audio_clip: the probability (0-dim CPU tensor) that `clip` [1, T] at 24 kHz (any device) was generated by Tortoise,
+    from AudioMiniEncoderWithClassifierHead with classifier.pth from models_dir.  The model runs on the current GPU; an fp16 overflow
+    rebuilds it with bf16 operands and classifies the clip again."""
+    if not isinstance(clip, torch.Tensor) or clip.dim() != 2 or clip.shape[0] != 1:
+        raise ValueError(f"classify_audio_clip takes a [1, T] clip at 24 kHz, got {tuple(clip.shape) if isinstance(clip, torch.Tensor) else type(clip).__name__}")
+    if clip.shape[1] < 1:
+        raise ValueError("classify_audio_clip: the clip is empty")
+    device = E.require_gpu()
+    key = (os.path.abspath(models_dir), str(device))
+    stage = _CLASSIFIERS.get(key)
+    if stage is None:
+        sd = _load_file(models_dir, "classifier.pth")
+        stage = stages.ClassifierStage(sd, device, E.TT_F16, max_samples=max(220000, clip.shape[1]))
+        stage.sd = sd
+        _CLASSIFIERS[key] = stage
+    while True:
+        logits, _ = stage.run(clip)
+        logits = logits.cpu()
+        if not stage.guard():
+            break
+        if stage.dtype != E.TT_F16:
+            raise E.OperandOverflow("the classifier stage produced non-finite values with bf16 operands (non-finite weights or audio?)")
+        import warnings
+        warnings.warn("tortoise_tts_amd: the classifier stage overflowed fp16 operands; rebuilding it with bf16 operands")
+        sd, cap = stage.sd, stage.max_samples
+        stage.close()
+        stage = stages.ClassifierStage(sd, device, E.TT_BF16, max_samples=cap)
+        stage.sd = sd
+        _CLASSIFIERS[key] = stage
+    return F.softmax(logits, dim=-1)[0]
 
 
 def utterance_batch_bytes(utterance_batch, max_candidates, max_mel_tokens, ar_cfg, diff_cfg, max_steps=512):

@@ -83,6 +83,23 @@ class CVVPConfig:
 
 
 @dataclass
+class ClassifierConfig:
+    """The Tortoise detector as api.classify_audio_clip builds it (reference: tortoise/api.py classify_audio_clip,
+    tortoise/models/classifier.py AudioMiniEncoderWithClassifierHead).  The engine implements exactly these numbers."""
+    spec_dim: int = 1
+    base_channels: int = 32
+    depth: int = 5
+    resnet_blocks: int = 2
+    kernel_size: int = 5
+    downsample_factor: int = 4
+    embedding_dim: int = 512
+    attn_blocks: int = 4
+    heads: int = 4
+    classes: int = 2
+    sample_rate: int = 24000
+
+
+@dataclass
 class VocoderConfig:
     """UnivNetGenerator (reference: tortoise/models/vocoder.py:225-265)."""
     noise_dim: int = 64

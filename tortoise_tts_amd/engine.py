@@ -171,6 +171,31 @@ class W2vWeights(C.Structure):
                 ("w_head", vp), ("b_head", vp)]
 
 
+CLS_DEPTH, CLS_RES_BLOCKS, CLS_ATTN_BLOCKS = 5, 2, 4
+
+
+class ClsConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dtype", "spec_dim", "base_channels", "depth", "resnet_blocks", "kernel_size", "downsample_factor",
+                                       "embedding_dim", "attn_blocks", "heads", "classes", "max_samples")]
+
+
+class ClsResBlock(C.Structure):
+    _fields_ = [(n, vp) for n in ("gn1_g", "gn1_b", "w1", "b1", "gn2_g", "gn2_b", "w2", "b2")]
+
+
+class ClsAttn(C.Structure):
+    _fields_ = [(n, vp) for n in ("norm_g", "norm_b", "w_qkv", "b_qkv", "w_proj", "b_proj")]
+
+
+class ClsWeights(C.Structure):
+    _fields_ = [("w_init", vp), ("b_init", vp), ("res", (ClsResBlock * CLS_RES_BLOCKS) * CLS_DEPTH), ("w_down", vp * CLS_DEPTH),
+                ("b_down", vp * CLS_DEPTH), ("final_g", vp), ("final_b", vp), ("w_final", vp), ("b_final", vp),
+                ("attn", ClsAttn * CLS_ATTN_BLOCKS), ("w_head", vp), ("b_head", vp)]
+
+
+# include/tortoise_mi355x_classify.h, order == tt_cls_struct_size(which)
+CLASSIFY_STRUCTS = [ClsConfig, ClsWeights]
+
 # include/tortoise_mi355x_align.h, order == tt_align_struct_size(which)
 ALIGN_STRUCTS = [W2vConfig, W2vWeights]
 
@@ -252,6 +277,16 @@ _ALIGN_PROTOS = {
     "tt_w2v_run": (_i, [vp, vp, _i, vp, vp, vp]),
     "tt_w2v_guard": (_i, [vp, _i]),
 }
+# include/tortoise_mi355x_classify.h: the Tortoise detector (classify_audio_clip; its own header and version, same library)
+_CLASSIFY_PROTOS = {
+    "tt_cls_abi_version": (_i, []),
+    "tt_cls_struct_size": (_sz, [_i]),
+    "tt_cls_max_samples": (_i, []),
+    "tt_cls_create": (_i, [C.POINTER(ClsConfig), C.POINTER(ClsWeights), C.POINTER(vp)]),
+    "tt_cls_destroy": (None, [vp]),
+    "tt_cls_run": (_i, [vp, vp, _i, vp, vp, vp]),
+    "tt_cls_guard": (_i, [vp, _i]),
+}
 # include/tortoise_mi355x_test.h: operator-level TEST entries + the A/B switch (not part of the boundary a maintainer binds)
 _TEST_PROTOS = {
     "ttx_kernel_variant": (_i, [_i, _i]),
@@ -276,6 +311,12 @@ _TEST_PROTOS = {
     "tt_op_w2v_conv0": (_i, [_i, vp, vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
     "tt_op_layernorm_act": (_i, [_i, vp, _i, _i, vp, vp, _f, _i, vp, vp, vp]),
     "tt_op_w2v_argmax": (_i, [vp, _i, _i, _i, vp, vp, vp]),
+    "tt_op_cls_workspace": (_sz, [_i]),
+    "tt_op_cls_init": (_i, [vp, _i, vp, vp, vp, vp, vp]),
+    "tt_op_cls_stats": (_i, [vp, _i, _i, _i, vp, vp]),
+    "tt_op_cls_conv": (_i, [_i, _i, _i, _i, vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_op_cls_attention": (_i, [_i, vp, _i, _i, vp, vp]),
+    "tt_op_cls_head": (_i, [vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None
@@ -294,7 +335,7 @@ def load_library():
     # both have to bind to the ONE HIP runtime that torch ships (libamdhip64.so.7, resolved by SONAME).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()):
+    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -304,6 +345,10 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(ALIGN_STRUCTS):
         want = lib.tt_align_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(CLASSIFY_STRUCTS):
+        want = lib.tt_cls_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     _lib = lib

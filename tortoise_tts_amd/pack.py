@@ -12,7 +12,7 @@ import ctypes as C
 import torch
 
 from . import engine as E
-from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig
+from .config import ARConfig, ClassifierConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig
 
 
 def torch_dtype(dtype):
@@ -500,5 +500,38 @@ def pack_w2v(sd, fields, device, dtype):
     w.w_head = _p(wop(head))
     w.b_head = _p(h.f32(bias))
     h.layers = layers
+    h.weights = w
+    return h
+
+
+def pack_classifier(sd, device, dtype, cfg: ClassifierConfig = ClassifierConfig()):
+    """classifier.pth state_dict -> tt_cls_weights: convolutions in the GEMM's [out][tap][in] layout (operand dtype), the 1 x 1 convs as
+    [out][in], the init conv and the head in f32.  The qkv rows keep the reference's legacy per-head [q | k | v] order."""
+    h = Holder(device, dtype)
+    w = E.ClsWeights()
+    w.w_init = _p(h.f32(sd["enc.init.0.weight"].float().reshape(cfg.base_channels, 3)))
+    w.b_init = _p(h.f32(sd["enc.init.0.bias"]))
+    i = 0
+    for lv in range(cfg.depth):
+        for r in range(cfg.resnet_blocks):
+            p = f"enc.res.{i}"
+            rb = w.res[lv][r]
+            rb.gn1_g, rb.gn1_b = _p(h.f32(sd[f"{p}.in_layers.0.weight"])), _p(h.f32(sd[f"{p}.in_layers.0.bias"]))
+            rb.w1, rb.b1 = _p(h.conv(sd[f"{p}.in_layers.2.weight"])), _p(h.f32(sd[f"{p}.in_layers.2.bias"]))
+            rb.gn2_g, rb.gn2_b = _p(h.f32(sd[f"{p}.out_layers.0.weight"])), _p(h.f32(sd[f"{p}.out_layers.0.bias"]))
+            rb.w2, rb.b2 = _p(h.conv(sd[f"{p}.out_layers.3.weight"])), _p(h.f32(sd[f"{p}.out_layers.3.bias"]))
+            i += 1
+        w.w_down[lv] = _p(h.conv(sd[f"enc.res.{i}.op.weight"]))
+        w.b_down[lv] = _p(h.f32(sd[f"enc.res.{i}.op.bias"]))
+        i += 1
+    w.final_g, w.final_b = _p(h.f32(sd["enc.final.0.weight"])), _p(h.f32(sd["enc.final.0.bias"]))
+    w.w_final, w.b_final = _p(h.op(sd["enc.final.2.weight"])), _p(h.f32(sd["enc.final.2.bias"]))
+    for a in range(cfg.attn_blocks):
+        p = f"enc.attn.{a}"
+        A = w.attn[a]
+        A.norm_g, A.norm_b = _p(h.f32(sd[f"{p}.norm.weight"])), _p(h.f32(sd[f"{p}.norm.bias"]))
+        A.w_qkv, A.b_qkv = _p(h.op(sd[f"{p}.qkv.weight"])), _p(h.f32(sd[f"{p}.qkv.bias"]))
+        A.w_proj, A.b_proj = _p(h.op(sd[f"{p}.proj_out.weight"])), _p(h.f32(sd[f"{p}.proj_out.bias"]))
+    w.w_head, w.b_head = _p(h.f32(sd["head.weight"])), _p(h.f32(sd["head.bias"]))
     h.weights = w
     return h

@@ -469,6 +469,48 @@ class AlignerStage(_GuardedHandle):
         return self.run(audio).cpu().tolist()
 
 
+class ClassifierStage(_GuardedHandle):
+    """The Tortoise detector (api.py classify_audio_clip: AudioMiniEncoderWithClassifierHead over one 24 kHz clip) -> the head's two
+    logits and the 512-d embedding of frame 0.  The handle is re-created for a longer clip than it was built for."""
+
+    api = "tt_cls"
+
+    def __init__(self, sd, device="cuda", dtype=E.TT_F16, max_samples=220000):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self.w = pack.pack_classifier(sd, self.device, dtype)
+        self.h = E.vp()
+        self.max_samples = 0
+        self._build(max_samples)
+
+    def _build(self, max_samples):
+        from .config import ClassifierConfig
+        cfg = ClassifierConfig()
+        self.close()
+        c = E.ClsConfig()
+        c.dtype, c.spec_dim, c.base_channels, c.depth, c.resnet_blocks = self.dtype, cfg.spec_dim, cfg.base_channels, cfg.depth, cfg.resnet_blocks
+        c.kernel_size, c.downsample_factor, c.embedding_dim = cfg.kernel_size, cfg.downsample_factor, cfg.embedding_dim
+        c.attn_blocks, c.heads, c.classes, c.max_samples = cfg.attn_blocks, cfg.heads, cfg.classes, int(max_samples)
+        self._create(C.byref(c), C.byref(self.w.weights))
+        self.max_samples = int(max_samples)
+
+    def run(self, clip):
+        """clip f32 [n] or [1, n] at 24 kHz (any device) -> (logits f32 [2], embedding f32 [512]) on the device."""
+        x = clip.reshape(-1).to(device=self.device, dtype=torch.float32).contiguous()
+        n = x.shape[0]
+        if n < 1:
+            raise ValueError("an empty clip cannot be classified")
+        if n > self.lib.tt_cls_max_samples():
+            raise ValueError(f"a clip of {n} samples exceeds the classifier's index range ({self.lib.tt_cls_max_samples()} samples)")
+        if n > self.max_samples:
+            self._build(n)
+        logits = torch.empty(2, device=self.device, dtype=torch.float32)
+        emb = torch.empty(512, device=self.device, dtype=torch.float32)
+        E.check(self.lib.tt_cls_run(self.h, E.ptr(x), n, E.ptr(logits), E.ptr(emb), E.stream_ptr()))
+        return logits, emb
+
+
 class DiffusionStage(_GuardedHandle):
     """DiffusionTts + SpacedDiffusion.p_sample_loop (api.py:117-130)."""
 

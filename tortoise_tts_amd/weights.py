@@ -15,7 +15,7 @@ from collections import OrderedDict
 import math
 import torch
 
-from .config import ARConfig, DiffusionConfig, CLVPConfig, CVVPConfig, VocoderConfig
+from .config import ARConfig, ClassifierConfig, DiffusionConfig, CLVPConfig, CVVPConfig, VocoderConfig
 
 
 # ----------------------------------------------------------------------------- manifests
@@ -263,6 +263,39 @@ def rlg_manifest(channels):
 
 
 # ----------------------------------------------------------------------------- synthetic weights
+def classifier_manifest(cfg: ClassifierConfig = ClassifierConfig()):
+    """Key set and shapes of classifier.pth (classifier.py AudioMiniEncoderWithClassifierHead; ResBlock keys in_layers.{0,2},
+    out_layers.{0,3}, Downsample `op`, arch_util AttentionBlock without relative position bias)."""
+    d = OrderedDict()
+    k = cfg.kernel_size
+    d["enc.init.0.weight"] = (cfg.base_channels, cfg.spec_dim, 3)
+    d["enc.init.0.bias"] = (cfg.base_channels,)
+    ch = cfg.base_channels
+    i = 0
+    for _ in range(cfg.depth):
+        for _ in range(cfg.resnet_blocks):
+            p = f"enc.res.{i}"
+            for norm, conv in (("in_layers.0", "in_layers.2"), ("out_layers.0", "out_layers.3")):
+                d[f"{p}.{norm}.weight"] = (ch,)
+                d[f"{p}.{norm}.bias"] = (ch,)
+                d[f"{p}.{conv}.weight"] = (ch, ch, k)
+                d[f"{p}.{conv}.bias"] = (ch,)
+            i += 1
+        d[f"enc.res.{i}.op.weight"] = (2 * ch, ch, 5)
+        d[f"enc.res.{i}.op.bias"] = (2 * ch,)
+        i += 1
+        ch *= 2
+    d["enc.final.0.weight"] = (ch,)
+    d["enc.final.0.bias"] = (ch,)
+    d["enc.final.2.weight"] = (cfg.embedding_dim, ch, 1)
+    d["enc.final.2.bias"] = (cfg.embedding_dim,)
+    for a in range(cfg.attn_blocks):
+        d.update(_attention_block(f"enc.attn.{a}", cfg.embedding_dim, cfg.heads, rel_pos=False))
+    d["head.weight"] = (cfg.classes, cfg.embedding_dim)
+    d["head.bias"] = (cfg.classes,)
+    return d
+
+
 def _is_norm_gain(key):
     k = key
     return (k.endswith(".g") or ".ln_" in k or ".ln_f." in k or "final_norm" in k or ".norm." in k
