@@ -149,7 +149,9 @@ int tt_ar_stream_latents(tt_ar* h, int B, int n, float* out, void* stream);
  *                             max_groups >= max_batch, and a prefix capacity whose keys and values fit the decode attention's 160 KB
  *                             of LDS next to the scores (max_prefix <= about 600 at max_new_tokens = 500; the exact bound is
  *                             8 KB per 64 prefix rows + 1 KB per 8 + 4 bytes per prefix row and KV slot); selects the GEMV-shaped
- *                             decode step for the handle's whole life.  A session's
+ *                             decode step for the handle's whole life.  Value 2 makes a WIDE session handle: the same, with
+ *                             max_batch <= 16 (csrc/gemv.hip's row-group GEMV; rows of free and finished slots skip their products)
+ *                             and the same other conditions; everything below holds for both values.  A session's
  *                             codes and latents are bit-identical to the same session alone on a max_batch = 1 handle, whatever the
  *                             other rows do and whichever slot it sits in.  On a session handle:
  *                               tt_ar_prefill_group(h, slot, S, prefix, P, stream) admits a session into a free slot (the running

@@ -58,7 +58,7 @@ int tt_op_decode_attention(int dtype, const void* q, const void* kp, const void*
  * slot_rows are DEVICE int [B]; p1_cap >= every p1_rows[b] sizes the LDS. */
 int tt_op_decode_attention_rows(int dtype, const void* q, const void* kp, const void* vp, long long prefix_stride, const int* p1_rows, int p1_cap,
                                 const void* kc, const void* vc, int tmax, const int* slot_rows, void* out, int B, int heads, void* stream);
-/* GEMV-shaped decode GEMM (csrc/gemv.hip): A T [M][K], W T [N][K], M <= 4, K in {1024, 2048, 4096}, N % 4 == 0;
+/* GEMV-shaped decode GEMM (csrc/gemv.hip): A T [M][K], W T [N][K], M <= 16, K in {1024, 2048, 4096}, N % 4 == 0;
  * epi 0: out_f32 [M][N] = A W^T + bias; 1: out_f32 += A W^T + bias (residual rows, in place); 2: out_t T [M][N] = gelu_tanh(A W^T + bias) */
 int tt_op_gemv(int dtype, const void* A, const void* W, int M, int N, int K, const float* bias, int epi, float* out_f32, void* out_t, void* stream);
 /* out_t[M][N] = gelu_tanh(LayerNorm(x[M][1024] f32; g, b, eps) W^T + bias): the same kernel with the layer norm inside */

@@ -16,8 +16,8 @@ teacher-forced latent re-pass) and csrc/hifigan.hip.
                             0, 2, 3, ... with kv_cache=True (autoregressive.py:134-149; oracle.ar_latents(stream_positions=True),
                             pinned live against the reference's sample_stream) - which the tests use as the check.
   * handle_chunks           api_fast.py:275-309, restated (host-side tensor slicing / cross-fade).
-  * max_streams = 2 .. 4    (engine-only) several streaming sessions share one decode batch: open_stream() admits a session at any
-                            time, stream_pieces() yields (session id, wav_chunk, done) with every session on exactly the piece schedule
+  * max_streams = 2 .. 4    (engine-only; 2 .. 16 with wide_sessions=True) several streaming sessions share one decode batch:
+                            open_stream() admits a session at any time, stream_pieces() yields (session id, wav_chunk, done) with every session on exactly the piece schedule
                             of tts_stream, tts_stream_many() wraps the two.  The AR handle is a session handle (TT_AR_OPT_SESSIONS):
                             one row per session, each with its own state on the device, all advanced by one captured decode step.
                             per_session_sampling=True lets every session keep its own sampling settings (TT_AR_OPT_SESSION_SAMPLING).
@@ -61,13 +61,14 @@ class TextToSpeech(_Common):
     """api_fast.py:180-229.  Engine-only keyword arguments as in tortoise_tts_amd.api.TextToSpeech: state_dicts
     ('autoregressive', 'hifidecoder', 'rlg_auto'), dtype, configs ('ar', 'hifigan'), max_mel_tokens, and max_streams (1 .. 4):
     streaming sessions served from one shared decode batch (open_stream / stream_pieces / tts_stream_many); 1 keeps the
-    single-sequence engine of tts() / tts_stream().  per_session_sampling=True (max_streams > 1): each session samples with the
-    settings it was opened with, whatever the other sessions use (else they must all match)."""
+    single-sequence engine of tts() / tts_stream(); wide_sessions=True allows max_streams = 2 .. 16 (a wide session handle).
+    per_session_sampling=True (max_streams > 1): each session samples with the settings it was opened with, whatever the other
+    sessions use (else they must all match)."""
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1,
-                 per_session_sampling=False):
+                 per_session_sampling=False, wide_sessions=False):
         self.models_dir = models_dir
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option")
@@ -88,8 +89,11 @@ class TextToSpeech(_Common):
         self.tokenizer_args = (tokenizer_vocab_file, tokenizer_basic)
         self._tokenizer = None
         self.max_mel_tokens_cap = max_mel_tokens
-        if not 1 <= int(max_streams) <= 4:
-            raise ValueError(f"max_streams={max_streams} outside 1 .. 4 (the sessions of one decode batch)")
+        self.wide_sessions = bool(wide_sessions)
+        if self.wide_sessions and not 2 <= int(max_streams) <= 16:
+            raise ValueError(f"max_streams={max_streams} outside 2 .. 16 (the sessions of one wide decode batch, wide_sessions=True)")
+        if not self.wide_sessions and not 1 <= int(max_streams) <= 4:
+            raise ValueError(f"max_streams={max_streams} outside 1 .. 4 (the sessions of one decode batch; up to 16 with wide_sessions=True)")
         self.max_streams = int(max_streams)
         self.per_session_sampling = bool(per_session_sampling)
         if self.per_session_sampling and self.max_streams == 1:

@@ -111,7 +111,7 @@ int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* v
   return flash_attention_launch(dtype, f, (hipStream_t)stream);
 }
 
-// GEMV-shaped decode GEMM (gemv.hip; handles of <= 4 sequences): epi 0 = out_f32 = A W^T + bias, 1 = x (out_f32) += A W^T + bias, 2 = out_t = gelu_tanh(A W^T + bias)
+// GEMV-shaped decode GEMM (gemv.hip; handles of <= 4 sequences, wide session handles of <= 16): epi 0 = out_f32 = A W^T + bias, 1 = x (out_f32) += A W^T + bias, 2 = out_t = gelu_tanh(A W^T + bias)
 int tt_op_gemv(int dtype, const void* A, const void* W, int M, int N, int K, const float* bias, int epi, float* out_f32, void* out_t, void* stream) {
   TT_REQUIRE(epi >= 0 && epi <= 2, "tt_op_gemv: epi %d (the QKV scatter is tested through the engine)", epi);
   GemvArgs v;

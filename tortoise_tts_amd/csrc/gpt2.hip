@@ -22,7 +22,7 @@ struct ArParams {
   unsigned long long keys[16];
   int row_offset;
   int pad[3];
-  SampleScalars rows[4];  // session handles: each row's sampling scalars (SampleArgs.rows), taken at its session's first step
+  SampleScalars rows[16];  // session handles: each row's sampling scalars (SampleArgs.rows), taken at its session's first step
 };
 
 struct tt_ar : EngineHandle {
@@ -94,7 +94,7 @@ struct tt_ar : EngineHandle {
   // SessPlane) - admitted (tt_ar_prefill_group into its slot), advanced (tt_ar_generate_chunk) and retired (TT_AR_OPT_SESSION_CLOSE)
   // independently of the others, all through ONE captured step graph.  Its prefix lives in prefix-cache group `slot`; its first token
   // is drawn from pre_logits[slot], the logits of its admission.  The host mirror below is refreshed at the end of every call.
-  int sessions = 0;
+  int sessions = 0;               // the option's value: 1 (<= 4 rows) | 2 (a wide handle: 5 .. 16 rows, gemv.hip's gemv_rows_kernel)
   int* sess = nullptr;
   int* sess_host = nullptr;       // pinned copy of sess, read back at the end of a chunk
   float* pre_logits = nullptr;    // [max_batch][Vp]
@@ -108,8 +108,13 @@ struct tt_ar : EngineHandle {
   // TT_AR_OPT_SESSION_SAMPLING: tt_ar_generate_chunk takes one tt_sampling per slot; s_rows[r] = what slot r's session started with
   int sess_sampling = 0;
   int admissions = 0;
-  tt_sampling s_rows[4];
+  tt_sampling s_rows[16];
 };
+
+// rows the GEMV-shaped step of a handle serves: a wide session handle's, or the <= 4 of the others (a property of the handle)
+static inline int ar_gemv_rows(const tt_ar* e) { return e->sessions == 2 ? 16 : 4; }
+// a wide session handle leaves the GEMV products of its free and finished rows out (GemvArgs.row_live = the slot plane)
+static inline const int* ar_gemv_live(const tt_ar* e) { return e->sessions == 2 ? e->sess + SESS_SLOT * e->cfg.max_batch : nullptr; }
 
 namespace tt { int g_ar_gemv = 2; }  // ttx_kernel_variant(TTX_AR_GEMV), read at tt_ar_create: handles of <= 4 sequences run 0 = the MFMA decode GEMMs | 1 = GEMV launches | 2 = GEMVs with the layer norms inside
 
@@ -227,11 +232,12 @@ static int ar_head_gemm(tt_ar* e, int M, hipStream_t s, int logits_row0 = 0, flo
     v.out_f32 = out; v.ldo32 = e->Vp;
     return gemv_launch(e->cfg.dtype, v, s);
   }
-  if (e->gemv && M <= 4) {
+  if (e->gemv && M <= ar_gemv_rows(e)) {
     GemvArgs v;
     memset(&v, 0, sizeof(v));
     v.A = e->h; v.lda = e->D; v.W = e->w_head_p; v.ldw = e->D; v.M = M; v.N = e->Vp; v.K = e->D; v.bias = e->b_head_p; v.epi = GEMV_F32;
     v.out_f32 = e->logits + (size_t)logits_row0 * e->Vp; v.ldo32 = e->Vp;
+    if (logits_row0 == 0 && M == e->cfg.max_batch) v.row_live = ar_gemv_live(e);  // (the decode step's rows)
     TT_TRY(gemv_launch(e->cfg.dtype, v, s));
     e->logits_rows = logits_row0 + M;
     return 0;
@@ -257,14 +263,15 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
   for (int l = 0; l < e->cfg.layers; ++l) {
     const tt_gpt_layer& w = e->L[l];
     if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln1_g, w.ln1_b, pend_bias, slabs, pend_slabs, nb, s));
-    if (e->gemv) {  // <= 4 sequences: GEMV-shaped launches, no split-K - the projections update x in place, the norms fold nothing
-      GemvArgs v;
+    if (e->gemv) {  // <= 4 sequences (wide session handles: <= 16): GEMV-shaped launches, no split-K - the projections update x in place,
+      GemvArgs v;   // the norms fold nothing
       memset(&v, 0, sizeof(v));
       v.A = e->h; v.lda = D; v.W = w.w_qkv; v.ldw = D; v.M = nb; v.N = 3 * D; v.K = D; v.bias = w.b_qkv; v.epi = GEMV_QKV;
       v.step = e->state + 1; v.qbuf = e->q; v.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es); v.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
       v.heads = H; v.tmax = e->tmax; v.dmodel = D; v.q_scale = 0.125f;
       if (e->sessions) { v.step = nullptr; v.row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; }
       if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln1_g; v.ln_b = w.ln1_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
+      v.row_live = ar_gemv_live(e);
       TT_TRY(gemv_launch(dt, v, s));
       DecodeAttnArgs a;
       memset(&a, 0, sizeof(a));
@@ -281,14 +288,17 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
       TT_TRY(decode_attention_launch(dt, a, s));
       memset(&v, 0, sizeof(v));
       v.A = e->attn; v.lda = D; v.W = w.w_proj; v.ldw = D; v.M = nb; v.N = D; v.K = D; v.bias = w.b_proj; v.epi = GEMV_RES; v.out_f32 = x; v.ldo32 = D;
+      v.row_live = ar_gemv_live(e);
       TT_TRY(gemv_launch(dt, v, s));
       if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln2_g, w.ln2_b, nullptr, slabs, 0, nb, s));
       memset(&v, 0, sizeof(v));
       if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln2_g; v.ln_b = w.ln2_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
       v.A = e->h; v.lda = D; v.W = w.w_fc; v.ldw = D; v.M = nb; v.N = 4 * D; v.K = D; v.bias = w.b_fc; v.epi = GEMV_GELU_T; v.out_t = e->ff; v.ldot = 4 * D;
+      v.row_live = ar_gemv_live(e);
       TT_TRY(gemv_launch(dt, v, s));
       memset(&v, 0, sizeof(v));
       v.A = e->ff; v.lda = 4 * D; v.W = w.w_proj2; v.ldw = 4 * D; v.M = nb; v.N = D; v.K = 4 * D; v.bias = w.b_proj2; v.epi = GEMV_RES; v.out_f32 = x; v.ldo32 = D;
+      v.row_live = ar_gemv_live(e);
       TT_TRY(gemv_launch(dt, v, s));
       pend_bias = nullptr;
       pend_slabs = 0;
@@ -967,6 +977,7 @@ int tt_ar_stat(tt_ar* e, int which) {
 // Engine options of a handle (defaults in brackets):
 //   TT_AR_OPT_LOOKAHEAD      [6]  decode steps the host may run ahead of the device (>= 1)
 //   TT_AR_OPT_SESSIONS       [0]  1: the handle serves streaming sessions, one per row (fresh handles of <= 4 rows, 16-bit, max_groups >= max_batch)
+//                                 2: the same on a wide handle of <= 16 rows
 //   TT_AR_OPT_SESSION_CLOSE       retire the session in slot `value` of a session handle
 //   TT_AR_OPT_SESSION_SAMPLING [0] 1: tt_ar_generate_chunk takes one tt_sampling per slot (session handles, before the first admission)
 int tt_ar_set_option(tt_ar* e, int option, int value) {
@@ -978,16 +989,26 @@ int tt_ar_set_option(tt_ar* e, int option, int value) {
       break;
     case TT_AR_OPT_SESSIONS: {
       const tt_ar_config& c = e->cfg;
-      TT_REQUIRE(value == 1 && !e->sessions, "tt_ar_set_option: sessions are switched on once, with value 1 (got %d)", value);
-      TT_REQUIRE(c.max_batch <= 4 && c.dtype != DT_F32 && c.max_groups >= c.max_batch && e->D == 1024,
-                 "tt_ar_set_option: sessions need max_batch <= 4, 16-bit operands, max_groups >= max_batch and model_dim 1024 (max_batch %d, dtype %d, max_groups %d)",
-                 c.max_batch, c.dtype, c.max_groups);
+      TT_REQUIRE((value == 1 || value == 2) && !e->sessions, "tt_ar_set_option: sessions are switched on once, with value 1 or 2 (got %d)", value);
+      if (value == 1)
+        TT_REQUIRE(c.max_batch <= 4 && c.dtype != DT_F32 && c.max_groups >= c.max_batch && e->D == 1024,
+                   "tt_ar_set_option: sessions need max_batch <= 4, 16-bit operands, max_groups >= max_batch and model_dim 1024 (max_batch %d, dtype %d, max_groups %d)",
+                   c.max_batch, c.dtype, c.max_groups);
+      else  // a wide session handle: the same conditions, up to 16 rows
+        TT_REQUIRE(c.max_batch <= 16 && c.dtype != DT_F32 && c.max_groups >= c.max_batch && e->D == 1024,
+                   "tt_ar_set_option: wide sessions need max_batch <= 16, 16-bit operands, max_groups >= max_batch and model_dim 1024 (max_batch %d, dtype %d, "
+                   "max_groups %d)",
+                   c.max_batch, c.dtype, c.max_groups);
       TT_REQUIRE(e->P1 == 0 && e->step.captures == 0 && !e->step.exec, "tt_ar_set_option: sessions must be switched on before the first prefill");
       // a session row stages its whole prefix capacity in the decode attention's LDS (about 600 prefix rows at 500 tokens)
       TT_REQUIRE(decode_attention_session_lds(c.max_prefix, e->tmax) <= DECODE_LDS_CAP,
                  "tt_ar_set_option: sessions need the prefix capacity in the attention's LDS: max_prefix %d with %d KV slots needs %zu bytes, %zu available",
                  c.max_prefix, e->tmax, decode_attention_session_lds(c.max_prefix, e->tmax), DECODE_LDS_CAP);
       int rc = e->arena.alloc_t(&e->sess, (size_t)4 * c.max_batch);
+      if (!rc && e->lat_batch < c.max_batch) {  // (tt_ar_create files streaming latents for handles of <= 8 rows)
+        e->lat_batch = c.max_batch;
+        rc = e->arena.alloc_t(&e->lat, (size_t)(e->tmax + 1) * e->lat_batch * e->D);
+      }
       if (!rc) rc = e->arena.alloc_t(&e->pre_logits, (size_t)c.max_batch * e->Vp);
       if (!rc && hipHostMalloc((void**)&e->sess_host, (size_t)4 * c.max_batch * sizeof(int)) != hipSuccess) {
         set_error("tt_ar_set_option: hipHostMalloc failed");
@@ -997,9 +1018,9 @@ int tt_ar_set_option(tt_ar* e, int option, int value) {
       // (arena memory is zeroed: every row starts SESS_FREE.  The slot plane of a free row must read -1)
       TT_CHECK_HIP(hipMemset(e->sess + SESS_SLOT * c.max_batch, 0xff, (size_t)c.max_batch * sizeof(int)));
       TT_CHECK_HIP(hipDeviceSynchronize());
-      // the GEMV-shaped step of a <= 4-sequence handle, for the whole life of the handle (its level as tt_ar_create picks it)
+      // the GEMV-shaped step of a <= 4-sequence handle (wide: <= 16), for the whole life of the handle (its level as tt_ar_create picks it)
       e->gemv = tt::g_ar_gemv ? tt::g_ar_gemv : 2;
-      e->sessions = 1;
+      e->sessions = value;
       e->B = c.max_batch;
       memset(e->s_n, 0, sizeof(e->s_n));
       memset(e->s_run, 0, sizeof(e->s_run));

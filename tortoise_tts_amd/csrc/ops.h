@@ -125,14 +125,14 @@ size_t decode_attention_session_lds(int p1_cap, int tmax);
 constexpr size_t DECODE_LDS_CAP = 160 * 1024;
 int decode_attn_f32_launch(const DecodeAttnArgs& a, hipStream_t stream);  // fp32 verification mode (attention_f32.hip)
 
-// ------------------------------------------------------------------------------ GEMV-shaped decode GEMMs (gemv.hip): M <= 4 rows
+// ------------------------------------------------------------------------------ GEMV-shaped decode GEMMs (gemv.hip): M <= 16 rows
 enum GemvEpi { GEMV_F32 = 0, GEMV_RES = 1, GEMV_GELU_T = 2, GEMV_QKV = 3 };
 struct GemvArgs {
   const void* A;      // [M][lda] T activation rows
   int lda;
   const void* W;      // [N][ldw] T
   int ldw;
-  int M, N, K;        // M <= 4; K in {1024, 2048, 4096}; N % 4 == 0
+  int M, N, K;        // M <= 16 (5 .. 16: the wide session handles); K in {1024, 2048, 4096}; N % 4 == 0
   const float* bias;  // [N] or null
   int epi;            // GemvEpi
   float* out_f32;     // GEMV_F32: [M][ldo32] = A W^T + bias; GEMV_RES: the residual rows, updated in place (x += A W^T + bias)
@@ -154,6 +154,9 @@ struct GemvArgs {
   const float* ln_b;
   float ln_eps;
   int* guard;  // counts rows whose variance is not finite (norm.hip's overflow guard), or null
+  // optional (M > 4): rows r with row_live[r] < 0 may be left out - a group of rows none of which is live is neither read, multiplied
+  // nor stored (a wide session handle's free and finished slots: their outputs are never read)
+  const int* row_live;
 };
 bool gemv_supported(int dtype, const GemvArgs& a);
 int gemv_launch(int dtype, const GemvArgs& a, hipStream_t stream);

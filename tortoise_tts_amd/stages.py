@@ -96,7 +96,8 @@ class ArStage(_GuardedHandle):
                  max_new_tokens=500, max_latent_candidates=4, share_weights_with=None, kv_cache=True, max_groups=1, sessions=False,
                  per_session_sampling=False):
         """sessions=True: a session handle (TT_AR_OPT_SESSIONS) - each of its max_batch <= 4 rows serves one streaming session, admitted,
-        advanced and retired on its own (admit / advance / session_codes / session_latents / close(slot)).  per_session_sampling=True
+        advanced and retired on its own (admit / advance / session_codes / session_latents / close(slot)); max_batch = 5 .. 16 opens a
+        wide session handle (option value 2).  per_session_sampling=True
         (TT_AR_OPT_SESSION_SAMPLING): every session keeps the sampling settings it was admitted with (admit(..., temperature=...))."""
         if per_session_sampling and not sessions:
             raise ValueError("per_session_sampling=True needs sessions=True")
@@ -128,7 +129,7 @@ class ArStage(_GuardedHandle):
         self._create(C.byref(c), C.byref(self.w.weights))
         self.sessions = bool(sessions)
         if self.sessions:
-            self.set_option(E.TT_AR_OPT_SESSIONS, 1)
+            self.set_option(E.TT_AR_OPT_SESSIONS, 1 if max_batch <= 4 else 2)
             self.per_session_sampling = bool(per_session_sampling)
             if self.per_session_sampling:
                 self.set_option(E.TT_AR_OPT_SESSION_SAMPLING, 1)
