@@ -35,6 +35,11 @@ int ttx_kernel_variant(int which, int v);
  * ============================================================================================ */
 int tt_op_gemm(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int seq_len,
                int splitk, const float* bias, int act, const float* res, float* out_f32, void* out_t, void* stream);
+/* tap convolution over seq_len-row slots with per-sequence valid lengths (the ragged HiFi-GAN batch, include/tortoise_mi355x_hifi.h):
+ * slot b = rows b * seq_len .. holds seq_vlen[b] (DEVICE int) valid rows; taps past them or before the slot read zero; tap t reads row
+ * s + (t - taps / 2) * dilation; M may end inside the last slot.  Same epilogue arguments as tt_op_gemm; 16-bit operand types. */
+int tt_op_gemm_segv(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int dilation, int seq_len,
+                    const int* seq_vlen, const float* bias, int act, const float* res, float* out_f32, void* out_t, void* stream);
 int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms,
                     void* out_t, float* out_f32, void* stream);
 int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift,

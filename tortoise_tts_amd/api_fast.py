@@ -184,6 +184,75 @@ class TextToSpeech(_Common):
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
         return wav.cpu()
 
+    @torch.no_grad()
+    def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
+        """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
+        state, clip for clip and bit for bit.  kwargs are tts()'s, shared by all texts; use_deterministic_seed is one seed or a list with
+        one per text.  On a max_streams=1 instance this loops tts().  On a session instance (max_streams >= 2) the texts are decoded as
+        rows of the shared decode batch - later texts take rows as earlier ones finish - each gets tts()'s latent re-pass, and the clips
+        are vocoded in ragged batches (HifiganStage.inference_many).  Returns a list of wav f32 [1, 1, S] on the CPU."""
+        texts = list(texts)
+        seeds = use_deterministic_seed if isinstance(use_deterministic_seed, (list, tuple)) else [use_deterministic_seed] * len(texts)
+        if len(seeds) != len(texts):
+            raise ValueError(f"tts_many: {len(seeds)} seeds for {len(texts)} texts")
+        bound = inspect.signature(TextToSpeech.tts).bind(self, "", **kwargs)  # (a TypeError for an unknown argument, before any work)
+        bound.apply_defaults()
+        a = bound.arguments
+        if self.max_streams == 1:
+            return [self.tts(t, voice_samples=voice_samples, conditioning_latents=conditioning_latents, use_deterministic_seed=sd, **kwargs)
+                    for t, sd in zip(texts, seeds)]
+        if self._sessions:
+            raise RuntimeError(f"tts_many: {len(self._sessions)} streaming session(s) are open on this instance; finish or close them first")
+        if "exp_noise" in a["hf_generate_kwargs"]:
+            raise ValueError("tts_many: injected exp_noise is not available on a session instance (rows draw from their Philox streams)")
+        top_k, typical_mass = sampler_kwargs(a["hf_generate_kwargs"])
+        settings = dict(temperature=float(a["temperature"]), top_p=float(a["top_p"]), repetition_penalty=float(a["repetition_penalty"]),
+                        top_k=int(top_k), typical_mass=float(typical_mass))
+        if self.per_session_sampling:
+            stages.session_sampling(**settings)  # (invalid settings raise before a row is taken)
+        max_mel_tokens = int(a["max_mel_tokens"])
+        if max_mel_tokens < 1:
+            raise ValueError(f"max_mel_tokens={max_mel_tokens} must be at least 1")
+        for t in texts:
+            self._text_tokens(t, max_mel_tokens)  # (too long a text raises before a row is taken)
+        rows = {}       # slot -> (index, cond, text_tokens)
+        n_row = {}      # slot -> tokens that row has sampled
+        clips = [None] * len(texts)
+        pending = list(range(len(texts)))
+        try:
+            while pending or rows:
+                while pending and len(rows) < self.max_streams:
+                    i = pending.pop(0)
+                    seed = self.deterministic_state(seed=seeds[i])  # (tts()'s order: reseed, then a random voice may be drawn)
+                    text_tokens, cond = self._prepare(texts[i], voice_samples, conditioning_latents, max_mel_tokens)
+                    slot = min(r for r in range(self.max_streams) if r not in rows)
+                    if self.per_session_sampling:
+                        self.ar.admit(slot, cond, text_tokens, seed, **settings)
+                    else:
+                        self.ar.admit(slot, cond, text_tokens, seed)
+                    rows[slot] = (i, cond, text_tokens)
+                    n_row[slot] = 0
+                step = max(1, min(max_mel_tokens - n_row[r] for r in rows))
+                if self.per_session_sampling:
+                    n_total, finished = self.ar.advance(step)
+                else:
+                    n_total, finished = self.ar.advance(step, **settings)
+                for slot in sorted(rows):
+                    n_row[slot] = n_total[slot]
+                    if not (finished[slot] or n_total[slot] >= max_mel_tokens):
+                        continue
+                    i, cond, text_tokens = rows.pop(slot)
+                    codes = self.ar.session_codes(slot)[:, :n_total[slot]]
+                    self.ar.close(slot)
+                    self.last_codes = codes
+                    clips[i] = (self.ar.latents(cond, text_tokens, codes), cond)  # tts()'s latent re-pass (api_fast.py:510-514)
+        finally:
+            for slot in rows:
+                self.ar.close(slot)
+        wavs = self.hifi_decoder.inference_many(clips) if hasattr(self.hifi_decoder, "inference_many") else \
+            [self.hifi_decoder.inference(lat, cond) for lat, cond in clips]
+        return [w.cpu() for w in wavs]
+
     def tts_with_preset(self, text, preset="fast", **kwargs):
         """api_fast.py:262-273: the preset table of this class only feeds kwargs to tts() (diffusion settings are unused on this
         path); a generator over the result, like the reference."""
@@ -325,29 +394,52 @@ class TextToSpeech(_Common):
                 return
         raise KeyError(f"close_stream: no open session {sid}")
 
-    def _session_piece(self, sess, n, finished):
-        """tts_stream's loop body for one session whose token count reached its piece boundary (or its end): the wav chunks it yields."""
+    def _session_latents(self, sess, n, finished):
+        """The first half of tts_stream's loop body for a session whose token count reached its piece boundary (or its end):
+        (latents to vocode, or None when there is nothing to decode; done; tokens they cover)."""
         codes = self.ar.session_codes(sess.slot)[:, :n]
         done = finished or n >= sess.max_mel_tokens
         if done and codes.shape[1] > 0 and int(codes[0, -1]) == self.stop_mel_token:
             codes = codes[:, :-1]
-        if codes.shape[1] == 0:  # (tts_stream yields nothing at all; the session still reports its end)
-            return [(torch.zeros(0, device=self.device), True)]
+        if codes.shape[1] == 0:
+            return None, done, 0
         self.last_codes = codes
         if self.stream_latents_from == "steps":
-            latents = self.ar.session_latents(sess.slot, codes.shape[1])
+            return self.ar.session_latents(sess.slot, codes.shape[1]), done, codes.shape[1]
+        return self.ar.latents(sess.cond, sess.text_tokens, codes, stream_positions=self.kv_cache), done, codes.shape[1]
+
+    def _session_piece(self, sess, n, finished, vocoded=None):
+        """tts_stream's loop body for one session whose token count reached its piece boundary (or its end): the wav chunks it yields.
+        vocoded: (wav_gen or None, done, tokens) when the caller has vocoded the session already (stream_pieces' batched call)."""
+        if vocoded is None:
+            latents, done, n_codes = self._session_latents(sess, n, finished)
+            wav_gen = None if latents is None else self.hifi_decoder.inference(latents, sess.cond).reshape(-1)
         else:
-            latents = self.ar.latents(sess.cond, sess.text_tokens, codes, stream_positions=self.kv_cache)
-        wav_gen = self.hifi_decoder.inference(latents, sess.cond).reshape(-1)
+            wav_gen, done, n_codes = vocoded
+        if wav_gen is None:  # (tts_stream yields nothing at all; the session still reports its end)
+            return [(torch.zeros(0, device=self.device), True)]
         wav_chunk, sess.wav_gen_prev, sess.wav_overlap = self.handle_chunks(wav_gen, sess.wav_gen_prev, sess.wav_overlap, sess.overlap)
         if not done:
-            sess.emitted, sess.threshold = codes.shape[1], sess.chunk
+            sess.emitted, sess.threshold = n_codes, sess.chunk
             sess.target = min(n + sess.chunk, sess.max_mel_tokens)
             return [(wav_chunk, False)]
-        if sess.stream_chunk_size > 0 and codes.shape[1] - sess.emitted == sess.threshold:  # the extra piece (see tts_stream)
+        if sess.stream_chunk_size > 0 and n_codes - sess.emitted == sess.threshold:  # the extra piece (see tts_stream)
             last, sess.wav_gen_prev, sess.wav_overlap = self.handle_chunks(wav_gen, sess.wav_gen_prev, sess.wav_overlap, sess.overlap)
             return [(wav_chunk, False), (last, True)]
         return [(wav_chunk, True)]
+
+    def _vocode_due(self, due):
+        """One batched vocoder call (HifiganStage.inference_many) for the sessions of this round whose piece is due: slot -> (wav_gen or
+        None, done, tokens).  {} for a stage without inference_many: those sessions are vocoded one at a time at their turn."""
+        if not hasattr(self.hifi_decoder, "inference_many"):
+            return {}
+        prep = {slot: self._session_latents(sess, n, fin) for slot, sess, n, fin in due}
+        todo = [(slot, lat, sess.cond) for slot, sess, _, _ in due for lat in [prep[slot][0]] if lat is not None]
+        wavs = self.hifi_decoder.inference_many([(lat, cond) for _, lat, cond in todo]) if todo else []
+        out = {slot: (None,) + prep[slot][1:] for slot in prep}
+        for (slot, _, _), wav in zip(todo, wavs):
+            out[slot] = (wav.reshape(-1),) + prep[slot][1:]
+        return out
 
     @torch.no_grad()
     def stream_pieces(self):
@@ -365,13 +457,16 @@ class TextToSpeech(_Common):
                 n_total, finished = self.ar.advance(max(step, 1), temperature=temperature, top_p=top_p, repetition_penalty=repetition_penalty,
                                                     top_k=top_k, typical_mass=typical_mass)
             batch = sorted(self._sessions.items())  # the sessions this advance served (open_stream / close_stream may run between pieces)
+            # every session whose piece is due is vocoded in one batched call before the first yield of the round
+            vocoded = self._vocode_due([(slot, sess, n_total[slot], finished[slot]) for slot, sess in batch
+                                        if finished[slot] or n_total[slot] >= sess.target])
             for slot, sess in batch:
                 if self._sessions.get(slot) is not sess:  # closed while an earlier piece of this round was out
                     continue
                 sess.n = n_total[slot]
                 if not (finished[slot] or n_total[slot] >= sess.target):
                     continue
-                pieces = self._session_piece(sess, n_total[slot], finished[slot])
+                pieces = self._session_piece(sess, n_total[slot], finished[slot], vocoded.get(slot))
                 if pieces[-1][1]:  # the session is over: its row is free for the next admission
                     del self._sessions[slot]
                     self.ar.close(slot)

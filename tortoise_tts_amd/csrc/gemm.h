@@ -29,6 +29,8 @@ struct GemmArgs {
   int taps;     // 1 = plain GEMM
   int dilation; // rows between conv taps (0 / 1: adjacent rows); tap t reads row s + (t - taps/2) * dilation
   int seq_len;  // rows per sequence (conv boundary / head-layout epilogues)
+  const int* seq_vlen;  // conv only, optional: DEVICE int per sequence - sequence b has seq_vlen[b] <= seq_len valid rows, taps past them read
+                        // zero (a batch of ragged sequences padded to seq_len-row slots); M may then end inside the last slot
   int cin;      // K / taps
   int splitk;   // >1: raw partial sums go to out_f32 + z * M * ldo32 (EPI_STD only)
   int serial_k; // >1: "serial split-K" - out_f32 = (((res + bias) + P0) + P1) + ... over serial_k equal K ranges inside ONE launch,

@@ -78,6 +78,7 @@ static void plan_core(const GemmArgs& a, int epi, GemmPlan& p, int force_tile = 
   c.dil = a.dilation > 0 ? a.dilation : 1;
   c.seq_len = a.seq_len;
   c.seq = make_fastdiv(a.seq_len > 0 ? a.seq_len : 1);
+  c.vlen = a.taps > 1 ? a.seq_vlen : nullptr;
   const int gx = cdiv(a.M, bm), gy = cdiv(a.N, bn);
   c.gx = gx; c.gy = gy;
   const unsigned nwg = (unsigned)gx * gy;
@@ -109,7 +110,7 @@ static void plan_core(const GemmArgs& a, int epi, GemmPlan& p, int force_tile = 
   // conditioned row keeps one accumulation order whether it is evaluated alone or batched)
   const bool al16 = (a.N & 3) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) && (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
                     a.out_f32 && ((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0;
-  p.conv3s = epi == EPI_STD && tile == TILE_128x64 && a.taps == 3 && a.dilation <= 1 && a.splitk == 1 && a.gn_part != nullptr && a.bias != nullptr &&
+  p.conv3s = epi == EPI_STD && !a.seq_vlen && tile == TILE_128x64 && a.taps == 3 && a.dilation <= 1 && a.splitk == 1 && a.gn_part != nullptr && a.bias != nullptr &&
              a.out_t == nullptr && a.act == ACT_NONE && a.A2 == nullptr && al16 && a.cin >= 256;
   p.prof_id = prof_class(tile, epi, a.taps > 1, a.gn_part != nullptr);
   // algorithmic work of this launch: 2*M*N*K flops; operands read once + ONE result written once (the extra split-K slabs
@@ -161,7 +162,10 @@ int gemm_launch(int dtype, int epi, const GemmArgs& a0, hipStream_t stream) {
     TT_REQUIRE(a.dmodel % 64 == 0 && a.N == 3 * a.dmodel && a.heads * 64 == a.dmodel, "gemm: qkv epilogue needs N == 3*dmodel, head_dim 64");
     TT_REQUIRE(a.bias == nullptr || ((size_t)a.bias & 15) == 0, "gemm: qkv bias must be 16-byte aligned");
   }
-  if (a.taps > 1 || epi == EPI_QKV_HEADS) TT_REQUIRE(a.seq_len > 0 && a.M % a.seq_len == 0, "gemm: M=%d is not a whole number of sequences of %d", a.M, a.seq_len);
+  if (a.seq_vlen)
+    TT_REQUIRE(epi == EPI_STD && a.taps > 1 && a.seq_len > 0 && a.splitk == 1 && !a.gn_part && !a.A2 && dtype != DT_F32,
+               "gemm: per-sequence valid lengths need a 16-bit tap convolution with the standard epilogue, no split-K and no statistics");
+  else if (a.taps > 1 || epi == EPI_QKV_HEADS) TT_REQUIRE(a.seq_len > 0 && a.M % a.seq_len == 0, "gemm: M=%d is not a whole number of sequences of %d", a.M, a.seq_len);
   GemmPlan plan;
   if (dtype == DT_F32) {
     plan_core(a, epi, plan, TILE_64x64);

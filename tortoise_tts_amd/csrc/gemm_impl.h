@@ -58,7 +58,7 @@ struct GemmCore {
   FastDiv hfull;           // 88  / hb
   FastDiv hlast;           // 96  / (row tiles of the last band)
   int sk_quot, sk_rem;     // 104 k-tiles per split-K slab (quotient, remainder)
-  int pad1, pad2;          // 112
+  const int* vlen;         // 112 SEGV conv kernels: valid rows of each seq_len-row slot (device int per sequence)
   // second activation source (HA2): k-tiles >= a2_tile read A2
   const void* A2;          // 120
   const int* a2_slot;      // 128
@@ -549,9 +549,12 @@ static __device__ __attribute__((aligned(16))) unsigned int g_zero_page[16] = {0
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
 
-// HA2: second activation source: -1 run-time test of c.A2, 0 never, 1 always
+// HA2: second activation source: -1 run-time test of c.A2, 0 never, 1 always.  A conv has no second source; there HA2 = 2 selects the
+// per-sequence valid lengths (SEGV): sequence b of the seq_len-row slots has c.vlen[b] valid rows and taps reaching past them read zero,
+// as at the slot's start, so a batch of ragged sequences padded to one slot length convolves each as if it were alone
 template <typename T, int BM, int BN, int NW, int WM, int ST, typename Epi, bool CONV, bool AL, int HA2>
 __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typename Epi::Args> g) {
+  constexpr bool SEGV = CONV && HA2 == 2;
   typedef typename Vec<T>::x8 x8;
   constexpr int BK = 64;
   constexpr int WGN = NW / WM;        // waves along N; WM waves along M
@@ -604,6 +607,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
   // per-piece lane geometry: this lane fills LDS chunk lc of row (piece * 8 + lr) with global chunk lc ^ swz(row)
   const int lr = lane >> 3, lc = lane & 7;
   int a_b[PA], a_s[PA], a_src[PA];
+  int a_end[SEGV ? PA : 1];  // SEGV: valid rows of each piece's sequence
   bool a_ok[PA];
 #pragma unroll
   for (int p = 0; p < PA; ++p) {
@@ -615,6 +619,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
       unsigned s_;
       a_b[p] = (int)fdiv((unsigned)m, c.seq, s_);
       a_s[p] = (int)s_;
+      if constexpr (SEGV) a_end[p] = a_ok[p] ? c.vlen[a_b[p]] : 0;
     } else {
       a_b[p] = 0;
       a_s[p] = a_ok[p] ? m : 0;  // rows beyond M re-read row 0: their outputs are never stored
@@ -646,7 +651,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
       const T* src;
       if (CONV) {
         const int s2 = a_s[p] + shift;
-        const bool ok = a_ok[p] && s2 >= 0 && s2 < c.seq_len;
+        bool ok;
+        if constexpr (SEGV) ok = a_ok[p] && s2 >= 0 && s2 < a_end[p];
+        else ok = a_ok[p] && s2 >= 0 && s2 < c.seq_len;
         src = ok ? A + ((size_t)a_b[p] * c.seq_len + s2) * c.lda + kin + a_src[p] : zero;
       } else if (HA2 != 0) {
         const bool second = A2 != nullptr && it >= c.a2_tile;  // block-uniform: k-tiles never straddle k_split (multiple of 64)
@@ -1031,10 +1038,17 @@ struct KernelRef {
 };
 
 // v(KernelRef) is called for the EPI_STD instantiation (tile, variant, conv, al); kNoKernel when that one does not exist
+// segv: the per-sequence valid-length conv (HA2 = 2 on a conv, HiFi-GAN's ragged batches): generic and run-time-output forms only
 template <typename T, int BM, int BN, int NW, int WM, int ST, typename V>
-static int visit_std_tile(int variant, bool conv, bool al, V&& v) {
+static int visit_std_tile(int variant, bool conv, bool al, bool segv, V&& v) {
   typedef EpiStd<T, -1, -1, -1> EGen;                                     // everything tested at run time
   typedef EpiStd<T, ACT_NONE, 0, -1> ENone;                               // no activation / statistics, run-time outputs
+  if (segv) {
+    if (!conv) return kNoKernel;
+    if (variant == V_GEN) return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, true, 2>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, false, 2>{});
+    if (variant == V_NONE && al) return v(KernelRef<T, BM, BN, NW, WM, ST, ENone, true, true, 2>{});
+    return kNoKernel;
+  }
   typedef EpiStd<T, ACT_NONE, 0, EB_SLAB> ESlab;                          // split-K partial sums (decode projections)
   typedef EpiStd<T, ACT_GELU_TANH, 0, EB_BIAS | EB_T> EGeluT;             // GPT-2 c_fc
   typedef EpiStd<T, ACT_NONE, 0, EB_BIAS | EB_T> EBiasT;                  // plain Linear / conv feeding the next GEMM
@@ -1089,14 +1103,14 @@ static int visit_skinny(int variant, bool conv, bool al, V&& v) {
   return kNoKernel;
 }
 template <typename T, typename V>
-static int visit_std(int tile, int variant, bool conv, bool al, V&& v) {
+static int visit_std(int tile, int variant, bool conv, bool al, V&& v, bool segv = false) {
   switch (tile) {
-    case TILE_32x16: return visit_skinny<T, 32, kSkinnyBN>(variant, conv, al, v);
-    case TILE_64x16: return visit_skinny<T, 64, kSkinnyBN>(variant, conv, al, v);
-    case TILE_256x256: return visit_std_tile<T, 256, 256, 16, 4, 2>(variant, conv, al, v);   // 4 x 4 waves of 64 x 64, two 64 KB stages
-    case TILE_128x128: return visit_std_tile<T, 128, 128, 8, 2, 2>(variant, conv, al, v);
-    case TILE_128x64: return visit_std_tile<T, 128, 64, 8, 4, 4>(variant, conv, al, v);   // 4 x 2 waves of 32 x 32: 1 LDS fragment read per MFMA (2 x 4 of 64 x 16: 1.25)
-    default: return visit_std_tile<T, 64, 64, 4, 2, 4>(variant, conv, al, v);
+    case TILE_32x16: return segv ? kNoKernel : visit_skinny<T, 32, kSkinnyBN>(variant, conv, al, v);
+    case TILE_64x16: return segv ? kNoKernel : visit_skinny<T, 64, kSkinnyBN>(variant, conv, al, v);
+    case TILE_256x256: return visit_std_tile<T, 256, 256, 16, 4, 2>(variant, conv, al, segv, v);   // 4 x 4 waves of 64 x 64, two 64 KB stages
+    case TILE_128x128: return visit_std_tile<T, 128, 128, 8, 2, 2>(variant, conv, al, segv, v);
+    case TILE_128x64: return visit_std_tile<T, 128, 64, 8, 4, 4>(variant, conv, al, segv, v);   // 4 x 2 waves of 32 x 32: 1 LDS fragment read per MFMA (2 x 4 of 64 x 16: 1.25)
+    default: return visit_std_tile<T, 64, 64, 4, 2, 4>(variant, conv, al, segv, v);
   }
 }
 template <typename T, typename Epi, typename V>
@@ -1183,8 +1197,9 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
       decltype(kr)::launch(ps, grid, stream, d);
       return 0;
     };
-    rc = visit_std<T>(plan.tile, variant, conv, al, go);
-    if (rc == kNoKernel && variant != V_SERIAL) rc = visit_std<T>(plan.tile, V_GEN, conv, al, go);
+    const bool segv = plan.core.vlen != nullptr;
+    rc = visit_std<T>(plan.tile, variant, conv, al, go, segv);
+    if (rc == kNoKernel && variant != V_SERIAL) rc = visit_std<T>(plan.tile, V_GEN, conv, al, go, segv);
   } else if (epi == EPI_QKV_HEADS) {
     GemmDev<EpiQkvHeadsArgs> d;
     d.c = plan.core;
@@ -1274,7 +1289,8 @@ int gemm_init_typed() {
   for (int tile = 0; tile < TILE_COUNT; ++tile) {
     for (int variant = 0; variant < V_COUNT; ++variant)
       for (int conv = 0; conv < 2; ++conv)
-        for (int al = 0; al < 2; ++al) (void)visit_std<T>(tile, variant, conv != 0, al != 0, setattr);
+        for (int al = 0; al < 2; ++al)
+          for (int segv = 0; segv < 2; ++segv) (void)visit_std<T>(tile, variant, conv != 0, al != 0, setattr, segv != 0);
     (void)visit_qkv<T, EpiQkvHeads<T>>(tile, setattr);
     (void)visit_qkv<T, EpiQkvDecode<T>>(tile, setattr);
     (void)visit_qkv<T, EpiGeglu<T>>(tile, setattr);

@@ -196,6 +196,10 @@ class ClsWeights(C.Structure):
 # include/tortoise_mi355x_classify.h, order == tt_cls_struct_size(which)
 CLASSIFY_STRUCTS = [ClsConfig, ClsWeights]
 
+# include/tortoise_mi355x_hifi.h, order == tt_hifi_batch_struct_size(which)
+HIFI_BATCH_STRUCTS = [HifiConfig, HifiWeights, HifiResBlock]
+HIFI_MAX_BATCH = 64  # TT_HIFI_MAX_BATCH
+
 # include/tortoise_mi355x_align.h, order == tt_align_struct_size(which)
 ALIGN_STRUCTS = [W2vConfig, W2vWeights]
 
@@ -287,10 +291,18 @@ _CLASSIFY_PROTOS = {
     "tt_cls_run": (_i, [vp, vp, _i, vp, vp, vp]),
     "tt_cls_guard": (_i, [vp, _i]),
 }
+# include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
+_HIFI_PROTOS = {
+    "tt_hifi_batch_abi_version": (_i, []),
+    "tt_hifi_batch_struct_size": (_sz, [_i]),
+    "tt_hifi_batch_capacity": (_i, [vp]),
+    "tt_hifi_run_batch": (_i, [vp, _i, vp, C.POINTER(_i), vp, vp, vp]),
+}
 # include/tortoise_mi355x_test.h: operator-level TEST entries + the A/B switch (not part of the boundary a maintainer binds)
 _TEST_PROTOS = {
     "ttx_kernel_variant": (_i, [_i, _i]),
     "tt_op_gemm": (_i, [_i, vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp]),
+    "tt_op_gemm_segv": (_i, [_i, vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "tt_op_layernorm": (_i, [_i, vp, _i, _i, vp, vp, _f, _i, vp, vp, vp]),
     "tt_op_groupnorm": (_i, [_i, vp, _i, _i, _i, vp, vp, vp, _i, vp, vp, vp, vp]),
     "tt_op_groupnorm_workspace": (_sz, [_i, _i]),
@@ -335,7 +347,8 @@ def load_library():
     # both have to bind to the ONE HIP runtime that torch ships (libamdhip64.so.7, resolved by SONAME).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()):
+    for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
+            list(_HIFI_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -345,6 +358,10 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(ALIGN_STRUCTS):
         want = lib.tt_align_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(HIFI_BATCH_STRUCTS):
+        want = lib.tt_hifi_batch_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(CLASSIFY_STRUCTS):

@@ -20,10 +20,15 @@ def chunk_owner(j, world):
 
 def read_long_form(tts, text, preset="standard", conditioning_latents=None, voice_samples=None, seed=None, texts_are_chunks=False,
                    **tts_kwargs):
-    """tts: a TextToSpeech built with candidate_sharding=False (one complete engine per rank).
+    """tts: a TextToSpeech built with candidate_sharding=False (one complete engine per rank), or a fast-path
+    tortoise_tts_amd.api_fast.TextToSpeech (the reference's read_fast.py): each rank then renders its chunks with one tts_many call -
+    tts()'s defaults plus tts_kwargs, the agreed seed for every chunk - and `preset` does not apply (read_fast.py passes none; the fast
+    path has no diffusion settings).
     text: the whole text (str; '|' splits it like read.py:46-50, else split_and_recombine_text) or, with texts_are_chunks=True,
     a list of chunks (str or pre-tokenised id sequences).
     Returns (full_audio f32 [1, n] or None, parts: list of per-chunk clips [1, 1, n_j]) on rank 0, (None, None) elsewhere."""
+    from .api_fast import TextToSpeech as FastTextToSpeech
+    fast = isinstance(tts, FastTextToSpeech)
     if getattr(tts, "world", 1) != 1:
         raise ValueError("read_long_form spreads chunks over the ranks: build TextToSpeech(candidate_sharding=False)")
     if texts_are_chunks:
@@ -39,7 +44,12 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     seed = tdist.broadcast_int(seed)
     mine = {}
     my_chunks = [j for j in range(len(texts)) if chunk_owner(j, world) == rank]
-    if getattr(tts, "utterance_batch", 1) > 1 and len(my_chunks) > 1:
+    if fast and my_chunks:
+        wavs = tts.tts_many([texts[j] for j in my_chunks], voice_samples=voice_samples, conditioning_latents=conditioning_latents,
+                            use_deterministic_seed=seed, **tts_kwargs)
+        mine = {j: w.cpu() for j, w in zip(my_chunks, wavs)}
+        my_chunks = []
+    elif getattr(tts, "utterance_batch", 1) > 1 and len(my_chunks) > 1:
         # this rank's chunks share decode batches (TextToSpeech.tts_many): same seed, same per-chunk codes as one after the other
         from .config import BASE_SETTINGS, PRESETS
         settings = dict(BASE_SETTINGS)

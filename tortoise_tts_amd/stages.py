@@ -811,6 +811,50 @@ class HifiganStage(_Handle):
         assert ns.value == n, (ns.value, n)
         return wav[None, None]
 
+    # a padded batch may carry this many idle slot rows beyond a quarter of its real ones (interpolated frames; about 15 latents)
+    _PAD_ALLOWANCE = 64
+
+    def batch_groups(self, lengths):
+        """Index groups (each one tt_hifi_run_batch call) for sequences of `lengths` latents: longest first, a sequence joins the open
+        group while the group fits the handle (n * (longest frames + 1) <= tt_hifi_batch_capacity, n <= TT_HIFI_MAX_BATCH) and its
+        padding stays within a quarter of the real rows plus _PAD_ALLOWANCE - so one long sequence is not padded against many short ones."""
+        cap = self.lib.tt_hifi_batch_capacity(self.h)
+        frames = [self.lib.tt_hifi_output_frames(int(T)) + 1 for T in lengths]
+        groups, cur, real = [], [], 0
+        for i in sorted(range(len(lengths)), key=lambda i: (-frames[i], i)):
+            if cur:
+                slot = frames[cur[0]]
+                n = len(cur) + 1
+                if n > E.HIFI_MAX_BATCH or n * slot > cap or n * slot > 1.25 * (real + frames[i]) + self._PAD_ALLOWANCE:
+                    groups.append(cur)
+                    cur, real = [], 0
+            cur.append(i)
+            real += frames[i]
+        if cur:
+            groups.append(cur)
+        return groups
+
+    def inference_many(self, items):
+        """items: list of (latents f32 [1, T_i, in_channels], g f32 [1, cond_channels]) -> list of wav f32 [1, 1, frames_i * hop] on the
+        device, in order.  Each wav is bit-identical to inference() of that item alone (csrc/hifigan.hip: one ragged batched pass per
+        group of batch_groups)."""
+        lats = [lat.to(self.device).float().reshape(-1, self.cfg.in_channels) for lat, _ in items]
+        gs = [g.to(self.device).float().reshape(-1) for _, g in items]
+        lengths = [int(x.shape[0]) for x in lats]
+        out = [None] * len(items)
+        for grp in self.batch_groups(lengths):
+            lat = torch.cat([lats[i] for i in grp], 0).contiguous()
+            gv = torch.stack([gs[i] for i in grp], 0).contiguous()
+            ns = [self.lib.tt_hifi_output_frames(lengths[i]) * self.cfg.hop for i in grp]
+            wav = torch.empty(sum(ns), device=self.device, dtype=torch.float32)
+            ln = (C.c_int * len(grp))(*[lengths[i] for i in grp])
+            E.check(self.lib.tt_hifi_run_batch(self.h, len(grp), E.ptr(lat), ln, E.ptr(gv), E.ptr(wav), E.stream_ptr()))
+            off = 0
+            for i, n in zip(grp, ns):
+                out[i] = wav[off:off + n][None, None]
+                off += n
+        return out
+
 
 class VocoderStage(_GuardedHandle):
     """UnivNetGenerator.inference (vocoder.py:300-312)."""
