@@ -40,6 +40,53 @@ int tt_op_gemm(int dtype, const void* A, int lda, const void* W, int ldw, int M,
  * s + (t - taps / 2) * dilation; M may end inside the last slot.  Same epilogue arguments as tt_op_gemm; 16-bit operand types. */
 int tt_op_gemm_segv(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int dilation, int seq_len,
                     const int* seq_vlen, const float* bias, int act, const float* res, float* out_f32, void* out_t, void* stream);
+/* Every GEMM form in one entry: the fields of csrc/gemm.h GemmArgs that a caller sets (same meanings; a zero leading dimension of an output
+ * or of the skip means N, seq_len 0 means M, q_scale 0 means 1).  tt_op_gemm_ex(dtype, epi, d, ran, stream): epi 0 standard, 1 QKV heads, 2 QKV decode, 3 GEGLU;
+ * the problem goes to the product dispatch unchanged.  ran (optional, int[4]) receives what actually launched, recorded on the host by the
+ * launch path: {tile (0 64x64, 1 128x64, 2 128x128, 3 256x256, 4 32x16, 5 64x16), standard-epilogue variant after any fallback to the
+ * generic kernel (0 GEN, 1 NONE, 2 SLAB, 3 GELU_T, 4 ST_F32, 5 ST_RES, 6 ST_A2, 7 BIAS_T, 8 SERIAL; -1 another epilogue), eight-phase
+ * 256 x 256 kernel (0 / 1), shared-halo 3-tap kernel (0 / 1)}. */
+typedef struct tt_op_gemm_desc {
+  const void* A;
+  const void* W;
+  const void* A2;        /* k >= k_split reads A2[m][k - k_split]; a2_slot (DEVICE int, optional) offsets A2 by *a2_slot * a2_slot_stride */
+  const int* a2_slot;
+  size_t a2_slot_stride;
+  int lda, ldw, lda2, k_split;
+  int M, N, K, taps, dilation, seq_len, splitk, serial_k;
+  const int* seq_vlen;   /* DEVICE int per sequence (tap convolutions over ragged slots) */
+  const float* bias;
+  const float* res;
+  float* out_f32;
+  void* out_t;
+  int act, ldres, ldo32, ldot;
+  float slope;
+  int act_t;
+  float slope_t;
+  float* gn_part;        /* GroupNorm statistics partials [row_tile][2][N / 16][2] */
+  int gn_seq, gn_vperiod;
+  int gn_vlen[32];
+  int dmodel, heads, seq_pad, tmax;
+  float q_scale;
+  void* q;
+  void* k;
+  void* v;
+  void* vt;
+  const int* step;       /* DEVICE int: the KV slot EPI_QKV_DECODE writes */
+  void* qbuf;
+  void* kc;
+  void* vc;
+} tt_op_gemm_desc;
+size_t tt_op_gemm_desc_size(void);
+int tt_op_gemm_ex(int dtype, int epi, const tt_op_gemm_desc* d, int* ran, void* stream);
+/* rows per statistics tile of the kernel tt_op_gemm_ex would pick for d (the part_rows its consumer needs) */
+int tt_op_gemm_stat_rows(int dtype, const tt_op_gemm_desc* d);
+/* GroupNorm32 apply on statistics a GEMM epilogue left (gemm_part of part_rows-row tiles; the path of the denoiser's GroupNorms): x f32
+ * [B][S][C]; vperiod > 0: sample b has vlen[b % vperiod] valid rows (host ints), the rest are left out of the statistics and written as
+ * zeros (1 <= vlen[i] <= S).  Same outputs as tt_op_groupnorm. */
+int tt_op_groupnorm_part(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
+                         const float* gemm_part, int part_rows, int vperiod, const int* vlen, void* out_t, float* out_f32, float* workspace,
+                         void* stream);
 int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms,
                     void* out_t, float* out_f32, void* stream);
 int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift,

@@ -20,21 +20,59 @@ int tt_init(void) {
   return gemm_init();
 }
 
+// the one argument mapping of the operator-level GEMM entries
+static GemmArgs gemm_desc_args(const tt_op_gemm_desc& d) {
+  GemmArgs g = gemm_args(d.A, d.lda, d.W, d.ldw, d.M, d.N, d.K);
+  g.A2 = d.A2; g.lda2 = d.lda2; g.k_split = d.k_split; g.a2_slot = d.a2_slot; g.a2_slot_stride = d.a2_slot_stride;
+  g.taps = d.taps; g.dilation = d.dilation; g.seq_len = d.seq_len > 0 ? d.seq_len : d.M; g.seq_vlen = d.seq_vlen; g.splitk = d.splitk; g.serial_k = d.serial_k;
+  g.bias = d.bias; g.act = d.act; g.slope = d.slope; g.res = d.res; g.ldres = d.ldres > 0 ? d.ldres : d.N;
+  g.out_f32 = d.out_f32; g.ldo32 = d.ldo32 > 0 ? d.ldo32 : d.N; g.out_t = d.out_t; g.ldot = d.ldot > 0 ? d.ldot : d.N;
+  g.act_t = d.act_t; g.slope_t = d.slope_t;
+  g.gn_part = d.gn_part; g.gn_seq = d.gn_seq; g.gn_vperiod = d.gn_vperiod;
+  for (int i = 0; i < 32; ++i) g.gn_vlen[i] = d.gn_vlen[i];
+  g.dmodel = d.dmodel; g.heads = d.heads; g.q = d.q; g.k = d.k; g.v = d.v; g.vt = d.vt; g.seq_pad = d.seq_pad; g.q_scale = d.q_scale != 0.f ? d.q_scale : 1.f;
+  g.step = d.step; g.qbuf = d.qbuf; g.kc = d.kc; g.vc = d.vc; g.tmax = d.tmax;
+  return g;
+}
+
+static tt_op_gemm_desc gemm_desc_std(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int seq_len, const float* bias, int act,
+                                     const float* res, float* out_f32, void* out_t) {
+  tt_op_gemm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.A = A; d.lda = lda; d.W = W; d.ldw = ldw; d.M = M; d.N = N; d.K = K; d.taps = taps; d.seq_len = seq_len; d.splitk = 1; d.q_scale = 1.f;
+  d.bias = bias; d.act = act; d.slope = 0.2f; d.res = res; d.out_f32 = out_f32; d.out_t = out_t;
+  return d;
+}
+
+size_t tt_op_gemm_desc_size(void) { return sizeof(tt_op_gemm_desc); }
+
+int tt_op_gemm_ex(int dtype, int epi, const tt_op_gemm_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr, "tt_op_gemm_ex: null descriptor");
+  const int rc = gemm_launch(dtype, epi, gemm_desc_args(*d), (hipStream_t)stream);
+  if (ran) {
+    ran[0] = g_gemm_ran.tile; ran[1] = g_gemm_ran.variant; ran[2] = g_gemm_ran.p8; ran[3] = g_gemm_ran.conv3s;
+  }
+  return rc;
+}
+
+int tt_op_gemm_stat_rows(int dtype, const tt_op_gemm_desc* d) {
+  TT_REQUIRE(d != nullptr, "tt_op_gemm_stat_rows: null descriptor");
+  return gemm_stat_rows(gemm_desc_args(*d), dtype);
+}
+
 int tt_op_gemm(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int seq_len, int splitk,
                const float* bias, int act, const float* res, float* out_f32, void* out_t, void* stream) {
-  GemmArgs g = gemm_args(A, lda, W, ldw, M, N, K);
-  g.taps = taps; g.seq_len = seq_len > 0 ? seq_len : M; g.splitk = splitk;
-  g.bias = bias; g.act = act; g.slope = 0.2f; g.res = res; g.ldres = N; g.out_f32 = out_f32; g.ldo32 = N; g.out_t = out_t; g.ldot = N;
-  return gemm_launch(dtype, EPI_STD, g, (hipStream_t)stream);
+  tt_op_gemm_desc d = gemm_desc_std(A, lda, W, ldw, M, N, K, taps, seq_len, bias, act, res, out_f32, out_t);
+  d.splitk = splitk;
+  return gemm_launch(dtype, EPI_STD, gemm_desc_args(d), (hipStream_t)stream);
 }
 
 int tt_op_gemm_segv(int dtype, const void* A, int lda, const void* W, int ldw, int M, int N, int K, int taps, int dilation, int seq_len,
                     const int* seq_vlen, const float* bias, int act, const float* res, float* out_f32, void* out_t, void* stream) {
   TT_REQUIRE(seq_vlen != nullptr, "tt_op_gemm_segv: seq_vlen is required");
-  GemmArgs g = gemm_args(A, lda, W, ldw, M, N, K);
-  g.taps = taps; g.dilation = dilation; g.seq_len = seq_len; g.seq_vlen = seq_vlen;
-  g.bias = bias; g.act = act; g.slope = 0.2f; g.res = res; g.ldres = N; g.out_f32 = out_f32; g.ldo32 = N; g.out_t = out_t; g.ldot = N;
-  return gemm_launch(dtype, EPI_STD, g, (hipStream_t)stream);
+  tt_op_gemm_desc d = gemm_desc_std(A, lda, W, ldw, M, N, K, taps, seq_len, bias, act, res, out_f32, out_t);
+  d.dilation = dilation; d.seq_vlen = seq_vlen;
+  return gemm_launch(dtype, EPI_STD, gemm_desc_args(d), (hipStream_t)stream);
 }
 
 int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms, void* out_t,
@@ -54,6 +92,20 @@ int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float*
   memset(&a, 0, sizeof(a));
   a.x = x; a.B = B; a.S = S; a.C = C; a.gamma = g; a.beta = b; a.eps = 1e-5f; a.scale_shift = scale_shift;
   a.ss_batch_stride = 2 * (size_t)C; a.act = act; a.out_t = out_t; a.ldot = C; a.out_f32 = out_f32; a.ldo32 = C; a.partial = workspace;
+  return groupnorm_launch(dtype, a, (hipStream_t)stream);
+}
+
+int tt_op_groupnorm_part(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
+                         const float* gemm_part, int part_rows, int vperiod, const int* vlen, void* out_t, float* out_f32, float* workspace,
+                         void* stream) {
+  TT_REQUIRE(gemm_part != nullptr && vperiod >= 0 && vperiod <= 32 && (vperiod == 0 || vlen != nullptr), "tt_op_groupnorm_part: bad arguments");
+  for (int i = 0; i < vperiod; ++i) TT_REQUIRE(vlen[i] > 0 && vlen[i] <= S, "tt_op_groupnorm_part: vlen[%d] = %d outside 1 .. S = %d", i, vlen[i], S);
+  GroupNormArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.B = B; a.S = S; a.C = C; a.gamma = g; a.beta = b; a.eps = 1e-5f; a.scale_shift = scale_shift;
+  a.ss_batch_stride = 2 * (size_t)C; a.act = act; a.out_t = out_t; a.ldot = C; a.out_f32 = out_f32; a.ldo32 = C; a.partial = workspace;
+  a.gemm_part = gemm_part; a.part_rows = part_rows; a.vperiod = vperiod;
+  for (int i = 0; i < vperiod; ++i) a.vlen[i] = vlen[i];
   return groupnorm_launch(dtype, a, (hipStream_t)stream);
 }
 

@@ -100,4 +100,10 @@ int gemm_launch(int dtype, int epi, const GemmArgs& a, hipStream_t stream);
 int gemm_init();  // sets dynamic-LDS attributes; called once per process
 int gemm_stat_rows(const GemmArgs& a, int dtype = DT_BF16);  // rows per statistics tile of the kernel gemm_launch would pick for `a`
 
+// What the last gemm_launch of this host thread actually launched (tt_op_gemm_ex, include/tortoise_mi355x_test.h): the tile (gemm_impl.h
+// Tile), the EPI_STD variant after any kNoKernel -> V_GEN fallback (StdVariant; -1: another epilogue), the eight-phase 256 x 256 kernel,
+// the shared-halo 3-tap kernel.  Written by the launch path itself: a few host stores per launch, nothing on the device.
+struct GemmRan { int tile, variant, p8, conv3s; };
+extern thread_local GemmRan g_gemm_ran;  // gemm.hip
+
 }  // namespace tt

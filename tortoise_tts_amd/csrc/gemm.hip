@@ -34,6 +34,7 @@ static bool skinny_ok(const GemmArgs& a, int epi) {
   return (a.N & 3) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) && (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
          (!a.out_f32 || (((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0)) && (!a.out_t || (((size_t)a.out_t & 7) == 0 && (a.ldot & 3) == 0));
 }
+thread_local GemmRan g_gemm_ran = {-1, -1, 0, 0};
 bool g_gemm_skinny = true;  // ttx_kernel_variant(TTX_GEMM_SKINNY): 0 = the 64 x 64 tile for small decode batches as well (A/B runs)
 
 static int pick_tile(const GemmArgs& a, int epi = EPI_STD) {
@@ -136,6 +137,7 @@ int gemm_stat_rows(const GemmArgs& a0, int dtype) {
 int gemm_launch(int dtype, int epi, const GemmArgs& a0, hipStream_t stream) {
   GemmArgs a = a0;
   normalise(a);
+  g_gemm_ran = GemmRan{-1, -1, 0, 0};
   TT_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   TT_REQUIRE(a.K % 64 == 0 && a.cin % 64 == 0, "gemm: K=%d (taps=%d) must be a multiple of 64 per tap", a.K, a.taps);
   TT_REQUIRE((a.lda % 8 == 0 && a.ldw % 8 == 0) || (dtype == DT_F32 && a.lda % 4 == 0 && a.ldw % 4 == 0), "gemm: lda=%d / ldw=%d must be multiples of 8 elements", a.lda, a.ldw);

@@ -98,6 +98,7 @@ int gemm_launch_typed<float>(int epi, const GemmArgs& a, const GemmPlan& plan, h
   const dim3 grid(plan.core.gx * plan.core.gy, 1, plan.splitk);
   ProfScope ps(plan.prof_id, stream, plan.flops, plan.bytes * 2.0, true);
   const bool conv = a.taps > 1;
+  g_gemm_ran = GemmRan{TILE_64x64, epi == EPI_STD ? V_GEN : -1, 0, 0};  // (one generic kernel per epilogue)
   if (epi == EPI_STD) {
     typedef EpiStd<float, -1, -1, -1> E;
     GemmDev<EpiStdArgs> d;

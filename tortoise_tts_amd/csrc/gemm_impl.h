@@ -510,7 +510,9 @@ __device__ __forceinline__ void run_epilogue(const GemmCore& c, const typename E
     }
   }
   if constexpr (Epi::kId == 0) {
-    if (stats) {
+    // (a wave tile that starts at or past M has no rows: writing its partials would reach past the cdiv(M, TM) row tiles the
+    //  partials buffers are sized for - by up to 3 tiles on the 128 x 64 tile)
+    if (stats && m0w < c.M) {
       const bool straddle = m0w + TM - 1 >= next_start;  // wave-uniform
 #pragma unroll
       for (int i = 0; i < FN; ++i) {
@@ -1029,6 +1031,7 @@ struct KernelRef {
   static void launch(const ProfScope& ps, dim3 grid, hipStream_t s, const GemmDev<EA>& d) {
     if constexpr (kP8) {
       if (g_gemm_p8 && p8_ok(d.c, grid)) {
+        g_gemm_ran.p8 = 1;
         launch_timed(ps, gemm_p8_kernel<T, Epi>, grid, dim3(512), kP8Smem, s, d);
         return;
       }
@@ -1157,10 +1160,12 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
   const dim3 grid(plan.core.gx * plan.core.gy, 1, plan.splitk);
   ProfScope ps(plan.prof_id, stream, plan.flops, plan.bytes, true);
   int rc = kNoKernel;
+  g_gemm_ran = GemmRan{plan.tile, -1, 0, plan.conv3s ? 1 : 0};
   if (epi == EPI_STD && plan.conv3s) {  // (gemm.hip decided: aligned, statistics epilogue, bias + f32 output (+ skip), 128x64 tile)
     GemmDev<EpiStdArgs> d;
     d.c = plan.core;
     d.e = make_epi_std(a);
+    g_gemm_ran.variant = a.res ? V_ST_RES : V_ST_F32;
     if (a.res) launch_timed(ps, gemm_conv3s_kernel<T, 128, 64, 8, 4, kConv3sStages, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_RES | EB_F32>, true>, grid, dim3(512), kConv3sSmem, stream, d);
     else launch_timed(ps, gemm_conv3s_kernel<T, 128, 64, 8, 4, kConv3sStages, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32>, true>, grid, dim3(512), kConv3sSmem, stream, d);
     TT_CHECK_HIP(hipGetLastError());
@@ -1199,7 +1204,11 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
     };
     const bool segv = plan.core.vlen != nullptr;
     rc = visit_std<T>(plan.tile, variant, conv, al, go, segv);
-    if (rc == kNoKernel && variant != V_SERIAL) rc = visit_std<T>(plan.tile, V_GEN, conv, al, go, segv);
+    if (rc == kNoKernel && variant != V_SERIAL) {
+      variant = V_GEN;
+      rc = visit_std<T>(plan.tile, V_GEN, conv, al, go, segv);
+    }
+    g_gemm_ran.variant = variant;
   } else if (epi == EPI_QKV_HEADS) {
     GemmDev<EpiQkvHeadsArgs> d;
     d.c = plan.core;

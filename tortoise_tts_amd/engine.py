@@ -196,6 +196,22 @@ class ClsWeights(C.Structure):
 # include/tortoise_mi355x_classify.h, order == tt_cls_struct_size(which)
 CLASSIFY_STRUCTS = [ClsConfig, ClsWeights]
 
+class GemmDesc(C.Structure):
+    """tt_op_gemm_desc (include/tortoise_mi355x_test.h): every GEMM form of the operator-level test entry tt_op_gemm_ex."""
+    _fields_ = [("A", vp), ("W", vp), ("A2", vp), ("a2_slot", vp), ("a2_slot_stride", C.c_size_t)] + [
+        (n, C.c_int) for n in ("lda", "ldw", "lda2", "k_split", "M", "N", "K", "taps", "dilation", "seq_len", "splitk", "serial_k")] + [
+        ("seq_vlen", vp), ("bias", vp), ("res", vp), ("out_f32", vp), ("out_t", vp)] + [
+        (n, C.c_int) for n in ("act", "ldres", "ldo32", "ldot")] + [("slope", C.c_float), ("act_t", C.c_int), ("slope_t", C.c_float),
+        ("gn_part", vp), ("gn_seq", C.c_int), ("gn_vperiod", C.c_int), ("gn_vlen", C.c_int * 32)] + [
+        (n, C.c_int) for n in ("dmodel", "heads", "seq_pad", "tmax")] + [("q_scale", C.c_float)] + [
+        (n, vp) for n in ("q", "k", "v", "vt", "step", "qbuf", "kc", "vc")]
+
+
+# tt_op_gemm_ex `ran` record: tiles (gemm_impl.h Tile) and standard-epilogue variants (StdVariant)
+GEMM_TILES = {0: "64x64", 1: "128x64", 2: "128x128", 3: "256x256", 4: "32x16", 5: "64x16"}
+GEMM_VARIANTS = {-1: "-", 0: "V_GEN", 1: "V_NONE", 2: "V_SLAB", 3: "V_GELU_T", 4: "V_ST_F32", 5: "V_ST_RES", 6: "V_ST_A2", 7: "V_BIAS_T", 8: "V_SERIAL"}
+EPI_STD, EPI_QKV_HEADS, EPI_QKV_DECODE, EPI_GEGLU = 0, 1, 2, 3
+
 # include/tortoise_mi355x_hifi.h, order == tt_hifi_batch_struct_size(which)
 HIFI_BATCH_STRUCTS = [HifiConfig, HifiWeights, HifiResBlock]
 HIFI_MAX_BATCH = 64  # TT_HIFI_MAX_BATCH
@@ -303,6 +319,10 @@ _TEST_PROTOS = {
     "ttx_kernel_variant": (_i, [_i, _i]),
     "tt_op_gemm": (_i, [_i, vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp]),
     "tt_op_gemm_segv": (_i, [_i, vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
+    "tt_op_gemm_desc_size": (_sz, []),
+    "tt_op_gemm_ex": (_i, [_i, _i, C.POINTER(GemmDesc), C.POINTER(_i), vp]),
+    "tt_op_gemm_stat_rows": (_i, [_i, C.POINTER(GemmDesc)]),
+    "tt_op_groupnorm_part": (_i, [_i, vp, _i, _i, _i, vp, vp, vp, _i, vp, _i, _i, C.POINTER(_i), vp, vp, vp, vp]),
     "tt_op_layernorm": (_i, [_i, vp, _i, _i, vp, vp, _f, _i, vp, vp, vp]),
     "tt_op_groupnorm": (_i, [_i, vp, _i, _i, _i, vp, vp, vp, _i, vp, vp, vp, vp]),
     "tt_op_groupnorm_workspace": (_sz, [_i, _i]),
@@ -368,6 +388,8 @@ def load_library():
         want = lib.tt_cls_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    if C.sizeof(GemmDesc) != lib.tt_op_gemm_desc_size():
+        raise EngineError("ABI mismatch: GemmDesc is %d bytes in Python, %d in the library" % (C.sizeof(GemmDesc), lib.tt_op_gemm_desc_size()))
     _lib = lib
     return lib
 
