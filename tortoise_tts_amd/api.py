@@ -243,12 +243,14 @@ class TextToSpeech(_Common):
     models_dir), `dtype` (MFMA operand type: 'bf16' | 'fp16' for every stage, or a dict per stage
     {'ar', 'clvp', 'diffusion', 'vocoder'}; see resolve_stage_dtypes for the defaults), `max_candidates`
     (per-GPU decode batch capacity), `configs` (ARConfig/CLVPConfig/DiffusionConfig/VocoderConfig overrides for tests), `aligner` ((config
-    dict, state_dict, vocab dict, tokenizer config dict) of the wav2vec2 redaction aligner instead of its files)."""
+    dict, state_dict, vocab dict, tokenizer config dict) of the wav2vec2 redaction aligner instead of its files), `winner_batch` (1 .. 16,
+    default 1: the k winners of tts() are rendered one after the other; W >= 2: in groups of up to W, each ONE shared denoiser pass per
+    diffusion step and ONE UnivNet call - DESIGN.md 5.20)."""
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, max_candidates=256, configs=None, max_mel_tokens=500, max_text_tokens=402,
-                 candidate_sharding=True, utterance_batch=1, aligner=None):
+                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1):
         self.models_dir = models_dir
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option; the MI355X engine "
@@ -304,6 +306,14 @@ class TextToSpeech(_Common):
                 raise ValueError(f"utterance_batch={self.utterance_batch} x max_candidates={cap} x max_mel_tokens={max_mel_tokens} needs "
                                  f"{need / 2 ** 30:.0f} GiB of KV cache + integrator slices, the device has {total / 2 ** 30:.0f} GiB: "
                                  f"lower utterance_batch or max_mel_tokens")
+        # winner_batch = W >= 2: tts(k > 1) renders this rank's winners in groups of up to W - one sample_many pass and one inference_many
+        # call per group (_render_winners).  At full width the batched denoiser agrees with the solo run within the operand tolerance, not
+        # bit for bit (DiffusionStage.sample_many), so the default stays 1: today's code path and today's bits.
+        self.winner_batch = int(winner_batch)
+        if not 1 <= self.winner_batch <= 16:
+            raise ValueError("winner_batch must lie in 1 .. 16 (winners of one utterance rendered per denoiser / UnivNet pass)")
+        # sequences one denoiser / UnivNet pass may hold: the diffusion handle's max_batch and the UnivNet handle's slots of max_S + 10 frames
+        self._render_batch = max(self.utterance_batch, self.winner_batch) if self.winner_batch >= 2 else self.utterance_batch
         self._caps = dict(cap=cap, max_text_tokens=max_text_tokens, max_mel_tokens=max_mel_tokens, max_S=max_S)
         self._state_dicts = sds
         # tts_many also pushes utterance_batch utterances through ONE denoiser pass per diffusion step (padded to the longest)
@@ -353,12 +363,15 @@ class TextToSpeech(_Common):
                 self.load_cvvp()
         elif name == "diffusion":
             self.diffusion = stages.DiffusionStage(self._sd("diffusion"), self.diff_cfg, self.device, dt, max_seq=c["max_S"],
-                                                   max_codes=c["max_mel_tokens"] + 8, max_steps=512, max_batch=self.utterance_batch)
+                                                   max_codes=c["max_mel_tokens"] + 8, max_steps=512, max_batch=self._render_batch)
         elif name == "vocoder":
             voc_sd = self._sd("vocoder")
             if any(k.endswith("weight_v") for k in voc_sd):
                 voc_sd = W.fold_weight_norm(voc_sd)  # UnivNetGenerator.eval(inference=True), vocoder.py:284-298
-            self.vocoder = stages.VocoderStage(voc_sd, self.voc_cfg, self.device, dt, max_frames=c["max_S"])
+            # (winner_batch >= 2: B clips of the longest length fit one call - B slots of max_S + 10 frames, about 150 KB of HBM per frame,
+            #  include/tortoise_mi355x_univnet.h; the default instance keeps today's size)
+            B = self._render_batch if self.winner_batch >= 2 else 1
+            self.vocoder = stages.VocoderStage(voc_sd, self.voc_cfg, self.device, dt, max_frames=B * (c["max_S"] + 10) - 10)
         else:
             raise ValueError(name)
 
@@ -556,7 +569,7 @@ class TextToSpeech(_Common):
         utterance), so every weight matrix streams once per step for all of them and the sampled codes of an utterance are
         bit-identical to rendering it alone.  With utterance_batch > 1 the CLVP ranking of a wave is ONE speech-tower pass over all its
         candidates (every score the bits of scoring the utterance alone) and the denoiser runs in shared, padded passes; the latent re-pass
-        and UnivNet (2 ms per utterance) run per utterance as in tts().  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py)."""
+        runs per utterance as in tts() and UnivNet vocodes a wave in one call (every clip the bits of vocoding it alone).  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py)."""
         if self.world != 1:
             raise ValueError("tts_many batches utterances on one GPU: build TextToSpeech(candidate_sharding=False)")
         args = inspect.signature(self.tts).bind(None, **kwargs)
@@ -740,9 +753,10 @@ class TextToSpeech(_Common):
         ev.mark(3)
         split = self.split_diffusion and k == 1 and bool(o.sched.cond_free)
         wavs, ok = {}, True
-        for i in range(k):
-            if (self.rank > 1) if split else (i % self.world != self.rank):
-                continue
+        mine = [i for i in range(k) if not ((self.rank > 1) if split else (i % self.world != self.rank))]
+        if self.winner_batch >= 2 and len(mine) >= 2:  # (one winner on this rank, the k = 1 split tail included: the single path below)
+            return self._render_winners(ev, mine, best, best_latents, diff, o, seed, keep_on_device)
+        for i in mine:
             item, z = self._winner_inputs(best[i], best_latents[i:i + 1], diff, o, seed, i)
             mel = self._diffuse(o.sched, item, split)
             if mel is None:
@@ -757,16 +771,46 @@ class TextToSpeech(_Common):
         ev.mark(5)
         return wavs, ok
 
-    def _render_wave(self, sched, items, zs):
-        """A wave's winners -> (clips on the CPU, all finite): ONE shared, padded sample_many pass in length order, UnivNet per utterance."""
+    def _render_winners(self, ev, mine, best, best_latents, diff, o, seed, keep_on_device):
+        """The winners `mine` of one utterance in groups of up to winner_batch: per group ONE shared, padded sample_many pass in length
+        order and ONE inference_many call.  Per winner nothing changes: its noise comes from seed + 7919 * (i + 1) in the same order, its
+        length from its own calm-token trim.  Marks `ev` 4 after the last denoiser pass and 5 after the vocoder -> ({winner: clip}, all finite)."""
+        W = self.winner_batch
+        wavs, ok, pending = {}, True, []
+        for g0 in range(0, len(mine), W):
+            grp = mine[g0:g0 + W]
+            items, zs = zip(*[self._winner_inputs(best[i], best_latents[i:i + 1], diff, o, seed, i) for i in grp])
+            pending.append((grp, self._diffuse_many(o.sched, items), zs))
+        ev.mark(4)
+        for grp, mels, zs in pending:
+            for i, audio in zip(grp, self._vocode_many(mels, zs)):
+                finite = torch.isfinite(audio).all()  # (a NaN survives the final clamp: the vocoder stage's overflow check)
+                wavs[i] = audio if keep_on_device else audio.cpu()
+                ok = ok and bool(finite)
+        ev.mark(5)
+        return wavs, ok
+
+    def _diffuse_many(self, sched, items):
+        """Diffusion items -> their mels in order: one item alone, several in ONE shared, padded sample_many pass in length order."""
         if len(items) == 1:
-            mels = [self._diffuse(sched, items[0])]
-        else:
-            order = sorted(range(len(items)), key=lambda u: items[u][2])
-            mels = [None] * len(items)
-            for u, mel in zip(order, self.diffusion.sample_many(sched, [items[u] for u in order])):
-                mels[u] = mel
-        wavs = [self.vocoder.inference(mel, z).cpu() for mel, z in zip(mels, zs)]
+            return [self._diffuse(sched, items[0])]
+        order = sorted(range(len(items)), key=lambda u: items[u][2])
+        mels = [None] * len(items)
+        for u, mel in zip(order, self.diffusion.sample_many(sched, [items[u] for u in order])):
+            mels[u] = mel
+        return mels
+
+    def _vocode_many(self, mels, zs):
+        """UnivNet over several (mel, z): ONE inference_many call when the vocoder stage has it (every clip the bits of inference() alone,
+        csrc/vocoder.hip), inference() per clip otherwise."""
+        many = getattr(self.vocoder, "inference_many", None)
+        if many is not None and len(mels) > 1:
+            return many(list(zip(mels, zs)))
+        return [self.vocoder.inference(mel, z) for mel, z in zip(mels, zs)]
+
+    def _render_wave(self, sched, items, zs):
+        """A wave's winners -> (clips on the CPU, all finite): ONE shared, padded sample_many pass in length order, then ONE UnivNet call."""
+        wavs = [w.cpu() for w in self._vocode_many(self._diffuse_many(sched, items), zs)]
         return wavs, all(bool(torch.isfinite(w).all()) for w in wavs)
 
     def _guarded(self, attempt):

@@ -42,7 +42,8 @@ def _digest(paths):
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
-    for name in ("tortoise_mi355x.h", "tortoise_mi355x_test.h", "tortoise_mi355x_align.h", "tortoise_mi355x_classify.h"):
+    for name in ("tortoise_mi355x.h", "tortoise_mi355x_test.h", "tortoise_mi355x_align.h", "tortoise_mi355x_classify.h", "tortoise_mi355x_hifi.h",
+                 "tortoise_mi355x_univnet.h"):
         hs.append(os.path.join(os.path.dirname(HERE), "include", name))
     return hs
 

@@ -165,8 +165,8 @@ int gemm_launch(int dtype, int epi, const GemmArgs& a0, hipStream_t stream) {
     TT_REQUIRE(a.bias == nullptr || ((size_t)a.bias & 15) == 0, "gemm: qkv bias must be 16-byte aligned");
   }
   if (a.seq_vlen)
-    TT_REQUIRE(epi == EPI_STD && a.taps > 1 && a.seq_len > 0 && a.splitk == 1 && !a.gn_part && !a.A2 && dtype != DT_F32,
-               "gemm: per-sequence valid lengths need a 16-bit tap convolution with the standard epilogue, no split-K and no statistics");
+    TT_REQUIRE(epi == EPI_STD && a.taps > 1 && a.seq_len > 0 && a.splitk == 1 && !a.gn_part && !a.A2,
+               "gemm: per-sequence valid lengths need a tap convolution with the standard epilogue, no split-K and no statistics");
   else if (a.taps > 1 || epi == EPI_QKV_HEADS) TT_REQUIRE(a.seq_len > 0 && a.M % a.seq_len == 0, "gemm: M=%d is not a whole number of sequences of %d", a.M, a.seq_len);
   GemmPlan plan;
   if (dtype == DT_F32) {

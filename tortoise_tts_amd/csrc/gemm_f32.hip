@@ -50,7 +50,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmDev<typename Ep
           unsigned s_;
           const unsigned b = fdiv((unsigned)m, c.seq, s_);
           const int s2 = (int)s_ + (tap - c.taps_half) * c.dil;
-          if (s2 >= 0 && s2 < c.seq_len) src = A + ((size_t)b * c.seq_len + s2) * c.lda + kin + lk;
+          const int end = c.vlen ? c.vlen[b] : c.seq_len;  // ragged batches: taps stop at the sequence's own length
+          if (s2 >= 0 && s2 < end) src = A + ((size_t)b * c.seq_len + s2) * c.lda + kin + lk;
         } else if (A2 != nullptr && kt >= c.a2_tile) {
           src = A2 + (size_t)m * c.lda2 + (kin - c.a2_tile * BK) + lk;
         } else {

@@ -298,12 +298,21 @@ int psample_launch(int dtype, const PSampleArgs& a, hipStream_t stream);
 int slot_advance_launch(int* slot, const float* ss_all, float* ss_cur, int row_floats, int last_slot, hipStream_t stream);
 
 // ------------------------------------------------------------------------------ UnivNet (fp32 VALU)
+// A ragged batch at the audio rate (include/tortoise_mi355x_univnet.h): sequence b owns slot b of every tensor - [C][P] each, P the T / Tin /
+// L * hop of the launch's arguments - and its first frames[b] * mul columns are valid.  The grid carries the sequence index; every output
+// element is computed with the one-sequence formula on the sequence's own length.  n = 0: one sequence that fills the tensor.
+constexpr int kVocSeqs = 32;  // TT_VOC_MAX_BATCH
+struct VocSeqs {
+  int n, mul;
+  int frames[kVocSeqs];
+};
 struct Conv1dArgs {
   const float* x;  // [Cin][T]
   const float* w;  // [Cout][Cin][k]
   const float* bias;
   float* y;        // [Cout][T]
   int Cin, Cout, T, k, dilation;
+  VocSeqs seq;     // ragged batch: x [n][Cin][T], y [n][Cout][T]
   int reflect;     // reflect padding (k/2 * dilation each side) instead of zeros
   float in_slope;  // LeakyReLU applied to the input when >= 0 (negative: none)
   int out_act;     // ACT_NONE / ACT_LRELU / 5 = tanh
@@ -317,6 +326,7 @@ struct ConvT1dArgs {
   float* y;        // [C][Tin*stride]
   int C, Tin, stride;
   float in_slope;
+  VocSeqs seq;     // ragged batch: x [n][C][Tin], y [n][C][Tin*stride]
 };
 int convt1d_launch(const ConvT1dArgs& a, hipStream_t stream);
 struct LvcArgs {
@@ -328,6 +338,7 @@ struct LvcArgs {
   int ldb, boff;
   float* x;             // [32][T] residual stream: x += sigmoid(o[:32]) * tanh(o[32:])
   int L, hop;
+  VocSeqs seq;          // ragged batch: x_in, x [n][32][L * hop], kernels / bias rows b * L + l; sequence b has frames[b] frames (mul unused)
   float in_slope;
   int* guard;           // optional device counter: += 1 per workgroup that staged a non-finite predicted kernel value (operand-overflow guard)
 };

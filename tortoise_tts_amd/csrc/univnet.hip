@@ -3,9 +3,25 @@
 // reference, and HBM/LDS-bound.  It runs as fp32 VALU kernels over channels-first [C][T] rows
 // (coalesced along T).  The mel-rate KernelPredictor convolutions (64 -> 24576 channels) are the
 // only GEMM-shaped part and go through the MFMA conv-GEMM (gemm.hip).
+//
+// Every kernel here takes a ragged batch (ops.h VocSeqs; include/tortoise_mi355x_univnet.h): one grid dimension is the sequence, slot b
+// of a tensor starts b * C * P elements in (P = the slot's columns = the row stride), and every bound - the reflect padding of conv_pre /
+// conv_post, the zero padding of the dilated and the location-variable convolutions, the transposed conv's last input - is the
+// sequence's OWN length.  An output element is computed by the one-sequence formula, in the same order, from the same values: a sequence
+// of a batch comes out bit-identical to running it alone.  The LDS tiles are indexed as before (the slot stride only moves global
+// addresses), so their bank behaviour is unchanged.
 #include "ops.h"
 
 namespace tt {
+
+// The launch's own copy of the batch descriptor: n = 0 (one sequence that fills the tensor) becomes a batch of one.
+static VocSeqs voc_seqs(const VocSeqs& q, int len) {
+  if (q.n > 0) return q;
+  VocSeqs r;
+  memset(&r, 0, sizeof(r));
+  r.n = 1; r.mul = 1; r.frames[0] = len;
+  return r;
+}
 
 // ---------------------------------------------------------------- direct conv1d, thread per output sample
 template <int COUT>
@@ -17,8 +33,12 @@ __global__ __launch_bounds__(256) void conv1d_direct_kernel(Conv1dArgs a) {
     wl[i] = a.w[((size_t)co * a.Cin + ci) * a.k + kk];
   }
   __syncthreads();
+  const int b = blockIdx.y;
+  const int T = a.seq.frames[b] * a.seq.mul;  // this sequence's own length (a.T: columns per slot)
+  const float* x = a.x + (size_t)b * a.Cin * a.T;
+  float* y = a.y + (size_t)b * COUT * a.T;
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= a.T) return;
+  if (t >= T) return;
   float acc[COUT];
 #pragma unroll
   for (int co = 0; co < COUT; ++co) acc[co] = a.bias ? a.bias[co] : 0.f;
@@ -27,12 +47,12 @@ __global__ __launch_bounds__(256) void conv1d_direct_kernel(Conv1dArgs a) {
     int tt_ = t + (kk - half) * a.dilation;
     if (a.reflect) {
       if (tt_ < 0) tt_ = -tt_;
-      if (tt_ >= a.T) tt_ = 2 * (a.T - 1) - tt_;
-    } else if (tt_ < 0 || tt_ >= a.T) {
+      if (tt_ >= T) tt_ = 2 * (T - 1) - tt_;
+    } else if (tt_ < 0 || tt_ >= T) {
       continue;
     }
     for (int ci = 0; ci < a.Cin; ++ci) {
-      float xv = a.x[(size_t)ci * a.T + tt_];
+      float xv = x[(size_t)ci * a.T + tt_];
       if (a.in_slope >= 0.f) xv = xv > 0.f ? xv : xv * a.in_slope;
       const float* wr = wl + (ci * a.k + kk) * COUT;
 #pragma unroll
@@ -44,7 +64,7 @@ __global__ __launch_bounds__(256) void conv1d_direct_kernel(Conv1dArgs a) {
     float v = acc[co];
     if (a.out_act == ACT_LRELU) v = v > 0.f ? v : v * a.out_slope;
     else if (a.out_act == 5) v = tanhf(v);
-    a.y[(size_t)co * a.T + t] = v;
+    y[(size_t)co * a.T + t] = v;
   }
 }
 
@@ -53,13 +73,18 @@ __global__ __launch_bounds__(256) void conv1d_direct_kernel(Conv1dArgs a) {
 // kidx = 3 ci + tap - exactly the weight's own [Cout][Cin][k] row.  v_mfma_f32_32x32x2_f32 multiplies f32 operands exactly (the f32
 // vector rate, 64 FLOP / clk / SIMD) but takes both operands from REGISTERS, one LDS read each per 4096 flops: the thread-per-sample
 // kernel above issues one broadcast LDS weight read per FMA and ran at ~10 % of the vector rate (45 us per launch at T = 225 280).
-// One workgroup = 128 samples: the input window (128 + 2 dil columns, LeakyReLU applied, zeros outside [0, T)) and the transposed
+// One workgroup = 128 samples of one sequence: the input window (128 + 2 dil columns, LeakyReLU applied, zeros outside the sequence's [0, T)) and the transposed
 // weights sit in LDS; wave w owns samples 32 w .. 32 w + 31, 48 MFMA steps of two k each.
 constexpr int CVM_TS = 128, CVM_MAXD = 27, CVM_ROW = CVM_TS + 2 * CVM_MAXD + 2;
 __global__ __launch_bounds__(256) void conv1d_mfma_kernel(Conv1dArgs a) {
   __shared__ float xs[32][CVM_ROW];
   __shared__ float wl[96][33];  // [kidx][co] (+1: the transposing fill is conflict-free)
+  const int b = blockIdx.y;
+  const int T = a.seq.frames[b] * a.seq.mul;  // this sequence's own length (a.T: columns per slot)
   const int t0 = blockIdx.x * CVM_TS, d = a.dilation, width = CVM_TS + 2 * d;
+  if (t0 >= T) return;  // (the whole workgroup: slot columns past a shorter sequence)
+  const float* x = a.x + (size_t)b * 32 * a.T;
+  float* y = a.y + (size_t)b * 32 * a.T;
   for (int i = threadIdx.x; i < 32 * 96; i += 256) {
     const int co = i / 96, kidx = i - co * 96;
     wl[kidx][co] = a.w[i];
@@ -67,7 +92,7 @@ __global__ __launch_bounds__(256) void conv1d_mfma_kernel(Conv1dArgs a) {
   for (int ci = threadIdx.x >> 6; ci < 32; ci += 4) {  // a wave per input row: coalesced
     for (int i = threadIdx.x & 63; i < width; i += 64) {
       const int t = t0 - d + i;
-      float v = (t >= 0 && t < a.T) ? a.x[(size_t)ci * a.T + t] : 0.f;
+      float v = (t >= 0 && t < T) ? x[(size_t)ci * a.T + t] : 0.f;
       if (a.in_slope >= 0.f) v = v > 0.f ? v : v * a.in_slope;
       xs[ci][i] = v;
     }
@@ -89,32 +114,36 @@ __global__ __launch_bounds__(256) void conv1d_mfma_kernel(Conv1dArgs a) {
     if (tap >= 3) { tap -= 3; ++ci; }
   }
   const int t = t0 + wave * 32 + j;
-  if (t < a.T) {
+  if (t < T) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int co = (r & 3) + 8 * (r >> 2) + 4 * h;
       float v = acc[r] + (a.bias ? a.bias[co] : 0.f);
       if (a.out_act == ACT_LRELU) v = v > 0.f ? v : v * a.out_slope;
       else if (a.out_act == 5) v = tanhf(v);
-      a.y[(size_t)co * a.T + t] = v;
+      y[(size_t)co * a.T + t] = v;
     }
   }
 }
 
 bool g_voc_mfma = true;  // tt_voc_variant: 0 = the thread-per-sample VALU kernels (A/B runs)
 
-int conv1d_direct_launch(const Conv1dArgs& a, hipStream_t stream) {
+int conv1d_direct_launch(const Conv1dArgs& a0, hipStream_t stream) {
+  Conv1dArgs a = a0;
+  a.seq = voc_seqs(a0.seq, a0.T);
+  const int n = a.seq.n;
+  TT_REQUIRE(n >= 1 && n <= kVocSeqs, "conv1d_direct: %d sequences (1 .. %d)", n, kVocSeqs);
   TT_REQUIRE(a.Cout == 32 || a.Cout == 1, "conv1d_direct: Cout=%d unsupported (32 or 1)", a.Cout);
   if (g_voc_mfma && a.Cin == 32 && a.Cout == 32 && a.k == 3 && !a.reflect && a.dilation >= 1 && a.dilation <= CVM_MAXD) {
-    ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T, 4.0 * (a.Cin + a.Cout) * (double)a.T);
-    conv1d_mfma_kernel<<<cdiv(a.T, CVM_TS), 256, 0, stream>>>(a);
+    ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T * n, 4.0 * (a.Cin + a.Cout) * (double)a.T * n);
+    conv1d_mfma_kernel<<<dim3(cdiv(a.T, CVM_TS), n), 256, 0, stream>>>(a);
     TT_CHECK_HIP(hipGetLastError());
     return 0;
   }
   const size_t smem = (size_t)a.Cin * a.k * a.Cout * sizeof(float);
   TT_REQUIRE(smem <= 60 * 1024, "conv1d_direct: weights do not fit LDS");
-  const int blocks = cdiv(a.T, 256);
-  ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T, 4.0 * (a.Cin + a.Cout) * (double)a.T);
+  const dim3 blocks(cdiv(a.T, 256), n);
+  ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T * n, 4.0 * (a.Cin + a.Cout) * (double)a.T * n);
   if (a.Cout == 32) conv1d_direct_kernel<32><<<blocks, 256, smem, stream>>>(a);
   else conv1d_direct_kernel<1><<<blocks, 256, smem, stream>>>(a);
   TT_CHECK_HIP(hipGetLastError());
@@ -123,7 +152,7 @@ int conv1d_direct_launch(const Conv1dArgs& a, hipStream_t stream) {
 
 // ---------------------------------------------------------------- ConvTranspose1d(C->C, k=2s, stride s, pad s/2)
 // Output sample t = s*j + r - p receives x[:, j] * w[:, :, r] + x[:, j-1] * w[:, :, r+s]; one block
-// column per phase r keeps both weight slices (2 x C x C) in LDS.
+// column per phase r keeps both weight slices (2 x C x C) in LDS.  blockIdx.z = sequence.
 __global__ __launch_bounds__(256) void convt1d_kernel(ConvT1dArgs a) {
   __shared__ float w0[32 * 32], w1[32 * 32];  // [ci][co]
   const int C = a.C, s = a.stride, r = blockIdx.y;
@@ -134,16 +163,21 @@ __global__ __launch_bounds__(256) void convt1d_kernel(ConvT1dArgs a) {
     w1[i] = a.w[((size_t)ci * C + co) * (2 * s) + r + s];
   }
   __syncthreads();
+  const int b = blockIdx.z;
+  const int Tin = a.seq.frames[b] * a.seq.mul;  // this sequence's own input length (a.Tin: columns per slot)
+  const size_t ldo = (size_t)a.Tin * s;
+  const float* x = a.x + (size_t)b * C * a.Tin;
+  float* y = a.y + (size_t)b * C * ldo;
   const int j = blockIdx.x * 256 + threadIdx.x;
-  const int Tout = a.Tin * s;
+  const int Tout = Tin * s;
   const int t = s * j + r - p;
-  if (j > a.Tin || t < 0 || t >= Tout) return;
+  if (j > Tin || t < 0 || t >= Tout) return;
   float acc[32];
 #pragma unroll
   for (int co = 0; co < 32; ++co) acc[co] = co < C ? a.bias[co] : 0.f;
   for (int ci = 0; ci < C; ++ci) {
-    float x0 = j < a.Tin ? a.x[(size_t)ci * a.Tin + j] : 0.f;
-    float x1 = j >= 1 ? a.x[(size_t)ci * a.Tin + j - 1] : 0.f;
+    float x0 = j < Tin ? x[(size_t)ci * a.Tin + j] : 0.f;
+    float x1 = j >= 1 ? x[(size_t)ci * a.Tin + j - 1] : 0.f;
     if (a.in_slope >= 0.f) {
       x0 = x0 > 0.f ? x0 : x0 * a.in_slope;
       x1 = x1 > 0.f ? x1 : x1 * a.in_slope;
@@ -151,12 +185,16 @@ __global__ __launch_bounds__(256) void convt1d_kernel(ConvT1dArgs a) {
 #pragma unroll
     for (int co = 0; co < 32; ++co) acc[co] += x0 * w0[ci * C + co] + x1 * w1[ci * C + co];
   }
-  for (int co = 0; co < C; ++co) a.y[(size_t)co * Tout + t] = acc[co];
+  for (int co = 0; co < C; ++co) y[(size_t)co * ldo + t] = acc[co];
 }
-int convt1d_launch(const ConvT1dArgs& a, hipStream_t stream) {
+int convt1d_launch(const ConvT1dArgs& a0, hipStream_t stream) {
+  ConvT1dArgs a = a0;
+  a.seq = voc_seqs(a0.seq, a0.Tin);
+  const int n = a.seq.n;
+  TT_REQUIRE(n >= 1 && n <= kVocSeqs, "convt1d: %d sequences (1 .. %d)", n, kVocSeqs);
   TT_REQUIRE(a.C == 32 && a.stride % 2 == 0, "convt1d: C=%d stride=%d unsupported (C == 32, even stride)", a.C, a.stride);
-  dim3 grid(cdiv(a.Tin + 1, 256), a.stride);
-  ProfScope ps(PROF_CONVT, stream, 2.0 * a.C * a.C * 2.0 * a.Tin * a.stride, 4.0 * a.C * (double)a.Tin * (1 + a.stride));
+  dim3 grid(cdiv(a.Tin + 1, 256), a.stride, n);
+  ProfScope ps(PROF_CONVT, stream, 2.0 * a.C * a.C * 2.0 * a.Tin * a.stride * n, 4.0 * a.C * (double)a.Tin * (1 + a.stride) * n);
   convt1d_kernel<<<grid, 256, 0, stream>>>(a);
   TT_CHECK_HIP(hipGetLastError());
   return 0;
@@ -193,29 +231,34 @@ __device__ __forceinline__ bool lvc_stage_kernel(const void* kernels, size_t ele
 }
 
 // vocoder.py:182-216 (dilation 1) fused with the sigmoid*tanh gate and the residual add (vocoder.py:178-179).
-// One block per mel frame l: its [32][64][3] kernel and the (hop+2)-sample input window sit in LDS.
+// One block per mel frame l of sequence blockIdx.y: its [32][64][3] kernel and the (hop+2)-sample input window sit in LDS.
 template <typename KT, int HOP>
 __global__ __launch_bounds__(256) void lvc_kernel(LvcArgs a) {
   constexpr int OG = 256 / HOP;     // output groups across threads
   constexpr int HALF = 32 / OG;     // gate pairs per thread
   __shared__ __attribute__((aligned(16))) float wk[32 * 64 * 3];
   __shared__ float xs[32][HOP + 2];
-  const int l = blockIdx.x;
-  const int T = a.L * HOP;
-  const bool bad = lvc_stage_kernel<KT>(a.kernels, (size_t)l * a.ldk + a.koff, wk);
+  const int l = blockIdx.x, b = blockIdx.y;
+  if (l >= a.seq.frames[b]) return;  // (the whole workgroup: slot frames past a shorter sequence)
+  const int T = a.seq.frames[b] * HOP;     // this sequence's own length
+  const size_t P = (size_t)a.L * HOP;      // columns per slot
+  const size_t row = (size_t)b * a.L + l;  // its row of the predicted kernels / biases
+  const float* x_in = a.x_in + (size_t)b * 32 * P;
+  float* x = a.x + (size_t)b * 32 * P;
+  const bool bad = lvc_stage_kernel<KT>(a.kernels, row * a.ldk + a.koff, wk);
   // an overflowed fp16 KernelPredictor operand shows up HERE as inf / NaN taps; behind the sigmoid * tanh gate it would be a finite sample
   if (a.guard && __any(bad) && (threadIdx.x & 63) == 0) atomicAdd(a.guard, 1);
   for (int i = threadIdx.x; i < 32 * (HOP + 2); i += 256) {
     const int ci = i / (HOP + 2), off = i % (HOP + 2);
     const int t = l * HOP + off - 1;
-    float v = (t >= 0 && t < T) ? a.x_in[(size_t)ci * T + t] : 0.f;
+    float v = (t >= 0 && t < T) ? x_in[(size_t)ci * P + t] : 0.f;
     if (a.in_slope >= 0.f) v = v > 0.f ? v : v * a.in_slope;
     xs[ci][off] = v;
   }
   __syncthreads();
   const int s = threadIdx.x % HOP, og = threadIdx.x / HOP;
   float acc[2 * HALF];
-  const float* bl = a.bias + (size_t)l * a.ldb + a.boff;
+  const float* bl = a.bias + row * a.ldb + a.boff;
 #pragma unroll
   for (int u = 0; u < HALF; ++u) {
     acc[u] = bl[og * HALF + u];
@@ -237,7 +280,7 @@ __global__ __launch_bounds__(256) void lvc_kernel(LvcArgs a) {
   for (int u = 0; u < HALF; ++u) {
     const int o = og * HALF + u;
     const float g = 1.f / (1.f + expf(-acc[u]));
-    a.x[(size_t)o * T + t] += g * tanhf(acc[HALF + u]);
+    x[(size_t)o * P + t] += g * tanhf(acc[HALF + u]);
   }
 }
 // The same on the f32 matrix cores (round 5; hops of 64 and 256 samples): per frame, out[64][HOP] = K_l[64][96] . X_unf[96][HOP] with
@@ -250,15 +293,20 @@ __global__ __launch_bounds__(256) void lvc_mfma_kernel(LvcArgs a) {
   constexpr int SBW = NSB >= 4 ? NSB / 4 : 1;      // sample blocks per wave (waves beyond NSB idle after the staging)
   __shared__ __attribute__((aligned(16))) float wk[32 * 64 * 3];
   __shared__ float xs[32][HOP + 2];
-  const int l = blockIdx.x;
-  const int T = a.L * HOP;
-  const bool bad = lvc_stage_kernel<KT>(a.kernels, (size_t)l * a.ldk + a.koff, wk);
+  const int l = blockIdx.x, b = blockIdx.y;
+  if (l >= a.seq.frames[b]) return;  // (the whole workgroup: slot frames past a shorter sequence)
+  const int T = a.seq.frames[b] * HOP;     // this sequence's own length
+  const size_t P = (size_t)a.L * HOP;      // columns per slot
+  const size_t row = (size_t)b * a.L + l;  // its row of the predicted kernels / biases
+  const float* x_in = a.x_in + (size_t)b * 32 * P;
+  float* x = a.x + (size_t)b * 32 * P;
+  const bool bad = lvc_stage_kernel<KT>(a.kernels, row * a.ldk + a.koff, wk);
   // an overflowed fp16 KernelPredictor operand shows up HERE as inf / NaN taps; behind the sigmoid * tanh gate it would be a finite sample
   if (a.guard && __any(bad) && (threadIdx.x & 63) == 0) atomicAdd(a.guard, 1);
   for (int i = threadIdx.x; i < 32 * (HOP + 2); i += 256) {
     const int ci = i / (HOP + 2), off = i % (HOP + 2);
     const int t = l * HOP + off - 1;
-    float v = (t >= 0 && t < T) ? a.x_in[(size_t)ci * T + t] : 0.f;
+    float v = (t >= 0 && t < T) ? x_in[(size_t)ci * P + t] : 0.f;
     if (a.in_slope >= 0.f) v = v > 0.f ? v : v * a.in_slope;
     xs[ci][off] = v;
   }
@@ -286,7 +334,7 @@ __global__ __launch_bounds__(256) void lvc_mfma_kernel(LvcArgs a) {
     tap += 2;
     if (tap >= 3) { tap -= 3; ++ci; }
   }
-  const float* bl = a.bias + (size_t)l * a.ldb + a.boff;
+  const float* bl = a.bias + row * a.ldb + a.boff;
 #pragma unroll
   for (int u = 0; u < SBW; ++u) {
     const int t = l * HOP + (wave * SBW + u) * 32 + j;
@@ -294,26 +342,32 @@ __global__ __launch_bounds__(256) void lvc_mfma_kernel(LvcArgs a) {
     for (int r = 0; r < 16; ++r) {
       const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
       const float g = 1.f / (1.f + expf(-(acc[u][0][r] + bl[o])));
-      a.x[(size_t)o * T + t] += g * tanhf(acc[u][1][r] + bl[32 + o]);
+      x[(size_t)o * P + t] += g * tanhf(acc[u][1][r] + bl[32 + o]);
     }
   }
 }
 
-int lvc_launch(const LvcArgs& a, hipStream_t stream) {
+int lvc_launch(const LvcArgs& a0, hipStream_t stream) {
+  LvcArgs a = a0;
+  a.seq = voc_seqs(a0.seq, a0.L);
+  const int n = a.seq.n;
+  TT_REQUIRE(n >= 1 && n <= kVocSeqs, "lvc: %d sequences (1 .. %d)", n, kVocSeqs);
   const int eb = a.dtype == DT_F32 ? 4 : 2;
   const int al = 16 / eb;  // elements per 16-byte staging load
   TT_REQUIRE(a.dtype == DT_BF16 || a.dtype == DT_F16 || a.dtype == DT_F32, "lvc: unknown kernel dtype %d", a.dtype);
   TT_REQUIRE(a.ldk % al == 0 && a.koff % al == 0 && ((size_t)a.kernels & 15) == 0, "lvc: kernel rows must be 16-byte aligned");
   // algorithmic bytes: the predicted kernels (L x 6144, operand type) are read once, x_in read + x updated
-  ProfScope ps(PROF_LVC, stream, 2.0 * 96 * 64 * (double)a.L * a.hop, (double)eb * 6144.0 * a.L + 4.0 * 64 * a.L + 4.0 * 96 * (double)a.L * a.hop);
+  const double rows = (double)a.L * n;
+  ProfScope ps(PROF_LVC, stream, 2.0 * 96 * 64 * rows * a.hop, (double)eb * 6144.0 * rows + 4.0 * 64 * rows + 4.0 * 96 * rows * a.hop);
+  const dim3 grid(a.L, n);
   const bool mfma = g_voc_mfma && a.in_slope < 0.f && (a.hop == 64 || a.hop == 256);
 #define TT_LVC(T)                                                                  \
   do {                                                                             \
-    if (mfma && a.hop == 64) lvc_mfma_kernel<T, 64><<<a.L, 256, 0, stream>>>(a);   \
-    else if (mfma) lvc_mfma_kernel<T, 256><<<a.L, 256, 0, stream>>>(a);            \
-    else if (a.hop == 8) lvc_kernel<T, 8><<<a.L, 256, 0, stream>>>(a);             \
-    else if (a.hop == 64) lvc_kernel<T, 64><<<a.L, 256, 0, stream>>>(a);           \
-    else if (a.hop == 256) lvc_kernel<T, 256><<<a.L, 256, 0, stream>>>(a);         \
+    if (mfma && a.hop == 64) lvc_mfma_kernel<T, 64><<<grid, 256, 0, stream>>>(a);   \
+    else if (mfma) lvc_mfma_kernel<T, 256><<<grid, 256, 0, stream>>>(a);            \
+    else if (a.hop == 8) lvc_kernel<T, 8><<<grid, 256, 0, stream>>>(a);             \
+    else if (a.hop == 64) lvc_kernel<T, 64><<<grid, 256, 0, stream>>>(a);           \
+    else if (a.hop == 256) lvc_kernel<T, 256><<<grid, 256, 0, stream>>>(a);         \
     else { set_error("lvc: hop=%d unsupported (8, 64, 256)", a.hop); return -1; }  \
   } while (0)
   if (a.dtype == DT_F32) TT_LVC(float);

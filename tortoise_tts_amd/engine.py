@@ -216,6 +216,10 @@ EPI_STD, EPI_QKV_HEADS, EPI_QKV_DECODE, EPI_GEGLU = 0, 1, 2, 3
 HIFI_BATCH_STRUCTS = [HifiConfig, HifiWeights, HifiResBlock]
 HIFI_MAX_BATCH = 64  # TT_HIFI_MAX_BATCH
 
+# include/tortoise_mi355x_univnet.h, order == tt_voc_batch_struct_size(which)
+VOC_BATCH_STRUCTS = [VocConfig, VocWeights, VocBlock]
+VOC_MAX_BATCH = 32  # TT_VOC_MAX_BATCH
+
 # include/tortoise_mi355x_align.h, order == tt_align_struct_size(which)
 ALIGN_STRUCTS = [W2vConfig, W2vWeights]
 
@@ -314,6 +318,13 @@ _HIFI_PROTOS = {
     "tt_hifi_batch_capacity": (_i, [vp]),
     "tt_hifi_run_batch": (_i, [vp, _i, vp, C.POINTER(_i), vp, vp, vp]),
 }
+# include/tortoise_mi355x_univnet.h: ragged batches of the UnivNet vocoder (its own header and version, same library)
+_UNIVNET_PROTOS = {
+    "tt_voc_batch_abi_version": (_i, []),
+    "tt_voc_batch_struct_size": (_sz, [_i]),
+    "tt_voc_batch_capacity": (_i, [vp]),
+    "tt_voc_run_batch": (_i, [vp, _i, C.POINTER(C.c_void_p), C.POINTER(_i), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp]),
+}
 # include/tortoise_mi355x_test.h: operator-level TEST entries + the A/B switch (not part of the boundary a maintainer binds)
 _TEST_PROTOS = {
     "ttx_kernel_variant": (_i, [_i, _i]),
@@ -368,7 +379,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_HIFI_PROTOS.items()):
+            list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -382,6 +393,10 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(HIFI_BATCH_STRUCTS):
         want = lib.tt_hifi_batch_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(VOC_BATCH_STRUCTS):
+        want = lib.tt_voc_batch_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(CLASSIFY_STRUCTS):

@@ -879,3 +879,46 @@ class VocoderStage(_GuardedHandle):
         audio = torch.empty(S * self.cfg.hop_length, device=self.device, dtype=torch.float32)
         E.check(self.lib.tt_voc_run(self.h, E.ptr(m), S, E.ptr(zz), E.ptr(audio), E.stream_ptr()))
         return audio.clamp(-1, 1)[None, None]
+
+    # a padded batch may carry this many idle slot frames beyond a quarter of its real ones
+    _PAD_ALLOWANCE = 64
+
+    def batch_groups(self, lengths):
+        """Index groups (each one tt_voc_run_batch call) for mels of `lengths` frames - the rule of HifiganStage.batch_groups: longest
+        first, a sequence joins the open group while the group fits the handle (n * (longest S + 10) <= tt_voc_batch_capacity,
+        n <= TT_VOC_MAX_BATCH) and its padding stays within a quarter of the real frames plus _PAD_ALLOWANCE."""
+        cap = self.lib.tt_voc_batch_capacity(self.h)
+        frames = [int(S) + 10 for S in lengths]
+        groups, cur, real = [], [], 0
+        for i in sorted(range(len(lengths)), key=lambda i: (-frames[i], i)):
+            if cur:
+                slot = frames[cur[0]]
+                n = len(cur) + 1
+                if n > E.VOC_MAX_BATCH or n * slot > cap or n * slot > 1.25 * (real + frames[i]) + self._PAD_ALLOWANCE:
+                    groups.append(cur)
+                    cur, real = [], 0
+            cur.append(i)
+            real += frames[i]
+        if cur:
+            groups.append(cur)
+        return groups
+
+    def inference_many(self, items):
+        """items: list of (mel f32 [1, 100, S_i], z f32 [1, 64, S_i + 10]) -> list of audio f32 [1, 1, S_i * 256] on the device, in
+        order, clamped like inference().  Each clip is bit-identical to inference() of that item alone (csrc/vocoder.hip: one ragged
+        batched pass per group of batch_groups)."""
+        mels = [mel[0].to(self.device).float().contiguous() for mel, _ in items]
+        zs = [z[0].to(self.device).float().contiguous() for _, z in items]
+        lengths = [int(m.shape[1]) for m in mels]
+        for zz, S in zip(zs, lengths):
+            assert zz.shape == (self.cfg.noise_dim, S + 10)
+        out = [None] * len(items)
+        for grp in self.batch_groups(lengths):
+            n = len(grp)
+            audio = [torch.empty(lengths[i] * self.cfg.hop_length, device=self.device, dtype=torch.float32) for i in grp]
+            arr = lambda ts: (C.c_void_p * n)(*[E.ptr(t) for t in ts])
+            ln = (C.c_int * n)(*[lengths[i] for i in grp])
+            E.check(self.lib.tt_voc_run_batch(self.h, n, arr([mels[i] for i in grp]), ln, arr([zs[i] for i in grp]), arr(audio), E.stream_ptr()))
+            for i, a in zip(grp, audio):
+                out[i] = a.clamp(-1, 1)[None, None]
+        return out
