@@ -183,6 +183,11 @@ int tt_ar_stream_latents(tt_ar* h, int B, int n, float* out, void* stream);
 #define TT_AR_OPT_SESSIONS 5
 #define TT_AR_OPT_SESSION_CLOSE 6
 #define TT_AR_OPT_SESSION_SAMPLING 7
+/*   TT_AR_OPT_FUSED_QKV_ATTN [1]  the decode step's QKV projection and attention run as ONE launch where the batch is eligible (16-bit
+ *                             operands, 16 heads of 64, one or two full rounds of 16-sequence workgroups on the CUs = 256 or 512 candidates, one utterance, no sessions, the
+ *                             prefix within the LDS): tt_ar_stat(h, 2) then reports 6 launches per layer instead of 7.  Value 0 keeps the
+ *                             two launches (A/B runs); the sampled codes are the same either way. */
+#define TT_AR_OPT_FUSED_QKV_ATTN 8
 int tt_ar_set_option(tt_ar* h, int option, int value);
 /* Operand-overflow guard: the row norms and the sampler count launches that met a non-finite value (an fp16 operand beyond 65504
  * upstream).  Returns the count as of the last finished tt_ar_generate[_chunk] / tt_ar_latents (>= 0; tt_last_error() then names

@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--iterations", type=int, default=200)
     ap.add_argument("--ar-variants", default="",
                     help="';'-separated host-lookahead settings of tt_ar_set_option to time one after the other on ONE handle")
+    ap.add_argument("--qkv-variants", default="",
+                    help="';'-separated TT_AR_OPT_FUSED_QKV_ATTN values (1 = QKV projection inside the decode-attention launch, 0 = two launches) timed "
+                         "one after the other on ONE handle, e.g. '0;1;0;1;0;1'")
     ap.add_argument("--typical-variants", default="",
                     help="';'-separated typical_mass settings (0 = off) of the AR stage's sampler, timed one after the other on ONE handle, e.g. '0;0.9;0;0.9'")
     ap.add_argument("--flash-variants", default="",
@@ -60,12 +63,17 @@ def main():
             masses = [float(v) for v in args.typical_variants.split(";") if v.strip()]
             if masses:
                 variants = [("typical", m) for m in masses]
+            if args.qkv_variants.strip():
+                variants = [("qkv", int(v)) for v in args.qkv_variants.split(";") if v.strip()]
             for var in variants:
                 tag = args.tag
                 mass = 0.0
                 if var is not None and var[0] == "typical":
                     mass = var[1]
                     tag = "typical=%g" % mass
+                elif var is not None and var[0] == "qkv":
+                    ar.set_option(E.TT_AR_OPT_FUSED_QKV_ATTN, var[1])
+                    tag = "fused_qkv=%d" % var[1]
                 elif var is not None:
                     ar.set_option(E.TT_AR_OPT_LOOKAHEAD, var[0])
                     tag = "look=%d" % var[0]

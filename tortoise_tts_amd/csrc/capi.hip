@@ -211,6 +211,32 @@ int tt_op_decode_attention(int dtype, const void* q, const void* kp, const void*
   return 0;
 }
 
+// The decode step's QKV projection + attention in one launch (attention.hip decode_qkv_attn_kernel) on caller-provided caches: own keys
+// 0 .. tgen - 2 are in the caches, the launch appends slot tgen - 1 from h W^T + bias and attends [prefix | own keys 0 .. tgen - 1].
+int tt_op_decode_qkv_attention(int dtype, const void* h, const void* w_qkv, const float* b_qkv, float q_scale, const void* kp, const void* vp, int P1,
+                               void* kc, void* vc, int tmax, int tgen, void* q_out, void* out, int B, int heads, void* stream) {
+  TT_REQUIRE(h && w_qkv && kp && vp && kc && vc && out && tgen >= 1 && tgen <= tmax, "tt_op_decode_qkv_attention: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  int* step = nullptr;
+  TT_CHECK_HIP(hipMalloc((void**)&step, sizeof(int)));
+  const int newest = tgen - 1;
+  hipError_t e = hipMemcpyAsync(step, &newest, sizeof(int), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) (void)hipFree(step);  // (the step word is freed on every path)
+  TT_CHECK_HIP(e);
+  DecodeQkvAttnArgs g;
+  memset(&g, 0, sizeof(g));
+  g.d.kp = kp; g.d.vp = vp; g.d.P1 = P1; g.d.kc = kc; g.d.vc = vc; g.d.tmax = tmax; g.d.step = step; g.d.host_tgen = tgen;
+  g.d.out = out; g.d.B = B; g.d.heads = heads;
+  g.h = h; g.w_qkv = w_qkv; g.b_qkv = b_qkv; g.q_scale = q_scale; g.q_out = q_out;
+  int rc = decode_qkv_attention_launch(dtype, g, s);
+  e = hipStreamSynchronize(s);
+  (void)hipFree(step);
+  TT_TRY(rc);
+  TT_CHECK_HIP(e);
+  return 0;
+}
+
 int tt_op_decode_attention_rows(int dtype, const void* q, const void* kp, const void* vp, long long prefix_stride, const int* p1_rows, int p1_cap,
                                 const void* kc, const void* vc, int tmax, const int* slot_rows, void* out, int B, int heads, void* stream) {
   TT_REQUIRE(q && kp && vp && p1_rows && kc && vc && slot_rows && out && prefix_stride > 0 && p1_cap >= 1 && B >= 1 && heads >= 1 && tmax >= 1,

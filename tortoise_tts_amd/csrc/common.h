@@ -207,6 +207,7 @@ enum ProfId {  // one class per kernel instantiation that actually runs (names: 
   PROF_GEMM_GNA,          // GEMM with the GroupNorm apply on its A path (gemm_gna.h)
   PROF_GEMM_32x16_STD, PROF_GEMM_32x16_QKVDEC, PROF_GEMM_64x16_STD, PROF_GEMM_64x16_QKVDEC,  // skinny decode tiles (small batches)
   PROF_GEMV,              // GEMV-shaped decode GEMMs of handles with max_batch <= 4 (gemv.hip)
+  PROF_DECODE_QKV_ATTN,   // the decode step's QKV projection + attention in one launch (attention.hip decode_qkv_attn_kernel)
   PROF_COUNT
 };
 extern bool g_prof_on;

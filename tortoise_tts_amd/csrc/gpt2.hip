@@ -7,6 +7,8 @@
 //                (split-K slabs), LayerNorm (folds them), c_fc GEMM + gelu, MLP projection (slabs).  Sampling on device; the whole step
 //                is replayed from one hipGraph.  Batches of <= 64 sequences (the per-rank share of a candidate-sharded job) run their
 //                GEMMs on 16-column tiles so that the weight stream is spread over 192 - 512 workgroups (gemm_impl.h Tile).
+//                At 256 / 512 candidates (full rounds of the attention's 16-sequence workgroups) the QKV GEMM and the attention are ONE launch
+//                (attention.hip decode_qkv_attn_kernel, TT_AR_OPT_FUSED_QKV_ATTN; same bits): six launches per layer.
 //                (A five-launch form - LayerNorm folded into the GEMMs algebraically, split-K folded in-launch behind arrival tickets -
 //                was built and measured 0.7 - 10 % slower at every batch size from 16 to 256: profiles/r05_ab_ar_five_launch_step.txt,
 //                profiles/r06_ab_small_batch_decode.txt; it is not in the library.)
@@ -109,7 +111,23 @@ struct tt_ar : EngineHandle {
   int sess_sampling = 0;
   int admissions = 0;
   tt_sampling s_rows[16];
+  // TT_AR_OPT_FUSED_QKV_ATTN: the decode step's QKV projection and attention as ONE launch where the batch is eligible (ar_fused_qkv_attn)
+  int fused_qkv = 1;
+  int cu_count = 0;
 };
+
+// Whether the decode step of the current batch takes decode_qkv_attn_kernel instead of the QKV GEMM + decode attention.  Decided from the
+// handle's configuration and the batch geometry alone (what the kept graph's key holds), so that capture and eager replay agree:
+// 16-bit operands, 16 heads of 64, one or two FULL rounds of 16-sequence workgroups on the chip's CUs (256 and 512 candidates on the
+// MI355X: the batches the launch was measured ahead at; 128 candidates would need an 8-row form and 272 .. 496 run a second,
+// partly filled round - neither was measured, so they keep two launches), one prefix group, no session rows, no GEMV-shaped step, and
+// the prefix + score rows + activation rows + weight rings within the LDS.
+static bool ar_fused_qkv_attn(const tt_ar* e) {
+  if (!e->fused_qkv || e->cfg.dtype == DT_F32 || e->D != 1024 || e->H != 16 || e->G != 1 || e->sessions || e->gemv) return false;
+  const int wgs = e->B * e->H / 16;
+  if (e->B % 16 != 0 || e->cu_count < 1 || (wgs != e->cu_count && wgs != 2 * e->cu_count) || e->P1 < 1) return false;
+  return decode_qkv_attention_lds(e->P1, e->tmax) <= DECODE_LDS_CAP;
+}
 
 // rows the GEMV-shaped step of a handle serves: a wide session handle's, or the <= 4 of the others (a property of the handle)
 static inline int ar_gemv_rows(const tt_ar* e) { return e->sessions == 2 ? 16 : 4; }
@@ -260,6 +278,7 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
   float* slabs = e->slabs;
   const float* pend_bias = nullptr;
   int pend_slabs = 0;
+  const bool fused = ar_fused_qkv_attn(e);
   for (int l = 0; l < e->cfg.layers; ++l) {
     const tt_gpt_layer& w = e->L[l];
     if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln1_g, w.ln1_b, pend_bias, slabs, pend_slabs, nb, s));
@@ -311,7 +330,7 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
     g.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es);
     g.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
     g.tmax = e->tmax;
-    TT_TRY(gemm_launch(dt, EPI_QKV_DECODE, g, s));
+    if (!fused) TT_TRY(gemm_launch(dt, EPI_QKV_DECODE, g, s));
     DecodeAttnArgs a;
     memset(&a, 0, sizeof(a));
     a.q = e->q;
@@ -324,7 +343,15 @@ static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
     }
     a.P1 = e->P1; a.kc = g.kc; a.vc = g.vc; a.tmax = e->tmax; a.step = e->state + 1;
     a.out = e->attn; a.B = nb; a.heads = H; a.host_tgen = e->host_slot + 1;
-    TT_TRY(decode_attention_launch(dt, a, s));
+    if (fused) {  // one launch: the workgroups of the attention project their own q / k / v rows (e->q is not written)
+      DecodeQkvAttnArgs f;
+      memset(&f, 0, sizeof(f));
+      f.d = a;
+      f.h = e->h; f.w_qkv = w.w_qkv; f.b_qkv = w.b_qkv; f.q_scale = 0.125f;
+      TT_TRY(decode_qkv_attention_launch(dt, f, s));
+    } else {
+      TT_TRY(decode_attention_launch(dt, a, s));
+    }
     // >= 1024 sequences (several utterances per batch): one block per output tile fills the chip, so the split-K partial
     // sums are folded inside the launch in slab order (gemm.h serial_k: the same bits as slabs + row norm, without the slab traffic)
     const bool serial = nb >= 1024;
@@ -399,6 +426,10 @@ int tt_ar_create(const tt_ar_config* cfg, const tt_ar_weights* w, tt_ar** out) {
 #endif
   const int D = e->D, H = e->H;
   int rc = e->open("tt_ar_create", true);
+  {
+    int dev = 0;
+    if (!rc && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&e->cu_count, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)) e->cu_count = 0;
+  }
   e->max_rows = std::max(std::max(cfg->max_prefix, cfg->max_full_rows), cfg->max_batch);
   const size_t rows = (size_t)e->max_rows + 64;
   e->prefix_layer_elems = (size_t)H * cfg->max_prefix * 64;
@@ -652,6 +683,7 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     memcpy(key.data(), &sa, sizeof(sa));
     int geo[24] = {B, e->G, e->P1, g_prof_on ? 1 : 0};
     for (int gi = 0; gi < 16; ++gi) geo[4 + gi] = gi < e->G ? e->P1g[gi] : 0;
+    geo[20] = ar_fused_qkv_attn(e) ? 1 : 0;
     memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
     TT_TRY(e->step.ensure(s, key.data(), key.size(), "tt_ar_generate", [&]() -> int {
       TT_TRY(decode_step_enqueue(e, s, true));
@@ -968,7 +1000,7 @@ int tt_ar_guard(tt_ar* e, int reset) {
 // 2 = kernel launches of one decode step (layers + head + sampler + step counter).
 int tt_ar_stat(tt_ar* e, int which) {
   if (!e) { set_error("tt_ar_stat: null handle"); return -1; }
-  const int per_step = 7 * e->cfg.layers + 4 + (e->typical ? 1 : 0) + (e->sessions && (e->sess_launch & SAMPLE_ROWS_WIDE) ? 1 : 0);
+  const int per_step = (ar_fused_qkv_attn(e) ? 6 : 7) * e->cfg.layers + 4 + (e->typical ? 1 : 0) + (e->sessions && (e->sess_launch & SAMPLE_ROWS_WIDE) ? 1 : 0);
   int captures = e->step.captures;
   for (const KeptGraph& g : e->sess_steps) captures += g.captures;
   return which == 0 ? captures : which == 1 ? e->drains : which == 2 ? per_step : -1;
@@ -980,6 +1012,7 @@ int tt_ar_stat(tt_ar* e, int which) {
 //                                 2: the same on a wide handle of <= 16 rows
 //   TT_AR_OPT_SESSION_CLOSE       retire the session in slot `value` of a session handle
 //   TT_AR_OPT_SESSION_SAMPLING [0] 1: tt_ar_generate_chunk takes one tt_sampling per slot (session handles, before the first admission)
+//   TT_AR_OPT_FUSED_QKV_ATTN [1]  0: eligible batches keep the QKV GEMM and the decode attention as two launches (A/B runs; same codes)
 int tt_ar_set_option(tt_ar* e, int option, int value) {
   TT_REQUIRE(e != nullptr, "tt_ar_set_option: null handle");
   switch (option) {
@@ -1026,6 +1059,10 @@ int tt_ar_set_option(tt_ar* e, int option, int value) {
       memset(e->s_run, 0, sizeof(e->s_run));
       break;
     }
+    case TT_AR_OPT_FUSED_QKV_ATTN:
+      TT_REQUIRE(value == 0 || value == 1, "tt_ar_set_option: TT_AR_OPT_FUSED_QKV_ATTN takes 0 or 1 (got %d)", value);
+      e->fused_qkv = value;
+      break;
     case TT_AR_OPT_SESSION_SAMPLING:
       TT_REQUIRE(e->sessions, "tt_ar_set_option: TT_AR_OPT_SESSION_SAMPLING needs a session handle (TT_AR_OPT_SESSIONS)");
       TT_REQUIRE(value == 1 && !e->sess_sampling, "tt_ar_set_option: per-session sampling is switched on once, with value 1 (got %d)", value);

@@ -125,6 +125,22 @@ size_t decode_attention_session_lds(int p1_cap, int tmax);
 constexpr size_t DECODE_LDS_CAP = 160 * 1024;
 int decode_attn_f32_launch(const DecodeAttnArgs& a, hipStream_t stream);  // fp32 verification mode (attention_f32.hip)
 
+// The decode step's QKV projection and attention in ONE launch (attention.hip decode_qkv_attn_kernel): a workgroup = one head x 16
+// sequences computes the 16 x 192 tile of the QKV GEMM it needs itself (K = 1024), appends the new K / V rows at slot *step and
+// attends [prefix | own keys 0 .. *step].  q, k, v carry the bits of gemm_glds<.., EpiQkvDecode>, the output those of
+// decode_attn_lds_kernel.  16-bit operands, model_dim 1024, 16 heads of 64, B % 16 == 0, one prefix group, no session rows.
+struct DecodeQkvAttnArgs {
+  DecodeAttnArgs d;     // d.q is not read; d.step = slot the new key is written to (own keys 0 .. *step - 1 are already in the cache)
+  const void* h;        // [B][1024] T  LN1 rows
+  const void* w_qkv;    // [3072][1024] T
+  const float* b_qkv;   // [3072] or null
+  float q_scale;
+  void* q_out;          // [B][1024] T or null: the scaled query rows (operator-level tests; the engine does not need them)
+};
+// LDS bytes of the fused launch for this prefix length / cache capacity; it is eligible while they stay <= DECODE_LDS_CAP
+size_t decode_qkv_attention_lds(int P1, int tmax);
+int decode_qkv_attention_launch(int dtype, const DecodeQkvAttnArgs& a, hipStream_t stream);
+
 // ------------------------------------------------------------------------------ GEMV-shaped decode GEMMs (gemv.hip): M <= 16 rows
 enum GemvEpi { GEMV_F32 = 0, GEMV_RES = 1, GEMV_GELU_T = 2, GEMV_QKV = 3 };
 struct GemvArgs {

@@ -16,6 +16,7 @@ TT_AR_OPT_LOOKAHEAD = 4
 TT_AR_OPT_SESSIONS = 5
 TT_AR_OPT_SESSION_CLOSE = 6
 TT_AR_OPT_SESSION_SAMPLING = 7
+TT_AR_OPT_FUSED_QKV_ATTN = 8
 TT_DIFF_OPT_OVERLAP_PREPASS = 1
 TT_DIFF_OPT_FUSED_GN = 2
 TTX_FLASH32, TTX_GEMM_P8, TTX_VOC_MFMA, TTX_GEMM_SKINNY, TTX_AR_GEMV = 0, 1, 2, 3, 4  # ttx_kernel_variant families (include/tortoise_mi355x_test.h)
@@ -341,6 +342,7 @@ _TEST_PROTOS = {
     "tt_op_gn_gemm_workspace": (_sz, [_i, _i]),
     "tt_op_flash_attention": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp]),
     "tt_op_decode_attention": (_i, [_i, vp, vp, vp, _i, vp, vp, _i, _i, vp, _i, _i, _i, vp]),
+    "tt_op_decode_qkv_attention": (_i, [_i, vp, vp, vp, C.c_float, vp, vp, _i, vp, vp, _i, _i, vp, vp, _i, _i, vp]),
     "tt_op_decode_attention_rows": (_i, [_i, vp, vp, vp, C.c_longlong, vp, _i, vp, vp, _i, vp, vp, _i, _i, vp]),
     "tt_op_gemv": (_i, [_i, vp, vp, _i, _i, _i, vp, _i, vp, vp, vp]),
     "tt_op_gemv_ln": (_i, [_i, vp, vp, vp, _f, vp, _i, _i, vp, vp, vp]),

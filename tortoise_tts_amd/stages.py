@@ -141,7 +141,7 @@ class ArStage(_GuardedHandle):
             self._finished = [False] * max_batch
             self._codes = self._codes_buffer(max_batch, max_new_tokens)
         # A/B switches of the measurement scripts (scripts/ab_stage.py); the product default is what tt_ar_create sets
-        for env, opt in (("TT_AR_LOOKAHEAD", E.TT_AR_OPT_LOOKAHEAD),):
+        for env, opt in (("TT_AR_LOOKAHEAD", E.TT_AR_OPT_LOOKAHEAD), ("TT_AR_FUSED_QKV_ATTN", E.TT_AR_OPT_FUSED_QKV_ATTN)):
             if os.environ.get(env):
                 self.set_option(opt, int(os.environ[env]))
 
