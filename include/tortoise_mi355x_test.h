@@ -87,6 +87,72 @@ int tt_op_gemm_stat_rows(int dtype, const tt_op_gemm_desc* d);
 int tt_op_groupnorm_part(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
                          const float* gemm_part, int part_rows, int vperiod, const int* vlen, void* out_t, float* out_f32, float* workspace,
                          void* stream);
+/* Every row-norm form in one entry: the fields of csrc/ops.h RowNormArgs that a caller sets, with the same meanings and no defaults (every
+ * leading dimension is given; mode 0 none, 1 LayerNorm, 2 RMSNorm).  tt_op_rownorm_ex(dtype, d, ran, stream) passes the problem to the product
+ * dispatch unchanged.  ran (optional, int[4]) receives what launched, recorded on the host by the launch path: {kernel (0 generic, 1 narrow,
+ * 2 wave), compiled slab count of the narrow kernel or -1 (a run-time loop), BIAS, RMS (the narrow kernel's template arguments; the other
+ * kernels: add_bias set, mode == 2)}. */
+typedef struct tt_op_rownorm_desc {
+  float* x;                /* [M][ldx] f32 rows (read unless x_in; written when write_x) */
+  int ldx;
+  const float* x_in;       /* optional separate source rows [M][ldxin] */
+  int ldxin;
+  int M, D;
+  const float* add_bias;   /* [D] */
+  const float* add_slabs;  /* [nslab][M][ldslab], slab_stride floats apart */
+  int nslab;
+  size_t slab_stride;
+  int ldslab;
+  int write_x;
+  int mode;
+  const float* g1;
+  const float* b1;
+  float eps1;
+  const float* g2;         /* optional second LayerNorm on the first one's output */
+  const float* b2;
+  float eps2;
+  void* out_t;
+  int ldot;
+  float* out_f32;
+  int ldo32;
+  const int* f32_slot;     /* DEVICE int: the f32 copy goes to out_f32 + (*f32_slot + f32_slot_base) * f32_slot_stride */
+  int f32_slot_base;
+  size_t f32_slot_stride;
+  const int* f32_row_slot; /* DEVICE int [M]: row r files its f32 copy under f32_row_slot[r] (+ f32_slot_base); negative: nothing filed */
+  int row_blocks;
+  int* guard;              /* DEVICE counter of rows with a non-finite value */
+  int act;
+} tt_op_rownorm_desc;
+size_t tt_op_rownorm_desc_size(void);
+int tt_op_rownorm_ex(int dtype, const tt_op_rownorm_desc* d, int* ran, void* stream);
+/* Every GroupNorm32 form in one entry: the caller-set fields of csrc/ops.h GroupNormArgs (x f32 [B][S][C]; partial = a workspace of
+ * tt_op_groupnorm_workspace(B, S) bytes; gemm_part / part_rows = statistics a GEMM epilogue left; vperiod > 0: sample b has
+ * vlen[b % vperiod] valid rows, the rest are left out of the statistics and written as zeros).  ran (optional, int[4]): {stand-alone
+ * statistics pass ran (0 / 1), apply kernel (0 generic, 1 the C = 1024 kernel), rows per apply block, fused-statistics template of the
+ * C = 1024 kernel (0 / 1)}. */
+typedef struct tt_op_groupnorm_desc {
+  const float* x;
+  int B, S, C;
+  const float* gamma;
+  const float* beta;
+  float eps;
+  const float* scale_shift;  /* optional: y = y * (1 + scale) + shift, block b / ss_batch_div of [..][2C], ss_batch_stride floats apart (0: shared) */
+  size_t ss_batch_stride;
+  int ss_batch_div;
+  int act;
+  void* out_t;
+  int ldot;
+  float* out_f32;
+  int ldo32;
+  float* partial;
+  const float* gemm_part;
+  int part_rows;
+  int vperiod;
+  int vlen[32];
+  int* guard;                /* DEVICE counter of (workgroup, group) pairs with non-finite statistics */
+} tt_op_groupnorm_desc;
+size_t tt_op_groupnorm_desc_size(void);
+int tt_op_groupnorm_ex(int dtype, const tt_op_groupnorm_desc* d, int* ran, void* stream);
 int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms,
                     void* out_t, float* out_f32, void* stream);
 int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift,

@@ -44,17 +44,20 @@ def test_struct_mirrors_match(lib):
     for i, st in enumerate(E.BOUNDARY_STRUCTS):
         assert C.sizeof(st) == lib.tt_struct_size(i), st.__name__
     assert lib.tt_abi_version() == 6
-    # the operator-level GEMM descriptor of the test header (tt_op_gemm_ex), field by field: a reordered field keeps the size
-    assert C.sizeof(E.GemmDesc) == lib.tt_op_gemm_desc_size()
-    names = [f[0] for f in E.GemmDesc._fields_]
+    # the operator-level descriptors of the test header (tt_op_gemm_ex, tt_op_rownorm_ex, tt_op_groupnorm_ex), field by field: a reordered
+    # field keeps the size
     src = open(os.path.join(ROOT, "include", "tortoise_mi355x_test.h")).read()
-    body = re.search(r"typedef struct tt_op_gemm_desc \{(.*?)\} tt_op_gemm_desc;", src, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    declared = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        rest = re.match(r"^(?:const\s+)?\w+\s*\**\s*(.*)$", decl, flags=re.S).group(1)
-        declared += [re.sub(r"\[\d+\]", "", n).strip(" *") for n in rest.split(",")]
-    assert declared == names, (declared, names)
+    for cname, mirror, size in (("tt_op_gemm_desc", E.GemmDesc, lib.tt_op_gemm_desc_size()), ("tt_op_rownorm_desc", E.RowNormDesc, lib.tt_op_rownorm_desc_size()),
+                                ("tt_op_groupnorm_desc", E.GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
+        assert C.sizeof(mirror) == size, cname
+        names = [f[0] for f in mirror._fields_]
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        declared = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            rest = re.match(r"^(?:const\s+)?\w+\s*\**\s*(.*)$", decl, flags=re.S).group(1)
+            declared += [re.sub(r"\[\d+\]", "", n).strip(" *") for n in rest.split(",")]
+        assert declared == names, (cname, declared, names)
 
 
 def test_fails_loudly_without_gpu(lib):

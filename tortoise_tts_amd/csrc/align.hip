@@ -392,15 +392,6 @@ int tt_op_w2v_conv0(int dtype, const float* y, const float* stats, int frames, i
   return w2v_conv0_launch(dtype, y, stats, frames, k, stride, w, b, g, beta, out_t, out_f32, nullptr, (hipStream_t)stream);
 }
 
-int tt_op_layernorm_act(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int act, void* out_t, float* out_f32,
-                        void* stream) {
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = (float*)x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER; a.g1 = g; a.b1 = b; a.eps1 = eps; a.act = act;
-  a.out_t = out_t; a.ldot = D; a.out_f32 = out_f32; a.ldo32 = D;
-  return rownorm_launch(dtype, a, (hipStream_t)stream);
-}
-
 int tt_op_w2v_argmax(const float* logits, int ld, int T, int V, int* ids, float* out, void* stream) {
   return w2v_argmax_launch(logits, ld, T, V, ids, out, (hipStream_t)stream);
 }

@@ -75,24 +75,92 @@ int tt_op_gemm_segv(int dtype, const void* A, int lda, const void* W, int ldw, i
   return gemm_launch(dtype, EPI_STD, gemm_desc_args(d), (hipStream_t)stream);
 }
 
-int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms, void* out_t,
-                    float* out_f32, void* stream) {
+// the one argument mapping of the operator-level row-norm entries
+static RowNormArgs rownorm_desc_args(const tt_op_rownorm_desc& d) {
   RowNormArgs a;
   memset(&a, 0, sizeof(a));
-  a.x = (float*)x; a.ldx = D; a.M = M; a.D = D; a.mode = rms ? NORM_RMS : NORM_LAYER; a.g1 = g; a.b1 = b; a.eps1 = eps;
-  a.out_t = out_t; a.ldot = D; a.out_f32 = out_f32; a.ldo32 = D;
-  return rownorm_launch(dtype, a, (hipStream_t)stream);
+  a.x = d.x; a.ldx = d.ldx; a.x_in = d.x_in; a.ldxin = d.ldxin; a.M = d.M; a.D = d.D;
+  a.add_bias = d.add_bias; a.add_slabs = d.add_slabs; a.nslab = d.nslab; a.slab_stride = d.slab_stride; a.ldslab = d.ldslab; a.write_x = d.write_x;
+  a.mode = d.mode; a.g1 = d.g1; a.b1 = d.b1; a.eps1 = d.eps1; a.g2 = d.g2; a.b2 = d.b2; a.eps2 = d.eps2;
+  a.out_t = d.out_t; a.ldot = d.ldot; a.out_f32 = d.out_f32; a.ldo32 = d.ldo32;
+  a.f32_slot = d.f32_slot; a.f32_slot_base = d.f32_slot_base; a.f32_slot_stride = d.f32_slot_stride; a.f32_row_slot = d.f32_row_slot;
+  a.row_blocks = d.row_blocks; a.guard = d.guard; a.act = d.act;
+  return a;
+}
+
+size_t tt_op_rownorm_desc_size(void) { return sizeof(tt_op_rownorm_desc); }
+
+int tt_op_rownorm_ex(int dtype, const tt_op_rownorm_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr, "tt_op_rownorm_ex: null descriptor");
+  const int rc = rownorm_launch(dtype, rownorm_desc_args(*d), (hipStream_t)stream);
+  if (ran) {
+    ran[0] = g_rownorm_ran.kernel; ran[1] = g_rownorm_ran.nslab; ran[2] = g_rownorm_ran.bias; ran[3] = g_rownorm_ran.rms;
+  }
+  return rc;
+}
+
+static tt_op_rownorm_desc rownorm_desc_std(const float* x, int M, int D, const float* g, const float* b, float eps, void* out_t, float* out_f32) {
+  tt_op_rownorm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = (float*)x; d.ldx = D; d.M = M; d.D = D; d.mode = NORM_LAYER; d.g1 = g; d.b1 = b; d.eps1 = eps;
+  d.out_t = out_t; d.ldot = D; d.out_f32 = out_f32; d.ldo32 = D;
+  return d;
+}
+
+int tt_op_layernorm(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int rms, void* out_t,
+                    float* out_f32, void* stream) {
+  tt_op_rownorm_desc d = rownorm_desc_std(x, M, D, g, b, eps, out_t, out_f32);
+  d.mode = rms ? NORM_RMS : NORM_LAYER;
+  return tt_op_rownorm_ex(dtype, &d, nullptr, stream);
+}
+
+// row LayerNorm + activation in one launch (the wav2vec2 feature encoder's LayerNorm + GELU, csrc/align.hip)
+int tt_op_layernorm_act(int dtype, const float* x, int M, int D, const float* g, const float* b, float eps, int act, void* out_t, float* out_f32,
+                        void* stream) {
+  tt_op_rownorm_desc d = rownorm_desc_std(x, M, D, g, b, eps, out_t, out_f32);
+  d.act = act;
+  return tt_op_rownorm_ex(dtype, &d, nullptr, stream);
 }
 
 size_t tt_op_groupnorm_workspace(int B, int S) { return groupnorm_partial_floats(B, S) * sizeof(float); }
 
-int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
-                    void* out_t, float* out_f32, float* workspace, void* stream) {
+// the one argument mapping of the operator-level GroupNorm entries
+static GroupNormArgs groupnorm_desc_args(const tt_op_groupnorm_desc& d) {
   GroupNormArgs a;
   memset(&a, 0, sizeof(a));
-  a.x = x; a.B = B; a.S = S; a.C = C; a.gamma = g; a.beta = b; a.eps = 1e-5f; a.scale_shift = scale_shift;
-  a.ss_batch_stride = 2 * (size_t)C; a.act = act; a.out_t = out_t; a.ldot = C; a.out_f32 = out_f32; a.ldo32 = C; a.partial = workspace;
-  return groupnorm_launch(dtype, a, (hipStream_t)stream);
+  a.x = d.x; a.B = d.B; a.S = d.S; a.C = d.C; a.gamma = d.gamma; a.beta = d.beta; a.eps = d.eps;
+  a.scale_shift = d.scale_shift; a.ss_batch_stride = d.ss_batch_stride; a.ss_batch_div = d.ss_batch_div; a.act = d.act;
+  a.out_t = d.out_t; a.ldot = d.ldot; a.out_f32 = d.out_f32; a.ldo32 = d.ldo32; a.partial = d.partial;
+  a.gemm_part = d.gemm_part; a.part_rows = d.part_rows; a.vperiod = d.vperiod;
+  for (int i = 0; i < 32; ++i) a.vlen[i] = d.vlen[i];
+  a.guard = d.guard;
+  return a;
+}
+
+static tt_op_groupnorm_desc groupnorm_desc_std(const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
+                                               void* out_t, float* out_f32, float* workspace) {
+  tt_op_groupnorm_desc d;
+  memset(&d, 0, sizeof(d));
+  d.x = x; d.B = B; d.S = S; d.C = C; d.gamma = g; d.beta = b; d.eps = 1e-5f; d.scale_shift = scale_shift;
+  d.ss_batch_stride = 2 * (size_t)C; d.act = act; d.out_t = out_t; d.ldot = C; d.out_f32 = out_f32; d.ldo32 = C; d.partial = workspace;
+  return d;
+}
+
+size_t tt_op_groupnorm_desc_size(void) { return sizeof(tt_op_groupnorm_desc); }
+
+int tt_op_groupnorm_ex(int dtype, const tt_op_groupnorm_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr && d->vperiod >= 0 && d->vperiod <= 32, "tt_op_groupnorm_ex: null descriptor or vperiod outside 0 .. 32");
+  const int rc = groupnorm_launch(dtype, groupnorm_desc_args(*d), (hipStream_t)stream);
+  if (ran) {
+    ran[0] = g_groupnorm_ran.stats; ran[1] = g_groupnorm_ran.apply; ran[2] = g_groupnorm_ran.rows; ran[3] = g_groupnorm_ran.fused;
+  }
+  return rc;
+}
+
+int tt_op_groupnorm(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
+                    void* out_t, float* out_f32, float* workspace, void* stream) {
+  const tt_op_groupnorm_desc d = groupnorm_desc_std(x, B, S, C, g, b, scale_shift, act, out_t, out_f32, workspace);
+  return tt_op_groupnorm_ex(dtype, &d, nullptr, stream);
 }
 
 int tt_op_groupnorm_part(int dtype, const float* x, int B, int S, int C, const float* g, const float* b, const float* scale_shift, int act,
@@ -100,13 +168,10 @@ int tt_op_groupnorm_part(int dtype, const float* x, int B, int S, int C, const f
                          void* stream) {
   TT_REQUIRE(gemm_part != nullptr && vperiod >= 0 && vperiod <= 32 && (vperiod == 0 || vlen != nullptr), "tt_op_groupnorm_part: bad arguments");
   for (int i = 0; i < vperiod; ++i) TT_REQUIRE(vlen[i] > 0 && vlen[i] <= S, "tt_op_groupnorm_part: vlen[%d] = %d outside 1 .. S = %d", i, vlen[i], S);
-  GroupNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.B = B; a.S = S; a.C = C; a.gamma = g; a.beta = b; a.eps = 1e-5f; a.scale_shift = scale_shift;
-  a.ss_batch_stride = 2 * (size_t)C; a.act = act; a.out_t = out_t; a.ldot = C; a.out_f32 = out_f32; a.ldo32 = C; a.partial = workspace;
-  a.gemm_part = gemm_part; a.part_rows = part_rows; a.vperiod = vperiod;
-  for (int i = 0; i < vperiod; ++i) a.vlen[i] = vlen[i];
-  return groupnorm_launch(dtype, a, (hipStream_t)stream);
+  tt_op_groupnorm_desc d = groupnorm_desc_std(x, B, S, C, g, b, scale_shift, act, out_t, out_f32, workspace);
+  d.gemm_part = gemm_part; d.part_rows = part_rows; d.vperiod = vperiod;
+  for (int i = 0; i < vperiod; ++i) d.vlen[i] = vlen[i];
+  return tt_op_groupnorm_ex(dtype, &d, nullptr, stream);
 }
 
 // Test entry of the fused in_layers launch (gemm_gna.h): out_f32[B*S][N] = Linear(act(GroupNorm32(x)))(W, bias) for x f32 [B][S][1024].

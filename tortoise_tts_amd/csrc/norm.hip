@@ -6,6 +6,9 @@
 
 namespace tt {
 
+thread_local RowNormRan g_rownorm_ran = {-1, -1, 0, 0};
+thread_local GroupNormRan g_groupnorm_ran = {0, -1, 0, 0};
+
 // ------------------------------------------------------------------------------- row norm
 // One 256-thread block per row, D <= 4096, D % 4 == 0.
 template <typename T, int NSLAB>
@@ -189,6 +192,7 @@ template <typename T, int NSLAB>
 static void rownorm_narrow_dispatch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
   const bool bias = a.add_bias != nullptr, rms = a.mode == NORM_RMS;
   const int grid = a.M;
+  g_rownorm_ran = RowNormRan{1, NSLAB, bias ? 1 : 0, rms ? 1 : 0};
   if (bias && rms) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, true, true>, dim3(grid), dim3(256), 0, stream, a);
   else if (bias) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, true, false>, dim3(grid), dim3(256), 0, stream, a);
   else if (rms) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, false, true>, dim3(grid), dim3(256), 0, stream, a);
@@ -315,8 +319,11 @@ int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream) {
   TT_REQUIRE(a.ldx % 4 == 0, "rownorm: ldx must be a multiple of 4");
   TT_REQUIRE(a.act == ACT_NONE || a.mode == NORM_LAYER, "rownorm: a post-norm activation needs the LayerNorm mode");
   ProfScope ps(PROF_ROWNORM, stream, 0.0, (double)a.M * a.D * (4.0 * (1 + a.nslab + (a.write_x ? 1 : 0)) + (a.out_t ? 2.0 : 0.0) + (a.out_f32 ? 4.0 : 0.0)), true);
-  // few rows (decode): one block per row keeps 4x more loads in flight; many rows: wave per row, no barriers
-  if (a.D <= 1024 && a.M >= 1024 && !a.row_blocks) {
+  // few rows (decode): one block per row keeps 4x more loads in flight; many rows: wave per row, no barriers (that kernel has no
+  // f32 slots: a problem that files its f32 copy under a counter stays on the generic kernel)
+  g_rownorm_ran = RowNormRan{0, -1, a.add_bias ? 1 : 0, a.mode == NORM_RMS ? 1 : 0};
+  if (a.D <= 1024 && a.M >= 1024 && !a.row_blocks && !a.f32_slot && !a.f32_row_slot) {
+    g_rownorm_ran.kernel = 2;
     TT_DISPATCH_T(dtype, T, launch_timed(ps, rownorm_wave_kernel<T>, dim3(cdiv(a.M, 4)), dim3(256), 0, stream, a));
   } else {
     bool narrow = false;
@@ -604,6 +611,7 @@ int groupnorm_launch(int dtype, const GroupNormArgs& a0, hipStream_t stream) {
   const bool few = a.C == 1024 && (long)a.B * a.S <= 4096;
   const int rpb = few ? 2 : GN_APPLY_ROWS;  // apply is pure streaming: many small blocks
   dim3 grid2(cdiv(a.S, rpb), a.B);
+  g_groupnorm_ran = GroupNormRan{a.gemm_part ? 0 : 1, a.C == 1024 ? 1 : 0, rpb, a.C == 1024 && a.gemm_part ? 1 : 0};
   if (a.C == 1024) {
     const int variant = (dtype == DT_BF16 ? 0 : dtype == DT_F16 ? 4 : 8) + (a.gemm_part ? 2 : 0) + (a.scale_shift ? 1 : 0);
 #define TT_GN(T, F, SSV)                                                                                              \

@@ -45,6 +45,11 @@ struct RowNormArgs {
                        // feature encoder's LayerNorm + GELU, csrc/align.hip)
 };
 int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream);
+// What the last rownorm_launch of this thread started, recorded on the host (as g_gemm_ran; the operator-level tests assert it):
+// kernel 0 generic, 1 narrow, 2 wave; nslab = the compiled slab count of the narrow kernel, -1 where the count is a run-time loop;
+// bias / rms = the narrow kernel's template arguments (the other kernels: whether add_bias is set / the mode is NORM_RMS)
+struct RowNormRan { int kernel, nslab, bias, rms; };
+extern thread_local RowNormRan g_rownorm_ran;  // norm.hip
 
 // ------------------------------------------------------------------------------ group norm
 struct GroupNormArgs {
@@ -74,6 +79,10 @@ struct GroupNormArgs {
   int* guard;  // optional device counter: += 1 per (workgroup, group) whose statistics came out non-finite (operand-overflow guard)
 };
 int groupnorm_launch(int dtype, const GroupNormArgs& a, hipStream_t stream);
+// What the last groupnorm_launch of this thread started: stats = the stand-alone statistics pass ran; apply 0 generic, 1 the C == 1024
+// kernel; rows = rows per apply block; fused = the C == 1024 kernel's fused-statistics template
+struct GroupNormRan { int stats, apply, rows, fused; };
+extern thread_local GroupNormRan g_groupnorm_ran;  // norm.hip
 size_t groupnorm_partial_floats(int B, int S);
 
 // ------------------------------------------------------------------------------ attention

@@ -208,6 +208,28 @@ class GemmDesc(C.Structure):
         (n, vp) for n in ("q", "k", "v", "vt", "step", "qbuf", "kc", "vc")]
 
 
+class RowNormDesc(C.Structure):
+    """tt_op_rownorm_desc (include/tortoise_mi355x_test.h): every row-norm form of the operator-level test entry tt_op_rownorm_ex."""
+    _fields_ = [("x", vp), ("ldx", C.c_int), ("x_in", vp), ("ldxin", C.c_int), ("M", C.c_int), ("D", C.c_int), ("add_bias", vp), ("add_slabs", vp),
+                ("nslab", C.c_int), ("slab_stride", C.c_size_t), ("ldslab", C.c_int), ("write_x", C.c_int), ("mode", C.c_int), ("g1", vp), ("b1", vp),
+                ("eps1", C.c_float), ("g2", vp), ("b2", vp), ("eps2", C.c_float), ("out_t", vp), ("ldot", C.c_int), ("out_f32", vp), ("ldo32", C.c_int),
+                ("f32_slot", vp), ("f32_slot_base", C.c_int), ("f32_slot_stride", C.c_size_t), ("f32_row_slot", vp), ("row_blocks", C.c_int),
+                ("guard", vp), ("act", C.c_int)]
+
+
+class GroupNormDesc(C.Structure):
+    """tt_op_groupnorm_desc (include/tortoise_mi355x_test.h): every GroupNorm32 form of the operator-level test entry tt_op_groupnorm_ex."""
+    _fields_ = [("x", vp), ("B", C.c_int), ("S", C.c_int), ("C", C.c_int), ("gamma", vp), ("beta", vp), ("eps", C.c_float), ("scale_shift", vp),
+                ("ss_batch_stride", C.c_size_t), ("ss_batch_div", C.c_int), ("act", C.c_int), ("out_t", vp), ("ldot", C.c_int), ("out_f32", vp),
+                ("ldo32", C.c_int), ("partial", vp), ("gemm_part", vp), ("part_rows", C.c_int), ("vperiod", C.c_int), ("vlen", C.c_int * 32),
+                ("guard", vp)]
+
+
+# tt_op_rownorm_ex / tt_op_groupnorm_ex `ran` records (csrc/ops.h RowNormRan, GroupNormRan)
+NORM_NONE, NORM_LAYER, NORM_RMS = 0, 1, 2
+ROWNORM_KERNELS = {0: "generic", 1: "narrow", 2: "wave"}
+GROUPNORM_APPLY = {0: "generic", 1: "c1024"}
+
 # tt_op_gemm_ex `ran` record: tiles (gemm_impl.h Tile) and standard-epilogue variants (StdVariant)
 GEMM_TILES = {0: "64x64", 1: "128x64", 2: "128x128", 3: "256x256", 4: "32x16", 5: "64x16"}
 GEMM_VARIANTS = {-1: "-", 0: "V_GEN", 1: "V_NONE", 2: "V_SLAB", 3: "V_GELU_T", 4: "V_ST_F32", 5: "V_ST_RES", 6: "V_ST_A2", 7: "V_BIAS_T", 8: "V_SERIAL"}
@@ -334,6 +356,10 @@ _TEST_PROTOS = {
     "tt_op_gemm_desc_size": (_sz, []),
     "tt_op_gemm_ex": (_i, [_i, _i, C.POINTER(GemmDesc), C.POINTER(_i), vp]),
     "tt_op_gemm_stat_rows": (_i, [_i, C.POINTER(GemmDesc)]),
+    "tt_op_rownorm_desc_size": (_sz, []),
+    "tt_op_rownorm_ex": (_i, [_i, C.POINTER(RowNormDesc), C.POINTER(_i), vp]),
+    "tt_op_groupnorm_desc_size": (_sz, []),
+    "tt_op_groupnorm_ex": (_i, [_i, C.POINTER(GroupNormDesc), C.POINTER(_i), vp]),
     "tt_op_groupnorm_part": (_i, [_i, vp, _i, _i, _i, vp, vp, vp, _i, vp, _i, _i, C.POINTER(_i), vp, vp, vp, vp]),
     "tt_op_layernorm": (_i, [_i, vp, _i, _i, vp, vp, _f, _i, vp, vp, vp]),
     "tt_op_groupnorm": (_i, [_i, vp, _i, _i, _i, vp, vp, vp, _i, vp, vp, vp, vp]),
@@ -405,8 +431,9 @@ def load_library():
         want = lib.tt_cls_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
-    if C.sizeof(GemmDesc) != lib.tt_op_gemm_desc_size():
-        raise EngineError("ABI mismatch: GemmDesc is %d bytes in Python, %d in the library" % (C.sizeof(GemmDesc), lib.tt_op_gemm_desc_size()))
+    for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     _lib = lib
     return lib
 
