@@ -250,8 +250,9 @@ class TextToSpeech(_Common):
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, max_candidates=256, configs=None, max_mel_tokens=500, max_text_tokens=402,
-                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1):
+                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1, mel_front_end="torch"):
         self.models_dir = models_dir
+        self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option; the MI355X engine "
                                       "always runs its own fused HIP path")
@@ -485,9 +486,18 @@ class TextToSpeech(_Common):
             self.conditioning = stages.ConditioningStage(self._sd("autoregressive"), self._sd("diffusion"), self.ar_cfg, self.diff_cfg,
                                                          self.device, self.dtype)
         auto_mels, diff_mels = [], []
+        device_mels = None
+        if self.mel_front_end_kind == "device":  # every waveform entry in one ragged call per mel (stages.MelFrontStage)
+            waves = [vs for vs in voice_samples if torch.is_tensor(vs)]
+            if waves:
+                if self.mel_front_end is None:
+                    self.mel_front_end = stages.MelFrontStage(self.models_dir, device=self.device)
+                device_mels = iter(self.mel_front_end.many(waves))
         for vs in voice_samples:
             if isinstance(vs, (tuple, list)) and len(vs) == 2:
                 am, dm = vs
+            elif torch.is_tensor(vs) and device_mels is not None:
+                am, dm = next(device_mels)
             elif torch.is_tensor(vs):
                 if self.mel_front_end is None:
                     from .audio import MelFrontEnd

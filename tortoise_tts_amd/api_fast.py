@@ -68,8 +68,9 @@ class TextToSpeech(_Common):
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1,
-                 per_session_sampling=False, wide_sessions=False):
+                 per_session_sampling=False, wide_sessions=False, mel_front_end="torch"):
         self.models_dir = models_dir
+        self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option")
         self.enable_redaction = bool(enable_redaction)
@@ -135,10 +136,22 @@ class TextToSpeech(_Common):
             voice_samples = [voice_samples]
         if self.conditioning is None:
             self.conditioning = stages.ConditioningStage(self._sd("autoregressive"), None, self.ar_cfg, None, self.device, self.dtype)
+        def ready(vs):
+            return torch.is_tensor(vs) and vs.dim() >= 2 and vs.shape[-2] == 80
+
         mels = []
+        device_mels = None
+        if self.mel_front_end_kind == "device":  # every waveform entry in one ragged call (stages.MelFrontStage; no diffusion mel here)
+            waves = [vs for vs in voice_samples if not ready(vs)]
+            if waves:
+                if self.mel_front_end is None:
+                    self.mel_front_end = stages.MelFrontStage(self.models_dir, device=self.device)
+                device_mels = iter(self.mel_front_end.auto_many(waves))
         for vs in voice_samples:
-            if torch.is_tensor(vs) and vs.dim() >= 2 and vs.shape[-2] == 80:
+            if ready(vs):
                 mels.append(vs.reshape(1, 80, vs.shape[-1]))
+            elif device_mels is not None:
+                mels.append(next(device_mels))
             else:
                 if self.mel_front_end is None:
                     from .audio import MelFrontEnd

@@ -78,12 +78,9 @@ def pad_or_truncate(t, length):
     return t[..., :length]
 
 
-def resample_sinc(wav, orig_freq=22050, new_freq=24000, lowpass_filter_width=6, rolloff=0.99):
-    """torchaudio.functional.resample (sinc_interp_hann): polyphase windowed-sinc kernel, one filter per output phase."""
-    g = math.gcd(int(orig_freq), int(new_freq))
-    orig, new = int(orig_freq) // g, int(new_freq) // g
-    if orig == new:
-        return wav
+def resample_taps(orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """The polyphase kernel of torchaudio.functional.resample (sinc_interp_hann) for the rates orig -> new (already divided by their gcd):
+    (fp64 taps [new, 2 * width + orig], width); output n * new + p is taps[p] over the input from n * orig - width on."""
     base = min(orig, new) * rolloff
     width = math.ceil(lowpass_filter_width * orig / base)
     idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
@@ -92,7 +89,17 @@ def resample_sinc(wav, orig_freq=22050, new_freq=24000, lowpass_filter_width=6, 
     window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
     t = t * math.pi
     kern = torch.where(t == 0, torch.ones_like(t), torch.sin(t) / t) * window * (base / orig)
-    kern = kern.to(dtype=wav.dtype, device=wav.device)
+    return kern.reshape(new, 2 * width + orig), width
+
+
+def resample_sinc(wav, orig_freq=22050, new_freq=24000, lowpass_filter_width=6, rolloff=0.99):
+    """torchaudio.functional.resample (sinc_interp_hann): polyphase windowed-sinc kernel, one filter per output phase."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    if orig == new:
+        return wav
+    kern, width = resample_taps(orig, new, lowpass_filter_width, rolloff)
+    kern = kern[:, None, :].to(dtype=wav.dtype, device=wav.device)
     shape = wav.shape
     x = wav.reshape(-1, 1, shape[-1])
     x = F.pad(x, (width, width + orig))

@@ -197,6 +197,21 @@ class ClsWeights(C.Structure):
 # include/tortoise_mi355x_classify.h, order == tt_cls_struct_size(which)
 CLASSIFY_STRUCTS = [ClsConfig, ClsWeights]
 
+MEL_MAX_CLIPS = 16
+
+
+class MelConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_fft", "hop", "n_mels", "bins_pad", "power", "clamp_input")] + [("floor", C.c_float)] + [
+        (n, C.c_int) for n in ("max_samples", "max_clips")]
+
+
+class MelTables(C.Structure):
+    _fields_ = [(n, vp) for n in ("basis", "fb", "scale")]
+
+
+# include/tortoise_mi355x_mel.h, order == tt_mel_struct_size(which)
+MEL_STRUCTS = [MelConfig, MelTables]
+
 class GemmDesc(C.Structure):
     """tt_op_gemm_desc (include/tortoise_mi355x_test.h): every GEMM form of the operator-level test entry tt_op_gemm_ex."""
     _fields_ = [("A", vp), ("W", vp), ("A2", vp), ("a2_slot", vp), ("a2_slot_stride", C.c_size_t)] + [
@@ -334,6 +349,21 @@ _CLASSIFY_PROTOS = {
     "tt_cls_run": (_i, [vp, vp, _i, vp, vp, vp]),
     "tt_cls_guard": (_i, [vp, _i]),
 }
+# include/tortoise_mi355x_mel.h: the mel front-end of the voice_samples path (its own header and version, same library)
+_ll = C.c_longlong
+_MEL_PROTOS = {
+    "tt_mel_abi_version": (_i, []),
+    "tt_mel_struct_size": (_sz, [_i]),
+    "tt_mel_create": (_i, [C.POINTER(MelConfig), C.POINTER(MelTables), C.POINTER(vp)]),
+    "tt_mel_destroy": (None, [vp]),
+    "tt_mel_frames": (_i, [vp, _i]),
+    "tt_mel_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
+    "tt_mel_spectrum": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
+    "tt_mel_resampler_create": (_i, [vp, _i, _i, _i, _i, C.POINTER(vp)]),
+    "tt_mel_resampler_destroy": (None, [vp]),
+    "tt_mel_resampled_length": (_i, [vp, _i]),
+    "tt_mel_resample": (_i, [vp, vp, _i, vp, vp]),
+}
 # include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
 _HIFI_PROTOS = {
     "tt_hifi_batch_abi_version": (_i, []),
@@ -407,7 +437,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -429,6 +459,10 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for i, st in enumerate(CLASSIFY_STRUCTS):
         want = lib.tt_cls_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(MEL_STRUCTS):
+        want = lib.tt_mel_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):

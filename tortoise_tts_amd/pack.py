@@ -535,3 +535,46 @@ def pack_classifier(sd, device, dtype, cfg: ClassifierConfig = ClassifierConfig(
     w.w_head, w.b_head = _p(h.f32(sd["head.weight"])), _p(h.f32(sd["head.bias"]))
     h.weights = w
     return h
+
+
+# ----------------------------------------------------------------------------------------- mel front-end (voice_samples path)
+MEL_N_FFT, MEL_HOP, MEL_BINS_PAD = 1024, 256, 544  # 513 bins padded to a multiple of 32 (include/tortoise_mi355x_mel.h)
+
+
+def stft_basis(n_fft=MEL_N_FFT, bins_pad=MEL_BINS_PAD):
+    """The windowed DFT basis of tt_mel_tables in fp64: [n_fft][2 * bins_pad], column 2 b = hann[k] cos(2 pi b k / n_fft), column 2 b + 1 =
+    -hann[k] sin(2 pi b k / n_fft) (periodic Hann window), zero for b > n_fft / 2.  The phase is reduced mod n_fft in integers first."""
+    k = torch.arange(n_fft, dtype=torch.int64)[:, None]
+    b = torch.arange(n_fft // 2 + 1, dtype=torch.int64)[None, :]
+    ang = ((k * b) % n_fft).double() * (2.0 * math.pi / n_fft)
+    win = 0.5 - 0.5 * torch.cos(torch.arange(n_fft, dtype=torch.float64) * (2.0 * math.pi / n_fft))
+    basis = torch.zeros(n_fft, bins_pad, 2, dtype=torch.float64)
+    basis[:, :n_fft // 2 + 1, 0] = win[:, None] * torch.cos(ang)
+    basis[:, :n_fft // 2 + 1, 1] = -win[:, None] * torch.sin(ang)
+    return basis.reshape(n_fft, 2 * bins_pad)
+
+
+def padded_filterbank(fb, bins_pad=MEL_BINS_PAD):
+    """[n_mels][n_bins] -> f32 [n_mels][bins_pad], zero beyond the last bin."""
+    out = torch.zeros(fb.shape[0], bins_pad, dtype=torch.float32)
+    out[:, :fb.shape[1]] = fb.float()
+    return out
+
+
+def melfront_tables(mel_norms):
+    """Host tables of the device mel front-end, each computed in fp64 and rounded once to f32 (the filter banks are audio.mel_filterbank's
+    own f32 values): {'basis', 'fb_auto', 'fb_diff', 'scale_auto' = 1 / mel_norms, 'taps' (147 -> 160, width 7), 'width'}."""
+    from . import audio
+    taps, width = audio.resample_taps(147, 160)
+    return {"basis": stft_basis().float(),
+            "fb_auto": padded_filterbank(audio.mel_filterbank(22050, MEL_N_FFT, 80, 0.0, 8000.0, htk=True)),
+            "fb_diff": padded_filterbank(audio.mel_filterbank(24000, MEL_N_FFT, 100, 0.0, 12000.0, htk=False)),
+            "scale_auto": (1.0 / torch.as_tensor(mel_norms).double().reshape(-1)).float(),
+            "taps": taps.float(), "width": width}
+
+
+def pack_melfront(mel_norms, device):
+    """-> (Holder, {name: device tensor}) of melfront_tables."""
+    h = Holder(device, E.TT_F32)
+    t = melfront_tables(mel_norms)
+    return h, {k: (h.f32(v) if torch.is_tensor(v) else v) for k, v in t.items()}

@@ -733,6 +733,139 @@ class ConditioningStage(_Handle):
         return (acc / total)[None]
 
 
+def mel_front_end_kind(value):
+    """The mel_front_end= argument of the TextToSpeech classes: 'torch' (audio.MelFrontEnd, the default) or 'device' (MelFrontStage)."""
+    if value not in ("torch", "device"):
+        raise ValueError(f"mel_front_end={value!r}: 'torch' (audio.MelFrontEnd) or 'device' (stages.MelFrontStage)")
+    return value
+
+
+class MelFrontStage:
+    """The wav -> mel front-end of the voice_samples path (api.py:271-287) on the device (csrc/melfront.hip, include/tortoise_mi355x_mel.h):
+    what audio.MelFrontEnd computes through torch.stft / F.conv1d / torch.matmul.  Two tt_mel handles - the autoregressive mel (80 HTK mels
+    of the 22.05 kHz clip, power spectrum, log / mel_norms) and the diffusion mel (100 Slaney mels of the clip resampled to 24 kHz and
+    clamped, magnitude spectrum, log) - and one 147 -> 160 resampler.  Pad, crop, pad-or-truncate and the random crop start stay on the
+    host exactly as audio.MelFrontEnd does them, so a caller's RNG stream is consumed identically on both paths.  The log mel is multiplied
+    by the f32 reciprocal of mel_norms where the reference divides: one more rounding (2^-24 relative) than audio.MelFrontEnd."""
+
+    def __init__(self, models_dir=None, mel_norms=None, device="cuda", max_clips=E.MEL_MAX_CLIPS):
+        from . import audio
+        if mel_norms is None:  # (before the library: a missing file is reported on any machine)
+            path = audio.find_mel_norms(models_dir)
+            if path is None:
+                raise FileNotFoundError("mel_norms.pth (tortoise/data/, arch_util.py:290) was not found: pass models_dir= or mel_norms=, "
+                                        "or give get_conditioning_latents ready (auto_mel, diffusion_mel) pairs")
+            mel_norms = torch.load(path, map_location="cpu")
+        self.mel_norms = torch.as_tensor(mel_norms).float()
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_clips = int(max_clips)
+        self.holder, self.t = pack.pack_melfront(self.mel_norms, self.device)
+        self.auto_samples, self.diff_samples = audio.AUTO_COND_SAMPLES, audio.DIFF_COND_SAMPLES
+        self.h_auto, self.h_diff, self.h_rs = E.vp(), E.vp(), E.vp()
+        self.h_auto = self._mel_handle(80, 2, 0, self.t["fb_auto"], self.t["scale_auto"], self.auto_samples)
+        self.h_diff = self._mel_handle(100, 1, 1, self.t["fb_diff"], None, self.diff_samples)
+        taps = self.t["taps"]
+        self.rs_new, self.rs_orig, self.rs_width = taps.shape[0], taps.shape[1] - 2 * self.t["width"], self.t["width"]
+        # output j < diff_samples reads no input beyond (diff_samples / new) * orig + taps: a longer clip is cut there before the resampler
+        self.rs_max_in = -(-self.diff_samples // self.rs_new) * self.rs_orig + taps.shape[1]
+        E.check(self.lib.tt_mel_resampler_create(E.ptr(taps), self.rs_orig, self.rs_new, self.rs_width, self.rs_max_in, C.byref(self.h_rs)))
+
+    def _mel_handle(self, n_mels, power, clamp, fb, scale, max_samples):
+        c = E.MelConfig()
+        c.n_fft, c.hop, c.n_mels, c.bins_pad, c.power, c.clamp_input = pack.MEL_N_FFT, pack.MEL_HOP, n_mels, pack.MEL_BINS_PAD, power, clamp
+        c.floor, c.max_samples, c.max_clips = 1e-5, max_samples, self.max_clips
+        t = E.MelTables()
+        t.basis, t.fb, t.scale = E.ptr(self.t["basis"]), E.ptr(fb), E.ptr(scale)
+        h = E.vp()
+        E.check(self.lib.tt_mel_create(C.byref(c), C.byref(t), C.byref(h)))
+        return h
+
+    def close(self):
+        if self.h_auto:
+            self.lib.tt_mel_destroy(self.h_auto)
+        if self.h_diff:
+            self.lib.tt_mel_destroy(self.h_diff)
+        if self.h_rs:
+            self.lib.tt_mel_resampler_destroy(self.h_rs)
+        self.h_auto, self.h_diff, self.h_rs = E.vp(), E.vp(), E.vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _auto_clip(self, clip, start=None):
+        """format_conditioning's pad / crop (audio.MelFrontEnd.auto_mel): -> f32 [auto_samples] on the device."""
+        clip = clip.float().reshape(1, -1)
+        gap = clip.shape[-1] - self.auto_samples
+        if gap < 0:
+            clip = F.pad(clip, (0, -gap))
+        elif gap > 0:
+            s = int(torch.randint(0, gap + 1, (1,))) if start is None else int(start)
+            clip = clip[:, s:s + self.auto_samples]
+        return clip.reshape(-1).to(self.device).contiguous()
+
+    def resample(self, clip):
+        """f32 [n] at 22.05 kHz -> f32 [ceil(160 n / 147)] at 24 kHz (torchaudio.functional.resample) on the device."""
+        x = clip.float().reshape(-1).to(self.device).contiguous()
+        n = x.shape[0]
+        if not 1 <= n <= self.rs_max_in:
+            raise ValueError(f"a clip of {n} samples is outside the resampler's range (1 .. {self.rs_max_in})")
+        out = torch.empty(self.lib.tt_mel_resampled_length(self.h_rs, n), device=self.device, dtype=torch.float32)
+        E.check(self.lib.tt_mel_resample(self.h_rs, E.ptr(x), n, E.ptr(out), E.stream_ptr()))
+        return out
+
+    def _diff_clip(self, clip):
+        """resample 22050 -> 24000, pad or truncate (audio.MelFrontEnd.diffusion_mel): -> f32 [diff_samples] on the device."""
+        from .audio import pad_or_truncate
+        x = clip.float().reshape(-1)
+        if x.shape[0] < 1:
+            raise ValueError("an empty clip has no mel spectrogram")
+        return pad_or_truncate(self.resample(x[:self.rs_max_in]), self.diff_samples)
+
+    def _run(self, h, n_mels, clips):
+        """clips: equally prepared f32 device vectors -> [1, n_mels, T] each, max_clips of them per ragged call."""
+        out = []
+        for i in range(0, len(clips), self.max_clips):
+            part = clips[i:i + self.max_clips]
+            k = len(part)
+            wav = torch.cat(part) if k > 1 else part[0]
+            lens = [int(p.shape[0]) for p in part]
+            frames = [self.lib.tt_mel_frames(h, n) for n in lens]
+            offs, ooffs, a, b = [], [], 0, 0
+            for n, T in zip(lens, frames):
+                offs.append(a)
+                ooffs.append(b)
+                a, b = a + n, b + n_mels * T
+            mel = torch.empty(b, device=self.device, dtype=torch.float32)
+            E.check(self.lib.tt_mel_run(h, E.ptr(wav), (C.c_longlong * k)(*offs), (C.c_int * k)(*lens), k, E.ptr(mel), (C.c_longlong * k)(*ooffs),
+                                        E.stream_ptr()))
+            out += [mel[o:o + n_mels * T].reshape(1, n_mels, T) for o, T in zip(ooffs, frames)]
+        return out
+
+    def auto_many(self, clips):
+        """-> [auto_mel f32 [1, 80, 517]] of every clip, one ragged call (the fast path needs no diffusion mel)."""
+        return self._run(self.h_auto, 80, [self._auto_clip(c) for c in clips])
+
+    def many(self, clips):
+        """-> [(auto_mel f32 [1, 80, 517], diffusion_mel f32 [1, 100, 401])] of every clip: one ragged call per handle."""
+        clips = list(clips)
+        auto = self._run(self.h_auto, 80, [self._auto_clip(c) for c in clips])
+        diff = self._run(self.h_diff, 100, [self._diff_clip(c) for c in clips])
+        return list(zip(auto, diff))
+
+    def auto_mel(self, clip, start=None):
+        return self._run(self.h_auto, 80, [self._auto_clip(clip, start)])[0]
+
+    def diffusion_mel(self, clip):
+        return self._run(self.h_diff, 100, [self._diff_clip(clip)])[0]
+
+    def __call__(self, clip):
+        return self.many([clip])[0]
+
+
 class RandomLatentStage:
     """get_random_conditioning_latents (api.py:301-309): the two RandomLatentConverter MLPs as six M = 1 GEMMs each.
     EqualLinear's constants are folded at pack time: leaky_relu is positively homogeneous, so
