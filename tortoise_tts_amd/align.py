@@ -7,6 +7,7 @@ import glob
 import json
 import math
 import os
+from dataclasses import dataclass, field
 
 import torch
 
@@ -317,3 +318,137 @@ def redact(audio, text, frame_ids_fn, tokenizer):
     S = audio.shape[-1]
     al = alignments_from_frames(frame_ids_fn(audio), tokenizer, bare, S)
     return torch.cat([audio[:, al[a]:al[b]] for a, b in keep], dim=-1)
+
+
+# ----------------------------------------------------------------------------------------- forced alignment (word timings)
+# The CTC Viterbi alignment of the text with the model's logits (stages.CtcAlignStage, csrc/ctc_align.hip) gives every character of the text
+# a first and a last frame and a confidence.  What follows is its host side: text -> target ids, frames -> samples, characters -> words.
+# The text is taken as it is spoken: numbers and abbreviations are NOT expanded here ("23" has no alignable character); callers pass
+# spoken-form text.
+class AlignmentTargets:
+    """ids: the CTC target; chars: its characters as the text has them (' ' for the word delimiter); index[i]: the target position text[i]
+    belongs to - its own when the character is part of the target, else that of the last kept character before it (-1: none)."""
+
+    def __init__(self, text, ids, chars, index, kept):
+        self.text, self.ids, self.chars, self.index, self.kept = text, ids, chars, index, kept
+
+
+def blank_id(tokenizer):
+    return tokenizer.encoder[tokenizer.pad]
+
+
+def alignment_targets(text, tokenizer):
+    """The text as the aligner's CTC target: case as the tokenizer has it, spaces -> the word delimiter (runs collapse, none at either end),
+    characters outside the vocabulary (punctuation the model does not spell, digits) dropped."""
+    cased = text.upper() if tokenizer.do_lower_case else text
+    enc, special = tokenizer.encoder, {tokenizer.pad, tokenizer.unk}
+    delim = enc.get(tokenizer.delim)
+    ids, chars, index, kept = [], [], [], []
+    for ch, orig in zip(cased, text):
+        tok = None
+        if ch.isspace():
+            if delim is not None and ids and ids[-1] != delim:
+                tok = delim
+                orig = " "
+        elif ch in enc and ch not in special and ch != tokenizer.delim:
+            tok = enc[ch]
+        if tok is not None:
+            ids.append(tok)
+            chars.append(orig)
+        kept.append(tok is not None)
+        index.append(len(ids) - 1)
+    if ids and ids[-1] == delim:  # a trailing delimiter: its text position falls back to the character before it
+        ids.pop()
+        chars.pop()
+        last = len(ids) - 1
+        for i in range(len(index)):
+            if index[i] > last:
+                index[i], kept[i] = last, False
+    return AlignmentTargets(text, ids, chars, index, kept)
+
+
+def frame_samples(fields):
+    """24 kHz samples one frame of the model covers: the feature encoder's total stride at 16 kHz, times 3 / 2."""
+    return math.prod(fields["conv_stride"]) * ORIG_SR // NEW_SR
+
+
+@dataclass
+class Alignment:
+    """Where a text is spoken in a clip of `samples` 24 kHz samples.  chars: (character, start_sample, end_sample, confidence) of every
+    character of the CTC target (' ' between words); words: (word, start_sample, end_sample, confidence) of every whitespace-separated word
+    of the text, confidence = the minimum over its characters (NaN and an empty span for a word with no alignable character).  Frames the
+    path spends in blanks belong to nobody: they are the pauses.  score: the path's log-probability."""
+    text: str
+    chars: list
+    words: list
+    score: float
+    samples: int
+    index: list = field(default_factory=list)  # text position -> position in chars (AlignmentTargets.index)
+    kept: list = field(default_factory=list)
+
+    def seconds(self, rate=ORIG_SR):
+        """words with their times in seconds: (word, start_s, end_s, confidence)."""
+        return [(w, a / rate, b / rate, c) for w, a, b, c in self.words]
+
+    def char_start(self, i):
+        """Sample where text[i] starts; a character that is not part of the target sits at the end of the last one before it that is."""
+        j = self.index[i]
+        return 0 if j < 0 else self.chars[j][1] if self.kept[i] else self.chars[j][2]
+
+    def char_end(self, i):
+        j = self.index[i]
+        return 0 if j < 0 else self.chars[j][2]
+
+    def to_srt(self, max_chars=42, rate=ORIG_SR):
+        """SubRip cues of at most max_chars characters, cut on word boundaries (a longer single word gets a cue of its own)."""
+        def stamp(n):
+            ms = (n * 1000 + rate // 2) // rate
+            return "%02d:%02d:%02d,%03d" % (ms // 3600000, ms // 60000 % 60, ms // 1000 % 60, ms % 1000)
+
+        cues, cur = [], []
+        for w in self.words:
+            if cur and len(" ".join(x[0] for x in cur)) + 1 + len(w[0]) > max_chars:
+                cues.append(cur)
+                cur = []
+            cur.append(w)
+        if cur:
+            cues.append(cur)
+        return "".join("%d\n%s --> %s\n%s\n\n" % (n + 1, stamp(c[0][1]), stamp(c[-1][2]), " ".join(x[0] for x in c)) for n, c in enumerate(cues))
+
+
+def build_alignment(targets, spans, conf, score, samples, frame_len):
+    """AlignmentTargets + the device's spans [L][2] (first, last frame) and conf [L] -> Alignment.  start = first * frame_len,
+    end = min(samples, (last + 1) * frame_len)."""
+    chars = [(ch, int(a) * frame_len, min(samples, (int(b) + 1) * frame_len), float(c)) for ch, (a, b), c in zip(targets.chars, spans, conf)]
+    words, text, i, prev_end = [], targets.text, 0, 0
+    while i < len(text):
+        if text[i].isspace():
+            i += 1
+            continue
+        j = i
+        while j < len(text) and not text[j].isspace():
+            j += 1
+        own = [chars[targets.index[p]] for p in range(i, j) if targets.kept[p]]
+        if own:
+            words.append((text[i:j], own[0][1], own[-1][2], min(c[3] for c in own)))
+            prev_end = own[-1][2]
+        else:
+            words.append((text[i:j], prev_end, prev_end, float("nan")))
+        i = j
+    return Alignment(text, chars, words, float(score), int(samples), list(targets.index), list(targets.kept))
+
+
+def empty_alignment(targets, samples):
+    """The alignment of a text with nothing alignable: no characters, every word an empty span at 0."""
+    return build_alignment(targets, [], [], 0.0, samples, 1)
+
+
+def redact_forced(audio, text, align_fn):
+    """redact() with the forced alignment: audio [1, S] -> the concatenation of the kept passages, each cut from the start of its first
+    character to the end of its last.  align_fn(audio, bare text) -> Alignment."""
+    plan = redaction_plan(text)
+    if plan is None:
+        return audio
+    bare, keep = plan
+    al = align_fn(audio, bare)
+    return torch.cat([audio[:, al.char_start(a):al.char_end(b)] for a, b in keep], dim=-1)  # (keep: first and last character, inclusive)

@@ -204,6 +204,9 @@ def resolve_stage_dtypes(dtype, half):
     return {k: E.dtype_code(v) for k, v in out.items()}
 
 
+ORIG_ALIGNER_SECONDS = 30  # the longest clip the aligner of a path without its own clip cap is built for
+
+
 class _Common:
     """What this module's TextToSpeech and api_fast.TextToSpeech share: the lazy tokenizer, the seed, the text front-end."""
     world = 1  # processes that share one utterance's work (TextToSpeech with candidate sharding sets its own)
@@ -236,6 +239,108 @@ class _Common:
                              f"(TextToSpeech(max_mel_tokens={self.max_mel_tokens_cap}))")
         return tokens
 
+    # ------------------------------------------------------------------ the wav2vec2 aligner: redaction and word timings
+    aligner = None
+    _aligner_source = None
+    aligner_dtype = E.TT_F16  # (bf16 after an overflow; not one of the four dtype_names() stages)
+    ctc = None
+
+    def _aligner_max_samples(self):
+        return ORIG_ALIGNER_SECONDS * align.ORIG_SR
+
+    def load_aligner(self):
+        """wav2vec_alignment.py:51-58: the wav2vec2 CTC aligner of the redaction path as a device stage, from `aligner=` or the files find_aligner
+        locates.  NotImplementedError when there are none (bracketed text cannot be redacted without them)."""
+        if self.aligner is None:
+            src = self._aligner_source if self._aligner_source is not None else align.find_aligner(self.models_dir)
+            if src is None:
+                raise NotImplementedError("text with [bracketed] passages is redacted from the audio by the wav2vec2 aligner (api.py:583-587), "
+                                          "whose files were not found: " + align.where_to_put_files(self.models_dir) +
+                                          "; or construct TextToSpeech(enable_redaction=False) to have the brackets spoken")
+            self._aligner_source = src
+            self.aligner = stages.AlignerStage(src, self.device, self.aligner_dtype, max_samples=self._aligner_max_samples())
+        return self.aligner
+
+    def load_ctc(self):
+        """The forced-alignment stage, sized from the aligner (rebuilt with it)."""
+        al = self.load_aligner()
+        if self.ctc is None or self._ctc_of is not al:
+            if self.ctc is not None:
+                self.ctc.close()
+            self.ctc, self._ctc_of = stages.CtcAlignStage.for_aligner(al), al
+        return self.ctc
+
+    def _aligner_run(self, clip, logits):
+        """One clip [1, n] through the aligner -> (the stage, frame ids as a host list | logits f32 [T, vocab] on the device).  An fp16
+        overflow rebuilds the aligner with bf16 operands and runs the same clip again."""
+        while True:
+            al = self.load_aligner()
+            out = al.run(clip, logits=True)[1] if logits else al.frame_ids(clip)
+            if logits and out.is_cuda:
+                torch.cuda.current_stream(out.device).synchronize()  # (the guard is read after the run)
+            if not al.guard():
+                return al, out
+            if al.dtype != E.TT_F16:
+                raise E.OperandOverflow("the aligner stage produced non-finite values with bf16 operands (non-finite weights or audio?)")
+            import warnings
+            warnings.warn("tortoise_tts_amd: the aligner stage overflowed fp16 operands; rebuilding it with bf16 operands")
+            al.close()
+            self.aligner, self.aligner_dtype = None, E.TT_BF16
+
+    @torch.no_grad()
+    def align_many(self, audios, texts):
+        """Where every text is spoken in its clip: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), texts in spoken form (numbers
+        and abbreviations are not expanded: a character the aligner's vocabulary lacks is given the boundary of the one before it) ->
+        [align.Alignment].  The aligner runs clip by clip; the CTC forced alignment of all of them is ONE device call.  ValueError for a
+        clip with fewer frames than its text needs."""
+        audios, texts = list(audios), list(texts)
+        if len(audios) != len(texts):
+            raise ValueError(f"{len(audios)} clips with {len(texts)} texts")
+        tok = self.load_aligner().tokenizer
+        targets = [align.alignment_targets(t, tok) for t in texts]
+        clips = [a.reshape(1, -1) for a in audios]
+        logits = [self._aligner_run(c, True)[1] for c in clips]
+        res = self.load_ctc().align_many(logits, [t.ids for t in targets])
+        frame_len = align.frame_samples(self.aligner.fields)
+        out = []
+        for i, (r, t, c, lg) in enumerate(zip(res, targets, clips, logits)):
+            n = c.shape[-1]
+            if r["status"] == E.CTC_OK:
+                out.append(align.build_alignment(t, r["spans"].tolist(), r["conf"].tolist(), r["score"], n, frame_len))
+            elif r["status"] == E.CTC_EMPTY:
+                out.append(align.empty_alignment(t, n))
+            elif r["status"] == E.CTC_INFEASIBLE:
+                raise ValueError(f"forced alignment: clip {i} has {lg.shape[0]} frames ({n} samples), too few for the {len(t.ids)} characters "
+                                 f"of its text")
+            else:
+                raise RuntimeError(f"forced alignment: clip {i} was refused by the device stage (status {r['status']})")
+        return out
+
+    def align(self, audio, text):
+        """align_many of one clip -> align.Alignment (characters and words with start / end samples and confidences, .seconds(), .to_srt())."""
+        return self.align_many([audio], [text])[0]
+
+    def _spoken_text(self, text):
+        """What a clip returned for `text` speaks: without the [bracketed] passages when they are redacted."""
+        if getattr(self, "redacts_brackets", False) and self.enable_redaction and "[" in text:
+            bare, keep = align.redaction_plan(text)
+            return " ".join(bare[a:b + 1] for a, b in keep)
+        return text
+
+    def tts_with_timings(self, text, **tts_kwargs):
+        """tts(text, **tts_kwargs) and where its words are -> (what tts returns, align.Alignment - a list of k of them for k > 1; None where
+        tts returns no audio, i.e. on the other ranks of a sharded job).  The text is aligned as spoken (see align_many)."""
+        if not isinstance(text, str):
+            raise TypeError("tts_with_timings aligns the text with the audio: pass it as a str, not as token ids")
+        self.load_aligner()  # (missing files are reported before anything renders)
+        res = self.tts(text, **tts_kwargs)
+        out = res[0] if tts_kwargs.get("return_deterministic_state") else res
+        if out is None:
+            return res, None
+        clips = out if isinstance(out, (list, tuple)) else [out]
+        als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
+        return res, (als if isinstance(out, (list, tuple)) else als[0])
+
 
 class TextToSpeech(_Common):
     """Main entry point; see the module docstring.  Engine-only keyword arguments (all optional, after
@@ -245,12 +350,16 @@ class TextToSpeech(_Common):
     (per-GPU decode batch capacity), `configs` (ARConfig/CLVPConfig/DiffusionConfig/VocoderConfig overrides for tests), `aligner` ((config
     dict, state_dict, vocab dict, tokenizer config dict) of the wav2vec2 redaction aligner instead of its files), `winner_batch` (1 .. 16,
     default 1: the k winners of tts() are rendered one after the other; W >= 2: in groups of up to W, each ONE shared denoiser pass per
-    diffusion step and ONE UnivNet call - DESIGN.md 5.20)."""
+    diffusion step and ONE UnivNet call - DESIGN.md 5.20), `redaction` ('reference', the default: the reference's greedy-transcript
+    heuristic, bit for bit; 'forced': the bracketed passages are cut at the character boundaries of the CTC forced alignment, which exists
+    whenever the clip has enough frames - DESIGN.md 5.23)."""
+
+    redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, max_candidates=256, configs=None, max_mel_tokens=500, max_text_tokens=402,
-                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1, mel_front_end="torch"):
+                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1, mel_front_end="torch", redaction="reference"):
         self.models_dir = models_dir
         self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
         if use_deepspeed:
@@ -259,9 +368,10 @@ class TextToSpeech(_Common):
         # enable_redaction (reference default True): every clip of a text with '[' loses its [bracketed] passages (api.py:583-587); the
         # wav2vec2 aligner that finds them is built on first use (load_aligner)
         self.enable_redaction = bool(enable_redaction)
+        if redaction not in ("reference", "forced"):
+            raise ValueError(f"redaction={redaction!r}: 'reference' (the reference's greedy-transcript heuristic) or 'forced' (CTC forced alignment)")
+        self.redaction = redaction
         self._aligner_source = aligner
-        self.aligner = None
-        self.aligner_dtype = E.TT_F16  # (bf16 after an overflow; not one of the four dtype_names() stages)
         self.kv_cache = bool(kv_cache)
         self.half = bool(half)
         # candidate_sharding=False: this instance renders whole utterances on its own GPU even inside a multi-rank job (the
@@ -384,18 +494,8 @@ class TextToSpeech(_Common):
                                          max_rows=max(c["cap"], 8) * c["max_mel_tokens"])
         return self.cvvp
 
-    def load_aligner(self):
-        """wav2vec_alignment.py:51-58: the wav2vec2 CTC aligner of the redaction path as a device stage, from `aligner=` or the files find_aligner
-        locates.  NotImplementedError when there are none (bracketed text cannot be redacted without them)."""
-        if self.aligner is None:
-            src = self._aligner_source if self._aligner_source is not None else align.find_aligner(self.models_dir)
-            if src is None:
-                raise NotImplementedError("text with [bracketed] passages is redacted from the audio by the wav2vec2 aligner (api.py:583-587), "
-                                          "whose files were not found: " + align.where_to_put_files(self.models_dir) +
-                                          "; or construct TextToSpeech(enable_redaction=False) to have the brackets spoken")
-            self._aligner_source = src
-            self.aligner = stages.AlignerStage(src, self.device, self.aligner_dtype, max_samples=self._caps["max_S"] * 256 + 256)
-        return self.aligner
+    def _aligner_max_samples(self):
+        return max(self._caps["max_S"] * 256 + 256, super()._aligner_max_samples())  # (its own clips, and align() of a caller's up to 30 s)
 
     def _redaction_text(self, text):
         """text when its clips are to be redacted (enable_redaction and a str with '['), else None.  Checked before anything renders: an
@@ -411,18 +511,11 @@ class TextToSpeech(_Common):
         An fp16 overflow rebuilds the aligner with bf16 operands and aligns the same clip again (the audio is not rendered again)."""
         t0 = time.perf_counter()
         clip = audio.reshape(1, -1)
-        while True:
-            al = self.load_aligner()
-            ids = al.frame_ids(clip)
-            if not al.guard():
-                break
-            if al.dtype != E.TT_F16:
-                raise E.OperandOverflow("the aligner stage produced non-finite values with bf16 operands (non-finite weights or audio?)")
-            import warnings
-            warnings.warn("tortoise_tts_amd: the aligner stage overflowed fp16 operands; rebuilding it with bf16 operands")
-            al.close()
-            self.aligner, self.aligner_dtype = None, E.TT_BF16
-        out = align.redact(clip, text, lambda _: ids, al.tokenizer).reshape(1, 1, -1)
+        if self.redaction == "forced":  # cut at the forced alignment's character boundaries: no "could not align"
+            out = align.redact_forced(clip, text, self.align).reshape(1, 1, -1)
+        else:
+            al, ids = self._aligner_run(clip, False)
+            out = align.redact(clip, text, lambda _: ids, al.tokenizer).reshape(1, 1, -1)
         self._redact_s += time.perf_counter() - t0
         return out
 

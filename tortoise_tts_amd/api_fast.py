@@ -68,8 +68,9 @@ class TextToSpeech(_Common):
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1,
-                 per_session_sampling=False, wide_sessions=False, mel_front_end="torch"):
+                 per_session_sampling=False, wide_sessions=False, mel_front_end="torch", aligner=None):
         self.models_dir = models_dir
+        self._aligner_source = aligner  # align() / tts_with_timings(): the wav2vec2 aligner's (config, state_dict, vocab, tokenizer config) instead of its files
         self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
         if use_deepspeed:
             raise NotImplementedError("use_deepspeed: DeepSpeed kernel injection is a CUDA-only reference option")

@@ -364,6 +364,16 @@ _MEL_PROTOS = {
     "tt_mel_resampled_length": (_i, [vp, _i]),
     "tt_mel_resample": (_i, [vp, vp, _i, vp, vp]),
 }
+# include/tortoise_mi355x_ctc.h: CTC forced alignment over the aligner's logits (its own header and version, same library)
+_CTC_PROTOS = {
+    "tt_ctc_abi_version": (_i, []),
+    "tt_ctc_create": (_i, [_i, _i, _i, _i, _i, C.POINTER(vp)]),
+    "tt_ctc_destroy": (None, [vp]),
+    "tt_ctc_align": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+CTC_ABI_VERSION = 1
+CTC_MAX_TOKENS = 511  # TT_CTC_MAX_TOKENS
+CTC_OK, CTC_INFEASIBLE, CTC_EMPTY, CTC_REFUSED = 0, 1, 2, 3
 # include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
 _HIFI_PROTOS = {
     "tt_hifi_batch_abi_version": (_i, []),
@@ -437,7 +447,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -465,6 +475,8 @@ def load_library():
         want = lib.tt_mel_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    if lib.tt_ctc_abi_version() != CTC_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_ctc.h is version %d in the library, %d in Python" % (lib.tt_ctc_abi_version(), CTC_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))

@@ -18,15 +18,37 @@ def chunk_owner(j, world):
     return j % world
 
 
+def merge_alignments(alignments, clip_samples):
+    """The alignments of consecutive chunks as one alignment of the concatenated audio: chunk j's samples are offset by the samples of the
+    chunks before it, the texts are joined with a space."""
+    from .align import Alignment
+    chars, words, index, kept, text, off, score = [], [], [], [], "", 0, 0.0
+    for j, (al, n) in enumerate(zip(alignments, clip_samples)):
+        if j:
+            text += " "
+            index.append(len(chars) - 1)
+            kept.append(False)
+        index += [i + len(chars) for i in al.index]  # (-1, nothing before it in its chunk: the last character of the chunks before)
+        kept += al.kept
+        chars += [(c, a + off, b + off, p) for c, a, b, p in al.chars]
+        words += [(w, a + off, b + off, p) for w, a, b, p in al.words]
+        text += al.text
+        score += al.score
+        off += int(n)
+    return Alignment(text, chars, words, score, off, index, kept)
+
+
 def read_long_form(tts, text, preset="standard", conditioning_latents=None, voice_samples=None, seed=None, texts_are_chunks=False,
-                   **tts_kwargs):
+                   return_timings=False, **tts_kwargs):
     """tts: a TextToSpeech built with candidate_sharding=False (one complete engine per rank), or a fast-path
     tortoise_tts_amd.api_fast.TextToSpeech (the reference's read_fast.py): each rank then renders its chunks with one tts_many call -
     tts()'s defaults plus tts_kwargs, the agreed seed for every chunk - and `preset` does not apply (read_fast.py passes none; the fast
     path has no diffusion settings).
     text: the whole text (str; '|' splits it like read.py:46-50, else split_and_recombine_text) or, with texts_are_chunks=True,
     a list of chunks (str or pre-tokenised id sequences).
-    Returns (full_audio f32 [1, n] or None, parts: list of per-chunk clips [1, 1, n_j]) on rank 0, (None, None) elsewhere."""
+    Returns (full_audio f32 [1, n] or None, parts: list of per-chunk clips [1, 1, n_j]) on rank 0, (None, None) elsewhere.
+    return_timings=True (str chunks): (full_audio, align.Alignment of the whole text in the concatenated audio) instead - every chunk is
+    aligned with its own clip in one forced-alignment call (tts.align_many) and merge_alignments offsets them."""
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
     if getattr(tts, "world", 1) != 1:
@@ -69,4 +91,7 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
         return None, None
     clips = [parts[j] for j in range(len(texts))]
     full = torch.cat([c.squeeze(0) for c in clips], dim=-1)  # read.py:74, 87
+    if return_timings:
+        als = tts.align_many(clips, [tts._spoken_text(t) for t in texts])
+        return full, merge_alignments(als, [c.shape[-1] for c in clips])
     return full, clips

@@ -470,6 +470,68 @@ class AlignerStage(_GuardedHandle):
         return self.run(audio).cpu().tolist()
 
 
+class CtcAlignStage(_Handle):
+    """CTC forced alignment of known targets with the aligner's logits (csrc/ctc_align.hip, include/tortoise_mi355x_ctc.h): ragged batches,
+    one tt_ctc_align call per max_clips clips, every clip's result bit-identical to aligning it alone."""
+
+    api = "tt_ctc"
+
+    def __init__(self, vocab, blank, max_frames, max_tokens=E.CTC_MAX_TOKENS, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.vocab, self.blank, self.max_frames, self.max_tokens, self.max_clips = int(vocab), int(blank), int(max_frames), int(max_tokens), int(max_clips)
+        self._create(self.max_frames, self.max_tokens, self.max_clips, self.vocab, self.blank)
+
+    @classmethod
+    def for_aligner(cls, aligner, max_clips=16):
+        """Sized from an AlignerStage: its vocabulary and blank, the frames of its longest clip."""
+        from . import align
+        f = aligner.fields
+        frames = max(1, align.frames_for(aligner.max_samples, f["conv_kernel"], f["conv_stride"]))
+        return cls(f["vocab"], align.blank_id(aligner.tokenizer), frames, max_clips=max_clips, device=aligner.device)
+
+    def align_many(self, logits_list, targets_list):
+        """logits f32 [T_i, vocab] (device or host) and target ids of every clip -> one dict per clip: status (E.CTC_*), and for status 0
+        path int32 [T_i], spans int32 [L_i, 2], conf f32 [L_i] (host tensors) and score.  ValueError for a target or a clip beyond the handle."""
+        if len(logits_list) != len(targets_list):
+            raise ValueError(f"{len(logits_list)} clips with {len(targets_list)} targets")
+        for i, (lg, tg) in enumerate(zip(logits_list, targets_list)):
+            if len(tg) > self.max_tokens:
+                raise ValueError(f"clip {i}: a target of {len(tg)} tokens exceeds the forced alignment's capacity ({self.max_tokens})")
+            if lg.dim() != 2 or lg.shape[1] != self.vocab:
+                raise ValueError(f"clip {i}: logits of shape {tuple(lg.shape)}, expected [frames, {self.vocab}]")
+            if lg.shape[0] > self.max_frames:
+                raise ValueError(f"clip {i}: {lg.shape[0]} frames exceed the forced alignment's capacity ({self.max_frames})")
+        out = []
+        for g in range(0, len(logits_list), self.max_clips):
+            out += self._group(logits_list[g:g + self.max_clips], targets_list[g:g + self.max_clips])
+        return out
+
+    def _group(self, logits_list, targets_list):
+        n, dev = len(logits_list), self.device
+        fo = np.concatenate(([0], np.cumsum([lg.shape[0] for lg in logits_list]))).astype(np.int32)
+        to = np.concatenate(([0], np.cumsum([len(tg) for tg in targets_list]))).astype(np.int32)
+        F_, L_ = int(fo[-1]), int(to[-1])
+        lg = torch.cat([x.to(device=dev, dtype=torch.float32).reshape(-1, self.vocab) for x in logits_list] + [torch.zeros(1, self.vocab, device=dev)])
+        host = torch.from_numpy(np.concatenate([fo, to, np.asarray([t for tg in targets_list for t in tg] + [0], dtype=np.int32)])).to(dev)
+        # one int32 result buffer (path | spans | status) and one f32 (conf | score): two copies back
+        ri = torch.zeros(F_ + 2 * L_ + n, device=dev, dtype=torch.int32)
+        rf = torch.zeros(L_ + n, device=dev, dtype=torch.float32)
+        hp, ip, fp = host.data_ptr(), ri.data_ptr(), rf.data_ptr()  # (pointer arithmetic: an empty slice has no data_ptr)
+        E.check(self.lib.tt_ctc_align(self.h, n, lg.data_ptr(), hp, hp + 4 * (2 * n + 2), hp + 4 * (n + 1), ip, ip + 4 * F_, fp, fp + 4 * L_,
+                                      ip + 4 * (F_ + 2 * L_), E.stream_ptr()))
+        ri, rf = ri.cpu(), rf.cpu()
+        out = []
+        for i in range(n):
+            st = int(ri[F_ + 2 * L_ + i])
+            r = {"status": st}
+            if st == E.CTC_OK:
+                r.update(path=ri[fo[i]:fo[i + 1]].clone(), spans=ri[F_ + 2 * to[i]:F_ + 2 * to[i + 1]].reshape(-1, 2).clone(),
+                         conf=rf[to[i]:to[i + 1]].clone(), score=float(rf[L_ + i]))
+            out.append(r)
+        return out
+
+
 class ClassifierStage(_GuardedHandle):
     """The Tortoise detector (api.py classify_audio_clip: AudioMiniEncoderWithClassifierHead over one 24 kHz clip) -> the head's two
     logits and the 512-d embedding of frame 0.  The handle is re-created for a longer clip than it was built for."""
