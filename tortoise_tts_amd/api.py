@@ -38,6 +38,7 @@ from . import align
 from . import dist as tdist
 from . import engine as E
 from . import stages
+from . import stretch as tsm
 from . import weights as W
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig, PRESETS, BASE_SETTINGS, CALM_TOKEN
 from .schedule import Schedule
@@ -341,6 +342,61 @@ class _Common:
         als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
         return res, (als if isinstance(out, (list, tuple)) else als[0])
 
+    # ------------------------------------------------------------------ speaking rate: WSOLA time-stretch of finished clips
+    stretcher = None
+
+    def load_stretch(self, max_samples=0):
+        """The time-stretch stage (stages.TimeStretchStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.TSM_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the time-stretch can take ({E.TSM_MAX_SAMPLES})")
+        if self.stretcher is None or self.stretcher.max_samples < max_samples:
+            if self.stretcher is not None:
+                self.stretcher.close()
+            self.stretcher = stages.TimeStretchStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE), device=self.device)
+        return self.stretcher
+
+    @torch.no_grad()
+    def stretch_many(self, audios, rates=None, durations=None, return_map=False):
+        """The same speech at another speed and the same pitch: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> the stretched
+        clips, each in the shape and on the device it came in.  Give exactly one of `rates` (2.0: twice as fast; one value or one per clip,
+        each in [0.5, 2.0]) and `durations` (seconds the clip shall last: rate = n / (duration * 24000)).  All clips go through ONE device
+        call per 16.  return_map=True: also, per clip, int64 [K, 2] anchors (output sample, input sample) of the frames the output was
+        assembled from (stretch.anchors), with which a time in the original clip is carried over to the stretched one."""
+        audios = list(audios)
+        if (rates is None) == (durations is None):
+            raise ValueError("stretch: give exactly one of rate and duration")
+        given = rates if durations is None else durations
+        given = list(given) if isinstance(given, (list, tuple)) else [given] * len(audios)
+        if len(given) != len(audios):
+            raise ValueError(f"stretch: {len(audios)} clips with {len(given)} {'rates' if durations is None else 'durations'}")
+        for i, a in enumerate(audios):
+            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
+                raise ValueError(f"stretch: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+        rqs = [tsm.rate_q(v if durations is None else tsm.rate_for_duration(a.shape[-1], v)) for a, v in zip(audios, given)]
+        if not audios:
+            return ([], []) if return_map else []
+        t0 = time.perf_counter()
+        res = self.load_stretch(max(a.shape[-1] for a in audios)).stretch_many([a.reshape(-1) for a in audios], rqs)
+        out = [y.to(a.device).reshape(a.shape[:-1] + (-1,)) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
+        self._stretch_s = time.perf_counter() - t0
+        return (out, [tsm.anchors(rq, off) for rq, (_, off) in zip(rqs, res)]) if return_map else out
+
+    def stretch(self, audio, rate=None, duration=None):
+        """stretch_many of one clip -> the stretched clip."""
+        return self.stretch_many([audio], rates=rate, durations=duration)[0]
+
+    def _at_rate(self, clips, rate):
+        """The clips a tts call is about to return ({winner: clip} or a list), at speaking_rate `rate`: one stretch_many call for all of
+        them, its time in timings['stretch_s']."""
+        self._stretch_s = 0.0
+        if isinstance(clips, dict):
+            keys = sorted(clips)
+            out = dict(zip(keys, self.stretch_many([clips[i] for i in keys], rates=rate)))
+        else:
+            out = self.stretch_many(clips, rates=rate)
+        self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+        return out
+
 
 class TextToSpeech(_Common):
     """Main entry point; see the module docstring.  Engine-only keyword arguments (all optional, after
@@ -352,7 +408,9 @@ class TextToSpeech(_Common):
     default 1: the k winners of tts() are rendered one after the other; W >= 2: in groups of up to W, each ONE shared denoiser pass per
     diffusion step and ONE UnivNet call - DESIGN.md 5.20), `redaction` ('reference', the default: the reference's greedy-transcript
     heuristic, bit for bit; 'forced': the bracketed passages are cut at the character boundaries of the CTC forced alignment, which exists
-    whenever the clip has enough frames - DESIGN.md 5.23)."""
+    whenever the clip has enough frames - DESIGN.md 5.23).  Engine-only keyword of tts() / tts_with_preset() / tts_many(), taken out of
+    **hf_generate_kwargs: `speaking_rate` (0.5 .. 2.0; None or 1.0: off) - every returned clip is time-stretched at the same pitch after
+    redaction (stretch / stretch_many, csrc/tsm.hip - DESIGN.md 5.24)."""
 
     redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
@@ -658,13 +716,14 @@ class TextToSpeech(_Common):
             self._redact_s = 0.0
             wavs = self._redact_clips(wavs, redact)
             self.timings["redact_s"] = self._redact_s
+        if o.speaking_rate is not None:  # (every rank stretches the clips it holds)
+            wavs = self._at_rate(wavs, o.speaking_rate)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
         res = None if wavs is None else [wavs[i] for i in range(k)] if k > 1 else wavs[0]
         return (res, (seed, text, voice_samples, conditioning_latents)) if return_deterministic_state else res
 
-    @torch.no_grad()
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
         """Several utterances of one voice in one call - what tortoise/read.py:66-71 does chunk after chunk with the same seed.
         Returns [tts(text, ...) for text in texts] (k = 1: one clip f32 [1, 1, n] per text), computed with the autoregressive stage
@@ -672,7 +731,16 @@ class TextToSpeech(_Common):
         utterance), so every weight matrix streams once per step for all of them and the sampled codes of an utterance are
         bit-identical to rendering it alone.  With utterance_batch > 1 the CLVP ranking of a wave is ONE speech-tower pass over all its
         candidates (every score the bits of scoring the utterance alone) and the denoiser runs in shared, padded passes; the latent re-pass
-        runs per utterance as in tts() and UnivNet vocodes a wave in one call (every clip the bits of vocoding it alone).  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py)."""
+        runs per utterance as in tts() and UnivNet vocodes a wave in one call (every clip the bits of vocoding it alone).  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py).
+        speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call."""
+        rate = tsm.speaking_rate(kwargs)
+        out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
+                             use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
+        return out if rate is None else self._at_rate(out, rate)
+
+    @torch.no_grad()
+    def _tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
+        """tts_many without the speaking rate."""
         if self.world != 1:
             raise ValueError("tts_many batches utterances on one GPU: build TextToSpeech(candidate_sharding=False)")
         args = inspect.signature(self.tts).bind(None, **kwargs)
@@ -755,6 +823,7 @@ class TextToSpeech(_Common):
         """tts()'s generation arguments (`args`: its parameters by name), validated -> what the phases read."""
         hf = dict(args["hf_generate_kwargs"])
         noise = hf.pop("noise_override", None) or {}
+        speaking_rate = tsm.speaking_rate(hf)
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
             raise ValueError(f"cvvp_amount={args['cvvp_amount']} must lie in [0, 1] (api.py:366-367)")
@@ -763,7 +832,7 @@ class TextToSpeech(_Common):
             sampling=dict(temperature=args["temperature"], top_p=args["top_p"], repetition_penalty=args["repetition_penalty"], top_k=top_k,
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
-            diffusion_temperature=args["diffusion_temperature"])
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

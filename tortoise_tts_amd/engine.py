@@ -374,6 +374,21 @@ _CTC_PROTOS = {
 CTC_ABI_VERSION = 1
 CTC_MAX_TOKENS = 511  # TT_CTC_MAX_TOKENS
 CTC_OK, CTC_INFEASIBLE, CTC_EMPTY, CTC_REFUSED = 0, 1, 2, 3
+# include/tortoise_mi355x_tsm.h: WSOLA time-stretch of rendered clips (its own header and version, same library)
+_TSM_PROTOS = {
+    "tt_tsm_abi_version": (_i, []),
+    "tt_tsm_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_tsm_destroy": (None, [vp]),
+    "tt_tsm_out_samples": (_i, [_i, _i]),
+    "tt_tsm_frames": (_i, [_i, _i]),
+    "tt_tsm_stretch": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+TSM_ABI_VERSION = 1
+TSM_WINDOW, TSM_HOP, TSM_SEARCH = 768, 384, 256  # TT_TSM_WINDOW, TT_TSM_HOP, TT_TSM_SEARCH
+TSM_RATE_ONE, TSM_RATE_MIN, TSM_RATE_MAX = 65536, 32768, 131072  # TT_TSM_RATE_*: 16.16 fixed point, rates 0.5 .. 2.0
+TSM_SAMPLE_RATE = 24000
+TSM_MAX_SAMPLES, TSM_MAX_CLIPS = 8388608, 64
+TSM_OK, TSM_EMPTY, TSM_REFUSED = 0, 1, 2
 # include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
 _HIFI_PROTOS = {
     "tt_hifi_batch_abi_version": (_i, []),
@@ -447,7 +462,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -477,6 +492,8 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     if lib.tt_ctc_abi_version() != CTC_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_ctc.h is version %d in the library, %d in Python" % (lib.tt_ctc_abi_version(), CTC_ABI_VERSION))
+    if lib.tt_tsm_abi_version() != TSM_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_tsm.h is version %d in the library, %d in Python" % (lib.tt_tsm_abi_version(), TSM_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))

@@ -532,6 +532,54 @@ class CtcAlignStage(_Handle):
         return out
 
 
+class TimeStretchStage(_Handle):
+    """WSOLA time-stretch of 24 kHz clips (csrc/tsm.hip, include/tortoise_mi355x_tsm.h): ragged batches, each clip with its own rate, one
+    tt_tsm_stretch call per max_clips clips, every clip's result bit-identical to stretching it alone."""
+
+    api = "tt_tsm"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        self._create(self.max_samples, self.max_clips)
+
+    def stretch_many(self, clips, rqs):
+        """clips f32 [n_i] (device or host) and the 16.16 rate of each (stretch.rate_q) -> one (y f32 [n_out_i] on the stage's device, chosen
+        offsets int32 [K_i] on the host) per clip.  ValueError for an empty clip, a clip beyond the handle or a rate outside the range."""
+        if len(clips) != len(rqs):
+            raise ValueError(f"{len(clips)} clips with {len(rqs)} rates")
+        for i, (x, rq) in enumerate(zip(clips, rqs)):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the time-stretch stage's capacity ({self.max_samples})")
+            if not E.TSM_RATE_MIN <= int(rq) <= E.TSM_RATE_MAX:
+                raise ValueError(f"clip {i}: rate {int(rq)} / 65536 is outside the supported range [0.5, 2.0]")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], [int(r) for r in rqs[g:g + self.max_clips]])
+        return out
+
+    def _group(self, clips, rqs):
+        n, dev = len(clips), self.device
+        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
+        oo = np.concatenate(([0], np.cumsum([self.lib.tt_tsm_out_samples(x.shape[0], r) for x, r in zip(clips, rqs)]))).astype(np.int32)
+        fo = np.concatenate(([0], np.cumsum([self.lib.tt_tsm_frames(x.shape[0], r) for x, r in zip(clips, rqs)]))).astype(np.int32)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, oo, fo, np.asarray(rqs, dtype=np.int32)])).to(dev)
+        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
+        ri = torch.zeros(int(fo[-1]) + n, device=dev, dtype=torch.int32)  # (offsets | status): one copy back
+        hp, ip = host.data_ptr(), ri.data_ptr()
+        E.check(self.lib.tt_tsm_stretch(self.h, n, audio.data_ptr(), hp, hp + 4 * 3 * (n + 1), y.data_ptr(), hp + 4 * (n + 1), ip,
+                                        hp + 4 * 2 * (n + 1), ip + 4 * int(fo[-1]), E.stream_ptr()))
+        ri = ri.cpu()
+        status = ri[int(fo[-1]):].tolist()
+        if any(st != E.TSM_OK for st in status):
+            raise RuntimeError(f"time-stretch: the device stage refused clips it was handed (status {status})")
+        return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
+
+
 class ClassifierStage(_GuardedHandle):
     """The Tortoise detector (api.py classify_audio_clip: AudioMiniEncoderWithClassifierHead over one 24 kHz clip) -> the head's two
     logits and the 512-d embedding of frame 0.  The handle is re-created for a longer clip than it was built for."""
