@@ -171,7 +171,7 @@ int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* v
  * variant 0 = chosen from the shape, 1 = per-wave prefix kernel, 2 / 3 = shared-prefix kernel with 16 / 4 sequences per workgroup */
 int tt_op_decode_attention(int dtype, const void* q, const void* kp, const void* vp, int P1, const void* kc, const void* vc, int tmax,
                            int tgen, void* out, int B, int heads, int variant, void* stream);
-/* the decode step's QKV projection and attention in ONE launch (TT_AR_OPT_FUSED_QKV_ATTN; csrc/attention.hip decode_qkv_attn_kernel):
+/* the decode step's QKV projection and attention in ONE launch (TT_AR_OPT_FUSED_QKV_ATTN; csrc/decode_attention.hip decode_qkv_attn_kernel):
  * h T [B][1024] the LN1 rows, w_qkv T [3072][1024], b_qkv f32 [3072] or NULL.  Own keys 0 .. tgen - 2 are in kc / vc (layouts above); the
  * launch writes slot tgen - 1 of both from h w_qkv^T + b_qkv (the bits of the EPI_QKV_DECODE GEMM), attends [prefix | own keys
  * 0 .. tgen - 1] and writes out T [B][1024]; q_out T [B][1024] (or NULL) receives the scaled query rows.  16 heads, B % 16 == 0,

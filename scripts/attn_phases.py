@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Where decode attention's time goes: phase stamps (100 MHz wall clock in scalar registers, wave 0 of EVERY workgroup) of
-csrc/attention.hip decode_attn_lds_kernel built with -DTT_ATTN_STAMPS, at the benchmark's shape (256 sequences x 16 heads, 59 shared keys).
+csrc/decode_attention.hip decode_attn_lds_kernel built with -DTT_ATTN_STAMPS, at the benchmark's shape (256 sequences x 16 heads, 59 shared keys).
     python -m tortoise_tts_amd.build --variant astamps -DTT_ATTN_STAMPS
     TORTOISE_MI355X_LIB=tortoise_tts_amd/lib/libtortoise_mi355x_astamps.so python scripts/attn_phases.py"""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""-m gpu: the decode step's QKV projection and attention as ONE launch (csrc/attention.hip decode_qkv_attn_kernel, TT_AR_OPT_FUSED_QKV_ATTN).
+"""-m gpu: the decode step's QKV projection and attention as ONE launch (csrc/decode_attention.hip decode_qkv_attn_kernel, TT_AR_OPT_FUSED_QKV_ATTN).
 
   * operator level: `tt_op_decode_qkv_attention` against the composition of the two launches it replaces (the EPI_QKV_DECODE GEMM through
     tt_op_gemm_ex, then tt_op_decode_attention) on the same inputs - BIT for bit on the attention rows, the scaled query rows and the whole

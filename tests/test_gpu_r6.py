@@ -1,6 +1,6 @@
 """-m gpu, round 6: the decode step pinned at the CONTEXTS the benchmark runs it at, and BASELINE config #2 at its own shapes.
 
-  * `tt_op_decode_attention` (the dominant kernel of the headline, csrc/attention.hip decode_attn_lds_kernel / decode_attn_kernel) at 16 heads x
+  * `tt_op_decode_attention` (the dominant kernel of the headline, csrc/decode_attention.hip decode_attn_lds_kernel / decode_attn_kernel) at 16 heads x
     256 sequences, 59 shared-prefix keys, 1 .. 500 own keys against torch fp32 from the same rounded operands - every other attention form
     already had such a test (tests/test_gpu_ops.py::test_flash_attention).
   * the autoregressive engine teacher-forced for 500 steps at B = 96 ('fast' preset, ragged on the 64-row decode tiles) and B = 256 against

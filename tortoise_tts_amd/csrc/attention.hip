@@ -11,10 +11,7 @@
 // K/V for one (batch, head) is at most a few hundred KB, i.e. L2 resident, so nothing is staged
 // through LDS (the only LDS use is the 129-entry relative-position table of DiffusionTts).
 //
-// decode_attention: one wave per (sequence, head), one new query against [shared prefix | own
-// generated keys].  HBM-bound on the per-sequence cache: keys are stored in 16-byte dim-chunks
-// that are key-major so the lane-per-key dot product issues fully coalesced 1-KiB loads; values are
-// row-major and read 8 whole rows (1 KiB) per wave instruction.
+// The decode-step attention (one new query against [shared prefix | own generated keys]) is in decode_attention.hip.
 #include "ops.h"
 
 namespace tt {
@@ -273,9 +270,6 @@ __global__ __launch_bounds__(256, 2) void flash_kernel(FlashArgs a) {  // 2 wave
 // max without the operand canonicalisation fmaxf() implies (the inputs are MFMA results / finite floats or -inf)
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-
-typedef __attribute__((address_space(3))) void lds_void_a;
-typedef __attribute__((address_space(1))) const void gbl_void_a;
 
 // KS = 2 ("key split"): 8 waves per block - wave w works on query group w & 3 like before, but only on half w >> 2 (32 keys) of
 // every staged 64-key tile, and the two partial softmax states of a query group are merged through the LDS at the end.  At the
@@ -845,849 +839,6 @@ int flash_attention_launch(int dtype, const FlashArgs& a, hipStream_t stream) {
   dim3 grid(cdiv(a.n, 16), a.BH);
   if (dtype == DT_BF16) launch_timed(ps, flash_kernel<bf16, 1, true>, grid, dim3(256), 0, stream, a);
   else launch_timed(ps, flash_kernel<f16, 1, true>, grid, dim3(256), 0, stream, a);
-  TT_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------- decode
-// 8-wide dot product with fp32 accumulation on the packed-pair dot instructions (v_dot2c_f32_bf16 / v_dot2c_f32_f16):
-// the query stays packed (32 VGPRs instead of 64 floats) and a key costs 32 VALU ops instead of 64 converts + 64 FMAs.
-__device__ __forceinline__ float dot8(Vec<bf16>::x8 a, Vec<bf16>::x8 b, float acc) {
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 4, 5), __builtin_shufflevector(b, b, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), acc, false);
-  return acc;
-}
-__device__ __forceinline__ float dot8(Vec<f16>::x8 a, Vec<f16>::x8 b, float acc) {
-  acc = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 4, 5), __builtin_shufflevector(b, b, 4, 5), acc, false);
-  acc = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), acc, false);
-  return acc;
-}
-
-// One wave per (sequence, head); 4 waves per block.  Sized to <= 128 VGPRs so that all B*heads = 4096 waves of the
-// full candidate batch are resident at once (16 waves per CU): with 3 blocks per CU the 1024 blocks ran as a full
-// round plus a quarter-full tail.  The shared prefix and the sequence's own keys are walked as separate, uniform
-// segments: every load is then (wave-uniform base) + (32-bit lane offset) - no 64-bit address pairs held in VGPRs -
-// and unconditional (clamped key index), because a branch between two groups of loads makes the compiler drain the
-// first group before it issues the second.
-constexpr int DEC_VROWS = 4;             // V key rows per lane per register set (two sets in flight)
-constexpr int DEC_VKEYS = 8 * DEC_VROWS;  // keys per wave per PV iteration: 8 key sub-rows x DEC_VROWS
-
-template <typename T>
-__global__ __launch_bounds__(256, 4) void decode_attn_kernel(DecodeAttnArgs a, int ctx_cap) {  // 4 waves per SIMD => <= 128 VGPRs
-  typedef typename Vec<T>::x8 x8;
-  extern __shared__ __attribute__((aligned(16))) float sc_all[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int pair = min((int)blockIdx.x * 4 + wave, a.B * a.heads - 1);  // surplus waves of the last block repeat its last pair
-  const int b = pair / a.heads;
-  const int h = pair % a.heads;
-  const int tgen = *a.step + 1;       // generated keys 0..*step
-  const int P1 = a.P1;
-  const int ctx = P1 + tgen;
-  float* sc = sc_all + (size_t)wave * ctx_cap;   // scores: [0, P1) prefix keys, [P1, ctx) own keys
-
-  const T* kp = (const T*)a.kp + (size_t)h * P1 * 64;
-  const T* vp = (const T*)a.vp + (size_t)h * P1 * 64;
-  const size_t bh = (size_t)b * a.heads + h;
-  const T* kc = (const T*)a.kc + bh * 8 * a.tmax * 8;
-  const T* vc = (const T*)a.vc + bh * a.tmax * 64;
-
-  float mx = -1e30f;
-  {
-    x8 qk[8];
-    const T* qp = (const T*)a.q + (size_t)b * a.heads * 64 + h * 64;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) qk[c] = *(const x8*)(qp + c * 8);
-    // Lane-per-key dot products, TWO key slots (16 x 16-byte loads) in flight per lane per iteration.  Slot list:
-    // prefix keys in 64-key slots (row-major rows of 64), then own keys in 64-key slots (chunk-major [8][tmax][8]).
-    const int nsp = (P1 + 63) >> 6, nso = (tgen + 63) >> 6;
-#pragma unroll 1
-    for (int sl0 = 0; sl0 < nsp + nso; sl0 += 2) {
-      x8 kk[2][8];
-      int key[2];
-      bool live[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int slot = min(sl0 + u, nsp + nso - 1);   // an odd slot count repeats the last slot (cached), result dropped
-        const bool pre = slot < nsp;                    // wave-uniform
-        const int k = (pre ? slot : slot - nsp) * 64 + lane;
-        const int lim = pre ? P1 : tgen;
-        const int kcl = min(k, lim - 1);
-        const char* base = (const char*)(pre ? kp : kc);
-        const unsigned off = (pre ? (unsigned)kcl * 64u : (unsigned)kcl * 8u) * (unsigned)sizeof(T);  // byte offsets, 32-bit
-        const unsigned cs = (pre ? 8u : (unsigned)a.tmax * 8u) * (unsigned)sizeof(T);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) kk[u][c] = *(const x8*)(base + (off + c * cs));
-        key[u] = (pre ? 0 : P1) + k;
-        live[u] = k < lim && sl0 + u < nsp + nso;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float sv = 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) sv = dot8(qk[c], kk[u][c], sv);
-        if (live[u]) {
-          sc[key[u]] = sv;
-          mx = fmaxf(mx, sv);
-        }
-      }
-    }
-  }
-
-  // PV: a V row is 128 bytes, read as 8 lanes x 16 bytes, so a wave instruction covers 8 whole key rows (1 KiB, like the K
-  // loads; 8-byte loads moved half as much per instruction and measured 6 % slower).  Lane -> (key sub-row kk8 = lane >> 3,
-  // channel group cg = lane & 7: 8 channels); iteration `it` covers DEC_VKEYS keys of one segment.
-  const int kk8 = lane >> 3, cg = lane & 7;
-  const int nvp = (P1 + DEC_VKEYS - 1) / DEC_VKEYS, nvo = (tgen + DEC_VKEYS - 1) / DEC_VKEYS;
-  const int nit = nvp + nvo;
-  auto load_v = [&](x8 (&t)[DEC_VROWS], int it) {
-    const int itc = min(it, nit - 1);  // past the end: repeat the last iteration's rows (cached), weighted 0
-    const bool pre = itc < nvp;
-    const char* base = (const char*)(pre ? vp : vc);
-    const int k0 = (pre ? itc : itc - nvp) * DEC_VKEYS + kk8, lim = pre ? P1 : tgen;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const unsigned jc = (unsigned)min(k0 + 8 * u, lim - 1);
-      t[u] = *(const x8*)(base + (jc * 64u + (unsigned)cg * 8u) * (unsigned)sizeof(T));  // uniform base + 32-bit byte offset
-    }
-  };
-  // the first V rows do not depend on the scores: request them before the softmax
-  x8 ta[DEC_VROWS], tb[DEC_VROWS];
-  load_v(ta, 0);
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < ctx; j += 64) {
-    const float e = __expf(sc[j] - mx);
-    sc[j] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  __syncthreads();  // every lane's sc[] writes are visible to the whole wave (and block)
-  float o[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) o[c] = 0.f;
-  auto consume = [&](const x8 (&t)[DEC_VROWS], int it) {
-    const bool pre = it < nvp;
-    const int k0 = (pre ? it : it - nvp) * DEC_VKEYS + kk8, lim = it < nit ? (pre ? P1 : tgen) : 0;
-    const float* scs = sc + (pre ? 0 : P1);
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const int j = k0 + 8 * u;
-      const float pj = j < lim ? scs[j] : 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) o[c] += pj * (float)t[u][c];
-    }
-  };
-#pragma unroll 1
-  for (int it = 0; it < nit; it += 2) {  // two register sets: the next rows are in flight while these are summed
-    load_v(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);  // fences keep exactly two row sets live (an early third set spills)
-    consume(ta, it);
-    __builtin_amdgcn_sched_barrier(0);
-    load_v(ta, it + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    consume(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {  // sum the 8 key sub-rows (lanes with equal channel group)
-    o[c] = add_xor8(o[c]);
-    o[c] = add_xor16(o[c]);
-    o[c] = add_xor32(o[c]);
-  }
-  if ((int)blockIdx.x * 4 + wave < a.B * a.heads && kk8 == 0) {
-    const float inv = 1.0f / sum;
-    x8 r;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) r[c] = (T)(o[c] * inv);
-    *(x8*)((T*)a.out + (size_t)b * a.heads * 64 + h * 64 + cg * 8) = r;
-  }
-}
-
-// Shared-prefix variant.  Every candidate of an utterance attends to the SAME [cond | text | start] prefix keys; the kernel
-// above reads them once per (sequence, head) wave - 15 KB per wave, 61 MB of L2 -> CU traffic per launch at 256 candidates,
-// which is on the critical path of every wave (per-CU L2 bandwidth is ~50 GB/s) although it never touches HBM.  Here a
-// workgroup is NSEQ waves = NSEQ sequences of ONE head: the head's prefix K / V are staged into LDS once per workgroup
-// (global_load_lds; K re-laid chunk-major on the fly through the per-lane source address so the lane-per-key reads are
-// conflict-free ds_read_b128), and only the per-sequence cache is streamed from HBM.  The first own-key slots are requested
-// before the workgroup waits for the staged prefix (counted vmcnt: the direct-to-LDS loads are older in the queue), so the
-// HBM stream starts at once.  Arithmetic and summation order per (sequence, head) are exactly those of decode_attn_kernel.
-// -DTT_ATTN_STAMPS (a variant build, scripts/attn_phases.py): wave 0 of every workgroup keeps the 100 MHz wall clock of its phase
-// boundaries in scalar registers (no vector-memory operation: the counted vmcnt waits are untouched) and files them at the end
-#ifdef TT_ATTN_STAMPS
-__device__ unsigned long long g_attn_stamps[4096][10];
-#define TT_ASTAMP(i) do { st[i] = wall_clock64(); } while (0)
-#else
-#define TT_ASTAMP(i)
-#endif
-template <typename T, int NSEQ>
-__global__ __launch_bounds__(NSEQ * 64, 4) void decode_attn_lds_kernel(DecodeAttnArgs a, int ctx_cap, int kl_bytes, int vl_bytes) {
-  typedef typename Vec<T>::x8 x8;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_dec[];
-#ifdef TT_ATTN_STAMPS
-  unsigned long long st[10];
-#endif
-  TT_ASTAMP(0);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int h = (int)blockIdx.x;      // grid = (heads, sequence groups)
-  const int b_raw = (int)blockIdx.y * NSEQ + wave;
-  const int b = min(b_raw, a.B - 1);  // surplus waves of the last group repeat its last sequence (never stored)
-  // generated keys 0..*step (read first: a scalar load, nothing in front of it to drain); a session handle's row (NSEQ == 1: one
-  // sequence per workgroup) reads its own newest slot, prefix length and prefix cache - a row that does not decode leaves at once
-  int tgen, P1 = a.P1;
-  size_t goff = 0;
-  if (NSEQ == 1 && a.row_slot) {
-    const int sl = a.row_slot[b];
-    if (sl < 0) return;
-    tgen = sl + 1;
-    P1 = a.row_p1[b];
-    goff = (size_t)b * a.prefix_group_stride;
-  } else {
-    tgen = *a.step + 1;
-  }
-  if (a.ngroups > 1) {  // several utterances in one batch: this workgroup's sequences all belong to one of them (group_size % NSEQ == 0)
-    const int grp = ((int)blockIdx.y * NSEQ) / a.group_size;
-    P1 = a.p1_tab[grp];
-    goff = (size_t)grp * a.prefix_group_stride;
-  }
-  const T* kp = (const T*)a.kp + goff + (size_t)h * P1 * 64;
-  const T* vp = (const T*)a.vp + goff + (size_t)h * P1 * 64;
-  unsigned char* Kl = smem_dec;                 // [slot][8 chunks][64 keys][8]  (chunk-major like the per-sequence cache)
-  unsigned char* Vl = smem_dec + kl_bytes;      // [key][64]
-  float* sc = (float*)(smem_dec + kl_bytes + vl_bytes) + (size_t)wave * ctx_cap;
-  const int nsp = (P1 + 63) >> 6;
-
-  // stage the prefix: K instruction (slot s, chunk c): lane k <- kp[s*64 + k][c*8 .. c*8+7]; V instruction i: rows 8i .. 8i+7
-  {
-    const int nk_ins = nsp * 8, nv_ins = (P1 + 7) >> 3;
-    for (int i = wave; i < nk_ins; i += NSEQ) {
-      const int sidx = i >> 3, c = i & 7;
-      const int key = min(sidx * 64 + lane, P1 - 1);
-      __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)((const char*)kp + ((size_t)key * 64 + c * 8) * sizeof(T)),
-                                       (__attribute__((address_space(3))) void*)(Kl + (size_t)i * 1024), 16, 0, 0);
-    }
-    for (int i = wave; i < nv_ins; i += NSEQ) {
-      const int row = min(i * 8 + (lane >> 3), P1 - 1);
-      __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)((const char*)vp + ((size_t)row * 64 + (lane & 7) * 8) * sizeof(T)),
-                                       (__attribute__((address_space(3))) void*)(Vl + (size_t)i * 1024), 16, 0, 0);
-    }
-  }
-  const int ctx = P1 + tgen;
-  const size_t bh = (size_t)b * a.heads + h;
-  const T* kc = (const T*)a.kc + bh * 8 * a.tmax * 8;
-  const T* vc = (const T*)a.vc + bh * a.tmax * 64;
-
-  float mx = -1e30f;
-  // The query is wave-uniform: it lives in 32 SGPRs (two s_load_dwordx16), not in 32 VGPRs per lane, and its load is not on
-  // the vector-memory counter, so nothing the compiler places between the staged prefix and the first use of q can force a
-  // vmcnt(0) that would also drain the own-key requests below.  (Inline asm: hipcc only emits scalar loads for memory it can
-  // prove read-only, and q was written by the previous kernel.)
-  typedef int int16v __attribute__((ext_vector_type(16)));
-  typedef int int4v __attribute__((ext_vector_type(4)));
-  int16v qlo, qhi;
-  {
-    const T* qp = (const T*)a.q + (size_t)b * a.heads * 64 + h * 64;
-    // early-clobber outputs: the second load still reads the address pair after the first one has been issued (and may have landed)
-    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40" : "=&s"(qlo), "=&s"(qhi) : "s"(qp) : "memory");
-  }
-  const int nso = (tgen + 63) >> 6;
-  auto load_own = [&](x8 (&kk)[8], int slot) {  // own keys of slot (clamped: an odd slot count repeats the last slot, result dropped)
-    const int k = min(slot, nso - 1) * 64 + lane;
-    const unsigned off = (unsigned)min(k, tgen - 1) * 8u * (unsigned)sizeof(T);
-    const unsigned cs = (unsigned)a.tmax * 8u * (unsigned)sizeof(T);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) kk[c] = *(const x8*)((const char*)kc + (off + c * cs));
-  };
-  x8 k0[8], k1[8];
-  load_own(k0, 0);
-  load_own(k1, 1);
-  TT_ASTAMP(1);
-  // the staged prefix must have landed (this wave's direct-to-LDS loads are older than the 16 register loads above)
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(qlo), "+s"(qhi)::"memory");  // q has landed (every later use depends on this statement)
-  TT_ASTAMP(2);
-  x8 qk[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int16v& src = c < 4 ? qlo : qhi;
-    int4v w;
-    w[0] = src[(c & 3) * 4 + 0]; w[1] = src[(c & 3) * 4 + 1]; w[2] = src[(c & 3) * 4 + 2]; w[3] = src[(c & 3) * 4 + 3];
-    qk[c] = __builtin_bit_cast(x8, w);
-  }
-  // prefix scores from LDS
-#pragma unroll 1
-  for (int sidx = 0; sidx < nsp; ++sidx) {
-    float sv = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) sv = dot8(qk[c], *(const x8*)(Kl + ((size_t)(sidx * 8 + c) * 64 + lane) * 16), sv);
-    const int k = sidx * 64 + lane;
-    if (k < P1) {
-      sc[k] = sv;
-      mx = fmaxf(mx, sv);
-    }
-  }
-  TT_ASTAMP(3);
-  // own scores, two slots per iteration
-#pragma unroll 1
-  for (int sl0 = 0; sl0 < nso; sl0 += 2) {
-    if (sl0 > 0) {
-      load_own(k0, sl0);
-      load_own(k1, sl0 + 1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s0 = dot8(qk[c], k0[c], s0);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s1 = dot8(qk[c], k1[c], s1);
-    const int ka = sl0 * 64 + lane, kb = ka + 64;
-    if (ka < tgen) {
-      sc[P1 + ka] = s0;
-      mx = fmaxf(mx, s0);
-    }
-    if (kb < tgen && sl0 + 1 < nso) {
-      sc[P1 + kb] = s1;
-      mx = fmaxf(mx, s1);
-    }
-  }
-
-  TT_ASTAMP(4);
-  const int kk8 = lane >> 3, cg = lane & 7;
-  const int nvp = (P1 + DEC_VKEYS - 1) / DEC_VKEYS, nvo = (tgen + DEC_VKEYS - 1) / DEC_VKEYS;
-  auto load_v = [&](x8 (&t)[DEC_VROWS], int it) {  // own rows of iteration `it` (past the end: the last rows again, weighted 0)
-    const int k0r = min(it, nvo - 1) * DEC_VKEYS + kk8;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const unsigned jc = (unsigned)min(k0r + 8 * u, tgen - 1);
-      t[u] = *(const x8*)((const char*)vc + (jc * 64u + (unsigned)cg * 8u) * (unsigned)sizeof(T));
-    }
-  };
-  x8 ta[DEC_VROWS], tb[DEC_VROWS];
-  load_v(ta, 0);  // the first V rows do not depend on the scores: request them before the softmax
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < ctx; j += 64) {
-    const float e = __expf(sc[j] - mx);
-    sc[j] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // sc[] is private to this wave: LDS operations of a wave execute in order
-  TT_ASTAMP(5);
-  float o[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) o[c] = 0.f;
-  // prefix rows from LDS
-#pragma unroll 1
-  for (int it = 0; it < nvp; ++it) {
-    const int k0r = it * DEC_VKEYS + kk8;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const int j = k0r + 8 * u;
-      const float pj = j < P1 ? sc[j] : 0.f;
-      const x8 t = *(const x8*)(Vl + ((size_t)min(j, P1 - 1) * 64 + cg * 8) * sizeof(T));
-#pragma unroll
-      for (int c = 0; c < 8; ++c) o[c] += pj * (float)t[c];
-    }
-  }
-  TT_ASTAMP(6);
-  auto consume = [&](const x8 (&t)[DEC_VROWS], int it) {
-    const int k0r = it * DEC_VKEYS + kk8, lim = it < nvo ? tgen : 0;
-    const float* scs = sc + P1;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const int j = k0r + 8 * u;
-      const float pj = j < lim ? scs[j] : 0.f;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) o[c] += pj * (float)t[u][c];
-    }
-  };
-#pragma unroll 1
-  for (int it = 0; it < nvo; it += 2) {  // two register sets: the next rows are in flight while these are summed
-    load_v(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    consume(ta, it);
-    __builtin_amdgcn_sched_barrier(0);
-    load_v(ta, it + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    consume(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  TT_ASTAMP(7);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {  // sum the 8 key sub-rows (lanes with equal channel group)
-    o[c] = add_xor8(o[c]);
-    o[c] = add_xor16(o[c]);
-    o[c] = add_xor32(o[c]);
-  }
-  if (b_raw < a.B && kk8 == 0) {
-    const float inv = 1.0f / sum;
-    x8 r;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) r[c] = (T)(o[c] * inv);
-    *(x8*)((T*)a.out + (size_t)b * a.heads * 64 + h * 64 + cg * 8) = r;
-  }
-#ifdef TT_ATTN_STAMPS
-  TT_ASTAMP(8);
-  if (threadIdx.x == 0) {
-    const int wg = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-    if (wg < 4096) {
-      for (int i = 0; i < 9; ++i) g_attn_stamps[wg][i] = st[i];
-      unsigned xcc = 0;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      g_attn_stamps[wg][9] = xcc;
-    }
-  }
-#endif
-}
-#ifdef TT_ATTN_STAMPS
-}  // namespace tt
-extern "C" int ttx_attn_stamps(unsigned long long* out, int nwg) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(tt::g_attn_stamps), (size_t)nwg * 10 * sizeof(unsigned long long));
-}
-namespace tt {
-#endif
-
-// ------------------------------------------------------------------------------- decode: QKV projection + attention, one launch
-// A workgroup = one head x 16 sequences (16 waves, the NSEQ = 16 geometry above).  What it needs of the QKV GEMM is a 16 x 192 tile
-// over K = 1024 - one MFMA row tile high - and it computes that tile itself instead of reading q and the newest K / V row back from a
-// launch before it: waves 0 .. 11 ("projectors") own one 16-column tile of q, k or v each; waves 12 .. 15 request their sequences' keys at
-// the top and never wait on the vector-memory counter until the projection is done.  A projector requests its own sequence's keys only
-// after its last weight tile (vmcnt retires in order: a weight wait behind an HBM row request would wait for HBM).
-// grid = (heads, groups): workgroup id h + 16 group, so under round-robin placement an XCD sees two heads and keeps 2 x 384 KB of the
-// weight in its L2 (speed only).
-// Bits: per output element the MFMA sequence of gemm_glds_kernel (W fragment as the A operand, k-tiles ascending, the two 32-wide
-// k-steps of a tile in order, accumulator from zero), then EpiQkvDecode's bias add, q_scale and rounding; the attention is
-// decode_attn_lds_kernel's, except that slot t (written by this launch) is taken from the LDS and never read back from memory.
-// LDS: [prefix K | prefix V | R | q 16x64 | new k 16x64 | new v 16x64], R = the 16 activation rows (as 16 swizzled [16][64] k-tiles, the
-// GEMM's A image) + the projectors' weight rings during the projection and the 16 score rows after it.
-// Where the time goes (profiles/r16_qkv_attn_phase_stamps.txt): a CU's vector-memory path answers in request order, so the
-// weight stream is NOT hidden behind the K / V stream as a second, independent stream would be - the projection ends ~14 us after entry
-// and the attention of every wave follows it; the launch is still 2.8 us shorter than the two it replaces (one launch ramp, no q / k / v
-// round trip through memory, the prefix staged beside the projection).
-#ifdef TT_ATTN_STAMPS  // waves 0 and 15 of every workgroup file five wall-clock stamps each (scalar registers until the end)
-#define TT_QSTAMP(i) do { qst[i] = wall_clock64(); } while (0)
-#else
-#define TT_QSTAMP(i)
-#endif
-template <typename T, int QA_DEPTH>  // QA_DEPTH: k-tiles of a projector wave's weight ring (2 KiB each): 4 where the LDS has room, else 3
-__global__ __launch_bounds__(1024, 4) void decode_qkv_attn_kernel(DecodeQkvAttnArgs g, int ctx_cap, int kl_bytes, int vl_bytes, int r_bytes) {
-  typedef typename Vec<T>::x8 x8;
-  typedef typename Vec<T>::x4 x4;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_qa[];
-  const DecodeAttnArgs& a = g.d;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef TT_ATTN_STAMPS
-  unsigned long long qst[5];
-  qst[2] = 0;
-#endif
-  TT_QSTAMP(0);
-  const int h = (int)blockIdx.x;                 // grid = (16 heads, B / 16)
-  const int row0 = (int)blockIdx.y * 16;         // first sequence of the group
-  const int b = row0 + wave;
-  const int t = *a.step;                         // slot of the new key (scalar load, first in the queue); keys 0 .. t-1 are in the cache
-  const int tgen = t + 1;
-  const int P1 = a.P1;
-  const T* kp = (const T*)a.kp + (size_t)h * P1 * 64;
-  const T* vp = (const T*)a.vp + (size_t)h * P1 * 64;
-  unsigned char* Kl = smem_qa;                   // [slot][8 chunks][64 keys][8]
-  unsigned char* Vl = smem_qa + kl_bytes;        // [key][64]
-  unsigned char* R = smem_qa + kl_bytes + vl_bytes;
-  float* sc = (float*)R + (size_t)wave * ctx_cap;
-  T* qs = (T*)(R + r_bytes);                     // [16 sequences][64]
-  T* kn = qs + 16 * 64;
-  T* vn = kn + 16 * 64;
-  const int nsp = (P1 + 63) >> 6;
-
-  {  // stage the prefix (as decode_attn_lds_kernel) and the 16 activation rows: piece i = k-tile i >> 1, rows 8 (i & 1) .. + 7
-    const int nk_ins = nsp * 8, nv_ins = (P1 + 7) >> 3;
-    for (int i = wave; i < nk_ins; i += 16) {
-      const int sidx = i >> 3, c = i & 7;
-      const int key = min(sidx * 64 + lane, P1 - 1);
-      __builtin_amdgcn_global_load_lds((gbl_void_a*)((const char*)kp + ((size_t)key * 64 + c * 8) * sizeof(T)), (lds_void_a*)(Kl + (size_t)i * 1024), 16, 0, 0);
-    }
-    for (int i = wave; i < nv_ins; i += 16) {
-      const int row = min(i * 8 + (lane >> 3), P1 - 1);
-      __builtin_amdgcn_global_load_lds((gbl_void_a*)((const char*)vp + ((size_t)row * 64 + (lane & 7) * 8) * sizeof(T)), (lds_void_a*)(Vl + (size_t)i * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int i = wave + 16 * u;
-      const int row = (i & 1) * 8 + (lane >> 3);
-      const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-      const T* src = (const T*)g.h + (size_t)(row0 + row) * 1024 + (i >> 1) * 64 + chunk * 8;
-      __builtin_amdgcn_global_load_lds((gbl_void_a*)src, (lds_void_a*)(R + (size_t)i * 1024), 16, 0, 0);
-    }
-  }
-  const size_t bh = (size_t)b * 16 + h;
-  const T* kc = (const T*)a.kc + bh * 8 * a.tmax * 8;
-  const T* vc = (const T*)a.vc + bh * a.tmax * 64;
-  // Newest own key that may be read from memory.  At t == 0 there is none: the (clamped, unconditional) requests then have no valid row of the
-  // cache to repeat.  The key requests still name slot 0 - whatever they return only feeds a score that is replaced by s_new or never
-  // stored - but a value row is MULTIPLIED by its zero weight, and 0 x a stale NaN / Inf of the cache would poison the output row: at
-  // t == 0 the value requests read row 0 of the staged head's prefix values instead (P1 >= 1; always written by the prefill, finite)
-  const int told = max(t - 1, 0);
-  const char* vrows = t > 0 ? (const char*)vc : (const char*)vp;
-  const int nso = (tgen + 63) >> 6;
-  auto load_own = [&](x8 (&kk)[8], int slot) {
-    const int k = min(slot, nso - 1) * 64 + lane;
-    const unsigned off = (unsigned)min(k, told) * 8u * (unsigned)sizeof(T);
-    const unsigned cs = (unsigned)a.tmax * 8u * (unsigned)sizeof(T);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) kk[c] = *(const x8*)((const char*)kc + (off + c * cs));
-  };
-  const int kk8 = lane >> 3, cg = lane & 7;
-  const int nvp = (P1 + DEC_VKEYS - 1) / DEC_VKEYS, nvo = (tgen + DEC_VKEYS - 1) / DEC_VKEYS;
-  auto load_v = [&](x8 (&tv)[DEC_VROWS], int it) {
-    const int k0r = min(it, nvo - 1) * DEC_VKEYS + kk8;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const unsigned jc = (unsigned)min(k0r + 8 * u, told);
-      tv[u] = *(const x8*)(vrows + (jc * 64u + (unsigned)cg * 8u) * (unsigned)sizeof(T));
-    }
-  };
-  x8 k0[8], k1[8];
-  const bool proj = wave < 12;                   // wave-uniform; projector w owns tile w: part (q, k, v) = w >> 2, columns 16 (w & 3) .. + 15 of the head
-  // A projector's weight tile goes global -> LDS directly, whole 128-byte lines (two 1-KiB pieces of 8 rows per k-tile, XOR-swizzled on the
-  // source side like the GEMM's W image), into a ring of its OWN: the wave that issued a piece is the only one that reads it, so a counted
-  // vmcnt is all the synchronisation the ring needs.  (Fragment loads straight from memory take half a line per row and reached 30 GB/s
-  // per CU; profiles/r16_qkv_attn_phase_stamps.txt.)
-  constexpr int DEPTH = QA_DEPTH;                // k-tiles per ring: DEPTH - 1 in flight while one is multiplied
-  const int fr = lane & 15, fg = lane >> 4;
-  const int part = wave >> 2, dcol = (wave & 3) * 16 + fg * 4;
-  unsigned char* ring = R + 16 * 1024 * 2 + (size_t)wave * (DEPTH * 2048);
-  const T* wsrc[2];
-  auto issue_w = [&](int kt) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      __builtin_amdgcn_global_load_lds((gbl_void_a*)(wsrc[j] + kt * 64), (lds_void_a*)(ring + (kt % DEPTH) * 2048 + j * 1024), 16, 0, 0);
-  };
-  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!proj) {
-    load_own(k0, 0);
-    load_own(k1, 1);
-    // the staged prefix and activation rows have landed: they are older in this wave's queue than the key requests.  Counted on the emitted
-    // code: load_own is 8 global_load_dwordx4 per call, so exactly 16 vector loads are younger than this wave's LDS-DMA pieces
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int r = j * 8 + (lane >> 3);
-      wsrc[j] = (const T*)g.w_qkv + (size_t)(part * 1024 + h * 64 + (wave & 3) * 16 + r) * 1024 + (((lane & 7) ^ ((r >> 1) & 7)) * 8);
-    }
-    // one global_load_dwordx4, issued AHEAD of the ring (the emitted order is bias, then the pieces), so every counted wait below covers it
-    // and none has to count it
-    if (g.b_qkv) bv = *(const float4*)(g.b_qkv + part * 1024 + h * 64 + dcol);
-    // The first DEPTH - 1 weight tiles (2 pieces each) are requested ahead of the staging barrier; the wait leaves exactly those
-    // (DEPTH - 1) * 2 pieces in flight.  (hipcc puts an s_waitcnt vmcnt(0) of its own at the top of this branch - it cannot tell the
-    // pending LDS-DMA from the LDS addresses computed here - so in the emitted code the staged rows have in fact landed before the
-    // first ring piece goes out; the source order is what a compiler without that wait would give.)
-#pragma unroll
-    for (int s_ = 0; s_ < DEPTH - 1; ++s_) issue_w(s_);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1) * 2) : "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  TT_QSTAMP(1);
-
-  if (proj) {
-    const unsigned char* ap = R + fr * 128;
-    const int asw = (fr >> 1) & 7;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < 16; ++kt) {
-      // tile kt has landed: of the tiles kt + 1 .. kt + DEPTH - 2 requested after it, those that exist may still be in flight (2 pieces
-      // per tile and nothing else on the counter: no other vector load or store is issued inside the loop).  hipcc adds a vmcnt(0) of its
-      // own in front of the first LDS read at kt = 0, so the ring starts from fully landed
-      switch ((kt + DEPTH - 2 < 16 ? DEPTH - 2 : 15 - kt) * 2) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 2) * 2) : "memory"); break;
-      }
-      if (kt + DEPTH - 1 < 16) issue_w(kt + DEPTH - 1);  // into the slot tile kt - 1 left
-      const unsigned char* ws = ring + (kt % DEPTH) * 2048 + fr * 128;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const x8 fw = *(const x8*)(ws + (((ks * 4 + fg) ^ asw) * 16));
-        const x8 fa = *(const x8*)(ap + kt * 2048 + (((ks * 4 + fg) ^ asw) * 16));
-        acc = mfma16(fw, fa, acc);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // EpiQkvDecode: lane (fr, fg) holds row fr, columns dcol .. dcol + 3 of the head
-    const size_t bhr = (size_t)(row0 + fr) * 16 + h;
-    acc[0] += bv.x; acc[1] += bv.y; acc[2] += bv.z; acc[3] += bv.w;
-    if (part == 0) {
-      const x4 qv = pack4<T>(acc[0] * g.q_scale, acc[1] * g.q_scale, acc[2] * g.q_scale, acc[3] * g.q_scale);
-      *(x4*)(qs + fr * 64 + dcol) = qv;
-      if (g.q_out) *(x4*)((T*)g.q_out + (size_t)(row0 + fr) * 1024 + h * 64 + dcol) = qv;
-    } else if (part == 1) {
-      const x4 kv = pack4<T>(acc[0], acc[1], acc[2], acc[3]);
-      *(x4*)(kn + fr * 64 + dcol) = kv;
-      *(x4*)((T*)a.kc + ((bhr * 8 + (dcol >> 3)) * a.tmax + t) * 8 + (dcol & 7)) = kv;
-    } else {
-      const x4 vv = pack4<T>(acc[0], acc[1], acc[2], acc[3]);
-      *(x4*)(vn + fr * 64 + dcol) = vv;
-      *(x4*)((T*)a.vc + (bhr * a.tmax + t) * 64 + dcol) = vv;
-    }
-    TT_QSTAMP(2);
-    load_own(k0, 0);
-    load_own(k1, 1);
-  }
-  // The projectors' q / k / v rows are in the LDS.  Behind the barrier hipcc places an s_waitcnt vmcnt(0) in front of the LDS read of q
-  // (pending LDS-DMA and LDS reads it cannot tell apart), which also waits for the 16 key requests: a projector, which asked for its keys
-  // just above, pays one HBM round trip there before its prefix scores start.  decode_attn_lds_kernel avoids that wait by taking q through
-  // scalar loads; here q only exists in the LDS.  The phase times of DESIGN 5.21 include it.
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef TT_ATTN_STAMPS
-  const unsigned long long qarrive = wall_clock64();  // every wave: its arrival at the second barrier
-#endif
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  TT_QSTAMP(3);
-
-  // ---- attention: decode_attn_lds_kernel's arithmetic and order; the activation image is dead, its place takes the score rows
-  const int ctx = P1 + tgen;
-  float mx = -1e30f;
-  // the query is wave-uniform: 32 SGPRs, not 32 VGPRs per lane (as in decode_attn_lds_kernel; here it comes from the LDS)
-  typedef int int4v __attribute__((ext_vector_type(4)));
-  x8 qk[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int4v w = *(const int4v*)(qs + wave * 64 + c * 8);
-    int4v u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) u[i] = __builtin_amdgcn_readfirstlane(w[i]);
-    qk[c] = __builtin_bit_cast(x8, u);
-  }
-#pragma unroll 1
-  for (int sidx = 0; sidx < nsp; ++sidx) {
-    float sv = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) sv = dot8(qk[c], *(const x8*)(Kl + ((size_t)(sidx * 8 + c) * 64 + lane) * 16), sv);
-    const int k = sidx * 64 + lane;
-    if (k < P1) {
-      sc[k] = sv;
-      mx = fmaxf(mx, sv);
-    }
-  }
-  float s_new = 0.f;  // the new key's score, from the LDS copy of its row
-#pragma unroll
-  for (int c = 0; c < 8; ++c) s_new = dot8(qk[c], *(const x8*)(kn + wave * 64 + c * 8), s_new);
-#pragma unroll 1
-  for (int sl0 = 0; sl0 < nso; sl0 += 2) {
-    if (sl0 > 0) {
-      load_own(k0, sl0);
-      load_own(k1, sl0 + 1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s0 = dot8(qk[c], k0[c], s0);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s1 = dot8(qk[c], k1[c], s1);
-    const int ka = sl0 * 64 + lane, kb = ka + 64;
-    if (ka == t) s0 = s_new;
-    if (kb == t) s1 = s_new;
-    if (ka < tgen) {
-      sc[P1 + ka] = s0;
-      mx = fmaxf(mx, s0);
-    }
-    if (kb < tgen && sl0 + 1 < nso) {
-      sc[P1 + kb] = s1;
-      mx = fmaxf(mx, s1);
-    }
-  }
-  x8 ta[DEC_VROWS], tb[DEC_VROWS];
-  load_v(ta, 0);  // the first V rows do not depend on the scores: request them before the softmax
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < ctx; j += 64) {
-    const float e = __expf(sc[j] - mx);
-    sc[j] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // sc[] is private to this wave: LDS operations of a wave execute in order
-  float o[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) o[c] = 0.f;
-#pragma unroll 1
-  for (int it = 0; it < nvp; ++it) {
-    const int k0r = it * DEC_VKEYS + kk8;
-#pragma unroll
-    for (int u = 0; u < DEC_VROWS; ++u) {
-      const int j = k0r + 8 * u;
-      const float pj = j < P1 ? sc[j] : 0.f;
-      const x8 tv = *(const x8*)(Vl + ((size_t)min(j, P1 - 1) * 64 + cg * 8) * sizeof(T));
-#pragma unroll
-      for (int c = 0; c < 8; ++c) o[c] += pj * (float)tv[c];
-    }
-  }
-  const int it_new = t / DEC_VKEYS;  // the PV iteration that holds slot t
-  auto consume = [&](const x8 (&tv)[DEC_VROWS], int it) {
-    const int k0r = it * DEC_VKEYS + kk8, lim = it < nvo ? tgen : 0;
-    const float* scs = sc + P1;
-    if (it == it_new) {  // wave-uniform: the lane whose row is slot t takes it from the LDS
-      const x8 vnew = *(const x8*)(vn + wave * 64 + cg * 8);
-#pragma unroll
-      for (int u = 0; u < DEC_VROWS; ++u) {
-        const int j = k0r + 8 * u;
-        const float pj = j < lim ? scs[j] : 0.f;
-        const x8 row = j == t ? vnew : tv[u];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o[c] += pj * (float)row[c];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < DEC_VROWS; ++u) {
-        const int j = k0r + 8 * u;
-        const float pj = j < lim ? scs[j] : 0.f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o[c] += pj * (float)tv[u][c];
-      }
-    }
-  };
-#pragma unroll 1
-  for (int it = 0; it < nvo; it += 2) {
-    load_v(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    consume(ta, it);
-    __builtin_amdgcn_sched_barrier(0);
-    load_v(ta, it + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    consume(tb, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    o[c] = add_xor8(o[c]);
-    o[c] = add_xor16(o[c]);
-    o[c] = add_xor32(o[c]);
-  }
-  if (kk8 == 0) {
-    const float inv = 1.0f / sum;
-    x8 r;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) r[c] = (T)(o[c] * inv);
-    *(x8*)((T*)a.out + (size_t)b * 1024 + h * 64 + cg * 8) = r;
-  }
-#ifdef TT_ATTN_STAMPS
-  TT_QSTAMP(4);
-  if (lane == 0 && (wave == 0 || wave == 15)) {
-    const int wg = (int)blockIdx.y * 16 + (int)blockIdx.x;
-    if (wg < 4096)
-      for (int i = 0; i < 5; ++i) g_attn_stamps[wg][(wave ? 5 : 0) + i] = qst[i];
-  }
-  if (lane == 0) {  // rows 256 .. 767: every wave's arrival at the second barrier (waves 0 .. 9, then 10 .. 15) of workgroups 0 .. 255
-    const int wg = (int)blockIdx.y * 16 + (int)blockIdx.x;
-    if (wg < 256) g_attn_stamps[(wave < 10 ? 256 : 512) + wg][wave < 10 ? wave : wave - 10] = qarrive;
-  }
-#endif
-}
-
-static size_t qkv_attention_lds(int P1, int tmax, int depth) {
-  const size_t kl = (size_t)((P1 + 63) >> 6) * 8 * 1024, vl = (size_t)((P1 + 7) >> 3) * 1024;
-  const size_t rows = ((size_t)16 * (P1 + tmax) * sizeof(float) + 15) & ~(size_t)15;
-  const size_t image = (size_t)16 * 1024 * 2 + (size_t)12 * depth * 2048;  // the activation rows + the projectors' weight rings
-  return kl + vl + (rows > image ? rows : image) + 3 * 16 * 64 * 2;
-}
-size_t decode_qkv_attention_lds(int P1, int tmax) { return qkv_attention_lds(P1, tmax, 3); }
-
-int decode_qkv_attention_launch(int dtype, const DecodeQkvAttnArgs& g, hipStream_t stream) {
-  const DecodeAttnArgs& a = g.d;
-  TT_REQUIRE(dtype == DT_BF16 || dtype == DT_F16, "decode_qkv_attention: 16-bit operands only");
-  TT_REQUIRE(a.B > 0 && a.B % 16 == 0 && a.heads == 16 && a.P1 >= 1 && a.tmax > 0 && a.ngroups <= 1 && !a.row_slot && a.step && g.h && g.w_qkv,
-             "decode_qkv_attention: needs 16 heads of 64, a multiple of 16 sequences, one prefix group and no session rows (B=%d heads=%d P1=%d)",
-             a.B, a.heads, a.P1);
-  const int depth = qkv_attention_lds(a.P1, a.tmax, 4) <= DECODE_LDS_CAP ? 4 : 3;
-  const size_t smem = qkv_attention_lds(a.P1, a.tmax, depth);
-  TT_REQUIRE(smem <= DECODE_LDS_CAP, "decode_qkv_attention: prefix %d with %d KV slots needs %zu bytes of LDS, %zu available", a.P1, a.tmax, smem, DECODE_LDS_CAP);
-  const int ctx_cap = a.P1 + a.tmax;
-  const int kl_bytes = ((a.P1 + 63) >> 6) * 8 * 1024, vl_bytes = ((a.P1 + 7) >> 3) * 1024;
-  const int r_bytes = (int)(smem - kl_bytes - vl_bytes - 3 * 16 * 64 * 2);
-  // projection 2 * B * 3072 * 1024 + attention; K / V rows + prefix + the QKV weight once + activation rows in, attention rows out
-  ProfScope ps(PROF_DECODE_QKV_ATTN, stream, 2.0 * a.B * 3072.0 * 1024.0 + 4.0 * a.B * a.heads * 64.0 * (a.P1 + a.host_tgen),
-               ((double)a.B * a.host_tgen + a.P1) * a.heads * 64 * 2 * 2.0 + 3072.0 * 1024.0 * 2.0 + 2.0 * a.B * 1024 * 2.0, true);
-  const dim3 blocks(16, a.B / 16);
-#define TT_QA(T, DP)                                                                                                                 \
-  do {                                                                                                                             \
-    static bool attr_done = false;                                                                                                 \
-    if (!attr_done) {                                                                                                              \
-      TT_CHECK_HIP(hipFuncSetAttribute((const void*)decode_qkv_attn_kernel<T, DP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-      attr_done = true;                                                                                                            \
-    }                                                                                                                              \
-    launch_timed(ps, decode_qkv_attn_kernel<T, DP>, blocks, dim3(1024), smem, stream, g, ctx_cap, kl_bytes, vl_bytes, r_bytes);     \
-  } while (0)
-  if (depth == 4) { if (dtype == DT_BF16) TT_QA(bf16, 4); else TT_QA(f16, 4); }
-  else { if (dtype == DT_BF16) TT_QA(bf16, 3); else TT_QA(f16, 3); }
-#undef TT_QA
-  TT_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-size_t decode_attention_session_lds(int p1_cap, int tmax) {
-  return (size_t)((p1_cap + 63) >> 6) * 8 * 1024 + (size_t)((p1_cap + 7) >> 3) * 1024 + (size_t)(p1_cap + tmax) * sizeof(float);
-}
-
-int decode_attention_launch(int dtype, const DecodeAttnArgs& a, hipStream_t stream) {
-  if (dtype == DT_F32) return decode_attn_f32_launch(a, stream);  // verification mode (attention_f32.hip)
-  TT_REQUIRE(a.B > 0 && a.heads > 0 && a.P1 >= 0 && a.tmax > 0, "decode_attention: bad shape");
-  const int ctx_cap = a.P1 + a.tmax;
-  // algorithmic bytes: every sequence reads its own generated K and V rows once (host_tgen keys) + the shared prefix once
-  ProfScope ps(PROF_DECODE_ATTN, stream, 4.0 * a.B * a.heads * 64.0 * (a.P1 + a.host_tgen),
-               ((double)a.B * a.host_tgen + a.P1) * a.heads * 64 * 2 * 2.0 + 2.0 * a.B * a.heads * 64 * 2.0, true);
-  // shared-prefix kernel with 4 sequences per workgroup (measured 2 % ahead of 16 at 256 candidates and 40 % ahead at 32:
-  // more, smaller workgroups); the per-wave kernel only when the staged prefix + score rows do not fit the LDS (very long prompts)
-  int nseq = a.variant == 1 ? 0 : a.variant == 2 ? 16 : 4;
-  if (a.row_slot) {  // session handle: one row per workgroup, the LDS sized for the prefix capacity a.P1
-    TT_REQUIRE(a.row_p1 && a.prefix_group_stride && a.ngroups <= 1 && a.P1 >= 1, "decode_attention: per-row sessions need row_p1, a prefix stride and a prefix capacity");
-    nseq = 1;
-  }
-  if (a.ngroups > 1) {
-    TT_REQUIRE(a.ngroups <= 16 && a.group_size > 0 && a.group_size % 4 == 0 && a.B == a.ngroups * a.group_size,
-               "decode_attention: %d groups of %d sequences (a multiple of 4) do not make %d sequences", a.ngroups, a.group_size, a.B);
-    nseq = 4;
-  }
-  const int kl_bytes = ((a.P1 + 63) >> 6) * 8 * 1024, vl_bytes = ((a.P1 + 7) >> 3) * 1024;
-  if (a.P1 < 1) nseq = 0;
-  TT_REQUIRE(!a.row_slot || decode_attention_session_lds(a.P1, a.tmax) <= DECODE_LDS_CAP,
-             "decode_attention: a session row's prefix capacity %d does not fit the LDS", a.P1);
-  if (nseq && (size_t)kl_bytes + vl_bytes + (size_t)nseq * ctx_cap * sizeof(float) > 160 * 1024) nseq = nseq == 16 ? 4 : 0;
-  if (nseq && (size_t)kl_bytes + vl_bytes + (size_t)nseq * ctx_cap * sizeof(float) > 160 * 1024) nseq = 0;
-  if (nseq) {
-    const size_t smem = (size_t)kl_bytes + vl_bytes + (size_t)nseq * ctx_cap * sizeof(float);
-    const dim3 blocks(a.heads, cdiv(a.B, nseq));
-#define TT_DEC(T, NS)                                                                                                              \
-    do {                                                                                                                             \
-      static bool attr_done = false;                                                                                                 \
-      if (!attr_done) {                                                                                                              \
-        TT_CHECK_HIP(hipFuncSetAttribute((const void*)decode_attn_lds_kernel<T, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        attr_done = true;                                                                                                            \
-      }                                                                                                                              \
-      launch_timed(ps, decode_attn_lds_kernel<T, NS>, blocks, dim3(NS * 64), smem, stream, a, ctx_cap, kl_bytes, vl_bytes);          \
-    } while (0)
-    if (dtype == DT_BF16) { if (nseq == 16) TT_DEC(bf16, 16); else if (nseq == 1) TT_DEC(bf16, 1); else TT_DEC(bf16, 4); }
-    else { if (nseq == 16) TT_DEC(f16, 16); else if (nseq == 1) TT_DEC(f16, 1); else TT_DEC(f16, 4); }
-#undef TT_DEC
-    TT_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  TT_REQUIRE(a.ngroups <= 1, "decode_attention: the prefixes of a multi-utterance batch (%d rows) do not fit the LDS", a.P1);
-  const size_t smem = (size_t)4 * ctx_cap * sizeof(float);
-  TT_REQUIRE(smem <= 64 * 1024, "decode_attention: context %d too long for the score buffer", ctx_cap);
-  const int blocks = cdiv(a.B * a.heads, 4);
-  if (dtype == DT_BF16) launch_timed(ps, decode_attn_kernel<bf16>, dim3(blocks), dim3(256), smem, stream, a, ctx_cap);
-  else launch_timed(ps, decode_attn_kernel<f16>, dim3(blocks), dim3(256), smem, stream, a, ctx_cap);
   TT_CHECK_HIP(hipGetLastError());
   return 0;
 }

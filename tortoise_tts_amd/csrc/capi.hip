@@ -276,7 +276,7 @@ int tt_op_decode_attention(int dtype, const void* q, const void* kp, const void*
   return 0;
 }
 
-// The decode step's QKV projection + attention in one launch (attention.hip decode_qkv_attn_kernel) on caller-provided caches: own keys
+// The decode step's QKV projection + attention in one launch (decode_attention.hip decode_qkv_attn_kernel) on caller-provided caches: own keys
 // 0 .. tgen - 2 are in the caches, the launch appends slot tgen - 1 from h W^T + bias and attends [prefix | own keys 0 .. tgen - 1].
 int tt_op_decode_qkv_attention(int dtype, const void* h, const void* w_qkv, const float* b_qkv, float q_scale, const void* kp, const void* vp, int P1,
                                void* kc, void* vc, int tmax, int tgen, void* q_out, void* out, int B, int heads, void* stream) {

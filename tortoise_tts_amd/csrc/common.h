@@ -61,6 +61,10 @@ template <typename T> __device__ __forceinline__ typename Vec<T>::x4 pack4(float
   return r;
 }
 
+// address-space-qualified void for __builtin_amdgcn_global_load_lds (global -> LDS directly)
+typedef __attribute__((address_space(3))) void lds_void_a;
+typedef __attribute__((address_space(1))) const void gbl_void_a;
+
 // Cross-lane exchanges without the LDS: __shfl_xor compiles to ds_bpermute_b32 + s_waitcnt (a ~100-cycle LDS round trip per
 // step, 6 of them in a wave reduction, and at one or two waves per SIMD nothing hides them).  Within a row of 16 lanes the
 // DPP modifier does the exchange inside the VALU instruction; across rows gfx950 has v_permlane16_swap / v_permlane32_swap.
@@ -207,7 +211,7 @@ enum ProfId {  // one class per kernel instantiation that actually runs (names: 
   PROF_GEMM_GNA,          // GEMM with the GroupNorm apply on its A path (gemm_gna.h)
   PROF_GEMM_32x16_STD, PROF_GEMM_32x16_QKVDEC, PROF_GEMM_64x16_STD, PROF_GEMM_64x16_QKVDEC,  // skinny decode tiles (small batches)
   PROF_GEMV,              // GEMV-shaped decode GEMMs of handles with max_batch <= 4 (gemv.hip)
-  PROF_DECODE_QKV_ATTN,   // the decode step's QKV projection + attention in one launch (attention.hip decode_qkv_attn_kernel)
+  PROF_DECODE_QKV_ATTN,   // the decode step's QKV projection + attention in one launch (decode_attention.hip decode_qkv_attn_kernel)
   PROF_COUNT
 };
 extern bool g_prof_on;

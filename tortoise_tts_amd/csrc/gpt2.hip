@@ -8,7 +8,7 @@
 //                is replayed from one hipGraph.  Batches of <= 64 sequences (the per-rank share of a candidate-sharded job) run their
 //                GEMMs on 16-column tiles so that the weight stream is spread over 192 - 512 workgroups (gemm_impl.h Tile).
 //                At 256 / 512 candidates (full rounds of the attention's 16-sequence workgroups) the QKV GEMM and the attention are ONE launch
-//                (attention.hip decode_qkv_attn_kernel, TT_AR_OPT_FUSED_QKV_ATTN; same bits): six launches per layer.
+//                (decode_attention.hip decode_qkv_attn_kernel, TT_AR_OPT_FUSED_QKV_ATTN; same bits): six launches per layer.
 //                (A five-launch form - LayerNorm folded into the GEMMs algebraically, split-K folded in-launch behind arrival tickets -
 //                was built and measured 0.7 - 10 % slower at every batch size from 16 to 256: profiles/r05_ab_ar_five_launch_step.txt,
 //                profiles/r06_ab_small_batch_decode.txt; it is not in the library.)

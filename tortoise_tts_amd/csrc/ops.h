@@ -134,7 +134,7 @@ size_t decode_attention_session_lds(int p1_cap, int tmax);
 constexpr size_t DECODE_LDS_CAP = 160 * 1024;
 int decode_attn_f32_launch(const DecodeAttnArgs& a, hipStream_t stream);  // fp32 verification mode (attention_f32.hip)
 
-// The decode step's QKV projection and attention in ONE launch (attention.hip decode_qkv_attn_kernel): a workgroup = one head x 16
+// The decode step's QKV projection and attention in ONE launch (decode_attention.hip decode_qkv_attn_kernel): a workgroup = one head x 16
 // sequences computes the 16 x 192 tile of the QKV GEMM it needs itself (K = 1024), appends the new K / V rows at slot *step and
 // attends [prefix | own keys 0 .. *step].  q, k, v carry the bits of gemm_glds<.., EpiQkvDecode>, the output those of
 // decode_attn_lds_kernel.  16-bit operands, model_dim 1024, 16 heads of 64, B % 16 == 0, one prefix group, no session rows.
