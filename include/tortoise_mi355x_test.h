@@ -165,6 +165,11 @@ int tt_op_gn_gemm(int dtype, const float* x, int B, int S, const float* gamma, c
 size_t tt_op_gn_gemm_workspace(int B, int S);
 int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
                           int causal, const float* relpos, void* stream);
+/* the same with padded batch rows and the kernel choice exposed: batch row b attends to (and computes) its first nv[b % nv_period] rows only
+ * (nv: HOST int [nv_period], nv_period <= 32, every entry in 1 .. n; NULL / 0: all n rows); rows of out beyond them are not written.
+ * variant 0 = chosen from the shape, 1 = never the key-split form, 2 = never the 32-query-wave kernel. */
+int tt_op_flash_attention_rows(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
+                               int causal, const float* relpos, const int* nv, int nv_period, int variant, void* stream);
 /* the decode step's attention (HF GPT2Attention under tortoise/models/autoregressive.py:150-163, one query per (sequence, head)):
  * q T [B][heads * 64] pre-scaled by 1/8; shared prefix kp, vp T [heads][P1][64]; per-sequence caches kc T [B][heads][8][tmax][8]
  * (key-major 16-byte chunks), vc T [B][heads][tmax][64] with own keys 0 .. tgen - 1 valid; out T [B][heads * 64].

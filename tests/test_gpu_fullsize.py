@@ -94,7 +94,7 @@ def test_full_ar_prefill_and_cached_steps(sds, name, dt, tdt, tol):
 @torch.no_grad()
 def test_full_clvp_production_config(sds, name, dt, tdt, tol):
     """768-d / 12 heads / 20 layers, 200 codes per candidate.  4 candidates (golden) and 256 candidates (the production
-    batch: flash_kernel<2,false>, 128x128 GEMMs), the latter fed the golden candidates cyclically."""
+    batch: flash32_kernel<T,1> - 6144 workgroups of 128 queries -, 128x128 GEMMs), the latter fed the golden candidates cyclically."""
     cfg = CLVPConfig()
     text, _, _ = GF.prompt()
     codes = GF.clvp_codes()

@@ -1,6 +1,7 @@
 """-m gpu: single HIP kernels (through the C-ABI operator entry points) against plain fp32 PyTorch
 references computed from the SAME operand-rounded inputs.  Tolerances: relative L2 of the output."""
 import ctypes as C
+import functools
 import math
 
 import pytest
@@ -154,13 +155,9 @@ def _attn_ref(q, k, v, causal, relpos):
     return torch.softmax(w, dim=-1) @ v
 
 
-@pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
-@pytest.mark.parametrize("mode", ["plain", "causal", "relpos"])
-@pytest.mark.parametrize("n,B", [(70, 2), (300, 40), (870, 2), (200, 96), (129, 3), (300, 60)])
-def test_flash_attention(lib, name, dt, tdt, tol, mode, n, B):
-    """n <= 128 and every causal case: the 16-query-wave kernels (register-prefetch / LDS-staged).  Non-causal n > 128 (round 5):
-    flash32_kernel, 32-query waves on v_mfma_f32_32x32x16 - 8 waves with a 2-way key split for launches of < 512 workgroups (n = 870 x 4
-    pairs: the denoiser's form; ragged tails 129 / 300; 300 x 120 pairs), 4 waves for more (200 x 1152 pairs)."""
+@functools.lru_cache(maxsize=None)
+def _flash_case(tdt, mode, n, B):
+    """Operands and the fp32 reference of one flash case, made once and shared by the tests below (none of them writes to these)."""
     g = torch.Generator().manual_seed(n)
     H = 2 if n != 200 else 12
     n_pad = (n + 31) // 32 * 32
@@ -170,12 +167,104 @@ def test_flash_attention(lib, name, dt, tdt, tol, mode, n, B):
     vt = torch.zeros(B, H, 64, n_pad, device="cuda", dtype=tdt)
     vt[..., :n] = v.transpose(-1, -2)
     relpos = dev(torch.randn(H, 129, generator=g)) if mode == "relpos" else None
+    ref = _attn_ref(q.float(), k.float(), v.float(), mode == "causal", relpos).permute(0, 2, 1, 3).reshape(B, n, H * 64)
+    return q, k, vt, relpos, ref, H, n_pad
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_flash_cases():
+    """The shared cases stay on the device while this module runs and go when it is done."""
+    yield
+    _flash_case.cache_clear()
+    torch.cuda.empty_cache()
+
+
+def _flash_run(lib, dt, tdt, mode, n, B, variant=0, flash32=1):
+    """One launch through tt_op_flash_attention_rows (flash32 = 0: with the TTX_FLASH32 switch off around the launch, nothing else)."""
+    q, k, vt, relpos, ref, H, n_pad = _flash_case(tdt, mode, n, B)
+    out = torch.zeros(B, n, H * 64, device="cuda", dtype=tdt)
+    torch.cuda.synchronize()
+    prev = lib.ttx_kernel_variant(E.TTX_FLASH32, flash32)
+    try:
+        E.check(lib.tt_op_flash_attention_rows(dt, E.ptr(q), E.ptr(k), E.ptr(vt), E.ptr(out), B, H, n, n_pad, int(mode == "causal"),
+                                               E.ptr(relpos), None, 0, variant, None))
+        torch.cuda.synchronize()
+    finally:
+        lib.ttx_kernel_variant(E.TTX_FLASH32, prev)
+    return out, ref
+
+
+@pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
+@pytest.mark.parametrize("mode", ["plain", "causal", "relpos"])
+@pytest.mark.parametrize("n,B", [(70, 2), (300, 40), (870, 2), (200, 96), (129, 3), (300, 60), (200, 24)])
+def test_flash_attention(lib, name, dt, tdt, tol, mode, n, B):
+    """n <= 128 and every causal case: the 16-query-wave kernels (register-prefetch / LDS-staged).  Non-causal n > 128 (round 5):
+    flash32_kernel, 32-query waves on v_mfma_f32_32x32x16 - 8 waves with a 2-way key split for launches of < 512 workgroups (n = 870 x 4
+    pairs: the denoiser's form; ragged tails 129 / 300; 300 x 120 pairs), 4 waves for more (200 x 1152 pairs; 200 x 288 pairs at the low
+    end of that range, whose causal case is the one that reaches flash_lds_kernel<T,1,1>: 1152 blocks of 64 queries)."""
+    q, k, vt, relpos, ref, H, n_pad = _flash_case(tdt, mode, n, B)
     out = torch.zeros(B, n, H * 64, device="cuda", dtype=tdt)
     E.check(lib.tt_op_flash_attention(dt, E.ptr(q), E.ptr(k), E.ptr(vt), E.ptr(out), B, H, n, n_pad, int(mode == "causal"),
                                       E.ptr(relpos), None))
     torch.cuda.synchronize()
-    ref = _attn_ref(q.float(), k.float(), v.float(), mode == "causal", relpos).permute(0, 2, 1, 3).reshape(B, n, H * 64)
     report(f"flash {name} {mode} n={n} B={B}", out.float(), ref, tol)
+
+
+@pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
+@pytest.mark.parametrize("mode", ["plain", "relpos"])
+@pytest.mark.parametrize("n,B", [(300, 40), (200, 24), (200, 96), (129, 3)])
+def test_flash_attention_16_query_waves(lib, name, dt, tdt, tol, mode, n, B):
+    """TTX_FLASH32 off: the non-causal shapes go to flash_lds_kernel, which then also runs with a relative-position table.  (300, 40)
+    <1,2>: window tiles, saturated tiles and a ragged tail; (200, 24) <1,1>; (200, 96) <2,1>; (129, 3) <1,2>, one key past a tile edge."""
+    out, ref = _flash_run(lib, dt, tdt, mode, n, B, flash32=0)
+    report(f"flash 16-query waves {name} {mode} n={n} B={B}", out.float(), ref, tol)
+
+
+@pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
+@pytest.mark.parametrize("mode,variant", [("plain", 1), ("causal", 1), ("plain", 2)])
+def test_flash_attention_variant(lib, name, dt, tdt, tol, mode, variant):
+    """variant 1 (never the key split) at 80 pairs x 300: flash32_kernel<T,1> non-causal, flash_lds_kernel<T,1,1> causal, both at a block
+    count the dispatch would split; variant 2 (never the 32-query waves) non-causal: flash_lds_kernel<T,1,2>."""
+    out, ref = _flash_run(lib, dt, tdt, mode, 300, 40, variant=variant)
+    report(f"flash {name} {mode} variant={variant}", out.float(), ref, tol)
+
+
+@pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
+@pytest.mark.parametrize("n,nv,mode,flash32", [(300, (300, 129, 64, 1), "plain", 1), (300, (300, 129, 64, 1), "relpos", 1),
+                                               (300, (300, 129, 64, 1), "plain", 0), (300, (300, 129, 64, 1), "relpos", 0),
+                                               (70, (70, 33, 16, 1), "plain", 1), (70, (70, 33, 16, 1), "causal", 1)])
+def test_flash_attention_padded_rows(lib, name, dt, tdt, tol, n, nv, mode, flash32):
+    """FlashArgs::nv / nv_period at the operator level: batch row b is attention over its first nv[b] rows (n stays the row stride), and the
+    rows of out at and beyond nv[b] are not written - they keep a sentinel bit for bit.  n = 300: flash32_kernel<T,2> / flash_lds_kernel
+    <T,1,2> (switch off); n = 70: flash_kernel."""
+    B, H = 4, 2
+    n_pad = (n + 31) // 32 * 32
+    g = torch.Generator().manual_seed(n + 1)
+    q = dev((torch.randn(B, H, n, 64, generator=g) * 0.125 * 2).to(tdt))
+    k = dev((torch.randn(B, H, n, 64, generator=g) * 2).to(tdt))
+    v = dev(torch.randn(B, H, n, 64, generator=g).to(tdt))
+    vt = torch.zeros(B, H, 64, n_pad, device="cuda", dtype=tdt)
+    vt[..., :n] = v.transpose(-1, -2)
+    relpos = dev(torch.randn(H, 129, generator=g)) if mode == "relpos" else None
+    sentinel = -77.0  # exact in both types
+    out = torch.full((B, n, H * 64), sentinel, device="cuda", dtype=tdt)
+    want = out.clone()
+    refs = []
+    for b in range(B):
+        m = nv[b]
+        refs.append(_attn_ref(q[b:b + 1, :, :m].float(), k[b:b + 1, :, :m].float(), v[b:b + 1, :, :m].float(), mode == "causal", relpos)
+                    .permute(0, 2, 1, 3).reshape(m, H * 64))
+    torch.cuda.synchronize()
+    prev = lib.ttx_kernel_variant(E.TTX_FLASH32, flash32)
+    try:
+        E.check(lib.tt_op_flash_attention_rows(dt, E.ptr(q), E.ptr(k), E.ptr(vt), E.ptr(out), B, H, n, n_pad, int(mode == "causal"),
+                                               E.ptr(relpos), (C.c_int * 4)(*nv), 4, 0, None))
+        torch.cuda.synchronize()
+    finally:
+        lib.ttx_kernel_variant(E.TTX_FLASH32, prev)
+    for b in range(B):
+        assert torch.equal(out[b, nv[b]:].view(torch.int16), want[b, nv[b]:].view(torch.int16)), f"row {b}: rows past nv = {nv[b]} were written"
+    report(f"flash {name} {mode} n={n} nv={nv} flash32={flash32}", torch.cat([out[b, :nv[b]] for b in range(B)]).float(), torch.cat(refs), tol)
 
 
 def test_sampler_matches_oracle(lib):

@@ -228,13 +228,24 @@ int ttx_kernel_variant(int which, int v) {
   return prev;
 }
 
-int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
-                          int causal, const float* relpos, void* stream) {
+int tt_op_flash_attention_rows(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
+                               int causal, const float* relpos, const int* nv, int nv_period, int variant, void* stream) {
+  TT_REQUIRE(nv_period >= 0 && nv_period <= 32 && (nv_period == 0 || nv != nullptr), "tt_op_flash_attention_rows: nv_period %d (0 .. 32, with nv)", nv_period);
+  TT_REQUIRE(variant >= 0 && variant <= 2, "tt_op_flash_attention_rows: variant %d", variant);
   FlashArgs f;
   memset(&f, 0, sizeof(f));
   f.q = q; f.k = k; f.vt = vt; f.out = out; f.ldo = heads * 64; f.BH = B * heads; f.heads = heads; f.n = n; f.n_pad = n_pad;
-  f.causal = causal; f.relpos = relpos;
+  f.causal = causal; f.relpos = relpos; f.variant = variant;
+  f.nv_period = nv_period;
+  for (int i = 0; i < nv_period; ++i) {
+    TT_REQUIRE(nv[i] >= 1 && nv[i] <= n, "tt_op_flash_attention_rows: nv[%d] = %d outside 1 .. %d", i, nv[i], n);
+    f.nv[i] = nv[i];
+  }
   return flash_attention_launch(dtype, f, (hipStream_t)stream);
+}
+int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
+                          int causal, const float* relpos, void* stream) {
+  return tt_op_flash_attention_rows(dtype, q, k, vt, out, B, heads, n, n_pad, causal, relpos, nullptr, 0, 0, stream);
 }
 
 // GEMV-shaped decode GEMM (gemv.hip; handles of <= 4 sequences, wide session handles of <= 16): epi 0 = out_f32 = A W^T + bias, 1 = x (out_f32) += A W^T + bias, 2 = out_t = gelu_tanh(A W^T + bias)

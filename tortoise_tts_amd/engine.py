@@ -422,6 +422,7 @@ _TEST_PROTOS = {
     "tt_op_gn_gemm": (_i, [_i, vp, _i, _i, vp, vp, _i, vp, vp, _i, vp, vp, vp]),
     "tt_op_gn_gemm_workspace": (_sz, [_i, _i]),
     "tt_op_flash_attention": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp]),
+    "tt_op_flash_attention_rows": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp, _i, _i, vp]),
     "tt_op_decode_attention": (_i, [_i, vp, vp, vp, _i, vp, vp, _i, _i, vp, _i, _i, _i, vp]),
     "tt_op_decode_qkv_attention": (_i, [_i, vp, vp, vp, C.c_float, vp, vp, _i, vp, vp, _i, _i, vp, vp, _i, _i, vp]),
     "tt_op_decode_attention_rows": (_i, [_i, vp, vp, vp, C.c_longlong, vp, _i, vp, vp, _i, vp, vp, _i, _i, vp]),
