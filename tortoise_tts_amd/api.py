@@ -38,6 +38,7 @@ from . import align
 from . import dist as tdist
 from . import engine as E
 from . import stages
+from . import loudness as loud
 from . import stretch as tsm
 from . import weights as W
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig, PRESETS, BASE_SETTINGS, CALM_TOKEN
@@ -206,6 +207,7 @@ def resolve_stage_dtypes(dtype, half):
 
 
 ORIG_ALIGNER_SECONDS = 30  # the longest clip the aligner of a path without its own clip cap is built for
+LOUDNESS_STAGE_SAMPLES = 16 * 30 * E.LOUD_SAMPLE_RATE  # samples of one call the loudness stage is first built for: sixteen clips of 30 s
 
 
 class _Common:
@@ -397,6 +399,78 @@ class _Common:
         self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
         return out
 
+    # ------------------------------------------------------------------ level: integrated loudness, true peak, gain under a ceiling
+    leveller = None
+
+    def load_loudness(self, max_samples=0):
+        """The loudness stage (stages.LoudnessStage), built on first use for sixteen clips of 30 s and rebuilt for a longer clip."""
+        if max_samples > E.LOUD_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the loudness stage can take ({E.LOUD_MAX_SAMPLES})")
+        if self.leveller is None or self.leveller.max_total_samples < max_samples:
+            if self.leveller is not None:
+                self.leveller.close()
+            self.leveller = stages.LoudnessStage(max(int(max_samples), LOUDNESS_STAGE_SAMPLES), device=self.device)
+        return self.leveller
+
+    @staticmethod
+    def _level_clips(audios, who):
+        audios = list(audios)
+        for i, a in enumerate(audios):
+            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
+                raise ValueError(f"{who}: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+        return audios
+
+    @torch.no_grad()
+    def loudness_many(self, audios):
+        """Integrated loudness (ITU-R BS.1770-4 / EBU R 128, gated) and 4x oversampled true peak of every clip: audios f32 [n] / [1, n] /
+        [1, 1, n] at 24 kHz (any device) -> [loudness.Loudness], all clips in ONE device call per 16."""
+        audios = self._level_clips(audios, "loudness")
+        if not audios:
+            return []
+        res = self.load_loudness(max(a.shape[-1] for a in audios)).measure_many([a.reshape(-1) for a in audios])
+        return [loud.reading(r) for r in res]
+
+    def loudness(self, audio):
+        """loudness_many of one clip -> loudness.Loudness."""
+        return self.loudness_many([audio])[0]
+
+    @torch.no_grad()
+    def normalize_many(self, audios, loudness=-23.0, true_peak=-1.0, limit="scale", return_info=False):
+        """Every clip brought to `loudness` LUFS under a true-peak ceiling of `true_peak` dBTP, each in the shape and on the device it came
+        in; measured and applied on the device without a round trip in between.  loudness / true_peak: one value or one per clip.  limit:
+        'scale' (the gain is lowered until the ceiling holds; the shortfall is reported), 'lookahead' (a 5 ms look-ahead limiter takes the
+        peaks down instead) or 'none'.  A clip shorter than 400 ms or without a block above -70 LUFS is returned unchanged.
+        return_info=True: also [loudness.Loudness]."""
+        audios = self._level_clips(audios, "normalize")
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(audios)
+        targets, peaks = per(loudness), per(true_peak)
+        if len(targets) != len(audios) or len(peaks) != len(audios):
+            raise ValueError(f"normalize: {len(audios)} clips with {len(targets)} targets and {len(peaks)} ceilings")
+        levels = [loud.level(T, p, limit) for T, p in zip(targets, peaks)]
+        if not audios:
+            return ([], []) if return_info else []
+        t0 = time.perf_counter()
+        res = self.load_loudness(max(a.shape[-1] for a in audios)).normalize_many(
+            [a.reshape(-1) for a in audios], [lv.loudness for lv in levels], [lv.ceiling for lv in levels], loud.MODES[limit or "scale"])
+        out = [y.to(a.device).reshape(a.shape) for a, (y, _) in zip(audios, res)]  # (the readings' copy back has synchronised)
+        self._level_s = time.perf_counter() - t0
+        return (out, [loud.reading(r, lv.loudness) for (_, r), lv in zip(res, levels)]) if return_info else out
+
+    def normalize(self, audio, loudness=-23.0, true_peak=-1.0, limit="scale"):
+        """normalize_many of one clip -> the clip at its level."""
+        return self.normalize_many([audio], loudness, true_peak, limit)[0]
+
+    def _at_level(self, clips, level):
+        """The clips a tts call is about to return ({winner: clip} or a list), at `level` (loudness.Level): one normalize_many call for all
+        of them, its time in timings['level_s'], the readings in self.loudness_info."""
+        self._level_s = 0.0
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        out, info = self.normalize_many([clips[i] for i in keys] if keys is not None else clips, level.loudness, level.true_peak, level.limit,
+                                        return_info=True)
+        self.loudness_info = info
+        self.timings = dict(getattr(self, "timings", None) or {}, level_s=self._level_s)
+        return dict(zip(keys, out)) if keys is not None else out
+
 
 class TextToSpeech(_Common):
     """Main entry point; see the module docstring.  Engine-only keyword arguments (all optional, after
@@ -410,7 +484,10 @@ class TextToSpeech(_Common):
     heuristic, bit for bit; 'forced': the bracketed passages are cut at the character boundaries of the CTC forced alignment, which exists
     whenever the clip has enough frames - DESIGN.md 5.23).  Engine-only keyword of tts() / tts_with_preset() / tts_many(), taken out of
     **hf_generate_kwargs: `speaking_rate` (0.5 .. 2.0; None or 1.0: off) - every returned clip is time-stretched at the same pitch after
-    redaction (stretch / stretch_many, csrc/tsm.hip - DESIGN.md 5.24)."""
+    redaction (stretch / stretch_many, csrc/tsm.hip - DESIGN.md 5.24); `loudness` (a target in LUFS, -70 .. -5; None: off) with `true_peak`
+    (the ceiling in dBTP, default -1) and `limit` ('scale', the default, 'lookahead' or 'none') - every returned clip is then brought to the
+    target under the ceiling, the last step after redaction and the speaking rate (normalize / normalize_many, csrc/loudness.hip - DESIGN.md
+    5.25; the readings are left in `loudness_info`)."""
 
     redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
@@ -718,6 +795,8 @@ class TextToSpeech(_Common):
             self.timings["redact_s"] = self._redact_s
         if o.speaking_rate is not None:  # (every rank stretches the clips it holds)
             wavs = self._at_rate(wavs, o.speaking_rate)
+        if o.level is not None:  # (the last step of the chain: redaction -> speaking rate -> level)
+            wavs = self._at_level(wavs, o.level)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -732,11 +811,13 @@ class TextToSpeech(_Common):
         bit-identical to rendering it alone.  With utterance_batch > 1 the CLVP ranking of a wave is ONE speech-tower pass over all its
         candidates (every score the bits of scoring the utterance alone) and the denoiser runs in shared, padded passes; the latent re-pass
         runs per utterance as in tts() and UnivNet vocodes a wave in one call (every clip the bits of vocoding it alone).  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py).
-        speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call."""
-        rate = tsm.speaking_rate(kwargs)
+        speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
+        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call."""
+        rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
-        return out if rate is None else self._at_rate(out, rate)
+        out = out if rate is None else self._at_rate(out, rate)
+        return out if level is None else self._at_level(out, level)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
@@ -823,7 +904,7 @@ class TextToSpeech(_Common):
         """tts()'s generation arguments (`args`: its parameters by name), validated -> what the phases read."""
         hf = dict(args["hf_generate_kwargs"])
         noise = hf.pop("noise_override", None) or {}
-        speaking_rate = tsm.speaking_rate(hf)
+        speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
             raise ValueError(f"cvvp_amount={args['cvvp_amount']} must lie in [0, 1] (api.py:366-367)")
@@ -832,7 +913,7 @@ class TextToSpeech(_Common):
             sampling=dict(temperature=args["temperature"], top_p=args["top_p"], repetition_penalty=args["repetition_penalty"], top_k=top_k,
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
-            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate)
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

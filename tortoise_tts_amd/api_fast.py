@@ -33,6 +33,7 @@ import torch
 
 from . import engine as E
 from . import stages
+from . import loudness as loud
 from . import stretch as tsm
 from . import weights as W
 from .api import MODELS_DIR, _Common, _load_state_dict, _load_file, sampler_kwargs
@@ -188,7 +189,7 @@ class TextToSpeech(_Common):
             cvvp_amount=.0, **hf_generate_kwargs):
         # (k and cvvp_amount are accepted and unused as in the reference: its fast path decodes ONE sample, there is nothing to rank)
         self._single("tts")
-        speaking_rate = tsm.speaking_rate(hf_generate_kwargs)
+        speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -198,7 +199,8 @@ class TextToSpeech(_Common):
         self.last_codes = codes
         latents = self.ar.latents(cond, text_tokens, codes)          # api_fast.py:510-514 (return_latent=True)
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
-        return wav.cpu() if speaking_rate is None else self._at_rate([wav.cpu()], speaking_rate)[0]
+        wav = wav.cpu() if speaking_rate is None else self._at_rate([wav.cpu()], speaking_rate)[0]
+        return wav if level is None else self._at_level([wav], level)[0]  # (the last step: speaking rate -> level)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
@@ -206,10 +208,12 @@ class TextToSpeech(_Common):
         one per text.  On a max_streams=1 instance this loops tts().  On a session instance (max_streams >= 2) the texts are decoded as
         rows of the shared decode batch - later texts take rows as earlier ones finish - each gets tts()'s latent re-pass, and the clips
         are vocoded in ragged batches (HifiganStage.inference_many).  Returns a list of wav f32 [1, 1, S] on the CPU.
-        speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call."""
-        rate = tsm.speaking_rate(kwargs)
+        speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
+        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call."""
+        rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
-        return out if rate is None else self._at_rate(out, rate)
+        out = out if rate is None else self._at_rate(out, rate)
+        return out if level is None else self._at_level(out, level)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs):
@@ -326,6 +330,7 @@ class TextToSpeech(_Common):
                    **hf_generate_kwargs):
         self._single("tts_stream")
         tsm.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -371,6 +376,7 @@ class TextToSpeech(_Common):
         when every slot is busy or when the sampling settings differ from those of the running sessions (they share one sampler) -
         with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken."""
         tsm.refuse_streaming(kwargs, "open_stream")
+        loud.refuse_streaming(kwargs, "open_stream")
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -504,6 +510,7 @@ class TextToSpeech(_Common):
         repetition_penalty, top_k, typical_sampling and typical_mass on an instance with per_session_sampling.  Texts beyond the free
         slots are admitted as earlier sessions end."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
+        loud.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):
             seeds = [seeds] * len(texts)

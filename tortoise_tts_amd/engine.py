@@ -389,6 +389,23 @@ TSM_RATE_ONE, TSM_RATE_MIN, TSM_RATE_MAX = 65536, 32768, 131072  # TT_TSM_RATE_*
 TSM_SAMPLE_RATE = 24000
 TSM_MAX_SAMPLES, TSM_MAX_CLIPS = 8388608, 64
 TSM_OK, TSM_EMPTY, TSM_REFUSED = 0, 1, 2
+# include/tortoise_mi355x_loud.h: loudness measurement, normalisation and true-peak limiting of rendered clips (its own header and version)
+_LOUD_PROTOS = {
+    "tt_loud_abi_version": (_i, []),
+    "tt_loud_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_loud_destroy": (None, [vp]),
+    "tt_loud_hops": (_i, [_i]),
+    "tt_loud_blocks": (_i, [_i]),
+    "tt_loud_measure": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_loud_normalize": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+LOUD_ABI_VERSION = 1
+LOUD_HOP, LOUD_BLOCK, LOUD_SEGMENT, LOUD_LOOKAHEAD = 2400, 9600, 150, 120  # TT_LOUD_HOP, TT_LOUD_BLOCK, TT_LOUD_SEGMENT, TT_LOUD_LOOKAHEAD
+LOUD_OVERSAMPLE, LOUD_TAPS = 4, 16
+LOUD_SAMPLE_RATE = 24000
+LOUD_MAX_SAMPLES, LOUD_MAX_CLIPS = 268435456, 64
+LOUD_NONE, LOUD_SCALE, LOUD_LOOKAHEAD_MODE = 0, 1, 2
+LOUD_OK, LOUD_SHORT, LOUD_SILENT, LOUD_EMPTY, LOUD_REFUSED = 0, 1, 2, 3, 4
 # include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
 _HIFI_PROTOS = {
     "tt_hifi_batch_abi_version": (_i, []),
@@ -463,7 +480,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -495,6 +512,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_ctc.h is version %d in the library, %d in Python" % (lib.tt_ctc_abi_version(), CTC_ABI_VERSION))
     if lib.tt_tsm_abi_version() != TSM_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_tsm.h is version %d in the library, %d in Python" % (lib.tt_tsm_abi_version(), TSM_ABI_VERSION))
+    if lib.tt_loud_abi_version() != LOUD_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))

@@ -48,9 +48,14 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     a list of chunks (str or pre-tokenised id sequences).
     Returns (full_audio f32 [1, n] or None, parts: list of per-chunk clips [1, 1, n_j]) on rank 0, (None, None) elsewhere.
     return_timings=True (str chunks): (full_audio, align.Alignment of the whole text in the concatenated audio) instead - every chunk is
-    aligned with its own clip in one forced-alignment call (tts.align_many) and merge_alignments offsets them."""
+    aligned with its own clip in one forced-alignment call (tts.align_many) and merge_alignments offsets them.
+    loudness= (LUFS; with true_peak= and limit=, see TextToSpeech.normalize_many) brings the reading to a level: loudness_scope='chunk' (the
+    default) every chunk to the target, in one normalize_many call per rank - the level no longer moves from chunk to chunk;
+    loudness_scope='whole' one gain for the concatenation."""
+    from . import loudness as loud
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
+    scope, level = loud.scope_option(tts_kwargs), loud.level_options(tts_kwargs)  # (applied here, to what the chunks' calls return)
     if getattr(tts, "world", 1) != 1:
         raise ValueError("read_long_form spreads chunks over the ranks: build TextToSpeech(candidate_sharding=False)")
     if texts_are_chunks:
@@ -86,11 +91,16 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
         gen = tts.tts_with_preset(texts[j], voice_samples=voice_samples, conditioning_latents=conditioning_latents, preset=preset, k=1,
                                   use_deterministic_seed=seed, **tts_kwargs)  # read.py:70-71
         mine[j] = gen.cpu()
+    if level is not None and scope == "chunk" and mine:  # every chunk of this rank to the target, in one call
+        mine = tts._at_level(mine, level)
     parts = tdist.collect_on_rank0(mine, len(texts))
     if parts is None:
         return None, None
     clips = [parts[j] for j in range(len(texts))]
     full = torch.cat([c.squeeze(0) for c in clips], dim=-1)  # read.py:74, 87
+    if level is not None and scope == "whole":  # one gain (and one limiter pass) for the concatenation; the parts are its pieces
+        full = tts._at_level([full], level)[0]
+        clips = [p.reshape(c.shape) for p, c in zip(full.split([c.shape[-1] for c in clips], dim=-1), clips)]
     if return_timings:
         als = tts.align_many(clips, [tts._spoken_text(t) for t in texts])
         return full, merge_alignments(als, [c.shape[-1] for c in clips])

@@ -4,6 +4,7 @@ call on the caller's current torch stream.  No model arithmetic happens here bey
 gathers for the once-per-utterance prefix (plumbing).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -578,6 +579,86 @@ class TimeStretchStage(_Handle):
         if any(st != E.TSM_OK for st in status):
             raise RuntimeError(f"time-stretch: the device stage refused clips it was handed (status {status})")
         return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
+
+
+class LoudnessStage(_Handle):
+    """Integrated loudness, true peak and the gain to a target under a ceiling (csrc/loudness.hip, include/tortoise_mi355x_loud.h): ragged
+    batches, each clip with its own target and ceiling, one tt_loud_measure / tt_loud_normalize call per group of at most max_clips clips and
+    max_total_samples samples, every clip's result bit-identical to running it alone."""
+
+    api = "tt_loud"
+
+    def __init__(self, max_total_samples, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_total_samples, self.max_clips = int(max_total_samples), int(max_clips)
+        self._create(self.max_total_samples, self.max_clips)
+
+    def measure_many(self, clips):
+        """clips f32 [n_i] (device or host) -> one dict per clip: status (E.LOUD_OK / SHORT / SILENT), lufs, true_peak (linear), blocks_abs,
+        blocks_rel, hop_energy (f64 host tensor).  ValueError for an empty clip or a clip beyond the handle."""
+        return [r for _, r in self._many(clips, None, None, E.LOUD_NONE)]
+
+    def normalize_many(self, clips, targets, ceilings, mode):
+        """clips, a target (LUFS) and a ceiling (linear true peak) each, one mode (E.LOUD_NONE / SCALE / LOOKAHEAD_MODE) -> one (y f32 [n_i] on
+        the stage's device, dict) per clip: measure_many's entries plus gain and out_true_peak (linear)."""
+        if not len(clips) == len(targets) == len(ceilings):
+            raise ValueError(f"{len(clips)} clips with {len(targets)} targets and {len(ceilings)} ceilings")
+        if mode not in (E.LOUD_NONE, E.LOUD_SCALE, E.LOUD_LOOKAHEAD_MODE):
+            raise ValueError(f"mode {mode}: expected E.LOUD_NONE, E.LOUD_SCALE or E.LOUD_LOOKAHEAD_MODE")
+        for i, (T, c) in enumerate(zip(targets, ceilings)):
+            if not math.isfinite(float(T)) or not (float(c) > 0 and math.isfinite(float(c))):
+                raise ValueError(f"clip {i}: target {T} LUFS / ceiling {c} (a finite target and a positive linear ceiling)")
+        return self._many(clips, [float(T) for T in targets], [float(c) for c in ceilings], mode)
+
+    def _many(self, clips, targets, ceilings, mode):
+        for i, x in enumerate(clips):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_total_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the loudness stage's capacity ({self.max_total_samples})")
+        out, g0 = [], 0
+        while g0 < len(clips):  # the longest run of clips the handle takes in one call
+            g1, total = g0, 0
+            while g1 < len(clips) and g1 - g0 < self.max_clips and total + clips[g1].shape[0] <= self.max_total_samples:
+                total += clips[g1].shape[0]
+                g1 += 1
+            out += self._group(clips[g0:g1], targets and targets[g0:g1], ceilings and ceilings[g0:g1], mode)
+            g0 = g1
+        return out
+
+    def _group(self, clips, targets, ceilings, mode):
+        n, dev = len(clips), self.device
+        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
+        ho = np.concatenate(([0], np.cumsum([self.lib.tt_loud_hops(x.shape[0]) for x in clips]))).astype(np.int32)
+        N, Hn = int(io[-1]), int(ho[-1])
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, ho])).to(dev)
+        rd = torch.zeros(n + Hn, device=dev, dtype=torch.float64)   # (lufs | hop_energy)
+        rf = torch.zeros(3 * n, device=dev, dtype=torch.float32)    # (true_peak | gain | out_true_peak)
+        ri = torch.zeros(3 * n, device=dev, dtype=torch.int32)      # (blocks_abs | blocks_rel | status)
+        hp, dp, fp, ip = host.data_ptr(), rd.data_ptr(), rf.data_ptr(), ri.data_ptr()
+        y = None
+        if targets is None:
+            E.check(self.lib.tt_loud_measure(self.h, n, audio.data_ptr(), hp, hp + 4 * (n + 1), dp, fp, ip, ip + 4 * n, dp + 8 * n, ip + 8 * n,
+                                             E.stream_ptr()))
+        else:
+            tc = torch.tensor(list(targets) + list(ceilings), dtype=torch.float32).to(dev)
+            y = torch.zeros(N + 1, device=dev, dtype=torch.float32)
+            E.check(self.lib.tt_loud_normalize(self.h, n, audio.data_ptr(), hp, hp + 4 * (n + 1), tc.data_ptr(), tc.data_ptr() + 4 * n, int(mode),
+                                               y.data_ptr(), dp, fp, ip, ip + 4 * n, dp + 8 * n, fp + 4 * n, fp + 8 * n, ip + 8 * n, E.stream_ptr()))
+        rd, rf, ri = rd.cpu(), rf.cpu(), ri.cpu()
+        status = ri[2 * n:].tolist()
+        if any(st not in (E.LOUD_OK, E.LOUD_SHORT, E.LOUD_SILENT) for st in status):
+            raise RuntimeError(f"loudness: the device stage refused clips it was handed (status {status})")
+        out = []
+        for i in range(n):
+            r = dict(status=status[i], lufs=float(rd[i]), true_peak=float(rf[i]), blocks_abs=int(ri[i]), blocks_rel=int(ri[n + i]),
+                     hop_energy=rd[n + ho[i]:n + ho[i + 1]].clone())
+            if y is not None:
+                r.update(gain=float(rf[n + i]), out_true_peak=float(rf[2 * n + i]))
+            out.append((None if y is None else y[io[i]:io[i + 1]], r))
+        return out
 
 
 class ClassifierStage(_GuardedHandle):
