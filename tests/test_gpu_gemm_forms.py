@@ -227,6 +227,91 @@ def test_conv_forms(lib, name, dt, tdt, case):
     check(f"{form} {name}", s, o32, ref, "f32", name, tile)
 
 
+# (form, M, N, K, splitk, tile, variant): fewer k-tiles per K range than ring stages - the clamped re-request goes into a dead ring slot
+RING_TAIL = [("ring tail 64x64 K=64 bias+f32", 100, 128, 64, 1, "64x64", "V_NONE"),
+             ("ring tail 32x16 K=64 bias+f32", 7, 1024, 64, 1, "32x16", "V_NONE"),
+             ("ring tail 32x16 K=128 slabs", 7, 1024, 128, 2, "32x16", "V_SLAB"),
+             ("ring tail 64x16 K=128 slabs", 40, 1024, 128, 2, "64x16", "V_SLAB")]
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT16)
+@pytest.mark.parametrize("case", RING_TAIL, ids=[c[0].replace(" ", "_") for c in RING_TAIL])
+def test_ring_tail_shorter_than_the_ring(lib, name, dt, tdt, case):
+    """one k-tile per K range on the 4- and 8-stage rings: every prologue fill but the first and every refill re-requests that tile"""
+    form, M, N, K, splitk, tile, variant = case
+    A, W, bias, _ = operands(M + K, M, N, K, tdt)
+    X = R.gemm_operand(A, K)
+    if splitk == 1:
+        o32 = torch.full((M + 1, N), SENTINEL, device="cuda")
+        s = expect(form, launch(lib, dt, 0, desc(A=A, lda=K, W=W, ldw=K, M=M, N=N, K=K, bias=bias, out_f32=o32)), tile, variant)
+        check(f"{form} {name} M={M}", s, o32[:M], R.std_reference(X, W, bias)[0], "f32", name, tile)
+        assert (o32[M] == SENTINEL).all(), f"{form}: written past the last row"
+        return
+    slabs = torch.zeros(splitk, M, N, device="cuda")
+    s = expect(form, launch(lib, dt, 0, desc(A=A, lda=K, W=W, ldw=K, M=M, N=N, K=K, splitk=splitk, out_f32=slabs)), tile, variant)
+    for z in range(splitk):
+        check(f"{form} {name} M={M} slab {z}", s, slabs[z], R.std_reference(X[:, z * 64:(z + 1) * 64], W[:, z * 64:(z + 1) * 64])[0], "f32", name, tile)
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT16)
+def test_ring_tail_statistics(lib, name, dt, tdt):
+    """K = 64 on the 128 x 64 tile's 4-stage ring through the statistics form, two sequences of 150 rows"""
+    M, N, K, seq = 300, 64, 64, 150
+    A, W, bias, _ = operands(M + K, M, N, K, tdt)
+    kw = dict(A=A, lda=K, W=W, ldw=K, M=M, N=N, K=K, bias=bias)
+    s, o32, _, _ = run_stats(lib, name, dt, "ring tail 128x64 K=64 statistics", kw, M, N, seq, "128x64", "V_ST_F32")
+    check(f"ring tail 128x64 K=64 statistics {name} M={M}", s, o32, R.std_reference(R.gemm_operand(A, K), W, bias)[0], "f32", name, "128x64")
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT16)
+def test_conv_split_k_slab_starts_inside_a_tap(lib, name, dt, tdt):
+    """taps 3, cin 128 (6 k-tiles), splitk 4: the slabs start at k-tiles 0, 2, 4, 5, so slab 3 starts at tap 2, slice 1 - the tap cursor's
+    one real division.  Every slab against the matching columns of the virtual conv operand."""
+    B, S, cin, taps, N, splitk = 2, 70, 128, 3, 128, 4
+    M, K = B * S, taps * cin
+    A, W, _, _ = operands(cin + splitk, M, N, K, tdt)
+    A = A[:, :cin].contiguous()
+    X = R.conv_operand(A, M, cin, taps, 1, S)
+    slabs = torch.zeros(splitk, M, N, device="cuda")
+    d = desc(A=A, lda=cin, W=W, ldw=K, M=M, N=N, K=K, taps=taps, dilation=1, seq_len=S, splitk=splitk, out_f32=slabs)
+    s = expect("conv split-K", launch(lib, dt, 0, d), "64x64", "V_NONE")
+    for z, (t0, t1) in enumerate(((0, 2), (2, 4), (4, 5), (5, 6))):
+        check(f"conv taps 3 cin 128 splitk 4 {name} slab {z}", s, slabs[z], R.std_reference(X[:, t0 * 64:t1 * 64], W[:, t0 * 64:t1 * 64])[0], "f32", name, "64x64")
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT16)
+def test_conv_unaligned(lib, name, dt, tdt):
+    """taps 3, cin 64, N = 130 (generic kernel, element-wise epilogue): bias, skip, f32 and T outputs, one sentinel row past each"""
+    B, S, cin, taps, N = 2, 70, 64, 3, 130
+    M, K = B * S, taps * cin
+    A, W, bias, res = operands(cin + N, M, N, K, tdt)
+    A = A[:, :cin].contiguous()
+    X = R.conv_operand(A, M, cin, taps, 1, S)
+    o32 = torch.full((M + 1, N), SENTINEL, device="cuda")
+    ot = torch.full((M + 1, N), SENTINEL, device="cuda", dtype=tdt)
+    d = desc(A=A, lda=cin, W=W, ldw=K, M=M, N=N, K=K, taps=taps, dilation=1, seq_len=S, bias=bias, res=res, out_f32=o32, out_t=ot)
+    s = expect("conv unaligned", launch(lib, dt, 0, d), "64x64", "V_GEN")
+    ref = R.std_reference(X, W, bias, res=res)[0]
+    check(f"conv taps 3 N=130 f32 {name}", s, o32[:M], ref, "f32", name, "64x64")
+    check(f"conv taps 3 N=130 (T) {name}", s, ot[:M], ref, name, name, "64x64")
+    assert (o32[M] == SENTINEL).all() and (ot[M] == SENTINEL).all(), "unaligned conv wrote past the last row"
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT16)
+@pytest.mark.parametrize("B,S,N,tile", [(4, 1024, 1024, "128x128"), (26, 870, 768, "256x256")])
+def test_conv_on_the_two_stage_tiles(lib, name, dt, tdt, B, S, N, tile):
+    """taps 3, cin 64, bias -> T on the 128 x 128 and the 16-wave 256 x 256 tile (a conv never takes the eight-phase kernel)"""
+    cin, taps = 64, 3
+    M, K = B * S, taps * cin
+    A, W, bias, _ = operands(M + N, M, N, K, tdt)
+    A = A[:, :cin].contiguous()
+    X = R.conv_operand(A, M, cin, taps, 1, S)
+    ot = torch.zeros(M, N, device="cuda", dtype=tdt)
+    d = desc(A=A, lda=cin, W=W, ldw=K, M=M, N=N, K=K, taps=taps, dilation=1, seq_len=S, bias=bias, out_t=ot)
+    s = expect(f"conv {tile}", launch(lib, dt, 0, d), tile, "V_BIAS_T")
+    check(f"conv taps 3 cin 64 bias->T {tile} {name} M={M}", s, ot, R.std_reference(X, W, bias)[0], name, name, tile)
+
+
 @pytest.mark.parametrize("name,dt,tdt", DT16 + [F32])
 def test_second_activation_source(lib, name, dt, tdt):
     """[A | A2] without the concatenation: k_split 1024 of 2048 with statistics (slot 2 of A2), and 192 of 320 on the generic kernel (slot 0)"""

@@ -49,8 +49,9 @@ def _headers():
 
 
 def build(force=False, verbose=True, variant=None, defines=()):
-    """variant / defines: an alternative library lib/libtortoise_mi355x_<variant>.so compiled with extra -D knobs (csrc/knobs.h)
-    for in-situ A/B runs (TORTOISE_MI355X_LIB selects it); the product library is the one built without them."""
+    """variant / defines: an alternative library lib/libtortoise_mi355x_<variant>.so compiled with extra -D knobs (the TT_* tuning
+    constants next to their measurements in csrc, e.g. TT_SKINNY_ST in gemm_impl.h) for in-situ A/B runs (TORTOISE_MI355X_LIB
+    selects it); the product library is the one built without them."""
     OBJ = os.path.join(CSRC, "build" if not variant else "build_" + variant)
     LIB = os.path.join(LIBDIR, "libtortoise_mi355x.so" if not variant else "libtortoise_mi355x_%s.so" % variant)
     FLAGS = globals()["FLAGS"] + ["-D" + d for d in defines]

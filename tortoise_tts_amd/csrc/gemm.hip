@@ -31,8 +31,7 @@ static bool skinny_ok(const GemmArgs& a, int epi) {
   if (a.M > 64 || a.N < 1024 || a.taps != 1 || a.A2 || a.gn_part || a.serial_k > 1 || a.act_t != ACT_NONE) return false;
   if (epi == EPI_QKV_DECODE) return true;
   if (epi != EPI_STD) return false;
-  return (a.N & 3) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) && (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
-         (!a.out_f32 || (((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0)) && (!a.out_t || (((size_t)a.out_t & 7) == 0 && (a.ldot & 3) == 0));
+  return epi_aligned(a);
 }
 thread_local GemmRan g_gemm_ran = {-1, -1, 0, 0};
 bool g_gemm_skinny = true;  // ttx_kernel_variant(TTX_GEMM_SKINNY): 0 = the 64 x 64 tile for small decode batches as well (A/B runs)
@@ -109,10 +108,9 @@ static void plan_core(const GemmArgs& a, int epi, GemmPlan& p, int force_tile = 
   p.splitk = a.splitk;
   // shared-halo 3-tap kernel: the denoiser's ResBlock convolutions (statistics epilogue => 128x64 tile at every M > 256, so the
   // conditioned row keeps one accumulation order whether it is evaluated alone or batched)
-  const bool al16 = (a.N & 3) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) && (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
-                    a.out_f32 && ((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0;
+  // (out_t == nullptr is tested here, so epi_aligned(a) && a.out_f32 is the f32-required form: N % 4, bias / skip / f32 output aligned)
   p.conv3s = epi == EPI_STD && !a.seq_vlen && tile == TILE_128x64 && a.taps == 3 && a.dilation <= 1 && a.splitk == 1 && a.gn_part != nullptr && a.bias != nullptr &&
-             a.out_t == nullptr && a.act == ACT_NONE && a.A2 == nullptr && al16 && a.cin >= 256;
+             a.out_t == nullptr && a.act == ACT_NONE && a.A2 == nullptr && a.out_f32 && epi_aligned(a) && a.cin >= 256;
   p.prof_id = prof_class(tile, epi, a.taps > 1, a.gn_part != nullptr);
   // algorithmic work of this launch: 2*M*N*K flops; operands read once + ONE result written once (the extra split-K slabs
   // a launch writes are an implementation cost: they show up in the PMC traffic, not here)
@@ -145,8 +143,7 @@ int gemm_launch(int dtype, int epi, const GemmArgs& a0, hipStream_t stream) {
   TT_REQUIRE(a.splitk <= a.K / 64, "gemm: splitk=%d exceeds the %d k-tiles", a.splitk, a.K / 64);
   if (a.serial_k > 1)
     TT_REQUIRE(epi == EPI_STD && a.splitk == 1 && a.bias && a.res && a.out_f32 && !a.out_t && !a.gn_part && a.taps == 1 && !a.A2 && a.act == ACT_NONE &&
-                   (a.K / 64) % a.serial_k == 0 && (a.N & 3) == 0 && ((size_t)a.bias & 15) == 0 && ((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0 &&
-                   ((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0,
+                   (a.K / 64) % a.serial_k == 0 && epi_aligned(a),
                "gemm: serial split-K needs the plain aligned bias + skip + f32 form and K / 64 = %d divisible by serial_k = %d", a.K / 64, a.serial_k);
   if (a.A2) TT_REQUIRE(a.taps == 1 && a.k_split > 0 && a.k_split < a.K && a.k_split % 64 == 0 && a.lda2 % 8 == 0, "gemm: bad second activation source (k_split=%d lda2=%d)", a.k_split, a.lda2);
   TT_REQUIRE(a.act_t == ACT_NONE || (a.act_t == ACT_LRELU && epi == EPI_STD && a.out_t && a.splitk == 1), "gemm: act_t supports LeakyReLU on the T-typed output of the standard epilogue only");
@@ -187,8 +184,8 @@ bool gemm_gna_supported(int dtype, int epi, const GemmArgs& a0, const GemmGnArgs
   const bool common = (dtype == DT_BF16 || dtype == DT_F16) && ((size_t)a.A & 15) == 0 && (a.lda & 3) == 0 && ((size_t)n.gamma & 15) == 0 && ((size_t)n.beta & 15) == 0 &&
                       (a.ldw & 7) == 0 && a.taps == 1 && a.splitk == 1 && a.serial_k <= 1 && a.K == kGnaC && !a.A2 && a.N % kGnaBN == 0 && a.M > 256 && a.M <= 4096 &&
                       n.S >= kGnaBM && a.M % n.S == 0 && n.gemm_part && n.part_rows > 0 && (n.part_rows & (n.part_rows - 1)) == 0 && n.S >= n.part_rows && a.gn_vperiod == 0 && !n.ss;
-  const bool al16 = a.bias && ((size_t)a.bias & 15) == 0 && a.out_f32 && ((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0;
-  return common && epi == EPI_STD && al16 && a.gn_part != nullptr && !a.res && !a.out_t && a.act == ACT_NONE && n.act == ACT_SILU;
+  // (N % 256 == 0, no skip, no T output: epi_aligned is the alignment of bias and the f32 output)
+  return common && epi == EPI_STD && a.bias && a.out_f32 && epi_aligned(a) && a.gn_part != nullptr && !a.res && !a.out_t && a.act == ACT_NONE && n.act == ACT_SILU;
 }
 
 bool g_gemm_p8 = true;  // tt_gemm_variant
@@ -206,7 +203,7 @@ int gemm_gna_launch(int dtype, int epi, const GemmArgs& a0, const GemmGnArgs& n,
   plan.bytes += (double)a.M * a.cin * 2.0;  // the activation rows are f32 here
   GnaArgs d;
   memset(&d, 0, sizeof(d));
-  d.gamma = n.gamma; d.beta = n.beta; d.ss = n.ss; d.ss_stride = n.ss_stride; d.ss_div = n.ss_div; d.gemm_part = n.gemm_part;
+  d.gamma = n.gamma; d.beta = n.beta; d.gemm_part = n.gemm_part;
   d.part_shift = 31 - __builtin_clz((unsigned)n.part_rows);
   d.S = n.S; d.eps = n.eps; d.act = n.act; d.guard = n.guard;
   d.inv_count = 1.0 / ((double)n.S * (double)(kGnaC / 32));

@@ -18,8 +18,8 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmDev<typename Ep
   const int bx = (int)(blockIdx.x % c.gx), by = (int)(blockIdx.x / c.gx);
   const int m0 = bx * BM, n0 = by * BN;
   const int z = blockIdx.z;
-  const int kt_begin = z * c.sk_quot + min(z, c.sk_rem);
-  const int kt_end = kt_begin + c.sk_quot + (z < c.sk_rem ? 1 : 0);
+  const KRange kr = splitk_range(c, z);
+  const int kt_begin = kr.begin, kt_end = kr.end;
   const float* A = (const float*)c.A;
   const float* W = (const float*)c.W;
   const float* A2 = nullptr;

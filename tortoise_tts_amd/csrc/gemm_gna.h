@@ -18,9 +18,6 @@ namespace tt {
 struct GnaArgs {
   const float* gamma;
   const float* beta;
-  const float* ss;          // scale / shift rows [2C]: batch row b reads ss + (b / ss_div) * ss_stride (nullptr: none)
-  size_t ss_stride;
-  int ss_div;
   const float* gemm_part;   // the producing GEMM's statistics partials [row_tile][slot][C / 16][2]
   int part_shift;           // log2(rows of a statistics tile)
   int S;                    // rows per sample
@@ -39,7 +36,7 @@ struct GemmGnaDev {
 constexpr int kGnaC = 1024;  // channels (= K): 32 groups of 32 channels = 2 statistics strips of 16 per group
 
 
-template <typename T, int BM, int BN, int NW, int WM, int PF, typename Epi, bool SS, bool SILU>
+template <typename T, int BM, int BN, int NW, int WM, int PF, typename Epi, bool SILU>
 __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<typename Epi::Args> g) {
   typedef typename Vec<T>::x8 x8;
   constexpr int BK = 64;
@@ -63,7 +60,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave % WM, wn = wave / WM;
   unsigned bx, by;
-  {  // XCD-aware tile order (see gemm_glds_kernel)
+  {  // XCD-aware tile order: the body of gemm_steps.h tile_origin, written out (through the function hipcc moves two waits of this
+     // kernel's last k-tiles and adds one in the epilogue)
     const unsigned id = blockIdx.x;
     const unsigned xcd = id & 7, loc = id >> 3;
     const unsigned nid = xcd * c.xq + min(xcd, c.xr) + loc;
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
   const bool straddle = m0 + BM - 1 >= next_start && next_start < c.M;  // block-uniform: the tile's last rows belong to sample b0 + 1
 
   // this thread's A chunks: row (tid >> 3) + 32 p, channels lc * 8 .. + 7 of the k-tile
-  const int lr = lane >> 3, lc = lane & 7;
+  const int lc = lane & 7;
   const float* a_ptr[PA];
   int a_dst[PA], a_slot[PA];
 #pragma unroll
@@ -97,7 +95,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
     const int q = tid & 15;                // QUAD: channels q * 4 .. + 3 = half (q & 1) of 16-byte chunk q >> 1
     const int m = min(m0 + row, c.M - 1);  // rows beyond M re-read the last row: never stored, left out of the statistics
     a_ptr[p] = X + (size_t)m * c.lda + (QUAD ? q * 4 : lc * 8);
-    a_dst[p] = QUAD ? row * BK + (((q >> 1) ^ ((row >> 1) & 7)) * 8) + (q & 1) * 4 : row * BK + ((lc ^ ((row >> 1) & 7)) * 8);
+    a_dst[p] = QUAD ? row * BK + swz(row, q >> 1) + (q & 1) * 4 : row * BK + swz(row, lc);
     a_slot[p] = (m >= next_start ? 1 : 0) * kGnaC + (QUAD ? q * 4 : lc * 8);
   }
   const T* w_ptr[PW];
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
     const int row = (tid >> 3) + RP * p;
     const int nn = n0 + row;
     w_ptr[p] = W + (size_t)(nn < c.N ? nn : c.N - 1) * c.ldw + lc * 8;
-    w_dst[p] = row * BK + ((lc ^ ((row >> 1) & 7)) * 8);
+    w_dst[p] = row * BK + swz(row, lc);
   }
   float4 ra[PF][PA][2];
   x8 rw[PF][PW];
@@ -137,12 +135,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
       for (int j = 0; j < (QUAD ? 2 : 4); ++j) {
         const float4 mo = tb[j];
         float y0 = fmaf(xs[2 * j], mo.x, mo.y), y1 = fmaf(xs[2 * j + 1], mo.z, mo.w);
-#ifndef TT_GNA_NOSILU
         if (SILU) {
           y0 *= __builtin_amdgcn_rcpf(1.0f + __expf(-y0));
           y1 *= __builtin_amdgcn_rcpf(1.0f + __expf(-y1));
         }
-#endif
         o[2 * j] = (T)y0;
         o[2 * j + 1] = (T)y1;
       }
@@ -165,17 +161,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
   const int ch = t8 * 4;     // this thread's four channels of the (multiplier, offset) table
   const float4 gm = *(const float4*)(n.gamma + ch);
   const float4 bt = *(const float4*)(n.beta + ch);
-  float4 sc[2], sh[2];
-  sc[0] = sc[1] = sh[0] = sh[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (SS) {
-    const int div = n.ss_div > 0 ? n.ss_div : 1;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const float* row = n.ss + (size_t)((b0 + (straddle ? s : 0)) / div) * n.ss_stride;
-      sc[s] = *(const float4*)(row + ch);
-      sh[s] = *(const float4*)(row + kGnaC + ch);
-    }
-  }
   // statistics of sample b0 (and b0 + 1 for the one tile that straddles): gn_finalize<1>'s sum, item by item in the same order
   {
     const int gq = t8 & 31, part = t8 >> 5;
@@ -186,10 +171,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
       const int t0 = (b * S) >> r_shift, t1 = ((b + 1) * S - 1) >> r_shift;
       const int nitems = (t1 - t0 + 1) << 1;
       double su = 0.0, qu = 0.0;
-#ifdef TT_GNA_NOSTATS
-      su = 1.0; qu = 2.0 / n.inv_count;
-      if (false)
-#endif
       for (int e0 = part; e0 < nitems; e0 += 64) {
         float2 v[8];
 #pragma unroll
@@ -230,19 +211,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
     for (int s = 0; s < nsamp; ++s) {
       const float mu = mean_s[s][t8 >> 3], rs = rstd_s[s][t8 >> 3];
       const float gmv[4] = {gm.x, gm.y, gm.z, gm.w}, btv[4] = {bt.x, bt.y, bt.z, bt.w};
-      const float scv[4] = {sc[s].x, sc[s].y, sc[s].z, sc[s].w}, shv[4] = {sh[s].x, sh[s].y, sh[s].z, sh[s].w};
       float4 o[2];
       float* of = (float*)o;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float mul = rs * gmv[i];
-        float off = btv[i] - mu * mul;
-        if (SS) {
-          mul *= 1.f + scv[i];
-          off = off * (1.f + scv[i]) + shv[i];
-        }
+        const float mul = rs * gmv[i];
         of[2 * i] = mul;
-        of[2 * i + 1] = off;
+        of[2 * i + 1] = btv[i] - mu * mul;
       }
       *(float4*)(tab + s * kGnaC + ch) = o[0];
       *(float4*)(tab + s * kGnaC + ch + 2) = o[1];
@@ -253,11 +228,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
   issue(PF, ra[0], rw[0]);
 
   f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int fr = lane & 15, fg = lane >> 4;
+  // (the k-tile step written out, not gemm_steps.h wave_tile_mfma: through the function hipcc moves three lgkmcnt waits of the first k-tile)
   auto compute = [&](int kt) {
     const T* as = As + (kt & 1) * BM * BK;
     const T* ws = Ws + (kt & 1) * BN * BK;
@@ -267,12 +240,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
 #pragma unroll
       for (int j = 0; j < FM; ++j) {
         const int r = wm * TM + j * 16 + fr;
-        fa[j] = *(const x8*)(as + r * BK + (((ks * 4 + fg) ^ ((r >> 1) & 7)) * 8));
+        fa[j] = *(const x8*)(as + r * BK + swz(r, ks * 4 + fg));
       }
 #pragma unroll
       for (int i = 0; i < FN; ++i) {
         const int r = wn * TN + i * 16 + fr;
-        fw[i] = *(const x8*)(ws + r * BK + (((ks * 4 + fg) ^ ((r >> 1) & 7)) * 8));
+        fw[i] = *(const x8*)(ws + r * BK + swz(r, ks * 4 + fg));
       }
 #pragma unroll
       for (int i = 0; i < FN; ++i)

@@ -103,6 +103,10 @@ struct GemmDev {
   EA e;
 };
 
+}  // namespace tt
+#include "gemm_steps.h"
+namespace tt {
+
 __device__ __forceinline__ float4 load_upto4(const float* p, int nvalid) {  // ragged / unaligned edge: element loads
   float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
   if (nvalid > 0) r.x = p[0];
@@ -212,13 +216,7 @@ struct EpiStd {
     if (has_f32(e)) {
       float* o = e.out_f32 + (size_t)m * e.ldo32 + n;
       if (AL || (nvalid == 4 && (e.ldo32 & 3) == 0)) {
-#if defined(TT_WT_F32)
-        // A/B knob (build.py --variant wt -DTT_WT_F32; profiles/r05_ab_writethrough_f32.txt): the f32 result written THROUGH (sc1), so that
-        // the kernel boundary finds no dirty lines to flush; every wave drains its stores at the end of run_epilogue
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(o), "v"(v) : "memory");
-#else
         *(float4*)o = make_float4(v[0], v[1], v[2], v[3]);
-#endif
       } else {
         for (int i = 0; i < nvalid; ++i) o[i] = v[i];
       }
@@ -420,16 +418,10 @@ __device__ __forceinline__ void run_epilogue(const GemmCore& c, const typename E
   float s0[FN], q0[FN], s1[FN], q1[FN];
   // big wave tiles read the skip here, strip by strip.  With the strip's own four quads as the only loads in flight the 256 x 256 tile's
   // epilogue is a chain of four dependent HBM round trips per wave (~40 us per tile at the pre-pass shapes, as long as its 16-k-tile main
-  // loop).  Requesting the NEXT strip's quads before this strip is worked on (AHEAD, round 5) needs 16 more live registers in a 128-VGPR
-  // wave: hipcc spills 40 bytes per lane and the long-form reading workload ran 2.3 % slower (profiles/r05_ab_flash_ks4_and_epilogue_prefetch.txt)
-  // - the knob stays off.
-#if defined(TT_EPI_PREFETCH)   // A/B knob (build.py --variant pf -DTT_EPI_PREFETCH), default OFF: measured slower, see below
-  constexpr bool AHEAD = true;
-#else
-  constexpr bool AHEAD = false;
-#endif
+  // loop).  Requesting the NEXT strip's quads before this strip is worked on (round 5) needs 16 more live registers in a 128-VGPR wave:
+  // hipcc spilled 40 bytes per lane and the long-form reading workload ran 2.3 % slower (profiles/r05_ab_flash_ks4_and_epilogue_prefetch.txt).
   constexpr bool LATE = Epi::kId == 0 && FM * FN > 8;
-  float4 rq_cur[LATE ? FM : 1], rq_nxt[LATE ? FM : 1];
+  float4 rq_cur[LATE ? FM : 1];
   auto fetch_skip = [&](float4 (&dst)[LATE ? FM : 1], int i) {
     if constexpr (LATE) {
       const int n = n0w + i * 16 + fg * 4;
@@ -445,11 +437,7 @@ __device__ __forceinline__ void run_epilogue(const GemmCore& c, const typename E
     const int nvalid = c.N - n >= 4 ? 4 : c.N - n;
     s0[i] = q0[i] = s1[i] = q1[i] = 0.f;
     if constexpr (LATE) {
-      if constexpr (AHEAD) {
-        if (i + 1 < FN) fetch_skip(rq_nxt, i + 1);
-      } else if (i > 0) {
-        fetch_skip(rq_cur, i);
-      }
+      if (i > 0) fetch_skip(rq_cur, i);
     }
 #pragma unroll
     for (int j = 0; j < FM; ++j) {
@@ -490,10 +478,6 @@ __device__ __forceinline__ void run_epilogue(const GemmCore& c, const typename E
         if (m < c.M && n < c.N) Epi::template store<AL>(c, e, step_t, m, n, acc[i][j], nvalid, z);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (LATE && AHEAD) {
-#pragma unroll
-        for (int j = 0; j < FM; ++j) rq_cur[j] = rq_nxt[j];
-      }
     }
   }
   // phase 3: stores, back to back
@@ -534,16 +518,13 @@ __device__ __forceinline__ void run_epilogue(const GemmCore& c, const typename E
       }
     }
   }
-#if defined(TT_WT_F32)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------------
 // Direct-to-LDS staging (global_load_lds_dwordx4): tiles go HBM/L2 -> LDS without passing through VGPRs or
 // ds_write instructions.  A wave instruction fills 1 KiB = 8 rows x 128 B, lane-linear, so rows are
-// unpadded; bank conflicts are removed by an XOR swizzle applied on the SOURCE side: LDS chunk c of row r
-// holds global 16-byte chunk c ^ ((r >> 1) & 7), and fragment reads apply the same involution.
+// unpadded; bank conflicts are removed by an XOR swizzle applied on the SOURCE side (gemm_steps.h swz),
+// and fragment reads apply the same involution.
 // Conv padding / out-of-range rows cannot be zero-filled by a select any more: those lanes read a 16-byte
 // zero page instead.
 static __device__ __attribute__((aligned(16))) unsigned int g_zero_page[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -557,7 +538,6 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 template <typename T, int BM, int BN, int NW, int WM, int ST, typename Epi, bool CONV, bool AL, int HA2>
 __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typename Epi::Args> g) {
   constexpr bool SEGV = CONV && HA2 == 2;
-  typedef typename Vec<T>::x8 x8;
   constexpr int BK = 64;
   constexpr int WGN = NW / WM;        // waves along N; WM waves along M
   constexpr int TM = BM / WM, TN = BN / WGN;
@@ -572,32 +552,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave % WM, wn = wave / WM;
-  // XCD-aware tile order.  Hardware deals workgroup i to XCD i % 8, each with a private 4 MiB L2, and everything that is
-  // not in the LOCAL L2 arrives over the fabric at HBM-like bandwidth (~6.5 TB/s for the whole chip, Infinity-Cache hits
-  // included: scripts/kbench.py bw).  So the tile grid is cut into row bands and every XCD owns a contiguous run of
-  // (band, column, row-in-band)-ordered tiles, i.e. a rectangle of about (gx / bands) x (8 gy / ...) tiles: it pulls
-  // A / bands + W * bands / 8 over the fabric instead of all of A (one band, the decode shapes where A is tiny) or all
-  // of W (8 bands).  gemm_launch picks the band count to minimise that sum.  The grid is one-dimensional
-  // (gx * gy workgroups, z = split-K slab) and every division is a multiply-high by a host-computed reciprocal.
   unsigned bx, by;
-  {
-    const unsigned id = blockIdx.x;
-    const unsigned xcd = id & 7, loc = id >> 3;
-    const unsigned nid = xcd * c.xq + min(xcd, c.xr) + loc;
-    unsigned rem, rr;
-    const unsigned band = fdiv(nid, c.band, rem);
-    const bool lastb = band == c.last_band;
-    FastDiv hd;
-    hd.d = lastb ? c.hlast.d : c.hfull.d;
-    hd.m = lastb ? c.hlast.m : c.hfull.m;
-    by = fdiv(rem, hd, rr);
-    bx = band * c.hb + rr;
-  }
+  tile_origin(c, blockIdx.x, bx, by);
   const int m0 = bx * BM, n0 = by * BN;
   const int z = blockIdx.z;
-  // split-K slab z covers k-tiles [kt_begin, kt_end): nk_total / splitk each, the first nk_total % splitk slabs one more.
-  const int kt_begin = z * c.sk_quot + min(z, c.sk_rem);
-  const int kt_end = kt_begin + c.sk_quot + (z < c.sk_rem ? 1 : 0);
+  const KRange kr = splitk_range(c, z);
+  const int kt_begin = kr.begin, kt_end = kr.end;
   const T* A = (const T*)c.A;
   const T* W = (const T*)c.W;
   const T* zero = (const T*)g_zero_page;
@@ -614,7 +574,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
 #pragma unroll
   for (int p = 0; p < PA; ++p) {
     const int row = (wave + NW * p) * 8 + lr;
-    a_src[p] = (lc ^ ((row >> 1) & 7)) * 8;
+    a_src[p] = swz(row, lc);
     const int m = m0 + row;
     a_ok[p] = m < c.M;
     if (CONV) {
@@ -632,7 +592,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
   for (int p = 0; p < PW; ++p) {
     const int row = (wave + NW * p) * 8 + lr;
     const int n = n0 + row;
-    w_ptr[p] = W + (size_t)(n < c.N ? n : c.N - 1) * c.ldw + (lc ^ ((row >> 1) & 7)) * 8;
+    w_ptr[p] = W + (size_t)(n < c.N ? n : c.N - 1) * c.ldw + swz(row, lc);
   }
 
   // k-tile cursor of the NEXT tile to request: (it, tap, k-tile within the tap).  Advanced incrementally (no division
@@ -679,6 +639,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
   };
 
   f32x4 acc[FN][FM];
+  // (written out, not gemm_steps.h zero_acc: through the function - or with `= {}` - the 64 x 64 serial kernel takes 92 instead of 68 VGPRs)
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
@@ -712,28 +673,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
   };
 
   const int fr = lane & 15, fg = lane >> 4;
-  auto compute = [&](int buf) {
-    const T* as = As + buf * BM * BK;
-    const T* ws = Ws + buf * BN * BK;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      x8 fa[FM], fw[FN];
-#pragma unroll
-      for (int j = 0; j < FM; ++j) {
-        const int r = wm * TM + j * 16 + fr;
-        fa[j] = *(const x8*)(as + r * BK + (((ks * 4 + fg) ^ ((r >> 1) & 7)) * 8));
-      }
-#pragma unroll
-      for (int i = 0; i < FN; ++i) {
-        const int r = wn * TN + i * 16 + fr;
-        fw[i] = *(const x8*)(ws + r * BK + (((ks * 4 + fg) ^ ((r >> 1) & 7)) * 8));
-      }
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) acc[i][j] = mfma16(fw[i], fa[j], acc[i][j]);
-    }
-  };
+  auto compute = [&](int buf) { wave_tile_mfma<T, FM, FN>(acc, As + buf * BM * BK, Ws + buf * BN * BK, wm * TM + fr, wn * TN + fr, fg); };
 
   if constexpr (ST == 2) {
     // two-stage variant: every barrier drains the queue anyway, so the epilogue operands go out with the first tile
@@ -772,14 +712,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_glds_kernel(const GemmDev<typena
     for (int kt = kt_begin; kt < kt_end; ++kt) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * G) : "memory");
       __builtin_amdgcn_s_barrier();
-      int nslot = slot + ST - 1;
-      if (nslot >= ST) nslot -= ST;
-      issue(nslot);
+      issue(ring_fill_slot<ST>(slot));
       compute(slot);
       if constexpr (Epi::kSerial) {
         if (--ser_left == 0) ser_fold();
       }
-      slot = slot + 1 == ST ? 0 : slot + 1;
+      slot = ring_next_slot<ST>(slot);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
@@ -832,19 +770,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave % WM, wn = wave / WM;
   unsigned bx, by;
-  {
-    const unsigned id = blockIdx.x;
-    const unsigned xcd = id & 7, loc = id >> 3;
-    const unsigned nid = xcd * c.xq + min(xcd, c.xr) + loc;
-    unsigned rem, rr;
-    const unsigned band = fdiv(nid, c.band, rem);
-    const bool lastb = band == c.last_band;
-    FastDiv hd;
-    hd.d = lastb ? c.hlast.d : c.hfull.d;
-    hd.m = lastb ? c.hlast.m : c.hfull.m;
-    by = fdiv(rem, hd, rr);
-    bx = band * c.hb + rr;
-  }
+  tile_origin(c, blockIdx.x, bx, by);
   const int m0 = bx * BM, n0 = by * BN;
   const T* A = (const T*)c.A;
   const T* W = (const T*)c.W;
@@ -865,13 +791,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
       const int m = m0 + R - 8;                     // activation row it mirrors
       const bool wanted = R >= 7 && R <= BM + 8;    // body + the two halo rows
       if (wanted && m >= 0 && m < c.M) {
-        src[k] = A + (size_t)m * c.lda + (lc ^ ((R >> 1) & 7)) * 8;
+        src[k] = A + (size_t)m * c.lda + swz(R, lc);
         adv[k] = BK;
       }
     } else if (p < PIECES) {
       const int q = p - APIECES, t = q / WPT, row = (q - t * WPT) * 8 + lr;
       const int n = min(n0 + row, c.N - 1);
-      src[k] = W + (size_t)n * c.ldw + (size_t)t * cin + (lc ^ ((row >> 1) & 7)) * 8;
+      src[k] = W + (size_t)n * c.ldw + (size_t)t * cin + swz(row, lc);
       adv[k] = BK;
     }
   }
@@ -910,6 +836,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
   }
   const bool wave_edge = __builtin_amdgcn_ballot_w64(edge) != 0ull;
 
+  // the wave-tile step of gemm_steps.h (wave_tile_mfma) per tap, with the tap's row offset, W tile and edge mask - written out, as is the
+  // zeroing above: through the functions hipcc reorders the LDS reads and MFMAs of this loop (profiles/gemm_refactor_isa.txt)
   auto compute = [&](int buf, auto masked) {
     constexpr bool MASK = decltype(masked)::value;
     const T* as = ring + (size_t)buf * STAGE;
@@ -922,7 +850,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
 #pragma unroll
         for (int j = 0; j < FM; ++j) {
           const int R = 8 + wm * TM + j * 16 + fr + (t - 1);
-          fa[j] = *(const x8*)(as + R * BK + (((ks * 4 + fg) ^ ((R >> 1) & 7)) * 8));
+          fa[j] = *(const x8*)(as + R * BK + swz(R, ks * 4 + fg));
           if (MASK) {
             const bool pad = (t == 0 && first_row[j]) || (t == 2 && last_row[j]);
             if (pad) {
@@ -934,7 +862,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
 #pragma unroll
         for (int i = 0; i < FN; ++i) {
           const int r = wn * TN + i * 16 + fr;
-          fw[i] = *(const x8*)(ws + (t * BN + r) * BK + (((ks * 4 + fg) ^ ((r >> 1) & 7)) * 8));
+          fw[i] = *(const x8*)(ws + (t * BN + r) * BK + swz(r, ks * 4 + fg));
         }
 #pragma unroll
         for (int i = 0; i < FN; ++i)
@@ -953,12 +881,10 @@ __global__ __launch_bounds__(NW * 64) void gemm_conv3s_kernel(const GemmDev<type
     if (big) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * PMAX) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * PMIN) : "memory");
     __builtin_amdgcn_s_barrier();
-    int nslot = slot + ST - 1;
-    if (nslot >= ST) nslot -= ST;
-    issue(nslot);
+    issue(ring_fill_slot<ST>(slot));
     if (wave_edge) compute(slot, std::true_type{});
     else compute(slot, std::false_type{});
-    slot = slot + 1 == ST ? 0 : slot + 1;
+    slot = ring_next_slot<ST>(slot);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   run_epilogue<Epi, FM, FN, TM, TN, AL>(c, g.e, acc, eo, eo.step(), m0 + wm * TM, n0 + wn * TN, lane, 0);
@@ -1001,6 +927,14 @@ constexpr int kSkinnyStages = TT_SKINNY_ST, kSkinnyStages64 = TT_SKINNY_ST64, kS
 enum StdVariant { V_GEN = 0, V_NONE = 1, V_SLAB = 2, V_GELU_T = 3, V_ST_F32 = 4, V_ST_RES = 5, V_ST_A2 = 6, V_BIAS_T = 7, V_SERIAL = 8, V_COUNT = 9 };
 constexpr int kNoKernel = -100;  // visit_*: this combination is not instantiated
 
+// "Aligned epilogue": N % 4 == 0 and every operand / output that is present has 16-byte aligned rows (the T output: 8-byte), so the
+// epilogue moves whole quads (the kernels' AL = true).  gemm_launch_typed adds N >= 4; the shared-halo conv and gemm_gna need an f32 output
+// to be present and take no T output (their own tests).
+static inline bool epi_aligned(const GemmArgs& a) {
+  return (a.N & 3) == 0 && (!a.bias || ((size_t)a.bias & 15) == 0) && (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
+         (!a.out_f32 || (((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0)) && (!a.out_t || (((size_t)a.out_t & 7) == 0 && (a.ldot & 3) == 0));
+}
+
 struct GemmPlan {   // what gemm_launch (gemm.hip) decided: tile, grid, the device argument core
   GemmCore core;
   int tile;
@@ -1040,48 +974,51 @@ struct KernelRef {
   }
 };
 
+// the EPI_STD epilogues that are instantiated (StdVariant)
+template <typename T> using EGen = EpiStd<T, -1, -1, -1>;                               // everything tested at run time
+template <typename T> using EGenNoStats = EpiStd<T, -1, 0, -1>;                         // skinny tiles: the same without statistics
+template <typename T> using ENone = EpiStd<T, ACT_NONE, 0, -1>;                         // no activation / statistics, run-time outputs
+template <typename T> using ESlab = EpiStd<T, ACT_NONE, 0, EB_SLAB>;                    // split-K partial sums (decode projections)
+template <typename T> using EGeluT = EpiStd<T, ACT_GELU_TANH, 0, EB_BIAS | EB_T>;       // GPT-2 c_fc
+template <typename T> using EBiasT = EpiStd<T, ACT_NONE, 0, EB_BIAS | EB_T>;            // plain Linear / conv feeding the next GEMM
+template <typename T> using EStF32 = EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32>;          // denoiser 1x1 in front of a GroupNorm
+template <typename T> using EStRes = EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_RES | EB_F32>; // denoiser conv / attention projection + skip
+
 // v(KernelRef) is called for the EPI_STD instantiation (tile, variant, conv, al); kNoKernel when that one does not exist
 // segv: the per-sequence valid-length conv (HA2 = 2 on a conv, HiFi-GAN's ragged batches): generic and run-time-output forms only
 template <typename T, int BM, int BN, int NW, int WM, int ST, typename V>
 static int visit_std_tile(int variant, bool conv, bool al, bool segv, V&& v) {
-  typedef EpiStd<T, -1, -1, -1> EGen;                                     // everything tested at run time
-  typedef EpiStd<T, ACT_NONE, 0, -1> ENone;                               // no activation / statistics, run-time outputs
   if (segv) {
     if (!conv) return kNoKernel;
-    if (variant == V_GEN) return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, true, 2>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, false, 2>{});
-    if (variant == V_NONE && al) return v(KernelRef<T, BM, BN, NW, WM, ST, ENone, true, true, 2>{});
+    if (variant == V_GEN) return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, true, true, 2>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, true, false, 2>{});
+    if (variant == V_NONE && al) return v(KernelRef<T, BM, BN, NW, WM, ST, ENone<T>, true, true, 2>{});
     return kNoKernel;
   }
-  typedef EpiStd<T, ACT_NONE, 0, EB_SLAB> ESlab;                          // split-K partial sums (decode projections)
-  typedef EpiStd<T, ACT_GELU_TANH, 0, EB_BIAS | EB_T> EGeluT;             // GPT-2 c_fc
-  typedef EpiStd<T, ACT_NONE, 0, EB_BIAS | EB_T> EBiasT;                  // plain Linear / conv feeding the next GEMM
-  typedef EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32> EStF32;                // denoiser 1x1 in front of a GroupNorm
-  typedef EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_RES | EB_F32> EStRes;       // denoiser conv / attention projection + skip
   switch (variant) {
     case V_GEN:
-      if (conv) return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, true, -1>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen, true, false, -1>{});
-      return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen, false, true, -1>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen, false, false, -1>{});
+      if (conv) return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, true, true, -1>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, true, false, -1>{});
+      return al ? v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, false, true, -1>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EGen<T>, false, false, -1>{});
     case V_NONE:
       if (!al) return kNoKernel;
-      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, ENone, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, ENone, false, true, 0>{});
+      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, ENone<T>, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, ENone<T>, false, true, 0>{});
     case V_SLAB:
       if (!al || conv) return kNoKernel;
-      return v(KernelRef<T, BM, BN, NW, WM, ST, ESlab, false, true, 0>{});
+      return v(KernelRef<T, BM, BN, NW, WM, ST, ESlab<T>, false, true, 0>{});
     case V_GELU_T:
       if (!al || conv) return kNoKernel;
-      return v(KernelRef<T, BM, BN, NW, WM, ST, EGeluT, false, true, 0>{});
+      return v(KernelRef<T, BM, BN, NW, WM, ST, EGeluT<T>, false, true, 0>{});
     case V_ST_F32:
       if (!al) return kNoKernel;
-      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EStF32, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EStF32, false, true, 0>{});
+      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EStF32<T>, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EStF32<T>, false, true, 0>{});
     case V_ST_RES:
       if (!al) return kNoKernel;
-      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EStRes, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EStRes, false, true, 0>{});
+      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EStRes<T>, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EStRes<T>, false, true, 0>{});
     case V_ST_A2:
       if (!al || conv) return kNoKernel;
-      return v(KernelRef<T, BM, BN, NW, WM, ST, EStF32, false, true, 1>{});
+      return v(KernelRef<T, BM, BN, NW, WM, ST, EStF32<T>, false, true, 1>{});
     case V_BIAS_T:
       if (!al) return kNoKernel;
-      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EBiasT, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EBiasT, false, true, 0>{});
+      return conv ? v(KernelRef<T, BM, BN, NW, WM, ST, EBiasT<T>, true, true, 0>{}) : v(KernelRef<T, BM, BN, NW, WM, ST, EBiasT<T>, false, true, 0>{});
     case V_SERIAL:
       if constexpr ((BM / WM / 16) * (BN / (NW / WM) / 16) > 8) return kNoKernel;  // needs the skip quads in registers next to two accumulator sets
       else {
@@ -1097,11 +1034,11 @@ static int visit_skinny(int variant, bool conv, bool al, V&& v) {
   if (conv || !al) return kNoKernel;
   constexpr int NW = kSkinnyNW, WM = kSkinnyWM, ST = BM == 32 ? kSkinnyStages : kSkinnyStages64;
   switch (variant) {
-    case V_GEN: return v(KernelRef<T, BM, BN, NW, WM, ST, EpiStd<T, -1, 0, -1>, false, true, 0>{});
-    case V_NONE: return v(KernelRef<T, BM, BN, NW, WM, ST, EpiStd<T, ACT_NONE, 0, -1>, false, true, 0>{});
-    case V_SLAB: return v(KernelRef<T, BM, BN, NW, WM, ST, EpiStd<T, ACT_NONE, 0, EB_SLAB>, false, true, 0>{});
-    case V_GELU_T: return v(KernelRef<T, BM, BN, NW, WM, ST, EpiStd<T, ACT_GELU_TANH, 0, EB_BIAS | EB_T>, false, true, 0>{});
-    case V_BIAS_T: return v(KernelRef<T, BM, BN, NW, WM, ST, EpiStd<T, ACT_NONE, 0, EB_BIAS | EB_T>, false, true, 0>{});
+    case V_GEN: return v(KernelRef<T, BM, BN, NW, WM, ST, EGenNoStats<T>, false, true, 0>{});
+    case V_NONE: return v(KernelRef<T, BM, BN, NW, WM, ST, ENone<T>, false, true, 0>{});
+    case V_SLAB: return v(KernelRef<T, BM, BN, NW, WM, ST, ESlab<T>, false, true, 0>{});
+    case V_GELU_T: return v(KernelRef<T, BM, BN, NW, WM, ST, EGeluT<T>, false, true, 0>{});
+    case V_BIAS_T: return v(KernelRef<T, BM, BN, NW, WM, ST, EBiasT<T>, false, true, 0>{});
   }
   return kNoKernel;
 }
@@ -1150,10 +1087,22 @@ static inline EpiStdArgs make_epi_std(const GemmArgs& a) {
 }
 
 // shared-halo 3-tap convolution (gemm_conv3s_kernel): 128 x 64 tile, 8 waves as 4 x 2, 3-stage ring of 42 KB stages
-constexpr int kConv3sStages = 3;
-constexpr int kConv3sSmem = kConv3sStages * ((128 + 16) / 8 + 3 * 64 / 8) * 1024;
 template <typename T, typename Epi>
-static const void* conv3s_fn() { return (const void*)gemm_conv3s_kernel<T, 128, 64, 8, 4, kConv3sStages, Epi, true>; }
+struct Conv3sRef {
+  typedef typename Epi::Args EA;
+  static constexpr int BM = 128, BN = 64, NW = 8, WM = 4, ST = 3;
+  static constexpr int smem = ST * ((BM + 16) / 8 + 3 * BN / 8) * 1024;
+  static const void* fn() { return (const void*)gemm_conv3s_kernel<T, BM, BN, NW, WM, ST, Epi, true>; }
+  static const void* fn_p8() { return nullptr; }
+  static void launch(const ProfScope& ps, dim3 grid, hipStream_t s, const GemmDev<EA>& d) {
+    launch_timed(ps, gemm_conv3s_kernel<T, BM, BN, NW, WM, ST, Epi, true>, grid, dim3(NW * 64), smem, s, d);
+  }
+};
+// v(Conv3sRef) for the two statistics epilogues it is built with (with / without skip)
+template <typename T, typename V>
+static int visit_conv3s(bool res, V&& v) {
+  return res ? v(Conv3sRef<T, EStRes<T>>{}) : v(Conv3sRef<T, EStF32<T>>{});
+}
 
 template <typename T>
 int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStream_t stream) {
@@ -1161,24 +1110,24 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
   ProfScope ps(plan.prof_id, stream, plan.flops, plan.bytes, true);
   int rc = kNoKernel;
   g_gemm_ran = GemmRan{plan.tile, -1, 0, plan.conv3s ? 1 : 0};
+  auto launch = [&](const auto& d) {  // visitor: launch the instantiation a visit_* picked on the argument block d
+    return [&](auto kr) -> int {
+      decltype(kr)::launch(ps, grid, stream, d);
+      return 0;
+    };
+  };
   if (epi == EPI_STD && plan.conv3s) {  // (gemm.hip decided: aligned, statistics epilogue, bias + f32 output (+ skip), 128x64 tile)
     GemmDev<EpiStdArgs> d;
     d.c = plan.core;
     d.e = make_epi_std(a);
     g_gemm_ran.variant = a.res ? V_ST_RES : V_ST_F32;
-    if (a.res) launch_timed(ps, gemm_conv3s_kernel<T, 128, 64, 8, 4, kConv3sStages, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_RES | EB_F32>, true>, grid, dim3(512), kConv3sSmem, stream, d);
-    else launch_timed(ps, gemm_conv3s_kernel<T, 128, 64, 8, 4, kConv3sStages, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32>, true>, grid, dim3(512), kConv3sSmem, stream, d);
-    TT_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (epi == EPI_STD) {
+    rc = visit_conv3s<T>(a.res != nullptr, launch(d));
+  } else if (epi == EPI_STD) {
     GemmDev<EpiStdArgs> d;
     d.c = plan.core;
     d.e = make_epi_std(a);
     // aligned fast path: whole-quad operand fetches and stores with no per-element fallback code in the kernel
-    const bool al = (a.N & 3) == 0 && a.N >= 4 && (!a.bias || ((size_t)a.bias & 15) == 0) &&
-                    (!a.res || (((size_t)a.res & 15) == 0 && (a.ldres & 3) == 0)) &&
-                    (!a.out_f32 || (((size_t)a.out_f32 & 15) == 0 && (a.ldo32 & 3) == 0)) && (!a.out_t || (((size_t)a.out_t & 7) == 0 && (a.ldot & 3) == 0));
+    const bool al = a.N >= 4 && epi_aligned(a);
     const bool conv = a.taps > 1, stats = a.gn_part != nullptr, a2 = a.A2 != nullptr;
     int variant = V_GEN;
     if (a.serial_k > 1) {
@@ -1198,10 +1147,7 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
         variant = V_GELU_T;
       }
     }
-    auto go = [&](auto kr) -> int {
-      decltype(kr)::launch(ps, grid, stream, d);
-      return 0;
-    };
+    auto go = launch(d);
     const bool segv = plan.core.vlen != nullptr;
     rc = visit_std<T>(plan.tile, variant, conv, al, go, segv);
     if (rc == kNoKernel && variant != V_SERIAL) {
@@ -1215,10 +1161,7 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
     memset(&d.e, 0, sizeof(d.e));
     d.e.bias = a.bias; d.e.q = a.q; d.e.k = a.k; d.e.v = a.v; d.e.vt = a.vt; d.e.heads = a.heads; d.e.seq_pad = a.seq_pad; d.e.q_scale = a.q_scale;
     d.e.dmodel = make_fastdiv(a.dmodel);
-    rc = visit_qkv<T, EpiQkvHeads<T>>(plan.tile, [&](auto kr) -> int {
-      decltype(kr)::launch(ps, grid, stream, d);
-      return 0;
-    });
+    rc = visit_qkv<T, EpiQkvHeads<T>>(plan.tile, launch(d));
   } else if (epi == EPI_QKV_DECODE) {
     GemmDev<EpiQkvDecodeArgs> d;
     d.c = plan.core;
@@ -1226,18 +1169,12 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
     d.e.bias = a.bias; d.e.step = a.step; d.e.qbuf = a.qbuf; d.e.kc = a.kc; d.e.vc = a.vc; d.e.heads = a.heads; d.e.tmax = a.tmax; d.e.dmodel_i = a.dmodel;
     d.e.q_scale = a.q_scale;
     d.e.dmodel = make_fastdiv(a.dmodel);
-    rc = visit_qkv<T, EpiQkvDecode<T>>(plan.tile, [&](auto kr) -> int {
-      decltype(kr)::launch(ps, grid, stream, d);
-      return 0;
-    });
+    rc = visit_qkv<T, EpiQkvDecode<T>>(plan.tile, launch(d));
   } else if (epi == EPI_GEGLU) {
     GemmDev<EpiGegluArgs> d;
     d.c = plan.core;
     d.e.bias = a.bias; d.e.out_t = a.out_t; d.e.ldot = a.ldot;
-    rc = visit_qkv<T, EpiGeglu<T>>(plan.tile, [&](auto kr) -> int {
-      decltype(kr)::launch(ps, grid, stream, d);
-      return 0;
-    });
+    rc = visit_qkv<T, EpiGeglu<T>>(plan.tile, launch(d));
   }
   if (rc == kNoKernel) {
     set_error("gemm: no kernel for epilogue %d tile %d", epi, plan.tile);
@@ -1265,21 +1202,18 @@ int gemm_launch_typed(int epi, const GemmArgs& a, const GemmPlan& plan, hipStrea
 #endif
 constexpr int kGnaBM = TT_GNA_BM, kGnaBN = TT_GNA_BN, kGnaWM = TT_GNA_WM, kGnaST = TT_GNA_PF, kGnaNW = TT_GNA_NW;  // (kGnaST: prefetch depth in k-tiles)
 constexpr int kGnaSmem = 0;
-template <typename T, typename Epi, bool SS, bool SILU>
-static const void* gna_fn() { return (const void*)gemm_gna_kernel<T, kGnaBM, kGnaBN, kGnaNW, kGnaWM, kGnaST, Epi, SS, SILU>; }
 
 template <typename T>
 int gemm_gna_launch_typed(const GemmArgs& a, const GemmPlan& plan, const GnaArgs& n, hipStream_t stream) {
   const dim3 grid(plan.core.gx * plan.core.gy, 1, 1);
   ProfScope ps(plan.prof_id, stream, plan.flops, plan.bytes, true);
-  typedef EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32> EStF32;
   GemmGnaDev<EpiStdArgs> d;
   d.c = plan.core;
   d.e = make_epi_std(a);
   d.n = n;
-  if (n.act == ACT_SILU && !n.ss) launch_timed(ps, gemm_gna_kernel<T, kGnaBM, kGnaBN, kGnaNW, kGnaWM, kGnaST, EStF32, false, true>, grid, dim3(kGnaNW * 64), kGnaSmem, stream, d);
+  if (n.act == ACT_SILU) launch_timed(ps, gemm_gna_kernel<T, kGnaBM, kGnaBN, kGnaNW, kGnaWM, kGnaST, EStF32<T>, true>, grid, dim3(kGnaNW * 64), kGnaSmem, stream, d);
   else {
-    set_error("gemm_gna: no kernel for act %d scale_shift %d", n.act, n.ss != nullptr);
+    set_error("gemm_gna: no kernel for act %d", n.act);
     return -1;
   }
   TT_CHECK_HIP(hipGetLastError());
@@ -1304,8 +1238,7 @@ int gemm_init_typed() {
     (void)visit_qkv<T, EpiQkvDecode<T>>(tile, setattr);
     (void)visit_qkv<T, EpiGeglu<T>>(tile, setattr);
   }
-  if (hipFuncSetAttribute(conv3s_fn<T, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_RES | EB_F32>>(), hipFuncAttributeMaxDynamicSharedMemorySize, kConv3sSmem) != hipSuccess) ++bad;
-  if (hipFuncSetAttribute(conv3s_fn<T, EpiStd<T, ACT_NONE, 1, EB_BIAS | EB_F32>>(), hipFuncAttributeMaxDynamicSharedMemorySize, kConv3sSmem) != hipSuccess) ++bad;
+  for (int res = 0; res < 2; ++res) (void)visit_conv3s<T>(res != 0, setattr);
   if (bad) {
     set_error("gemm: hipFuncSetAttribute failed for %d kernel(s): %s", bad, hipGetErrorString(hipGetLastError()));
     return -2;

@@ -42,24 +42,12 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const GemmDev<typename Epi
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
   unsigned bx, by;
-  {  // XCD-aware tile order (see gemm_glds_kernel)
-    const unsigned id = blockIdx.x;
-    const unsigned xcd = id & 7, loc = id >> 3;
-    const unsigned nid = xcd * c.xq + min(xcd, c.xr) + loc;
-    unsigned rem, rr;
-    const unsigned band = fdiv(nid, c.band, rem);
-    const bool lastb = band == c.last_band;
-    FastDiv hd;
-    hd.d = lastb ? c.hlast.d : c.hfull.d;
-    hd.m = lastb ? c.hlast.m : c.hfull.m;
-    by = fdiv(rem, hd, rr);
-    bx = band * c.hb + rr;
-  }
+  tile_origin(c, blockIdx.x, bx, by);
   const int m0 = bx * BM, n0 = by * BN;
   const int nk = c.sk_quot;  // (no split-K: all k-tiles)
 
   // LDS-DMA geometry: a wave fills pieces `wave` and `wave + 8` (8 rows of 128 bytes each) of every half-tile; lane -> (row lr, chunk lc),
-  // LDS chunk lc of row r holds global chunk lc ^ ((r >> 1) & 7).  Rows beyond M / N re-read row 0 / N - 1 (never stored).
+  // swizzled on the source side (gemm_steps.h swz).  Rows beyond M / N re-read row 0 / N - 1 (never stored).
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)c.A, 0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)c.W, 0, 0x7fffffff, 0x00020000);
   const int lr = lane >> 3, lc = lane & 7;
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const GemmDev<typename Epi
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int row = (wave + 8 * p) * 8 + lr;
-    const int sw = (lc ^ ((row >> 1) & 7)) * 8;
+    const int sw = swz(row, lc);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int m = m0 + h * 128 + row, n = n0 + h * 128 + row;
@@ -88,17 +76,13 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const GemmDev<typename Epi
 
   f32x4 acc[4][2][4];  // [quadrant = 2 * (A half) + (W half)][16-column strip][16-row tile]
 #pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[q][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < 4; ++q) zero_acc(acc[q]);
   x8 fa[4][2];      // [row tile][k-step] of the current A half
   x8 fw[2][2][2];   // [W half][strip][k-step]
   const int fr = lane & 15, fg = lane >> 4;
-  // fragment addresses: row r of a half-tile at r * 64 elements, 16-byte chunk (ks * 4 + fg) ^ ((r >> 1) & 7); r = 16 t + fr + 64 wr (A) or
-  // 16 t + fr + 32 wc (W), so (r >> 1) & 7 == fr >> 1 for every tile t
-  const int ch0 = ((0 * 4 + fg) ^ (fr >> 1)) * 8, ch1 = ((1 * 4 + fg) ^ (fr >> 1)) * 8;
+  // fragment addresses: row r of a half-tile at r * 64 elements, chunk ks * 4 + fg at swz(r, ks * 4 + fg); r = 16 t + fr + 64 wr (A) or
+  // 16 t + fr + 32 wc (W): a multiple of 16 plus fr, so swz(r, .) == swz(fr, .) for every tile t and the two offsets are formed once
+  const int ch0 = swz(fr, 0 * 4 + fg), ch1 = swz(fr, 1 * 4 + fg);
   const int a_row = (wr * 64 + fr) * BK, w_row = (wc * 32 + fr) * BK;
   auto read_a = [&](int d, int half) {
     const T* s = L + (d * 4 + 1 + 2 * half) * HT + a_row;
@@ -124,15 +108,10 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const GemmDev<typename Epi
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[q][i][j] = mfma16(fw[wh][i][ks], fa[j][ks], acc[q][i][j]);
   };
-#if defined(TT_P8_NO_LGKM0)   // A/B knob: leave the fragment-read waits to the compiler's counted lgkmcnt in front of each MFMA
-#define TT_P8_LGKM0
-#else
-#define TT_P8_LGKM0 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
 #define TT_P8_SYNC_MFMA(q, wh)                          \
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      \
   __builtin_amdgcn_s_barrier();                         \
-  TT_P8_LGKM0                                           \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    \
   __builtin_amdgcn_sched_barrier(0);                    \
   __builtin_amdgcn_s_setprio(1);                        \
   quadrant(q, wh);                                      \
@@ -176,7 +155,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const GemmDev<typename Epi
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the surplus re-fills of the tail)
 #undef TT_P8_KTILE
 #undef TT_P8_SYNC_MFMA
-#undef TT_P8_LGKM0
 
   // epilogue, quadrant by quadrant.  The fragment registers are dead: the operands (bias, skip quads) of TT_P8_EPI_DEPTH quadrants are requested
   // before the first one is worked on and each finished quadrant's slot is re-used for the quadrant DEPTH ahead.
