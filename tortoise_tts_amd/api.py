@@ -39,6 +39,7 @@ from . import dist as tdist
 from . import engine as E
 from . import stages
 from . import loudness as loud
+from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig, PRESETS, BASE_SETTINGS, CALM_TOKEN
@@ -886,7 +887,7 @@ class TextToSpeech(_Common):
                 best = self._rank(wave, samples, 1, grouped=True)
                 items, zs = zip(*[self._winner_inputs(b[0], self.ar.latents(voice[0], t, b), voice[1], o, seed, 0) for t, b in zip(wave, best)])
                 t0 = lap(clock, "clvp_s", t0)
-                wavs, wave_ok = self._render_wave(o.sched, items, zs)
+                wavs, wave_ok = self._render_wave(o.solver if o.solver is not None else o.sched, items, zs)
                 clock["diffusion_s"] += time.perf_counter() - t0
                 out += wavs
                 ok = ok and wave_ok
@@ -905,6 +906,7 @@ class TextToSpeech(_Common):
         hf = dict(args["hf_generate_kwargs"])
         noise = hf.pop("noise_override", None) or {}
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
+        plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
             raise ValueError(f"cvvp_amount={args['cvvp_amount']} must lie in [0, 1] (api.py:366-367)")
@@ -913,6 +915,7 @@ class TextToSpeech(_Common):
             sampling=dict(temperature=args["temperature"], top_p=args["top_p"], repetition_penalty=args["repetition_penalty"], top_k=top_k,
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
+            solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
             diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
@@ -970,22 +973,28 @@ class TextToSpeech(_Common):
 
     def _winner_inputs(self, codes, latents, cond, o, seed, i):
         """Winner i (codes [n], re-passed latents [1, n, D]) -> diffusion item (latents cut at the calm run, cond, S, x_T, step_noise) and
-        vocoder noise z, drawn in that order from seed + 7919 * (i + 1) unless noise_override supplies them (api.py:122, 547-556)."""
+        vocoder noise z, drawn in that order from seed + 7919 * (i + 1) unless noise_override supplies them (api.py:122, 547-556).  With a
+        solver (o.solver) there is no step noise: x_T, then z, are drawn, nothing is allocated for the steps and a supplied step_noise is
+        ignored - so z differs from a p sampler's run at the same seed."""
         dev = self.device
         latents = latents[:, :calm_trim_length(codes)]
         S = latents.shape[1] * 4 * 24000 // 22050
         gen = torch.Generator(device=dev).manual_seed(seed + 7919 * (i + 1))
         x_T, step_noise, z = (o.noise.get(key) for key in ("x_T", "step_noise", "z"))
         x_T = (torch.randn(1, 100, S, device=dev, generator=gen) if x_T is None else x_T.to(dev)) * o.diffusion_temperature
-        if step_noise is None:
+        if o.solver is not None:
+            step_noise = None
+        elif step_noise is None:
             step_noise = torch.randn(o.sched.num_timesteps, 1, 100, S, device=dev, generator=gen)
         z = torch.randn(1, self.voc_cfg.noise_dim, S + 10, device=dev, generator=gen) if z is None else z.to(dev)
         return (latents, cond, S, x_T, step_noise), z
 
     def _diffuse(self, sched, item, split=False):
-        """Diffusion item -> mel.  split: ranks 0 and 1 evaluate denoiser row 0 / 1 of every step; rank 1 only lends its GPU and gets None."""
+        """Diffusion item -> mel (sched: the p sampler's Schedule or a solver's SolverPlan).  split: ranks 0 and 1 evaluate denoiser row 0 / 1 of every step; rank 1 only lends its GPU and gets None."""
         latents, cond, S, x_T, step_noise = item
         self.diffusion.condition(latents, cond, S)
+        if isinstance(sched, fastsolver.SolverPlan):  # (never split: _utterance)
+            return self.diffusion.solve(sched, x_T)
         if not split:
             return self.diffusion.sample(sched, x_T, step_noise)
         mel = self.diffusion.sample_split(sched, x_T, step_noise, self.rank, tdist.exchange_rows)
@@ -1004,14 +1013,15 @@ class TextToSpeech(_Common):
         ev.mark(2)
         best_latents = self.ar.latents(auto, tokens, best)
         ev.mark(3)
-        split = self.split_diffusion and k == 1 and bool(o.sched.cond_free)
+        split = self.split_diffusion and k == 1 and bool(o.sched.cond_free) and o.solver is None  # (a solver's winner renders unsplit on rank 0)
+        plan = o.solver if o.solver is not None else o.sched
         wavs, ok = {}, True
         mine = [i for i in range(k) if not ((self.rank > 1) if split else (i % self.world != self.rank))]
         if self.winner_batch >= 2 and len(mine) >= 2:  # (one winner on this rank, the k = 1 split tail included: the single path below)
             return self._render_winners(ev, mine, best, best_latents, diff, o, seed, keep_on_device)
         for i in mine:
             item, z = self._winner_inputs(best[i], best_latents[i:i + 1], diff, o, seed, i)
-            mel = self._diffuse(o.sched, item, split)
+            mel = self._diffuse(plan, item, split)
             if mel is None:
                 continue
             ev.mark(4)
@@ -1033,7 +1043,7 @@ class TextToSpeech(_Common):
         for g0 in range(0, len(mine), W):
             grp = mine[g0:g0 + W]
             items, zs = zip(*[self._winner_inputs(best[i], best_latents[i:i + 1], diff, o, seed, i) for i in grp])
-            pending.append((grp, self._diffuse_many(o.sched, items), zs))
+            pending.append((grp, self._diffuse_many(o.solver if o.solver is not None else o.sched, items), zs))
         ev.mark(4)
         for grp, mels, zs in pending:
             for i, audio in zip(grp, self._vocode_many(mels, zs)):
@@ -1049,7 +1059,8 @@ class TextToSpeech(_Common):
             return [self._diffuse(sched, items[0])]
         order = sorted(range(len(items)), key=lambda u: items[u][2])
         mels = [None] * len(items)
-        for u, mel in zip(order, self.diffusion.sample_many(sched, [items[u] for u in order])):
+        many = self.diffusion.solve_many if isinstance(sched, fastsolver.SolverPlan) else self.diffusion.sample_many
+        for u, mel in zip(order, many(sched, [items[u] for u in order])):
             mels[u] = mel
         return mels
 

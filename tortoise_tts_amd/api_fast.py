@@ -34,6 +34,7 @@ import torch
 from . import engine as E
 from . import stages
 from . import loudness as loud
+from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
 from .api import MODELS_DIR, _Common, _load_state_dict, _load_file, sampler_kwargs
@@ -331,6 +332,7 @@ class TextToSpeech(_Common):
         self._single("tts_stream")
         tsm.refuse_streaming(hf_generate_kwargs, "tts_stream")
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -377,6 +379,7 @@ class TextToSpeech(_Common):
         with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken."""
         tsm.refuse_streaming(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
+        fastsolver.refuse_streaming(kwargs, "open_stream")
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -511,6 +514,7 @@ class TextToSpeech(_Common):
         slots are admitted as earlier sessions end."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
+        fastsolver.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):
             seeds = [seeds] * len(texts)

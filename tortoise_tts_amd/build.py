@@ -43,7 +43,7 @@ def _digest(paths):
 def _headers():
     hs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     for name in ("tortoise_mi355x.h", "tortoise_mi355x_test.h", "tortoise_mi355x_align.h", "tortoise_mi355x_classify.h", "tortoise_mi355x_hifi.h",
-                 "tortoise_mi355x_univnet.h", "tortoise_mi355x_mel.h", "tortoise_mi355x_ctc.h", "tortoise_mi355x_tsm.h", "tortoise_mi355x_loud.h"):
+                 "tortoise_mi355x_univnet.h", "tortoise_mi355x_mel.h", "tortoise_mi355x_ctc.h", "tortoise_mi355x_tsm.h", "tortoise_mi355x_loud.h", "tortoise_mi355x_solver.h"):
         hs.append(os.path.join(os.path.dirname(HERE), "include", name))
     return hs
 

@@ -14,12 +14,17 @@
 // posterior mean, noise) is one fused kernel with no host round trip (the reference does a
 // .item() per step, diffusion.py:380).  Per-step scalars, the scale/shift rows and the noise slice
 // are all indexed by a device-side step counter, so one captured hipGraph replays every step.
+// The deterministic solvers of include/tortoise_mi355x_solver.h (DDIM, DPM-Solver++(2M)) run the same loop with another epilogue
+// kernel and their own kept graph (DiffUpdate, diff_sample_run).
 #include "runtime.h"
 #include "../../include/tortoise_mi355x.h"
+#include "../../include/tortoise_mi355x_solver.h"
 
 using namespace tt;
 
 static_assert(sizeof(PSampleStep) == sizeof(tt_diff_step), "PSampleStep must mirror tt_diff_step");
+static_assert(sizeof(SolverStep) == sizeof(tt_solver_step), "SolverStep must mirror tt_solver_step");
+static_assert(sizeof(SolverStep) <= sizeof(PSampleStep), "the solver's step records share the p sampler's device table");
 
 // Work buffers of one pass over the denoiser's layers.  Two sets: [0] the sampler loop / conditioning (rows of ONE step), [1] the
 // conditioning-integrator pre-pass, which runs over whole chunks of the schedule on its own stream WHILE the sampler loop walks the
@@ -79,6 +84,7 @@ struct tt_diff : EngineHandle {
   PSampleStep* steps_dev = nullptr;
   int* slot = nullptr;         // device step counter
   float* x = nullptr;          // [S][in]
+  float* hist = nullptr;       // [S][in]: the previous step's x0 (the solvers' one-tensor history, tortoise_mi355x_solver.h)
   void* x_t = nullptr;         // [2][S][in_pad] T
   float* out = nullptr;        // [2][S][out]
   // guard (EngineHandle): bumped by the GroupNorm / sampler kernels when they meet a non-finite value; every sampling run ends with
@@ -89,6 +95,7 @@ struct tt_diff : EngineHandle {
   const void** io_dev = nullptr;    // [16][2]: {step_noise, mel_out} per utterance
   const void** io_host = nullptr;   // pinned staging
   KeptGraph step;                   // the sampler step; step.captures feeds tt_diff_stat(0)
+  KeptGraph solver_step;            // the same step with the solver epilogue, under its own key: alternating the two re-captures neither
   // split sampling: this handle evaluates one denoiser row per step
   KeptGraph split;
   int split_row = -1, split_steps = 0, split_done = 0;
@@ -304,6 +311,31 @@ static void split_release(tt_diff* e) {
   e->split_steps = e->split_done = 0;
 }
 
+// What a sampler puts behind the denoiser: its step records, its epilogue kernel and the graph its step is kept in.
+struct DiffUpdate {
+  int solver;                      // 0: psample_kernel (p_sample), 1: solver_update_kernel; part of the kept graph's key
+  const void* steps_host;          // n_steps records in run order; the first field of a record is its timestep (int)
+  size_t step_bytes;
+  const float* const* step_noise;  // per utterance, or null: the sampler draws nothing
+  KeptGraph* graph;
+  const char* who;
+};
+
+// The fields PSampleArgs and SolverArgs share, for utterance u inside the padded batch of the current pass.
+template <typename Args>
+static void diff_update_args(tt_diff* e, int u, int cond_free, Args& p) {
+  const int S = e->S, IC = e->cfg.in_channels, IP = e->cfg.in_pad;
+  memset(&p, 0, sizeof(p));
+  p.slot = e->slot; p.x = e->x + (size_t)u * S * IC; p.x_t = offset_t(e->x_t, (size_t)u * S * IP, e->es); p.cpad = IP;
+  p.out = e->out + (size_t)u * S * e->cfg.out_channels;
+  p.has_uncond = cond_free ? 1 : 0; p.S = e->Su[u]; p.C = IC;
+  p.io = e->io_dev + 2 * u;  // {step_noise[u], mel_out[u]}: data of this call, not of the captured step
+  p.guard = e->guard.dev;
+  p.ld_rows = e->U * S;
+  p.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
+  p.mel_shift = -11.512925148010254f;
+}
+
 extern "C" {
 
 int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff** out) {
@@ -364,6 +396,7 @@ int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff*
   if (!rc) rc = e->arena.alloc_t(&e->steps_dev, cfg->max_steps);
   if (!rc) rc = e->arena.alloc_t(&e->slot, 4);
   if (!rc) rc = e->arena.alloc_t(&e->x, (size_t)e->UB * cfg->max_seq * cfg->in_channels);
+  if (!rc) rc = e->arena.alloc_t(&e->hist, (size_t)e->UB * cfg->max_seq * cfg->in_channels);
   if (!rc) rc = e->arena.alloc(&e->x_t, (B2 * cfg->max_seq + 8) * cfg->in_pad * es);
   if (!rc) rc = e->arena.alloc_t(&e->out, B2 * cfg->max_seq * cfg->out_channels);
   if (!rc) rc = e->arena.alloc_t(&e->io_dev, 32);
@@ -381,6 +414,7 @@ void tt_diff_destroy(tt_diff* e) {
   e->close();
   e->split.drop();
   e->step.drop();
+  e->solver_step.drop();
   if (e->io_host) (void)hipHostFree((void*)e->io_host);
   for (hipEvent_t ev : e->ev_chunk)
     if (ev) (void)hipEventDestroy(ev);
@@ -482,17 +516,16 @@ int tt_diff_forward(tt_diff* e, const float* x, int timestep, int cond_free, flo
   });
 }
 
-// p_sample_loop for the U utterances of the current batch (U = 1: the plain single-utterance run).  All of them walk the same
-// schedule; utterance u has Su[u] positions inside the padded length e->S.
-static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* const* step_noise, const tt_diff_step* steps_host, int n_steps,
-                           int cond_free, float* const* mel_out, hipStream_t s) {
+// The sampling loop for the U utterances of the current batch (U = 1: the plain single-utterance run) with the epilogue `up`.  All of
+// them walk the same schedule; utterance u has Su[u] positions inside the padded length e->S.
+static int diff_sample_run(tt_diff* e, const float* const* x_T, const DiffUpdate& up, int n_steps, int cond_free, float* const* mel_out, hipStream_t s) {
   const int S = e->S, U = e->U, IC = e->cfg.in_channels, IP = e->cfg.in_pad, dt = e->cfg.dtype;
   std::vector<int> ts(n_steps);
-  for (int i = 0; i < n_steps; ++i) ts[i] = steps_host[i].timestep;
+  for (int i = 0; i < n_steps; ++i) memcpy(&ts[i], (const char*)up.steps_host + (size_t)i * up.step_bytes, sizeof(int));
   TT_CHECK_HIP(hipMemcpyAsync(e->ts_dev, ts.data(), n_steps * sizeof(int), hipMemcpyHostToDevice, s));
-  TT_CHECK_HIP(hipMemcpyAsync(e->steps_dev, steps_host, n_steps * sizeof(tt_diff_step), hipMemcpyHostToDevice, s));
+  TT_CHECK_HIP(hipMemcpyAsync(e->steps_dev, up.steps_host, n_steps * up.step_bytes, hipMemcpyHostToDevice, s));
   for (int u = 0; u < U; ++u) {  // this call's noise / output pointers: data for the kept sampler-step graph
-    e->io_host[2 * u] = step_noise[u];
+    e->io_host[2 * u] = up.step_noise ? up.step_noise[u] : nullptr;
     e->io_host[2 * u + 1] = mel_out[u];
   }
   TT_CHECK_HIP(hipMemcpyAsync(e->io_dev, e->io_host, 32 * sizeof(void*), hipMemcpyHostToDevice, s));
@@ -543,36 +576,36 @@ static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* con
     }
     return 0;
   };
-  std::vector<PSampleArgs> pa(U);
-  for (int u = 0; u < U && !rc; ++u) {
-    PSampleArgs& p = pa[u];
-    memset(&p, 0, sizeof(p));
-    p.steps = e->steps_dev; p.slot = e->slot; p.x = e->x + (size_t)u * S * IC; p.x_t = offset_t(e->x_t, (size_t)u * S * IP, e->es); p.cpad = IP;
-    p.out = e->out + (size_t)u * S * e->cfg.out_channels;
-    p.has_uncond = cond_free ? 1 : 0; p.S = e->Su[u]; p.C = IC;
-    p.io = e->io_dev + 2 * u;  // {step_noise[u], mel_out[u]}: data of this call, not of the captured step
-    p.guard = e->guard.dev;
-    p.ld_rows = U * S;
-    p.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
-    p.mel_shift = -11.512925148010254f;
+  std::vector<PSampleArgs> pa(up.solver ? 0 : U);
+  std::vector<SolverArgs> sa(up.solver ? U : 0);
+  for (int u = 0; u < U; ++u) {
+    if (up.solver) {
+      diff_update_args(e, u, cond_free, sa[u]);
+      sa[u].steps = (const SolverStep*)e->steps_dev;
+      sa[u].hist = e->hist + (size_t)u * S * IC;
+    } else {
+      diff_update_args(e, u, cond_free, pa[u]);
+      pa[u].steps = e->steps_dev;
+    }
   }
   auto one_step = [&]() -> int {
     TT_TRY(diff_forward(e, B, s));
-    for (int u = 0; u < U; ++u) TT_TRY(psample_launch(dt, pa[u], s));
+    for (int u = 0; u < U; ++u) TT_TRY(up.solver ? solver_update_launch(dt, sa[u], s) : psample_launch(dt, pa[u], s));
     return slot_advance_launch(e->slot, e->ss_all, e->ss_cur, e->NR * 2 * e->C, e->n_steps_cur - 1, s);
   };
   if (!rc && graphs_enabled() && n_steps > 2) {
     // everything the captured step bakes in that a later call could change
     std::vector<int> key = {U, S, R, n_steps, dt, g_prof_on ? 1 : 0};
     for (int u = 0; u < 16; ++u) key.push_back(u < U ? e->Su[u] : 0);
-    rc = e->step.ensure(s, key.data(), key.size() * sizeof(int), "tt_diff_sample", one_step);
+    key.push_back(up.solver);
+    rc = up.graph->ensure(s, key.data(), key.size() * sizeof(int), up.who, one_step);
     for (int i = 0; i < n_steps && !rc; ++i) {
       rc = chunk_gate(i);
-      if (!rc) rc = e->step.launch(s, "tt_diff_sample");
+      if (!rc) rc = up.graph->launch(s, up.who);
     }
     if (rc) {
       (void)hipStreamSynchronize(s);
-      e->step.drop();
+      up.graph->drop();
     }
   } else {
     for (int i = 0; i < n_steps && !rc; ++i) {
@@ -586,13 +619,20 @@ static int diff_sample_run(tt_diff* e, const float* const* x_T, const float* con
   return rc;
 }
 
+static DiffUpdate diff_p_update(tt_diff* e, const float* const* step_noise, const tt_diff_step* steps_host) {
+  return DiffUpdate{0, steps_host, sizeof(tt_diff_step), step_noise, &e->step, "tt_diff_sample"};
+}
+static DiffUpdate diff_solver_update(tt_diff* e, const tt_solver_step* steps_host) {
+  return DiffUpdate{1, steps_host, sizeof(tt_solver_step), nullptr, &e->solver_step, "tt_diff_solve"};
+}
+
 int tt_diff_sample(tt_diff* e, const float* x_T, const float* step_noise, const tt_diff_step* steps_host, int n_steps, int cond_free,
                    float* mel_out, void* stream) {
   TT_REQUIRE(e && x_T && steps_host && mel_out && e->S > 0, "tt_diff_sample: call tt_diff_condition first");
   TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_sample: the handle holds a batch of %d utterances (tt_diff_sample_batch)", e->U);
   TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_sample: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
-    return diff_sample_run(e, &x_T, &step_noise, steps_host, n_steps, cond_free, &mel_out, s);
+    return diff_sample_run(e, &x_T, diff_p_update(e, &step_noise, steps_host), n_steps, cond_free, &mel_out, s);
   });
 }
 
@@ -603,8 +643,63 @@ int tt_diff_sample_batch(tt_diff* e, int U, const float* const* x_T, const float
   TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_sample_batch: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
   for (int u = 0; u < U; ++u) TT_REQUIRE(x_T[u] && mel_out[u] && (step_noise[u] || n_steps == 1), "tt_diff_sample_batch: null tensor for utterance %d", u);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
-    return diff_sample_run(e, x_T, step_noise, steps_host, n_steps, cond_free, mel_out, s);
+    return diff_sample_run(e, x_T, diff_p_update(e, step_noise, steps_host), n_steps, cond_free, mel_out, s);
   });
+}
+
+// ---- deterministic solvers (include/tortoise_mi355x_solver.h): the same run with the solver epilogue and its own kept graph
+int tt_solver_abi_version(void) { return 1; }  // ABI changes
+
+int tt_diff_solve(tt_diff* e, const float* x_T, const tt_solver_step* steps_host, int n_steps, int cond_free, float* mel_out, void* stream) {
+  TT_REQUIRE(e && x_T && steps_host && mel_out && e->S > 0, "tt_diff_solve: call tt_diff_condition first");
+  TT_REQUIRE(e->U == 1 && e->conditioned == 1u, "tt_diff_solve: the handle holds a batch of %d utterances (tt_diff_solve_batch)", e->U);
+  TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_solve: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    return diff_sample_run(e, &x_T, diff_solver_update(e, steps_host), n_steps, cond_free, &mel_out, s);
+  });
+}
+
+int tt_diff_solve_batch(tt_diff* e, int U, const float* const* x_T, const tt_solver_step* steps_host, int n_steps, int cond_free,
+                        float* const* mel_out, void* stream) {
+  TT_REQUIRE(e && x_T && steps_host && mel_out, "tt_diff_solve_batch: null argument");
+  TT_REQUIRE(U == e->U && e->conditioned == (U >= 32 ? ~0u : (1u << U) - 1u), "tt_diff_solve_batch: %d utterances, but the batch has %d and conditioning mask %#x (tt_diff_batch_begin / tt_diff_condition_slot)", U, e->U, e->conditioned);
+  TT_REQUIRE(n_steps >= 1 && n_steps <= e->cfg.max_steps, "tt_diff_solve_batch: %d steps exceed capacity %d", n_steps, e->cfg.max_steps);
+  for (int u = 0; u < U; ++u) TT_REQUIRE(x_T[u] && mel_out[u], "tt_diff_solve_batch: null tensor for utterance %d", u);
+  return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
+    return diff_sample_run(e, x_T, diff_solver_update(e, steps_host), n_steps, cond_free, mel_out, s);
+  });
+}
+
+int tt_diff_solve_stat(tt_diff* e, int which) {
+  if (!e) { set_error("tt_diff_solve_stat: null handle"); return -1; }
+  return which == 0 ? e->solver_step.captures : -1;
+}
+
+int tt_op_solver_update(int dtype, float* x, const float* model, int ld_rows, int has_uncond, float* hist, const tt_solver_step* step, int S,
+                        int C, int cpad, void* x_t, float* mel_out, int* guard, void* stream) {
+  TT_REQUIRE(x && model && hist && step, "tt_op_solver_update: null argument");
+  TT_REQUIRE(dtype == TT_BF16 || dtype == TT_F16 || dtype == TT_F32, "tt_op_solver_update: unknown dtype %d", dtype);
+  TT_REQUIRE(S >= 1 && C >= 1 && cpad >= C && ld_rows >= S, "tt_op_solver_update: bad shape S=%d C=%d cpad=%d ld_rows=%d", S, C, cpad, ld_rows);
+  hipStream_t s = (hipStream_t)stream;
+  char* tab = nullptr;  // [step record | slot]
+  if (hipMalloc((void**)&tab, 256) != hipSuccess) { set_error("tt_op_solver_update: hipMalloc failed"); return -2; }
+  int rc = 0;
+  if (hipMemsetAsync(tab, 0, 256, s) != hipSuccess || hipMemcpyAsync(tab, step, sizeof(*step), hipMemcpyHostToDevice, s) != hipSuccess) {
+    set_error("tt_op_solver_update: staging the step record failed");
+    rc = -2;
+  }
+  if (!rc) {
+    SolverArgs p;
+    memset(&p, 0, sizeof(p));
+    p.steps = (const SolverStep*)tab; p.slot = (const int*)(tab + 128); p.x = x; p.hist = hist; p.x_t = x_t; p.cpad = cpad; p.out = model;
+    p.has_uncond = has_uncond ? 1 : 0; p.S = S; p.C = C; p.mel_out = mel_out; p.ld_rows = ld_rows; p.guard = guard;
+    p.mel_scale = 2.3143386840820312f - (-11.512925148010254f);
+    p.mel_shift = -11.512925148010254f;
+    rc = solver_update_launch(dtype, p, s);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("tt_op_solver_update: the kernel failed"); rc = -2; }
+  (void)hipFree(tab);
+  return rc;
 }
 
 int tt_diff_split_begin(tt_diff* e, const float* x_T, const tt_diff_step* steps_host, int n_steps, int row, void* stream) {
@@ -683,7 +778,10 @@ int tt_diff_set_option(tt_diff* e, int option, int value) {
   TT_REQUIRE(option == TT_DIFF_OPT_OVERLAP_PREPASS || option == TT_DIFF_OPT_FUSED_GN, "tt_diff_set_option: unknown option %d", option);
   if (option == TT_DIFF_OPT_FUSED_GN) {
     TT_REQUIRE(value == 0 || value == 1, "tt_diff_set_option: TT_DIFF_OPT_FUSED_GN takes 0 (stand-alone applies) or 1 (default: ResBlock in_layers fused), got %d", value);
-    if (value != e->fuse_gn) e->step.drop();  // the kept sampler step was captured with the other launch sequence
+    if (value != e->fuse_gn) {  // the kept sampler steps were captured with the other launch sequence
+      e->step.drop();
+      e->solver_step.drop();
+    }
     e->fuse_gn = value;
     return 0;
   }

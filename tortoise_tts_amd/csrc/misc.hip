@@ -265,4 +265,54 @@ int psample_launch(int dtype, const PSampleArgs& a, hipStream_t stream) {
   return 0;
 }
 
+// One step of a deterministic solver (DDIM, DPM-Solver++(2M): include/tortoise_mi355x_solver.h) for the step record *slot selects.
+// Thread per (s, c) like psample_kernel; the learned-variance half of the model row is not read and no noise is drawn.
+template <typename T>
+__global__ void solver_update_kernel(SolverArgs a) {
+  const int S = a.S, C = a.C;
+  const long total = (long)S * a.cpad;
+  const int ld = a.ld_rows > 0 ? a.ld_rows : S;
+  const float* oc = a.out;
+  const float* ou = a.out + (size_t)ld * 2 * C;
+  const SolverStep st = a.steps[*a.slot];
+  float* mel_out = a.io ? (float*)a.io[1] : a.mel_out;
+  const bool with_hist = st.c != 0.f;  // a first-order step: the history may hold anything (an earlier run's values), so it is not loaded
+  bool bad = false;
+  for (long f = blockIdx.x * (long)blockDim.x + threadIdx.x; f < total; f += (long)gridDim.x * blockDim.x) {
+    const int s = (int)(f / a.cpad), c = (int)(f % a.cpad);
+    T xt = (T)0.f;
+    if (c < C) {
+      const size_t i = (size_t)s * C + c;
+      const float x = a.x[i];
+      float eps = oc[(size_t)s * 2 * C + c];
+      bad = bad || !(fabsf(eps) < INFINITY);
+      if (a.has_uncond) {
+        const float eu = ou[(size_t)s * 2 * C + c];
+        bad = bad || !(fabsf(eu) < INFINITY);
+        eps = (1.f + st.cfk) * eps - st.cfk * eu;
+      }
+      float x0 = st.sqrt_recip * x - st.sqrt_recipm1 * eps;
+      x0 = fminf(1.f, fmaxf(-1.f, x0));
+      float xn = fmaf(st.b, x0, st.a * x);
+      if (with_hist) xn = fmaf(st.c, a.hist[i], xn);
+      a.x[i] = xn;
+      a.hist[i] = x0;
+      if (mel_out) mel_out[(size_t)c * S + s] = (xn + 1.f) * 0.5f * a.mel_scale + a.mel_shift;
+      xt = (T)xn;
+    }
+    if (a.x_t) {
+      T* d = (T*)a.x_t;
+      d[(size_t)s * a.cpad + c] = xt;
+      if (a.has_uncond) d[((size_t)ld + s) * a.cpad + c] = xt;
+    }
+  }
+  if (a.guard && __ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(a.guard, 1);
+}
+int solver_update_launch(int dtype, const SolverArgs& a, hipStream_t stream) {
+  const int blocks = (int)std::min<long>(cdiv64((long)a.S * a.cpad, 256), 4096);
+  TT_DISPATCH_T(dtype, T, solver_update_kernel<T><<<blocks, 256, 0, stream>>>(a));
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace tt

@@ -322,6 +322,30 @@ struct PSampleArgs {
 int psample_launch(int dtype, const PSampleArgs& a, hipStream_t stream);
 int slot_advance_launch(int* slot, const float* ss_all, float* ss_cur, int row_floats, int last_slot, hipStream_t stream);
 
+// Deterministic solver epilogue (include/tortoise_mi355x_solver.h): x' = a x + b x0 + c x0_prev on the guided, clamped x0.  Same layout,
+// step table and step counter as the p_sample epilogue.
+struct SolverStep {     // same layout as tt_solver_step
+  int timestep;
+  float cfk, sqrt_recip, sqrt_recipm1, a, b, c;
+};
+struct SolverArgs {
+  const SolverStep* steps;   // device array; entry *slot is used
+  const int* slot;
+  float* x;             // [S][C] f32 state, updated in place
+  float* hist;          // [S][C] f32 x0 of the step before: read only when the step's c != 0, always written
+  void* x_t;            // optional [2][S][cpad] operand copy for the next step's inp_block (both batch rows)
+  int cpad;
+  const float* out;     // [2][S][2C] model output rows; only eps (cols 0..C-1) is read
+  int has_uncond;
+  int S, C;
+  float* mel_out;       // optional [C][S] channels-first denormalised mel
+  float mel_scale, mel_shift;
+  int ld_rows;          // as PSampleArgs
+  const void* const* io;  // optional: mel_out is read from io[1] (the {step_noise, mel_out} pair of PSampleArgs; io[0] is unused)
+  int* guard;           // optional device counter: += 1 per wave that read a non-finite model output
+};
+int solver_update_launch(int dtype, const SolverArgs& a, hipStream_t stream);
+
 // ------------------------------------------------------------------------------ UnivNet (fp32 VALU)
 // A ragged batch at the audio rate (include/tortoise_mi355x_univnet.h): sequence b owns slot b of every tensor - [C][P] each, P the T / Tin /
 // L * hop of the launch's arguments - and its first frames[b] * mul columns are valid.  The grid carries the sequence index; every output

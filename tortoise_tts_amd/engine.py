@@ -100,6 +100,10 @@ class DiffStep(C.Structure):
         "min_log", "max_log", "cfk", "sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "nonzero")]
 
 
+class SolverStep(C.Structure):  # tt_solver_step (include/tortoise_mi355x_solver.h)
+    _fields_ = [("timestep", C.c_int)] + [(n, C.c_float) for n in ("cfk", "sqrt_recip", "sqrt_recipm1", "a", "b", "c")]
+
+
 class VocBlock(C.Structure):
     _fields_ = [("w_convt", vp), ("b_convt", vp), ("w_kp_in", vp), ("b_kp_in", vp),
                 ("w_kp_res", vp * 6), ("b_kp_res", vp * 6), ("w_kp_kernel", vp), ("b_kp_kernel", vp),
@@ -406,6 +410,15 @@ LOUD_SAMPLE_RATE = 24000
 LOUD_MAX_SAMPLES, LOUD_MAX_CLIPS = 268435456, 64
 LOUD_NONE, LOUD_SCALE, LOUD_LOOKAHEAD_MODE = 0, 1, 2
 LOUD_OK, LOUD_SHORT, LOUD_SILENT, LOUD_EMPTY, LOUD_REFUSED = 0, 1, 2, 3, 4
+# include/tortoise_mi355x_solver.h: DDIM / DPM-Solver++(2M) on a tt_diff handle (its own header and version, same library)
+_SOLVER_PROTOS = {
+    "tt_solver_abi_version": (_i, []),
+    "tt_diff_solve": (_i, [vp, vp, C.POINTER(SolverStep), _i, _i, vp, vp]),
+    "tt_diff_solve_batch": (_i, [vp, _i, C.POINTER(C.c_void_p), C.POINTER(SolverStep), _i, _i, C.POINTER(C.c_void_p), vp]),
+    "tt_diff_solve_stat": (_i, [vp, _i]),
+    "tt_op_solver_update": (_i, [_i, vp, vp, _i, _i, vp, C.POINTER(SolverStep), _i, _i, _i, vp, vp, vp, vp]),
+}
+SOLVER_ABI_VERSION = 1
 # include/tortoise_mi355x_hifi.h: ragged batches of the HiFi-GAN decoder (its own header and version, same library)
 _HIFI_PROTOS = {
     "tt_hifi_batch_abi_version": (_i, []),
@@ -480,7 +493,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -514,6 +527,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_tsm.h is version %d in the library, %d in Python" % (lib.tt_tsm_abi_version(), TSM_ABI_VERSION))
     if lib.tt_loud_abi_version() != LOUD_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
+    if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_solver.h is version %d in the library, %d in Python" % (lib.tt_solver_abi_version(), SOLVER_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))

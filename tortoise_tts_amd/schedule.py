@@ -31,15 +31,19 @@ def space_timesteps(num_timesteps, section_counts):
     return set(all_steps)
 
 
+def base_alphas_cumprod(trained_steps=4000):
+    """get_named_beta_schedule('linear', trained_steps) -> cumprod(1 - beta), float64 [trained_steps] (diffusion.py:94-111, 203)."""
+    scale = 1000 / trained_steps
+    base_betas = np.linspace(scale * 0.0001, scale * 0.02, trained_steps, dtype=np.float64)
+    return np.cumprod(1.0 - base_betas, axis=0)
+
+
 class Schedule:
     def __init__(self, steps, trained_steps=4000, cond_free=True, cond_free_k=2.0):
-        scale = 1000 / trained_steps
-        base_betas = np.linspace(scale * 0.0001, scale * 0.02, trained_steps, dtype=np.float64)
-        base_alphas_cumprod = np.cumprod(1.0 - base_betas, axis=0)
         use = space_timesteps(trained_steps, [steps])
         last = 1.0
         betas, tmap = [], []
-        for i, ac in enumerate(base_alphas_cumprod):
+        for i, ac in enumerate(base_alphas_cumprod(trained_steps)):
             if i in use:
                 betas.append(1 - ac / last)
                 last = ac

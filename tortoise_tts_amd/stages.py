@@ -816,6 +816,56 @@ class DiffusionStage(_GuardedHandle):
         self.S = 0  # the handle holds a batch: condition() again before sample()
         return [t[5][None] for t in keep]
 
+    # ---- deterministic solvers (include/tortoise_mi355x_solver.h; solver.SolverPlan) ---------------------------
+    @staticmethod
+    def _solver_steps(plan):
+        """tt_solver_step records in the order the steps run (i = M-1 ... 0)."""
+        M = plan.n_steps
+        steps = (E.SolverStep * M)()
+        for j, i in enumerate(reversed(range(M))):
+            st = steps[j]
+            st.timestep = int(plan.timestep_map[i])
+            st.cfk = plan.f32(plan.cfk, i)
+            st.sqrt_recip = plan.f32(plan.sqrt_recip, i)
+            st.sqrt_recipm1 = plan.f32(plan.sqrt_recipm1, i)
+            st.a, st.b, st.c = plan.f32(plan.a, i), plan.f32(plan.b, i), plan.f32(plan.c, i)
+        return steps
+
+    def solve_stat(self, which):
+        return self.lib.tt_diff_solve_stat(self.h, int(which))
+
+    def solve(self, plan, x_T):
+        """The plan's solver from x_T f32 [1, 100, S]: no noise is drawn after x_T.  Returns the denormalised mel [1, 100, S]."""
+        if self.S <= 0:
+            raise ValueError("solve() needs condition() first (after sample_many / solve_many the handle holds a batch)")
+        x = x_T[0].to(self.device).float().contiguous()
+        mel = torch.empty(self.cfg.in_channels, self.S, device=self.device, dtype=torch.float32)
+        E.check(self.lib.tt_diff_solve(self.h, E.ptr(x), self._solver_steps(plan), plan.n_steps, int(plan.cond_free), E.ptr(mel), E.stream_ptr()))
+        return mel[None]
+
+    def solve_many(self, plan, items):
+        """sample_many with the plan's solver (tt_diff_solve_batch): the same item tuples, whose noise entry may be None and is ignored.
+        Returns the list of denormalised mels [1, 100, S_u]; each agrees with solve() alone within the operand tolerance, as sample_many
+        does with sample()."""
+        U = len(items)
+        if not 1 <= U <= self.max_batch:
+            raise ValueError(f"{U} utterances exceed this stage's batch capacity {self.max_batch}")
+        S_pad = max(int(it[2]) for it in items)
+        E.check(self.lib.tt_diff_batch_begin(self.h, U, S_pad, E.stream_ptr()))
+        keep = []
+        for u, (lat, cond, S, x_T, _) in enumerate(items):
+            lat_ = lat[0].to(self.device).float().contiguous()
+            cond_ = cond[0].to(self.device).float().contiguous()
+            idx = torch.from_numpy(nearest_interp_index(lat_.shape[0], S)).to(self.device)
+            E.check(self.lib.tt_diff_condition_slot(self.h, u, E.ptr(lat_), lat_.shape[0], E.ptr(cond_), E.ptr(idx), int(S), E.stream_ptr()))
+            x = x_T[0].to(self.device).float().contiguous()
+            mel = torch.empty(self.cfg.in_channels, int(S), device=self.device, dtype=torch.float32)
+            keep.append((lat_, cond_, idx, x, mel))
+        arr = lambda k: (C.c_void_p * U)(*[E.ptr(t[k]) for t in keep])
+        E.check(self.lib.tt_diff_solve_batch(self.h, U, arr(3), self._solver_steps(plan), plan.n_steps, int(plan.cond_free), arr(4), E.stream_ptr()))
+        self.S = 0  # the handle holds a batch: condition() again before solve()
+        return [t[4][None] for t in keep]
+
     # ---- split sampling (SURVEY.md §8f-2): this engine evaluates ONE denoiser row per step ---------------------
     def split_begin(self, sched: Schedule, x_T, step_noise, row):
         """row 0 = conditioned, 1 = conditioning-free.  Keeps the run-order noise and the output buffers alive."""
