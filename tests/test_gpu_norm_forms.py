@@ -259,10 +259,19 @@ def gn_ref(C_, B, S, ss, act, vlen, seed_shift=0, big_mean=False):
     return N.groupnorm_reference(d["x"], d["gamma"], d["beta"], 1e-5, list(vlen) if vlen else None, ssb, act)
 
 
-def run_gn(lib, name, dt, tdt, C_, B, S, ss=None, act=R.ACT_NONE, outs="both", vlen=None, guard=False, seed_shift=0, big_mean=False, x=None, check=None):
+@functools.lru_cache(maxsize=None)
+def gn_part(C_, B, S, seed_shift, part_rows, vlen):
+    """the statistics partials of a case in the producing GEMM epilogue's layout (tiles of part_rows rows that straddle the samples), from the host"""
+    x = gn_data(C_, B, S, seed_shift)["x"].reshape(B * S, C_)
+    return R.gn_partials_reference(x, part_rows, S, len(vlen) if vlen else 0, list(vlen) if vlen else None).float()
+
+
+def run_gn(lib, name, dt, tdt, C_, B, S, ss=None, act=R.ACT_NONE, outs="both", vlen=None, guard=False, seed_shift=0, big_mean=False, x=None, check=None,
+           part_rows=0):
     """one tt_op_groupnorm_ex launch; asserts `ran`, kappa <= 128 for the case's own data (big_mean: its own wide bound and finiteness only),
-    every bound, the exact zeros past vlen and every sentinel"""
+    every bound, the exact zeros past vlen and every sentinel.  part_rows: the statistics come as fused partials (gn_part), no statistics pass"""
     d = gn_data(C_, B, S, seed_shift, big_mean)
+    part = gn_part(C_, B, S, seed_shift, part_rows, tuple(vlen) if vlen else None).cuda() if part_rows else None
     xd = (d["x"] if x is None else x).cuda()
     dev = {k: d[k].cuda() for k in ("gamma", "beta", "ss")}
     nws = lib.tt_op_groupnorm_workspace(B, S) // 4
@@ -272,7 +281,7 @@ def run_gn(lib, name, dt, tdt, C_, B, S, ss=None, act=R.ACT_NONE, outs="both", v
     gcount = torch.zeros(1, device="cuda", dtype=torch.int32) if guard else None
     desc = fill(E.GroupNormDesc(), x=xd, B=B, S=S, C=C_, gamma=dev["gamma"], beta=dev["beta"], eps=1e-5, scale_shift=dev["ss"] if ss else None,
                 ss_batch_stride=SS_FORMS[ss][1] * C_ if ss else 0, ss_batch_div=SS_FORMS[ss][0] if ss else 0, act=act, out_t=out_t, ldot=C_ + PAD, out_f32=o32,
-                ldo32=C_ + PAD, partial=ws, vperiod=len(vlen) if vlen else 0, guard=gcount)
+                ldo32=C_ + PAD, partial=ws, vperiod=len(vlen) if vlen else 0, guard=gcount, gemm_part=part, part_rows=part_rows)
     for i, v in enumerate(vlen or ()):
         desc.vlen[i] = v
     ran = (C.c_int * 4)()
@@ -280,7 +289,7 @@ def run_gn(lib, name, dt, tdt, C_, B, S, ss=None, act=R.ACT_NONE, outs="both", v
     torch.cuda.synchronize()
     ran = tuple(ran)
     what = f"GroupNorm {name} C={C_} B={B} S={S} ss={ss} act={act} vlen={vlen} [stats={ran[0]} {E.GROUPNORM_APPLY.get(ran[1], ran[1])} rows={ran[2]} fused={ran[3]}]"
-    assert ran == (1, int(C_ == 1024), 2 if C_ == 1024 and B * S <= 4096 else 4, 0), what
+    assert ran == (0 if part_rows else 1, int(C_ == 1024), 2 if C_ == 1024 and B * S <= 4096 else 4, int(bool(part_rows) and C_ == 1024)), what
     assert bool((ws[nws:] == SENTINEL).all()), f"{what}: statistics written past the workspace"
     ref, kappa = gn_ref(C_, B, S, ss, act, tuple(vlen) if vlen else None, seed_shift, big_mean)
     if big_mean:
@@ -345,6 +354,27 @@ def test_groupnorm_guard(lib, name, dt, tdt, C_):
     x = gn_data(C_, B, S)["x"].clone()
     x[1, 40, 5] = float("inf")
     assert run_gn(lib, name, dt, tdt, C_, B, S, guard=True, x=x, check=[0, 2])[1] > 0
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT)
+@pytest.mark.parametrize("C_", [512, 2048])
+def test_groupnorm_fused_statistics_on_the_generic_apply_kernel(lib, name, dt, tdt, C_):
+    """fused partials with one and four 16-column strips per group (C = 512, 2048) on the generic apply kernel: 32-row tiles that straddle
+    the 77-row samples, a sample of 9 valid rows; run_gn asserts ran == (0, 0, 4, 0), the bound, the zeros past vlen and the sentinels"""
+    run_gn(lib, name, dt, tdt, C_, 4, 77, "sample", R.ACT_SILU, "both", vlen=(77, 9), seed_shift=1, part_rows=32)
+
+
+GN_FUSED_LONG_S = 1100  # 35 tiles of 32 rows = 70 partial items per sample: the loop behind the GN_HEAD requested-ahead items runs
+
+
+@pytest.mark.parametrize("name,dt,tdt", DT)
+@pytest.mark.parametrize("ss", [None, "sample"])
+@pytest.mark.parametrize("B", [2, 4])
+def test_groupnorm_fused_statistics_remainder_loop(lib, name, dt, tdt, B, ss):
+    """C = 1024 on fused partials with more items per thread than are requested ahead: 2200 rows (two rows per block) and 4400 rows (four),
+    with and without scale / shift; run_gn asserts ran == (0, 1, 2 | 4, 1) and kappa <= KAPPA_MAX (the data of gn_seed(1024, B, 1100) has
+    kappa 1.7 at B = 2 and 2.1 at B = 4, computed on the host)"""
+    run_gn(lib, name, dt, tdt, 1024, B, GN_FUSED_LONG_S, ss, R.ACT_SILU, "both", part_rows=32)
 
 
 @pytest.mark.parametrize("name,dt,tdt", DT)

@@ -405,11 +405,12 @@ def test_univnet_kernels(lib):
 
 
 @pytest.mark.parametrize("name,dt,tdt,tol", DTYPES)
-@pytest.mark.parametrize("B,S,N", [(2, 870, 1024), (1, 870, 1024), (3, 333, 256), (8, 33, 512), (1, 4096, 1024), (2, 129, 1024)])
+@pytest.mark.parametrize("B,S,N", [(2, 870, 1024), (1, 870, 1024), (3, 333, 256), (8, 33, 512), (1, 4096, 1024), (2, 129, 1024), (2, 1025, 256)])
 def test_groupnorm_silu_on_the_gemm_a_path(lib, name, dt, tdt, tol, B, S, N):
     """The fused ResBlock in_layers launch (csrc/gemm_gna.h, diffusion_decoder.py:60-80 GroupNorm32 -> SiLU -> 1x1 conv) against torch
     fp32: samples whose boundary falls inside a 32-row tile (S = 870, 333, 33, 129), a row count that is no multiple of the tile
-    (2 x 129, 3 x 333), one sample, the largest row count the kernel takes; activations with a per-group offset and spread so that the
+    (2 x 129, 3 x 333), one sample, the largest row count the kernel takes, two samples of more than 64 statistics items each (S = 1025: the straddling tile
+    sums both on the second trip of the item loop); activations with a per-group offset and spread so that the
     mean / rstd folding has something to cancel.  The reference rounds the normalised activations to the operand type as the kernel does."""
     if dt == E.TT_F32:
         pytest.skip("the fused launch is a 16-bit-operand kernel (the fp32 verification mode keeps the stand-alone apply)")

@@ -12,6 +12,7 @@
 // return out of order") - the A rows' waits drained the whole queue every k-step (measured: +7.7 us per launch).  With plain loads only,
 // the compiler's waits are counted and no hand-written vmcnt is needed.
 #pragma once
+#include "norm_steps.h"
 
 namespace tt {
 
@@ -161,28 +162,23 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
   const int ch = t8 * 4;     // this thread's four channels of the (multiplier, offset) table
   const float4 gm = *(const float4*)(n.gamma + ch);
   const float4 bt = *(const float4*)(n.beta + ch);
-  // statistics of sample b0 (and b0 + 1 for the one tile that straddles): gn_finalize<1>'s sum, item by item in the same order
+  // statistics of sample b0 (and b0 + 1 for the one tile that straddles): the sum norm.hip's gn_finalize<1> makes, from the same steps
+  // (norm_steps.h) and in the same order - thread (part, gq) takes items part, part + 8, ... of group gq
   {
     const int gq = t8 & 31, part = t8 >> 5;
     const int r_shift = n.part_shift, nc16 = kGnaC >> 4;
     const int nsamp = straddle ? 2 : 1;
     for (int s = 0; s < nsamp; ++s) {
       const int b = b0 + s;
-      const int t0 = (b * S) >> r_shift, t1 = ((b + 1) * S - 1) >> r_shift;
-      const int nitems = (t1 - t0 + 1) << 1;
+      const GnItems it = gn_items<1>(b, S, r_shift);
       double su = 0.0, qu = 0.0;
-      for (int e0 = part; e0 < nitems; e0 += 64) {
+      for (int e0 = part; e0 < it.n; e0 += 64) {
         float2 v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {  // eight independent requests, clamped
-          const int ec = min(e0 + 8 * k, nitems - 1);
-          const int t = t0 + (ec >> 1), strip = (gq << 1) + (ec & 1);
-          const int slot = ((t << r_shift) < b * S) ? 1 : 0;
-          v[k] = *(const float2*)(n.gemm_part + (((size_t)t * 2 + slot) * nc16 + strip) * 2);
-        }
+        for (int k = 0; k < 8; ++k) v[k] = gn_partial_item<1>(n.gemm_part, S, b, gq, e0 + 8 * k, it, nc16, r_shift);  // eight independent requests, clamped
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          if (e0 + 8 * k < nitems) {
+          if (e0 + 8 * k < it.n) {
             su += (double)v[k].x;
             qu += (double)v[k].y;
           }
@@ -192,20 +188,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_gna_kernel(const GemmGnaDev<type
       part_s[part][gq] = su;
       part_q[part][gq] = qu;
       __syncthreads();
-      if (tid < 32) {
-        double ss_ = 0.0, qq = 0.0;
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-          ss_ += part_s[p][tid];
-          qq += part_q[p][tid];
-        }
-        const double mu = ss_ * n.inv_count;
-        double var = qq * n.inv_count - mu * mu;
-        if (n.guard && !(var < 1.0e300)) atomicAdd(n.guard, 1);  // NaN / inf statistics: an operand overflowed upstream
-        if (var < 0.0) var = 0.0;
-        mean_s[s][tid] = (float)mu;
-        rstd_s[s][tid] = rsqrtf((float)var + n.eps);
-      }
+      if (tid < 32) gn_mean_rstd(gn_combine(part_s, part_q, tid), n.inv_count, n, mean_s[s][tid], rstd_s[s][tid]);
     }
     __syncthreads();
     for (int s = 0; s < nsamp; ++s) {

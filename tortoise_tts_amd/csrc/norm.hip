@@ -2,7 +2,8 @@
 // token-major GroupNorm (stats + apply) for DiffusionTts.  All statistics are fp32 (GroupNorm's
 // cross-chunk combine is fp64); normalised activations are emitted directly in the GEMM operand
 // type so no separate cast pass exists anywhere in the engine.
-#include "ops.h"
+#include <type_traits>
+#include "norm_steps.h"
 
 namespace tt {
 
@@ -10,255 +11,34 @@ thread_local RowNormRan g_rownorm_ran = {-1, -1, 0, 0};
 thread_local GroupNormRan g_groupnorm_ran = {0, -1, 0, 0};
 
 // ------------------------------------------------------------------------------- row norm
-// One 256-thread block per row, D <= 4096, D % 4 == 0.
-template <typename T, int NSLAB>
-__global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
-  __shared__ float red[4];
-  const int row = blockIdx.x;
-  const int tid = threadIdx.x;
+// D <= 4096, D % 4 == 0.  One body for the two run-time forms: a row shared by a span of threads (norm_steps.h), four quads per thread,
+// the run-time slab count one round trip per slab; RMSNorm, or LayerNorm (two-pass variance in registers) optionally followed by a
+// second LayerNorm and an activation.  SLOTS: the f32 copy can be filed under a device-side counter.
+template <typename T, class Span, bool SLOTS>
+__device__ __forceinline__ void rownorm_row(const RowNormArgs& a, int row, Span sp) {
   constexpr int J = 4;
   float4 v[J];
   float* xr = a.x + (size_t)row * a.ldx;
   float sum = 0.f;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    const int c = (tid + 256 * j) * 4;
+    const int c = span_col(sp, j);
     if (c < a.D) {
-      float4 t = a.x_in ? *(const float4*)(a.x_in + (size_t)row * a.ldxin + c) : *(const float4*)(xr + c);
-      if (a.add_bias) {
-        const float4 b = *(const float4*)(a.add_bias + c);
-        t.x += b.x; t.y += b.y; t.z += b.z; t.w += b.w;
-      }
-      if constexpr (NSLAB >= 0) {
-        float4 sl[NSLAB > 0 ? NSLAB : 1];
-#pragma unroll
-        for (int s = 0; s < NSLAB; ++s)  // all partial-sum slabs requested at once, summed in slab order
-          sl[s] = *(const float4*)(a.add_slabs + (size_t)s * a.slab_stride + (size_t)row * a.ldslab + c);
-#pragma unroll
-        for (int s = 0; s < NSLAB; ++s) {
-          t.x += sl[s].x; t.y += sl[s].y; t.z += sl[s].z; t.w += sl[s].w;
-        }
-      } else {  // odd slab counts: same order, one round trip per slab
-        for (int s = 0; s < a.nslab; ++s) {
-          const float4 p = *(const float4*)(a.add_slabs + (size_t)s * a.slab_stride + (size_t)row * a.ldslab + c);
-          t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
-        }
-      }
-      if (a.write_x) *(float4*)(xr + c) = t;
-      v[j] = t;
-      sum += t.x + t.y + t.z + t.w;
-    } else {
-      v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  if (a.mode == NORM_NONE) return;
-
-  float* o32 = a.out_f32;
-  if (o32 && a.f32_slot) o32 += (size_t)(*a.f32_slot + a.f32_slot_base) * a.f32_slot_stride;
-  if (o32 && a.f32_row_slot) {  // (block-uniform: one row per block)
-    const int sl = a.f32_row_slot[row];
-    o32 = sl < 0 ? nullptr : o32 + (size_t)(sl + a.f32_slot_base) * a.f32_slot_stride;
-  }
-  auto emit = [&](const float4* y) {
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int c = (tid + 256 * j) * 4;
-      if (c < a.D) {
-        if (a.out_t) *(typename Vec<T>::x4*)((T*)a.out_t + (size_t)row * a.ldot + c) = pack4<T>(y[j].x, y[j].y, y[j].z, y[j].w);
-        if (o32) *(float4*)(o32 + (size_t)row * a.ldo32 + c) = y[j];
-      }
-    }
-  };
-
-  float4 y[J];
-  if (a.mode == NORM_RMS) {
-    // x-transformers RMSNorm: x / max(||x|| * D^-0.5, eps) * g
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; ++j) sq += v[j].x * v[j].x + v[j].y * v[j].y + v[j].z * v[j].z + v[j].w * v[j].w;
-    sq = block_sum_256(sq, red);
-    if (a.guard && tid == 0 && !(sq < INFINITY)) atomicAdd(a.guard, 1);  // NaN / inf in the row: an operand overflowed upstream
-    const float nrm = sqrtf(sq) * rsqrtf((float)a.D);
-    const float inv = 1.0f / fmaxf(nrm, a.eps1);
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int c = (tid + 256 * j) * 4;
-      if (c < a.D) {
-        const float4 g = *(const float4*)(a.g1 + c);
-        y[j] = make_float4(v[j].x * inv * g.x, v[j].y * inv * g.y, v[j].z * inv * g.z, v[j].w * inv * g.w);
-      }
-    }
-    emit(y);
-    return;
-  }
-
-  // LayerNorm (two-pass variance in registers), optionally followed by a second LayerNorm.
-  const float* gs[2] = {a.g1, a.g2};
-  const float* bs[2] = {a.b1, a.b2};
-  const float epss[2] = {a.eps1, a.eps2};
-  const int nln = a.g2 ? 2 : 1;
-  for (int l = 0; l < nln; ++l) {
-    if (l > 0) {
-      sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        const int c = (tid + 256 * j) * 4;
-        if (c < a.D) sum += v[j].x + v[j].y + v[j].z + v[j].w;
-      }
-    }
-    const float mean = block_sum_256(sum, red) / (float)a.D;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int c = (tid + 256 * j) * 4;
-      if (c < a.D) {
-        const float dx = v[j].x - mean, dy = v[j].y - mean, dz = v[j].z - mean, dw = v[j].w - mean;
-        sq += dx * dx + dy * dy + dz * dz + dw * dw;
-      }
-    }
-    const float var = block_sum_256(sq, red) / (float)a.D;
-    if (a.guard && l == 0 && tid == 0 && !(var < INFINITY)) atomicAdd(a.guard, 1);  // NaN / inf in the row: an operand overflowed upstream
-    const float rstd = rsqrtf(var + epss[l]);
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int c = (tid + 256 * j) * 4;
-      if (c < a.D) {
-        const float4 g = *(const float4*)(gs[l] + c);
-        const float4 b = *(const float4*)(bs[l] + c);
-        v[j] = make_float4((v[j].x - mean) * rstd * g.x + b.x, (v[j].y - mean) * rstd * g.y + b.y,
-                           (v[j].z - mean) * rstd * g.z + b.z, (v[j].w - mean) * rstd * g.w + b.w);
-      }
-    }
-  }
-  if (a.act != ACT_NONE) {
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-      v[j] = make_float4(apply_act(v[j].x, a.act, 0.f), apply_act(v[j].y, a.act, 0.f), apply_act(v[j].z, a.act, 0.f), apply_act(v[j].w, a.act, 0.f));
-  }
-  emit(v);
-}
-
-// Narrow rows (D <= 1024): one float4 per thread and every operand the row needs - input, bias, split-K slabs, affine
-// parameters - requested before the first use, so the row costs one memory round trip instead of three (input, slabs,
-// affine).  NSLAB / BIAS / RMS are compile-time so no branch sits between the requests.  Same arithmetic order as the
-// generic kernel: bias, slabs in order, two-pass variance.
-template <typename T, int NSLAB, bool BIAS, bool RMS>
-__global__ __launch_bounds__(256) void rownorm_narrow_kernel(RowNormArgs a) {
-  __shared__ float red[8];  // one 4-float array per reduction: no barrier is needed to recycle it
-  const int row = blockIdx.x, tid = threadIdx.x;
-  const bool live = tid * 4 < a.D;
-  const int c = min(tid * 4, a.D - 4);  // idle lanes re-read the last quad (no branch), masked below
-  float* xr = a.x + (size_t)row * a.ldx;
-  const float* src = a.x_in ? a.x_in + (size_t)row * a.ldxin : xr;
-  float4 t = *(const float4*)(src + c);
-  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (BIAS) bv = *(const float4*)(a.add_bias + c);
-  float4 sl[NSLAB > 0 ? NSLAB : 1];
-#pragma unroll
-  for (int s = 0; s < NSLAB; ++s) sl[s] = *(const float4*)(a.add_slabs + (size_t)s * a.slab_stride + (size_t)row * a.ldslab + c);
-  const float4 g = *(const float4*)(a.g1 + c);
-  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-  if constexpr (!RMS) b = *(const float4*)(a.b1 + c);
-  __builtin_amdgcn_sched_barrier(0);
-
-  if constexpr (BIAS) { t.x += bv.x; t.y += bv.y; t.z += bv.z; t.w += bv.w; }
-#pragma unroll
-  for (int s = 0; s < NSLAB; ++s) { t.x += sl[s].x; t.y += sl[s].y; t.z += sl[s].z; t.w += sl[s].w; }
-  if (a.write_x && live) *(float4*)(xr + c) = t;
-  if (!live) t = make_float4(0.f, 0.f, 0.f, 0.f);
-
-  float4 y;
-  if constexpr (RMS) {
-    const float sq = block_sum_256_fresh(t.x * t.x + t.y * t.y + t.z * t.z + t.w * t.w, red);
-    if (a.guard && tid == 0 && !(sq < INFINITY)) atomicAdd(a.guard, 1);
-    const float nrm = sqrtf(sq) * rsqrtf((float)a.D);
-    const float inv = 1.0f / fmaxf(nrm, a.eps1);
-    y = make_float4(t.x * inv * g.x, t.y * inv * g.y, t.z * inv * g.z, t.w * inv * g.w);
-  } else {
-    const float mean = block_sum_256_fresh(t.x + t.y + t.z + t.w, red) / (float)a.D;
-    const float dx = t.x - mean, dy = t.y - mean, dz = t.z - mean, dw = t.w - mean;
-    const float var = block_sum_256_fresh(live ? dx * dx + dy * dy + dz * dz + dw * dw : 0.f, red + 4) / (float)a.D;
-    if (a.guard && tid == 0 && !(var < INFINITY)) atomicAdd(a.guard, 1);  // NaN / inf in the row: an operand overflowed upstream
-    const float rstd = rsqrtf(var + a.eps1);
-    y = make_float4(dx * rstd * g.x + b.x, dy * rstd * g.y + b.y, dz * rstd * g.z + b.z, dw * rstd * g.w + b.w);
-  }
-  if (live) {
-    if (a.out_t) *(typename Vec<T>::x4*)((T*)a.out_t + (size_t)row * a.ldot + c) = pack4<T>(y.x, y.y, y.z, y.w);
-    if (a.out_f32) *(float4*)(a.out_f32 + (size_t)row * a.ldo32 + c) = y;
-  }
-}
-
-template <typename T, int NSLAB>
-static void rownorm_narrow_dispatch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
-  const bool bias = a.add_bias != nullptr, rms = a.mode == NORM_RMS;
-  const int grid = a.M;
-  g_rownorm_ran = RowNormRan{1, NSLAB, bias ? 1 : 0, rms ? 1 : 0};
-  if (bias && rms) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, true, true>, dim3(grid), dim3(256), 0, stream, a);
-  else if (bias) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, true, false>, dim3(grid), dim3(256), 0, stream, a);
-  else if (rms) launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, false, true>, dim3(grid), dim3(256), 0, stream, a);
-  else launch_timed(ps, rownorm_narrow_kernel<T, NSLAB, false, false>, dim3(grid), dim3(256), 0, stream, a);
-}
-
-template <typename T>
-static bool rownorm_narrow_launch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
-  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr || a.f32_row_slot != nullptr || a.act != ACT_NONE) return false;
-  switch (a.nslab) {
-    case 0: rownorm_narrow_dispatch<T, 0>(ps, a, stream); return true;
-    case 1: rownorm_narrow_dispatch<T, 1>(ps, a, stream); return true;
-    case 2: rownorm_narrow_dispatch<T, 2>(ps, a, stream); return true;
-    case 4: rownorm_narrow_dispatch<T, 4>(ps, a, stream); return true;
-    case 8: rownorm_narrow_dispatch<T, 8>(ps, a, stream); return true;
-    default: return false;
-  }
-}
-
-// Wave-per-row variant for D <= 1024: no block barriers, reductions are register shuffles only, four rows per
-// 256-thread block.  Same arithmetic order per row as the block variant is NOT required (tests compare to torch).
-template <typename T>
-__global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= a.M) return;
-  constexpr int J = 4;
-  float4 v[J];
-  float* xr = a.x + (size_t)row * a.ldx;
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int c = (lane + 64 * j) * 4;
-    if (c < a.D) {
-      float4 t = a.x_in ? *(const float4*)(a.x_in + (size_t)row * a.ldxin + c) : *(const float4*)(xr + c);
-      if (a.add_bias) {
-        const float4 b = *(const float4*)(a.add_bias + c);
-        t.x += b.x; t.y += b.y; t.z += b.z; t.w += b.w;
-      }
-      for (int s = 0; s < a.nslab; ++s) {
-        const float4 p = *(const float4*)(a.add_slabs + (size_t)s * a.slab_stride + (size_t)row * a.ldslab + c);
-        t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
-      }
-      if (a.write_x) *(float4*)(xr + c) = t;
-      v[j] = t;
-      sum += t.x + t.y + t.z + t.w;
+      RowQuad<-1, -1> q;
+      row_request(a, row, xr, c, q);
+      v[j] = row_update(a, row, xr, c, true, q);
+      sum += quad_sum(v[j]);
     } else {
       v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   if (a.mode == NORM_NONE) return;
   if (a.mode == NORM_RMS) {
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < J; ++j) sq += v[j].x * v[j].x + v[j].y * v[j].y + v[j].z * v[j].z + v[j].w * v[j].w;
-    sq = wave_sum(sq);
-    if (a.guard && lane == 0 && !(sq < INFINITY)) atomicAdd(a.guard, 1);
-    const float nrm = sqrtf(sq) * rsqrtf((float)a.D);
-    const float inv = 1.0f / fmaxf(nrm, a.eps1);
+    const float inv = rms_inv(v, sp, a.D, a.eps1, a.guard);
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      const int c = (lane + 64 * j) * 4;
-      if (c < a.D) {
-        const float4 g = *(const float4*)(a.g1 + c);
-        v[j] = make_float4(v[j].x * inv * g.x, v[j].y * inv * g.y, v[j].z * inv * g.z, v[j].w * inv * g.w);
-      }
+      const int c = span_col(sp, j);
+      if (c < a.D) v[j] = rms_scale(v[j], inv, *(const float4*)(a.g1 + c));
     }
   } else {
     const float* gs[2] = {a.g1, a.g2};
@@ -266,36 +46,12 @@ __global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
     const float epss[2] = {a.eps1, a.eps2};
     const int nln = a.g2 ? 2 : 1;
     for (int l = 0; l < nln; ++l) {
-      if (l > 0) {
-        sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-          const int c = (lane + 64 * j) * 4;
-          if (c < a.D) sum += v[j].x + v[j].y + v[j].z + v[j].w;
-        }
-      }
-      const float mean = wave_sum(sum) / (float)a.D;
-      float sq = 0.f;
+      if (l > 0) sum = row_sum(v, sp, a.D);
+      const LnStats st = ln_stats(v, sum, sp, a.D, epss[l], l == 0 ? a.guard : nullptr);
 #pragma unroll
       for (int j = 0; j < J; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < a.D) {
-          const float dx = v[j].x - mean, dy = v[j].y - mean, dz = v[j].z - mean, dw = v[j].w - mean;
-          sq += dx * dx + dy * dy + dz * dz + dw * dw;
-        }
-      }
-      const float var = wave_sum(sq) / (float)a.D;
-      if (a.guard && l == 0 && lane == 0 && !(var < INFINITY)) atomicAdd(a.guard, 1);
-      const float rstd = rsqrtf(var + epss[l]);
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        const int c = (lane + 64 * j) * 4;
-        if (c < a.D) {
-          const float4 g = *(const float4*)(gs[l] + c);
-          const float4 b = *(const float4*)(bs[l] + c);
-          v[j] = make_float4((v[j].x - mean) * rstd * g.x + b.x, (v[j].y - mean) * rstd * g.y + b.y,
-                             (v[j].z - mean) * rstd * g.z + b.z, (v[j].w - mean) * rstd * g.w + b.w);
-        }
+        const int c = span_col(sp, j);
+        if (c < a.D) v[j] = ln_affine(v[j], st, *(const float4*)(gs[l] + c), *(const float4*)(bs[l] + c));
       }
     }
     if (a.act != ACT_NONE) {
@@ -304,14 +60,78 @@ __global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
         v[j] = make_float4(apply_act(v[j].x, a.act, 0.f), apply_act(v[j].y, a.act, 0.f), apply_act(v[j].z, a.act, 0.f), apply_act(v[j].w, a.act, 0.f));
     }
   }
+  float* o32 = SLOTS ? row_f32_block(a, row) : a.out_f32;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    const int c = (lane + 64 * j) * 4;
-    if (c < a.D) {
-      if (a.out_t) *(typename Vec<T>::x4*)((T*)a.out_t + (size_t)row * a.ldot + c) = pack4<T>(v[j].x, v[j].y, v[j].z, v[j].w);
-      if (a.out_f32) *(float4*)(a.out_f32 + (size_t)row * a.ldo32 + c) = v[j];
-    }
+    const int c = span_col(sp, j);
+    if (c < a.D) row_emit<T>(a, o32, row, c, v[j]);
   }
+}
+
+// Generic form: one 256-thread block per row; the only one with the f32 slots.
+template <typename T>
+__global__ __launch_bounds__(256) void rownorm_kernel(RowNormArgs a) {
+  __shared__ float red[4];
+  rownorm_row<T, BlockSpan, true>(a, blockIdx.x, BlockSpan{red});
+}
+
+// Wave-per-row form for D <= 1024: no block barriers, four rows per 256-thread block.  Same arithmetic order per row as the block form
+// is NOT required (tests compare to fp64).
+template <typename T>
+__global__ __launch_bounds__(256) void rownorm_wave_kernel(RowNormArgs a) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.M) return;
+  rownorm_row<T, WaveSpan, false>(a, row, WaveSpan{});
+}
+
+// Narrow rows (D <= 1024): one float4 per thread and every operand the row needs - input, bias, split-K slabs, affine
+// parameters - requested before the first use, so the row costs one memory round trip instead of three (input, slabs,
+// affine).  NSLAB / BIAS / RMS are compile-time so no branch sits between the requests.  Same arithmetic order as the
+// generic kernel: bias, slabs in order, two-pass variance.
+template <typename T, int NSLAB, bool BIAS, bool RMS>
+__global__ __launch_bounds__(256) void rownorm_narrow_kernel(RowNormArgs a) {
+  __shared__ float red[8];
+  FreshBlockSpan sp{red};
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const bool live = tid * 4 < a.D;
+  const int c = min(tid * 4, a.D - 4);  // idle lanes re-read the last quad (no branch), masked below
+  float* xr = a.x + (size_t)row * a.ldx;
+  RowQuad<NSLAB, BIAS ? 1 : 0> q;
+  row_request(a, row, xr, c, q);
+  const float4 g = *(const float4*)(a.g1 + c);
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (!RMS) b = *(const float4*)(a.b1 + c);
+  __builtin_amdgcn_sched_barrier(0);
+
+  float4 v[1] = {row_update(a, row, xr, c, live, q)};
+  if (!live) v[0] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 y;
+  if constexpr (RMS) y = rms_scale(v[0], rms_inv(v, sp, a.D, a.eps1, a.guard), g);
+  else y = ln_affine(v[0], ln_stats(v, quad_sum(v[0]), sp, a.D, a.eps1, a.guard), g, b);
+  if (live) row_emit<T>(a, a.out_f32, row, c, y);
+}
+
+// f(std::integral_constant) for a run-time bool / one of the listed ints (false: v is none of them)
+template <class F> static void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <int... Vs, class F> static bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+template <typename T>
+static bool rownorm_narrow_launch(const ProfScope& ps, const RowNormArgs& a, hipStream_t stream) {
+  if (a.D > 1024 || a.mode == NORM_NONE || a.g2 != nullptr || a.f32_slot != nullptr || a.f32_row_slot != nullptr || a.act != ACT_NONE) return false;
+  const bool bias = a.add_bias != nullptr, rms = a.mode == NORM_RMS;
+  return dispatch_int<0, 1, 2, 4, 8>(a.nslab, [&](auto ns) {
+    dispatch_bool(bias, [&](auto bi) {
+      dispatch_bool(rms, [&](auto rm) {
+        g_rownorm_ran = RowNormRan{1, decltype(ns)::value, bias ? 1 : 0, rms ? 1 : 0};
+        launch_timed(ps, rownorm_narrow_kernel<T, decltype(ns)::value, decltype(bi)::value, decltype(rm)::value>, dim3(a.M), dim3(256), 0, stream, a);
+      });
+    });
+  });
 }
 
 int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream) {
@@ -328,7 +148,7 @@ int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream) {
   } else {
     bool narrow = false;
     TT_DISPATCH_T(dtype, T, narrow = rownorm_narrow_launch<T>(ps, a, stream));
-    if (!narrow) TT_DISPATCH_T(dtype, T, launch_timed(ps, (rownorm_kernel<T, -1>), dim3(a.M), dim3(256), 0, stream, a));
+    if (!narrow) TT_DISPATCH_T(dtype, T, launch_timed(ps, rownorm_kernel<T>, dim3(a.M), dim3(256), 0, stream, a));
   }
   TT_CHECK_HIP(hipGetLastError());
   return 0;
@@ -390,33 +210,19 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
 
 // Per-(batch, group) mean / rstd from partial sums, fp64 combine in a fixed order.  Two sources:
 //   a.gemm_part == nullptr : partial[b][chunk][32][2] from gn_stats_kernel
-//   a.gemm_part != nullptr : [row_tile][slot][C/16][2] written by the producing GEMM's epilogue
+//   a.gemm_part != nullptr : [row_tile][slot][C/16][2] written by the producing GEMM's epilogue (norm_steps.h gn_partial_item)
 // The first GN_HEAD fused partials of every thread can be requested ahead of the activation rows (gn_partial_head) so the
-// statistics round trip overlaps the row loads; gn_finalize then sums head + remainder in the same fixed order.
+// statistics round trip overlaps the row loads; gn_finalize then sums head + remainder in the same fixed order: thread (part, g) takes
+// items part, part + 8, ... of group g, and the 8 parts are combined in part order.
 constexpr int GN_HEAD = 8;
-
-// All index arithmetic here is shifts and compares: part_rows (the producing GEMM's wave-tile height) is a power of two
-// and the strips per group (C / 32 / 16) are a compile-time power of two on the C == 1024 path (SPG_SHIFT = 1), 
-// because this code sits in front of every activation load of the kernel (integer divisions by run-time values cost
-// ~30 instructions each, 3 per partial item).
-template <int SPG_SHIFT>
-__device__ __forceinline__ float2 gn_partial_item(const GroupNormArgs& a, int b, int g, int e, int t0, int nitems, int nc16, int r_shift) {
-  const int ec = min(e, nitems - 1);  // clamped, unconditional load; out-of-range items are zeroed by the caller
-  const int t = t0 + (ec >> SPG_SHIFT), strip = (g << SPG_SHIFT) + (ec & ((1 << SPG_SHIFT) - 1));
-  // a row tile's slot 0 holds the rows of the sequence its FIRST row belongs to, slot 1 those of the next sequence: tile t of
-  // sample b starts inside sample b unless it is the first tile and straddles in from sample b - 1
-  const int slot = ((t << r_shift) < b * a.S) ? 1 : 0;
-  return *(const float2*)(a.gemm_part + (((size_t)t * 2 + slot) * nc16 + strip) * 2);
-}
 
 template <int SPG_SHIFT>
 __device__ __forceinline__ void gn_partial_head(const GroupNormArgs& a, int b, int tid, float2 (&head)[GN_HEAD]) {
   const int g = tid & 31, part = tid >> 5;
-  const int S = a.S, r_shift = 31 - __builtin_clz(a.part_rows), nc16 = a.C >> 4;
-  const int t0 = (b * S) >> r_shift, t1 = ((b + 1) * S - 1) >> r_shift;
-  const int nitems = (t1 - t0 + 1) << SPG_SHIFT;
+  const int r_shift = 31 - __builtin_clz(a.part_rows), nc16 = a.C >> 4;
+  const GnItems it = gn_items<SPG_SHIFT>(b, a.S, r_shift);
 #pragma unroll
-  for (int k = 0; k < GN_HEAD; ++k) head[k] = gn_partial_item<SPG_SHIFT>(a, b, g, part + 8 * k, t0, nitems, nc16, r_shift);
+  for (int k = 0; k < GN_HEAD; ++k) head[k] = gn_partial_item<SPG_SHIFT>(a.gemm_part, a.S, b, g, part + 8 * k, it, nc16, r_shift);
 }
 
 template <int SPG_SHIFT>
@@ -425,22 +231,21 @@ __device__ __forceinline__ void gn_finalize(const GroupNormArgs& a, int b, int t
   const int g = tid & 31, part = tid >> 5;
   double s = 0.0, q = 0.0;
   if (a.gemm_part) {
-    const int S = a.S, r_shift = 31 - __builtin_clz(a.part_rows), nc16 = a.C >> 4;
-    const int t0 = (b * S) >> r_shift, t1 = ((b + 1) * S - 1) >> r_shift;
-    const int nitems = (t1 - t0 + 1) << SPG_SHIFT;  // 16-column strips per group x row tiles
+    const int r_shift = 31 - __builtin_clz(a.part_rows), nc16 = a.C >> 4;
+    const GnItems it = gn_items<SPG_SHIFT>(b, a.S, r_shift);
     int e = part;
     if (head) {
 #pragma unroll
       for (int k = 0; k < GN_HEAD; ++k, e += 8) {
-        if (e < nitems) {
+        if (e < it.n) {
           s += (double)head[k].x;
           q += (double)head[k].y;
         }
       }
     }
 #pragma unroll 4
-    for (; e < nitems; e += 8) {
-      const float2 v = gn_partial_item<SPG_SHIFT>(a, b, g, e, t0, nitems, nc16, r_shift);
+    for (; e < it.n; e += 8) {
+      const float2 v = gn_partial_item<SPG_SHIFT>(a.gemm_part, a.S, b, g, e, it, nc16, r_shift);
       s += (double)v.x;
       q += (double)v.y;
     }
@@ -461,28 +266,20 @@ __device__ __forceinline__ void gn_finalize(const GroupNormArgs& a, int b, int t
   part_q[part][g] = q;
   __syncthreads();
   if (tid < 32) {
-    double ss = 0.0, qq = 0.0;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      ss += part_s[p][tid];
-      qq += part_q[p][tid];
-    }
-    // the sums are combined in fp64 (E[x^2] - E[x]^2 cancels in fp32); the reciprocal square root of the O(1) result is an
-    // fp32 instruction, not an fp64 divide + square root (hundreds of cycles on the one wave every block waits for)
+    const GnSums t = gn_combine(part_s, part_q, tid);
     // 1 / (S * C / 32), set by groupnorm_launch; a padded batch counts the sample's valid rows only
     const double inv_n = a.vperiod > 0 ? 1.0 / ((double)a.vlen[b % a.vperiod] * (double)(a.C / 32)) : a.inv_count;
-    const double m = ss * inv_n;
-    double var = qq * inv_n - m * m;
-    if (a.guard && !(var < 1.0e300)) atomicAdd(a.guard, 1);  // NaN / inf statistics: an operand overflowed upstream
-    if (var < 0.0) var = 0.0;
-    mean_s[tid] = (float)m;
-    rstd_s[tid] = rsqrtf((float)var + a.eps);
+    gn_mean_rstd(t, inv_n, a, mean_s[tid], rstd_s[tid]);
   }
   __syncthreads();
 }
 
+__device__ __forceinline__ const float* gn_ss_block(const GroupNormArgs& a, int b) {
+  return a.scale_shift + (size_t)(b / (a.ss_batch_div > 0 ? a.ss_batch_div : 1)) * a.ss_batch_stride;
+}
+
 template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_kernel(GroupNormArgs a, int nchunk, int rows_per_chunk, int rows_per_block) {
+__global__ __launch_bounds__(256) void gn_apply_kernel(GroupNormArgs a, int nchunk, int rows_per_block) {
   __shared__ float mean_s[32], rstd_s[32];
   __shared__ double part_s[8][32], part_q[8][32];
   const int chunk = blockIdx.x, b = blockIdx.y;
@@ -508,33 +305,20 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GroupNormArgs a, int nchu
     const float4 t = *(const float4*)(a.x + off * C + c);
     const float4 gm = *(const float4*)(a.gamma + c);
     const float4 bt = *(const float4*)(a.beta + c);
-    const float mu = mean_s[g], rs = rstd_s[g];
-    float y[4] = {(t.x - mu) * rs * gm.x + bt.x, (t.y - mu) * rs * gm.y + bt.y, (t.z - mu) * rs * gm.z + bt.z,
-                  (t.w - mu) * rs * gm.w + bt.w};
+    float4 y = gn_affine(t, mean_s[g], rstd_s[g], gm, bt);
     if (a.scale_shift) {
-      const float* ss = a.scale_shift + (size_t)(b / (a.ss_batch_div > 0 ? a.ss_batch_div : 1)) * a.ss_batch_stride;
-      const float4 sc = *(const float4*)(ss + c);
-      const float4 sh = *(const float4*)(ss + C + c);
-      y[0] = y[0] * (1.f + sc.x) + sh.x;
-      y[1] = y[1] * (1.f + sc.y) + sh.y;
-      y[2] = y[2] * (1.f + sc.z) + sh.z;
-      y[3] = y[3] * (1.f + sc.w) + sh.w;
+      const float* ss = gn_ss_block(a, b);
+      y = gn_scale_shift(y, *(const float4*)(ss + c), *(const float4*)(ss + C + c));
     }
-    if (a.act != ACT_NONE) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) y[i] = apply_act(y[i], a.act, 0.f);
-    }
-    if (r >= vl) y[0] = y[1] = y[2] = y[3] = 0.f;  // padding rows of a shorter sequence: exact zeros (the next conv's zero padding)
-    if (a.out_t) *(typename Vec<T>::x4*)((T*)a.out_t + off * a.ldot + c) = pack4<T>(y[0], y[1], y[2], y[3]);
-    if (a.out_f32) *(float4*)(a.out_f32 + off * a.ldo32 + c) = make_float4(y[0], y[1], y[2], y[3]);
+    gn_emit<T>(a, off, c, gn_act_pad(y, a.act, r >= vl));
   }
 }
 
-// C == 1024 fast path: thread t owns channels 4t..4t+3 (group t/8) of GN_APPLY_ROWS consecutive rows.  The x rows
-// are requested BEFORE the statistics are finalised, so the streaming loads overlap the (latency-bound) prologue.
-constexpr int GN_APPLY_ROWS = 4;  // 4 rows per block: 2 blocks per CU at the denoiser's 1740 rows, so one block's statistics prologue overlaps the other's stream
+// C == 1024 fast path: thread t owns channels 4t..4t+3 (group t/8) of ROWS consecutive rows.  The x rows are requested BEFORE the
+// statistics are finalised, so the streaming loads overlap the (latency-bound) prologue.
 // ROWS per block: 4 in general (two blocks per CU overlap each other's statistics prologue); 2 for passes of <= 4096 rows (the
 // denoiser alone, 1740 rows: 870 blocks instead of 435 - in-situ A/B -1.7 % on the sampler iteration; 1 row and 8 rows are slower)
+constexpr int GN_APPLY_ROWS = 4;
 template <typename T, bool FUSED, bool SS, int ROWS>
 __global__ __launch_bounds__(256) void gn_apply_c1024_kernel(GroupNormArgs a, int nchunk) {
   __shared__ float mean_s[32], rstd_s[32];
@@ -557,7 +341,7 @@ __global__ __launch_bounds__(256) void gn_apply_c1024_kernel(GroupNormArgs a, in
   const float4 bt = *(const float4*)(a.beta + c);
   float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
   if constexpr (SS) {  // SS <=> a.scale_shift != nullptr
-    const float* ss = a.scale_shift + (size_t)(b / (a.ss_batch_div > 0 ? a.ss_batch_div : 1)) * a.ss_batch_stride;
+    const float* ss = gn_ss_block(a, b);
     sc = *(const float4*)(ss + c);
     sh = *(const float4*)(ss + C + c);
   }
@@ -569,23 +353,9 @@ __global__ __launch_bounds__(256) void gn_apply_c1024_kernel(GroupNormArgs a, in
   for (int i = 0; i < ROWS; ++i) {
     const int r = r0 + i;
     if (r >= S) break;
-    const float4 t = xr[i];
-    float y[4] = {(t.x - mu) * rs * gm.x + bt.x, (t.y - mu) * rs * gm.y + bt.y, (t.z - mu) * rs * gm.z + bt.z,
-                  (t.w - mu) * rs * gm.w + bt.w};
-    if constexpr (SS) {
-      y[0] = y[0] * (1.f + sc.x) + sh.x;
-      y[1] = y[1] * (1.f + sc.y) + sh.y;
-      y[2] = y[2] * (1.f + sc.z) + sh.z;
-      y[3] = y[3] * (1.f + sc.w) + sh.w;
-    }
-    if (a.act != ACT_NONE) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) y[k] = apply_act(y[k], a.act, 0.f);
-    }
-    if (r >= vl) y[0] = y[1] = y[2] = y[3] = 0.f;  // padding rows of a shorter sequence: exact zeros
-    const size_t off = (size_t)b * S + r;
-    if (a.out_t) *(typename Vec<T>::x4*)((T*)a.out_t + off * a.ldot + c) = pack4<T>(y[0], y[1], y[2], y[3]);
-    if (a.out_f32) *(float4*)(a.out_f32 + off * a.ldo32 + c) = make_float4(y[0], y[1], y[2], y[3]);
+    float4 y = gn_affine(xr[i], mu, rs, gm, bt);
+    if constexpr (SS) y = gn_scale_shift(y, sc, sh);
+    gn_emit<T>(a, (size_t)b * S + r, c, gn_act_pad(y, a.act, r >= vl));
   }
 }
 
@@ -612,30 +382,16 @@ int groupnorm_launch(int dtype, const GroupNormArgs& a0, hipStream_t stream) {
   const int rpb = few ? 2 : GN_APPLY_ROWS;  // apply is pure streaming: many small blocks
   dim3 grid2(cdiv(a.S, rpb), a.B);
   g_groupnorm_ran = GroupNormRan{a.gemm_part ? 0 : 1, a.C == 1024 ? 1 : 0, rpb, a.C == 1024 && a.gemm_part ? 1 : 0};
-  if (a.C == 1024) {
-    const int variant = (dtype == DT_BF16 ? 0 : dtype == DT_F16 ? 4 : 8) + (a.gemm_part ? 2 : 0) + (a.scale_shift ? 1 : 0);
-#define TT_GN(T, F, SSV)                                                                                              \
-    do {                                                                                                                \
-      if (few) launch_timed(ps, gn_apply_c1024_kernel<T, F, SSV, 2>, grid2, dim3(256), 0, stream, a, nchunk);          \
-      else launch_timed(ps, gn_apply_c1024_kernel<T, F, SSV, GN_APPLY_ROWS>, grid2, dim3(256), 0, stream, a, nchunk);  \
-    } while (0)
-    switch (variant) {
-      case 0: TT_GN(bf16, false, false); break;
-      case 1: TT_GN(bf16, false, true); break;
-      case 2: TT_GN(bf16, true, false); break;
-      case 3: TT_GN(bf16, true, true); break;
-      case 4: TT_GN(f16, false, false); break;
-      case 5: TT_GN(f16, false, true); break;
-      case 6: TT_GN(f16, true, false); break;
-      case 7: TT_GN(f16, true, true); break;
-      case 8: TT_GN(float, false, false); break;   // (the fp32 verification mode)
-      case 9: TT_GN(float, false, true); break;
-      case 10: TT_GN(float, true, false); break;
-      default: TT_GN(float, true, true); break;
-    }
-#undef TT_GN
+  if (a.C == 1024) {  // (T = float: the fp32 verification mode)
+    TT_DISPATCH_T(dtype, T, dispatch_bool(a.gemm_part != nullptr, [&](auto fused) {
+      dispatch_bool(a.scale_shift != nullptr, [&](auto ss) {
+        dispatch_int<2, GN_APPLY_ROWS>(rpb, [&](auto rows) {
+          launch_timed(ps, gn_apply_c1024_kernel<T, decltype(fused)::value, decltype(ss)::value, decltype(rows)::value>, grid2, dim3(256), 0, stream, a, nchunk);
+        });
+      });
+    }));
   } else {
-    TT_DISPATCH_T(dtype, T, launch_timed(ps, gn_apply_kernel<T>, grid2, dim3(256), 0, stream, a, nchunk, rpc, rpb));
+    TT_DISPATCH_T(dtype, T, launch_timed(ps, gn_apply_kernel<T>, grid2, dim3(256), 0, stream, a, nchunk, rpb));
   }
   TT_CHECK_HIP(hipGetLastError());
   return 0;

@@ -31,12 +31,13 @@ struct RowNormArgs {
   int ldot;
   float* out_f32;      // optional f32 copy of the normalised row
   int ldo32;
-  // optional (generic kernel only): the f32 copy goes to out_f32 + (*f32_slot + f32_slot_base) * f32_slot_stride - a device-side
+  // optional (rownorm_kernel only - the wave form of the same body is built without the slots, the narrow kernel has none; rownorm_launch
+  // routes such a problem accordingly): the f32 copy goes to out_f32 + (*f32_slot + f32_slot_base) * f32_slot_stride - a device-side
   // step counter selects the destination block, so a captured decode step can file its row under the step it belongs to
   const int* f32_slot;
   int f32_slot_base;
   size_t f32_slot_stride;
-  // optional, session handles (generic kernel only): row r files its f32 copy under its own counter f32_row_slot[r] (+ f32_slot_base);
+  // optional, session handles (rownorm_kernel only, as f32_slot): row r files its f32 copy under its own counter f32_row_slot[r] (+ f32_slot_base);
   // a negative counter files nothing for that row
   const int* f32_row_slot;
   int row_blocks;      // 1: always one workgroup per row (the decode step: a row's arithmetic order must not depend on how many rows the batch has)
@@ -46,7 +47,8 @@ struct RowNormArgs {
 };
 int rownorm_launch(int dtype, const RowNormArgs& a, hipStream_t stream);
 // What the last rownorm_launch of this thread started, recorded on the host (as g_gemm_ran; the operator-level tests assert it):
-// kernel 0 generic, 1 narrow, 2 wave; nslab = the compiled slab count of the narrow kernel, -1 where the count is a run-time loop;
+// kernel 0 generic (block per row), 1 narrow, 2 wave (wave per row; the generic kernel's body); nslab = the compiled slab count of the narrow
+// kernel, -1 where the count is a run-time loop;
 // bias / rms = the narrow kernel's template arguments (the other kernels: whether add_bias is set / the mode is NORM_RMS)
 struct RowNormRan { int kernel, nslab, bias, rms; };
 extern thread_local RowNormRan g_rownorm_ran;  // norm.hip
