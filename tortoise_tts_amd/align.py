@@ -385,9 +385,11 @@ class Alignment:
     samples: int
     index: list = field(default_factory=list)  # text position -> position in chars (AlignmentTargets.index)
     kept: list = field(default_factory=list)
+    rate: int = ORIG_SR  # samples per second of the clip the positions count (another one after a sample-rate conversion)
 
-    def seconds(self, rate=ORIG_SR):
+    def seconds(self, rate=None):
         """words with their times in seconds: (word, start_s, end_s, confidence)."""
+        rate = self.rate if rate is None else rate
         return [(w, a / rate, b / rate, c) for w, a, b, c in self.words]
 
     def char_start(self, i):
@@ -399,8 +401,10 @@ class Alignment:
         j = self.index[i]
         return 0 if j < 0 else self.chars[j][2]
 
-    def to_srt(self, max_chars=42, rate=ORIG_SR):
+    def to_srt(self, max_chars=42, rate=None):
         """SubRip cues of at most max_chars characters, cut on word boundaries (a longer single word gets a cue of its own)."""
+        rate = self.rate if rate is None else rate
+
         def stamp(n):
             ms = (n * 1000 + rate // 2) // rate
             return "%02d:%02d:%02d,%03d" % (ms // 3600000, ms // 60000 % 60, ms // 1000 % 60, ms % 1000)
@@ -436,6 +440,16 @@ def build_alignment(targets, spans, conf, score, samples, frame_len):
             words.append((text[i:j], prev_end, prev_end, float("nan")))
         i = j
     return Alignment(text, chars, words, float(score), int(samples), list(targets.index), list(targets.kept))
+
+
+def resample_alignment(al, to_rate, n_out):
+    """An alignment of a clip at al.rate -> the same alignment of that clip converted to `to_rate` Hz, n_out samples long: every position
+    goes through resample.map_sample, s -> min(n_out, (s Q + P / 2) / P) with P / Q = al.rate / to_rate."""
+    from . import resample as rs
+    P, Q = rs.ratio(al.rate, to_rate)
+    f = lambda s_: rs.map_sample(s_, P, Q, n_out)
+    return Alignment(al.text, [(c, f(a), f(b), p) for c, a, b, p in al.chars], [(w, f(a), f(b), p) for w, a, b, p in al.words], al.score,
+                     int(n_out), list(al.index), list(al.kept), int(to_rate))
 
 
 def empty_alignment(targets, samples):

@@ -39,6 +39,7 @@ from . import dist as tdist
 from . import engine as E
 from . import stages
 from . import loudness as loud
+from . import resample as rs
 from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
@@ -333,16 +334,24 @@ class _Common:
 
     def tts_with_timings(self, text, **tts_kwargs):
         """tts(text, **tts_kwargs) and where its words are -> (what tts returns, align.Alignment - a list of k of them for k > 1; None where
-        tts returns no audio, i.e. on the other ranks of a sharded job).  The text is aligned as spoken (see align_many)."""
+        tts returns no audio, i.e. on the other ranks of a sharded job).  The text is aligned as spoken (see align_many).  With sample_rate=
+        the clip is aligned at 24 kHz and converted afterwards; the Alignment then counts samples of the returned audio and carries its
+        rate (.seconds() and .to_srt() use it)."""
         if not isinstance(text, str):
             raise TypeError("tts_with_timings aligns the text with the audio: pass it as a str, not as token ids")
         self.load_aligner()  # (missing files are reported before anything renders)
+        sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (the aligner reads 24 kHz: converted after it)
         res = self.tts(text, **tts_kwargs)
         out = res[0] if tts_kwargs.get("return_deterministic_state") else res
         if out is None:
             return res, None
         clips = out if isinstance(out, (list, tuple)) else [out]
         als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
+        if sample_rate is not None:  # the returned audio and its timings are at sample_rate
+            conv = self._at_sample_rate(list(clips), sample_rate)
+            als = [align.resample_alignment(al, sample_rate, c.shape[-1]) for al, c in zip(als, conv)]
+            out = conv if isinstance(out, (list, tuple)) else conv[0]
+            res = (out,) + tuple(res[1:]) if tts_kwargs.get("return_deterministic_state") else out
         return res, (als if isinstance(out, (list, tuple)) else als[0])
 
     # ------------------------------------------------------------------ speaking rate: WSOLA time-stretch of finished clips
@@ -473,6 +482,115 @@ class _Common:
         return dict(zip(keys, out)) if keys is not None else out
 
 
+    # ------------------------------------------------------------------ pitch and output sample rate: the arbitrary-ratio resampler
+    resampler = None
+
+    def load_resample(self, max_samples=0):
+        """The resampling stage (stages.ResampleStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.RS_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the resampler can take ({E.RS_MAX_SAMPLES})")
+        if self.resampler is None or self.resampler.max_samples < max_samples:
+            if self.resampler is not None:
+                self.resampler.close()
+            self.resampler = stages.ResampleStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE), device=self.device)
+        return self.resampler
+
+    def _resample_ratios(self, audios, ratios, return_info):
+        """audios (validated) at (P, Q) each -> the clips, each in the shape and on the device it came in; all of them through ONE device
+        call per 16.  A ratio of 1 is no call: the clip is returned as it is (the resampler's P = Q is a low-pass, not a copy)."""
+        t0 = time.perf_counter()
+        todo = [i for i, (P, Q) in enumerate(ratios) if P != Q]
+        out, peaks = list(audios), [None] * len(audios)
+        if todo:
+            res = self.load_resample(max(audios[i].shape[-1] for i in todo)).resample_many([audios[i].reshape(-1) for i in todo],
+                                                                                          [ratios[i] for i in todo])
+            for i, (y, pk) in zip(todo, res):  # (the peaks' copy back has synchronised)
+                out[i], peaks[i] = y.to(audios[i].device).reshape(audios[i].shape[:-1] + (-1,)), pk
+        if return_info:
+            peaks = [float(a.abs().max()) if pk is None else pk for a, pk in zip(audios, peaks)]
+        self._resample_s = time.perf_counter() - t0
+        return (out, peaks) if return_info else out
+
+    @torch.no_grad()
+    def resample_many(self, audios, to_rates, from_rates=rs.SAMPLE_RATE, return_info=False):
+        """The same audio at another sample rate: audios f32 [n] / [1, n] / [1, 1, n] (any device) -> the converted clips, each in the shape
+        and on the device it came in.  to_rates / from_rates: Hz, one value or one per clip, any positive integers whose reduced ratio has
+        terms up to 2^20 and lies in 1/8 .. 8 (24000 -> 8000 / 16000 / 44100 / 48000, or a 44100 Hz voice clip -> 22050).  A Kaiser-windowed
+        sinc with its cutoff at 0.9 of the narrower Nyquist frequency (csrc/resample.hip): pass-band within 0.001 dB, everything else below
+        -100 dB.  All clips go through ONE device call per 16.  return_info=True: also the sample peak max |y| of every returned clip."""
+        audios = self._level_clips(audios, "resample")
+        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(audios)
+        to_rates, from_rates = per(to_rates), per(from_rates)
+        if len(to_rates) != len(audios) or len(from_rates) != len(audios):
+            raise ValueError(f"resample: {len(audios)} clips with {len(to_rates)} target rates and {len(from_rates)} source rates")
+        return self._resample_ratios(audios, [rs.ratio(f, t) for f, t in zip(from_rates, to_rates)], return_info)
+
+    def resample(self, audio, to_rate, from_rate=rs.SAMPLE_RATE):
+        """resample_many of one clip -> the clip at to_rate."""
+        return self.resample_many([audio], to_rate, from_rate)[0]
+
+    @torch.no_grad()
+    def shift_pitch_many(self, audios, semitones, return_info=False):
+        """The same speech at another pitch and the same duration: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), semitones
+        (+: up; one value or one per clip, each within +-12) -> the shifted clips.  Two batched device calls: a time-stretch at rate
+        65536^2 / pq (rounded; pq = round(2^(s/12) 65536)), then a resampling by (pq, 65536), which undoes the stretch's change of duration
+        (to within the rounding of the two lengths) and moves every frequency by 2^(s/12).  Pitch by resampling moves the formants with
+        the pitch: it stays natural for a few semitones, and nobody has rendered a trained checkpoint through it.  0 semitones returns the
+        clip as it is.  return_info=True: also the sample peak of every returned clip."""
+        audios = self._level_clips(audios, "shift_pitch")
+        semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
+        if len(semis) != len(audios):
+            raise ValueError(f"shift_pitch: {len(audios)} clips with {len(semis)} pitches")
+        plans = [rs.pitch(s_) for s_ in semis]
+        t0 = time.perf_counter()
+        todo = [i for i, (pq, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
+        mid = list(audios)
+        if todo:  # (rate 1.0 is the input itself: not stretched)
+            for i, y in zip(todo, self.stretch_many([audios[i] for i in todo], rates=[plans[i][1] / E.TSM_RATE_ONE for i in todo])):
+                mid[i] = y
+        res = self._resample_ratios(mid, [(pq, E.RS_PITCH_ONE) for pq, _ in plans], return_info)
+        self._resample_s = time.perf_counter() - t0
+        return res
+
+    def shift_pitch(self, audio, semitones):
+        """shift_pitch_many of one clip -> the shifted clip."""
+        return self.shift_pitch_many([audio], semitones)[0]
+
+    def _at_pitch(self, clips, rate, semitones):
+        """The clips a tts call is about to return ({winner: clip} or a list) at speaking_rate `rate` (None: 1.0) and pitch `semitones`: ONE
+        stretch_many call at rq_eff = round(rq 65536 / pq) and ONE resampling by (pq, 65536) for all of them; their time in
+        timings['stretch_s'] / ['pitch_s']."""
+        pq, rq_eff = rs.pitch(semitones, rate)
+        self._stretch_s = 0.0
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        if rq_eff != E.TSM_RATE_ONE:
+            seq = self.stretch_many(seq, rates=rq_eff / E.TSM_RATE_ONE)  # (rq_eff / 65536 is exact: stretch.rate_q returns rq_eff)
+        seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE)] * len(seq), False)
+        self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s, pitch_s=self._resample_s)
+        return dict(zip(keys, seq)) if keys is not None else seq
+
+    def _at_sample_rate(self, clips, sample_rate):
+        """The clips a tts call is about to return ({winner: clip} or a list) converted from 24 kHz to `sample_rate`: the last step, one
+        call for all of them, its time in timings['resample_s'], the sample peaks of the returned clips in self.resample_info."""
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        seq, peaks = self._resample_ratios(seq, [rs.ratio(rs.SAMPLE_RATE, sample_rate)] * len(seq), True)
+        self.resample_info = peaks
+        self.timings = dict(getattr(self, "timings", None) or {}, resample_s=self._resample_s)
+        return dict(zip(keys, seq)) if keys is not None else seq
+
+    def _voiced(self, clips, rate, pitch, level, sample_rate):
+        """The chain behind redaction: speaking rate and pitch together, then the level (at 24 kHz), then the output sample rate."""
+        if pitch is not None:
+            clips = self._at_pitch(clips, rate, pitch)
+        elif rate is not None:
+            clips = self._at_rate(clips, rate)
+        if level is not None:
+            clips = self._at_level(clips, level)
+        return clips if sample_rate is None else self._at_sample_rate(clips, sample_rate)
+
+
 class TextToSpeech(_Common):
     """Main entry point; see the module docstring.  Engine-only keyword arguments (all optional, after
     the reference's): `state_dicts` (dict of reference-layout state_dicts instead of files in
@@ -488,7 +606,12 @@ class TextToSpeech(_Common):
     redaction (stretch / stretch_many, csrc/tsm.hip - DESIGN.md 5.24); `loudness` (a target in LUFS, -70 .. -5; None: off) with `true_peak`
     (the ceiling in dBTP, default -1) and `limit` ('scale', the default, 'lookahead' or 'none') - every returned clip is then brought to the
     target under the ceiling, the last step after redaction and the speaking rate (normalize / normalize_many, csrc/loudness.hip - DESIGN.md
-    5.25; the readings are left in `loudness_info`)."""
+    5.25; the readings are left in `loudness_info`); `pitch` (semitones, +-12; None or 0: off) - every returned clip is shifted by ONE
+    time-stretch at rate speaking_rate / 2^(pitch/12) and ONE resampling by 2^(pitch/12), together with the speaking rate (shift_pitch,
+    csrc/resample.hip - DESIGN.md 5.27; pitch by resampling moves the formants with the pitch: natural for a few semitones, and nobody has
+    rendered a trained checkpoint through it); `sample_rate` (Hz, an integer in 8000 .. 96000; None or 24000: off) - every returned clip
+    is converted from 24 kHz last (resample).  The `true_peak` ceiling is enforced at 24 kHz, before that conversion: down-conversion
+    removes content and can move the peak; the sample peaks of the converted clips are left in `resample_info`."""
 
     redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
@@ -794,10 +917,8 @@ class TextToSpeech(_Common):
             self._redact_s = 0.0
             wavs = self._redact_clips(wavs, redact)
             self.timings["redact_s"] = self._redact_s
-        if o.speaking_rate is not None:  # (every rank stretches the clips it holds)
-            wavs = self._at_rate(wavs, o.speaking_rate)
-        if o.level is not None:  # (the last step of the chain: redaction -> speaking rate -> level)
-            wavs = self._at_level(wavs, o.level)
+        # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> level -> output sample rate
+        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -813,12 +934,14 @@ class TextToSpeech(_Common):
         candidates (every score the bits of scoring the utterance alone) and the denoiser runs in shared, padded passes; the latent re-pass
         runs per utterance as in tts() and UnivNet vocodes a wave in one call (every clip the bits of vocoding it alone).  Single-rank instances only (long-form reading spreads whole chunks over the ranks, longform.py).
         speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
-        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call."""
+        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
+        pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
+        96000) converts every clip last, in ONE call."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
+        pitch, sample_rate = rs.options(kwargs, rate)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
-        out = out if rate is None else self._at_rate(out, rate)
-        return out if level is None else self._at_level(out, level)
+        return self._voiced(out, rate, pitch, level, sample_rate)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
@@ -906,6 +1029,7 @@ class TextToSpeech(_Common):
         hf = dict(args["hf_generate_kwargs"])
         noise = hf.pop("noise_override", None) or {}
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
+        pitch, sample_rate = rs.options(hf, speaking_rate)
         plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
@@ -916,7 +1040,7 @@ class TextToSpeech(_Common):
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
             solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
-            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level)
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

@@ -34,6 +34,7 @@ import torch
 from . import engine as E
 from . import stages
 from . import loudness as loud
+from . import resample as rs
 from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
@@ -191,6 +192,7 @@ class TextToSpeech(_Common):
         # (k and cvvp_amount are accepted and unused as in the reference: its fast path decodes ONE sample, there is nothing to rank)
         self._single("tts")
         speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
+        pitch, sample_rate = rs.options(hf_generate_kwargs, speaking_rate)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -200,8 +202,7 @@ class TextToSpeech(_Common):
         self.last_codes = codes
         latents = self.ar.latents(cond, text_tokens, codes)          # api_fast.py:510-514 (return_latent=True)
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
-        wav = wav.cpu() if speaking_rate is None else self._at_rate([wav.cpu()], speaking_rate)[0]
-        return wav if level is None else self._at_level([wav], level)[0]  # (the last step: speaking rate -> level)
+        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate)[0]  # (speaking rate and pitch -> level -> sample rate)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
@@ -210,11 +211,13 @@ class TextToSpeech(_Common):
         rows of the shared decode batch - later texts take rows as earlier ones finish - each gets tts()'s latent re-pass, and the clips
         are vocoded in ragged batches (HifiganStage.inference_many).  Returns a list of wav f32 [1, 1, S] on the CPU.
         speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
-        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call."""
+        loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
+        pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
+        96000) converts every clip last, in ONE call."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
+        pitch, sample_rate = rs.options(kwargs, rate)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
-        out = out if rate is None else self._at_rate(out, rate)
-        return out if level is None else self._at_level(out, level)
+        return self._voiced(out, rate, pitch, level, sample_rate)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs):
@@ -332,6 +335,7 @@ class TextToSpeech(_Common):
         self._single("tts_stream")
         tsm.refuse_streaming(hf_generate_kwargs, "tts_stream")
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
@@ -379,6 +383,7 @@ class TextToSpeech(_Common):
         with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken."""
         tsm.refuse_streaming(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
+        rs.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
@@ -514,6 +519,7 @@ class TextToSpeech(_Common):
         slots are admitted as earlier sessions end."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
+        rs.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):

@@ -410,6 +410,21 @@ LOUD_SAMPLE_RATE = 24000
 LOUD_MAX_SAMPLES, LOUD_MAX_CLIPS = 268435456, 64
 LOUD_NONE, LOUD_SCALE, LOUD_LOOKAHEAD_MODE = 0, 1, 2
 LOUD_OK, LOUD_SHORT, LOUD_SILENT, LOUD_EMPTY, LOUD_REFUSED = 0, 1, 2, 3, 4
+# include/tortoise_mi355x_rs.h: arbitrary-ratio band-limited resampler of rendered clips: pitch and output sample rate (its own header and version)
+_RS_PROTOS = {
+    "tt_rs_abi_version": (_i, []),
+    "tt_rs_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_rs_destroy": (None, [vp]),
+    "tt_rs_out_samples": (_i, [_i, _i, _i]),
+    "tt_rs_resample": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+RS_ABI_VERSION = 1
+RS_ZEROS, RS_PER_ZERO, RS_TABLE, RS_BETA = 32, 512, 16385, 10  # TT_RS_ZEROS, TT_RS_PER_ZERO, TT_RS_TABLE, TT_RS_BETA
+RS_RHO_NUM, RS_RHO_DEN = 9, 10
+RS_PITCH_ONE = 65536
+RS_MAX_TERM, RS_MAX_RATIO = 1048576, 8
+RS_MAX_SAMPLES, RS_MAX_CLIPS = 8388608, 64
+RS_OK, RS_EMPTY, RS_REFUSED = 0, 1, 2
 # include/tortoise_mi355x_solver.h: DDIM / DPM-Solver++(2M) on a tt_diff handle (its own header and version, same library)
 _SOLVER_PROTOS = {
     "tt_solver_abi_version": (_i, []),
@@ -493,7 +508,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -527,6 +542,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_tsm.h is version %d in the library, %d in Python" % (lib.tt_tsm_abi_version(), TSM_ABI_VERSION))
     if lib.tt_loud_abi_version() != LOUD_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
+    if lib.tt_rs_abi_version() != RS_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_solver.h is version %d in the library, %d in Python" % (lib.tt_solver_abi_version(), SOLVER_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):

@@ -35,7 +35,7 @@ def merge_alignments(alignments, clip_samples):
         text += al.text
         score += al.score
         off += int(n)
-    return Alignment(text, chars, words, score, off, index, kept)
+    return Alignment(text, chars, words, score, off, index, kept, getattr(alignments[0], "rate", Alignment.rate) if alignments else Alignment.rate)
 
 
 def read_long_form(tts, text, preset="standard", conditioning_latents=None, voice_samples=None, seed=None, texts_are_chunks=False,
@@ -51,11 +51,16 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     aligned with its own clip in one forced-alignment call (tts.align_many) and merge_alignments offsets them.
     loudness= (LUFS; with true_peak= and limit=, see TextToSpeech.normalize_many) brings the reading to a level: loudness_scope='chunk' (the
     default) every chunk to the target, in one normalize_many call per rank - the level no longer moves from chunk to chunk;
-    loudness_scope='whole' one gain for the concatenation."""
+    loudness_scope='whole' one gain for the concatenation.
+    pitch= goes to the chunks' calls with speaking_rate=.  sample_rate= (Hz, 8000 .. 96000) is applied here, last: every chunk is converted
+    from 24 kHz in one call, after the level and after the alignment, whose positions then count samples of the returned audio (the
+    Alignment carries that rate)."""
     from . import loudness as loud
+    from . import resample as rs
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
     scope, level = loud.scope_option(tts_kwargs), loud.level_options(tts_kwargs)  # (applied here, to what the chunks' calls return)
+    sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (here too, after the level)
     if getattr(tts, "world", 1) != 1:
         raise ValueError("read_long_form spreads chunks over the ranks: build TextToSpeech(candidate_sharding=False)")
     if texts_are_chunks:
@@ -101,7 +106,12 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     if level is not None and scope == "whole":  # one gain (and one limiter pass) for the concatenation; the parts are its pieces
         full = tts._at_level([full], level)[0]
         clips = [p.reshape(c.shape) for p, c in zip(full.split([c.shape[-1] for c in clips], dim=-1), clips)]
+    als = tts.align_many(clips, [tts._spoken_text(t) for t in texts]) if return_timings else None  # (the aligner reads 24 kHz)
+    if sample_rate is not None:
+        from .align import resample_alignment
+        clips = tts._at_sample_rate(clips, sample_rate)
+        full = torch.cat([c.squeeze(0) for c in clips], dim=-1)
+        als = als and [resample_alignment(al, sample_rate, c.shape[-1]) for al, c in zip(als, clips)]
     if return_timings:
-        als = tts.align_many(clips, [tts._spoken_text(t) for t in texts])
         return full, merge_alignments(als, [c.shape[-1] for c in clips])
     return full, clips

@@ -581,6 +581,57 @@ class TimeStretchStage(_Handle):
         return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
 
 
+class ResampleStage(_Handle):
+    """Band-limited resampling at an arbitrary ratio (csrc/resample.hip, include/tortoise_mi355x_rs.h): ragged batches, each clip with its own
+    (P, Q) input samples per output sample, one tt_rs_resample call per max_clips clips, every clip's result bit-identical to resampling it
+    alone."""
+
+    api = "tt_rs"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        self._create(self.max_samples, self.max_clips)
+
+    def resample_many(self, clips, ratios):
+        """clips f32 [n_i] (device or host) and the (P, Q) of each (resample.ratio / pitch_ratio) -> one (y f32 [n_out_i] on the stage's
+        device, max |y| as a float) per clip.  ValueError for an empty clip, a clip beyond the handle or a ratio the device refuses."""
+        if len(clips) != len(ratios):
+            raise ValueError(f"{len(clips)} clips with {len(ratios)} ratios")
+        for i, (x, (P, Q)) in enumerate(zip(clips, ratios)):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the resampling stage's capacity ({self.max_samples})")
+            if not self.lib.tt_rs_out_samples(x.shape[0], int(P), int(Q)):
+                raise ValueError(f"clip {i}: ratio {int(P)}/{int(Q)} is outside what the resampler takes (terms up to {E.RS_MAX_TERM}, "
+                                 f"1/{E.RS_MAX_RATIO} .. {E.RS_MAX_RATIO}, reduced unless Q = {E.RS_PITCH_ONE})")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], [(int(P), int(Q)) for P, Q in ratios[g:g + self.max_clips]])
+        return out
+
+    def _group(self, clips, ratios):
+        n, dev = len(clips), self.device
+        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
+        oo = np.concatenate(([0], np.cumsum([self.lib.tt_rs_out_samples(x.shape[0], P, Q) for x, (P, Q) in zip(clips, ratios)]))).astype(np.int32)
+        pq = np.asarray([[P for P, _ in ratios], [Q for _, Q in ratios]], dtype=np.int32).reshape(-1)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, oo, pq])).to(dev)
+        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
+        res = torch.zeros(2 * n, device=dev, dtype=torch.int32)  # (peak as f32 bits | status): one copy back
+        hp, rp = host.data_ptr(), res.data_ptr()
+        E.check(self.lib.tt_rs_resample(self.h, n, audio.data_ptr(), hp, hp + 4 * 2 * (n + 1), hp + 4 * (2 * (n + 1) + n), y.data_ptr(),
+                                        hp + 4 * (n + 1), rp, rp + 4 * n, E.stream_ptr()))
+        res = res.cpu()
+        status = res[n:].tolist()
+        if any(st != E.RS_OK for st in status):
+            raise RuntimeError(f"resample: the device stage refused clips it was handed (status {status})")
+        peaks = res[:n].view(torch.float32).tolist()
+        return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
+
+
 class LoudnessStage(_Handle):
     """Integrated loudness, true peak and the gain to a target under a ceiling (csrc/loudness.hip, include/tortoise_mi355x_loud.h): ragged
     batches, each clip with its own target and ceiling, one tt_loud_measure / tt_loud_normalize call per group of at most max_clips clips and
