@@ -40,6 +40,7 @@ from . import engine as E
 from . import stages
 from . import loudness as loud
 from . import resample as rs
+from . import silence as sil
 from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
@@ -580,12 +581,91 @@ class _Common:
         self.timings = dict(getattr(self, "timings", None) or {}, resample_s=self._resample_s)
         return dict(zip(keys, seq)) if keys is not None else seq
 
-    def _voiced(self, clips, rate, pitch, level, sample_rate):
-        """The chain behind redaction: speaking rate and pitch together, then the level (at 24 kHz), then the output sample rate."""
+    # ------------------------------------------------------------------ pauses and silence: speech regions, edge trimming, pause capping
+    silencer = None
+
+    def load_silence(self, max_samples=0):
+        """The silence stage (stages.SilenceStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.SIL_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the silence stage can take ({E.SIL_MAX_SAMPLES})")
+        if self.silencer is None or self.silencer.max_samples < max_samples:
+            if self.silencer is not None:
+                self.silencer.close()
+            self.silencer = stages.SilenceStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * sil.SAMPLE_RATE), device=self.device)
+        return self.silencer
+
+    @torch.no_grad()
+    def speech_regions_many(self, audios, top_db=sil.DEFAULTS["top_db"], floor_db=sil.DEFAULTS["floor_db"],
+                            min_silence=sil.DEFAULTS["min_silence"], pad=sil.DEFAULTS["pad"]):
+        """Where the speech is: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> per clip (regions, pauses), lists of
+        (start, end) in samples: the speech regions in ascending order and the pauses between them (silence.pauses; the silence before the
+        first and after the last region is not listed).  A 10 ms frame is active when its energy is within top_db of the clip's loudest
+        frame and above floor_db dBFS; pauses shorter than min_silence seconds are bridged and every region is padded by `pad` seconds.
+        All clips go through ONE device call per 16.  A clip without an active frame has no region."""
+        audios = self._level_clips(audios, "speech_regions")
+        p = sil.params(lead=None, trail=None, max_pause=None, top_db=top_db, floor_db=floor_db, min_silence=min_silence, pad=pad)
+        if not audios:
+            return []
+        res = self.load_silence(max(a.shape[-1] for a in audios)).find_many([a.reshape(-1) for a in audios], [p] * len(audios))
+        return [(r["regions"], sil.pauses(r["regions"], a.shape[-1])) for r, a in zip(res, audios)]
+
+    def speech_regions(self, audio, **options):
+        """speech_regions_many of one clip -> (regions, pauses)."""
+        return self.speech_regions_many([audio], **options)[0]
+
+    def _trim_params(self, audios, params, return_map):
+        """audios (validated) through the silence stage with one silence.Params each -> the clips, each in the shape and on the device it
+        came in; ONE device call per 16.  The per-clip status and seconds removed are left in self.silence_info."""
+        t0 = time.perf_counter()
+        out, maps, info = [], [], []
+        if audios:
+            res = self.load_silence(max(a.shape[-1] for a in audios)).trim_many([a.reshape(-1) for a in audios], params)
+            for a, (y, d) in zip(audios, res):  # (the results' copy back has synchronised)
+                out.append(y.to(a.device).reshape(a.shape[:-1] + (-1,)))
+                maps.append(d["segments"])
+                info.append(dict(status=sil.STATUS[d["status"]], removed_s=(a.shape[-1] - y.shape[-1]) / sil.SAMPLE_RATE, regions=d["regions"]))
+        self.silence_info = info
+        self._silence_s = time.perf_counter() - t0
+        return (out, maps) if return_map else out
+
+    @torch.no_grad()
+    def trim_many(self, audios, lead=sil.DEFAULTS["lead"], trail=sil.DEFAULTS["trail"], max_pause=sil.DEFAULTS["max_pause"],
+                  top_db=sil.DEFAULTS["top_db"], floor_db=sil.DEFAULTS["floor_db"], min_silence=sil.DEFAULTS["min_silence"],
+                  pad=sil.DEFAULTS["pad"], return_map=False):
+        """Dead air cut away: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> the clips, each in the shape and on the device it
+        came in.  At most `lead` / `trail` seconds of silence stay before the first / after the last speech region (a cut end is faded
+        over 5 ms), and a pause longer than `max_pause` seconds is shortened to exactly that (its two ends cross-faded over 5 ms); None
+        leaves that part alone.  Detection as in speech_regions_many.  Everything that is not cut, cross-faded or faded is a bit-for-bit
+        copy; a clip without speech is returned as it is, never emptied.  All clips go through ONE device call per 16 (csrc/silence.hip),
+        found and edited without a round trip in between.  The defaults were chosen from the code: nobody has run a trained checkpoint's
+        audio through them.  return_map=True: also, per clip, the segment list [(output start, input start, length)], with which
+        silence.map_sample carries a time in the original clip over to the trimmed one.  Status and seconds removed: self.silence_info."""
+        audios = self._level_clips(audios, "trim")
+        p = sil.params(lead=lead, trail=trail, max_pause=max_pause, top_db=top_db, floor_db=floor_db, min_silence=min_silence, pad=pad)
+        return self._trim_params(audios, [p] * len(audios), return_map)
+
+    def trim(self, audio, **options):
+        """trim_many of one clip -> the trimmed clip."""
+        return self.trim_many([audio], **options)[0]
+
+    def _at_pauses(self, clips, params):
+        """The clips a tts call is about to return ({winner: clip} or a list) with their pauses shaped by `params` (silence.Params): one
+        call for all of them, its time in timings['silence_s'], status and seconds removed in self.silence_info."""
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        seq = self._trim_params(seq, [params] * len(seq), False)
+        self.timings = dict(getattr(self, "timings", None) or {}, silence_s=self._silence_s)
+        return dict(zip(keys, seq)) if keys is not None else seq
+
+    def _voiced(self, clips, rate, pitch, level, sample_rate, pauses=None):
+        """The chain behind redaction: speaking rate and pitch together, then the pauses (silence.Params: durations are then delivered
+        seconds), then the level (at 24 kHz: the loudness gate sees the final content), then the output sample rate."""
         if pitch is not None:
             clips = self._at_pitch(clips, rate, pitch)
         elif rate is not None:
             clips = self._at_rate(clips, rate)
+        if pauses is not None:
+            clips = self._at_pauses(clips, pauses)
         if level is not None:
             clips = self._at_level(clips, level)
         return clips if sample_rate is None else self._at_sample_rate(clips, sample_rate)
@@ -611,7 +691,11 @@ class TextToSpeech(_Common):
     csrc/resample.hip - DESIGN.md 5.27; pitch by resampling moves the formants with the pitch: natural for a few semitones, and nobody has
     rendered a trained checkpoint through it); `sample_rate` (Hz, an integer in 8000 .. 96000; None or 24000: off) - every returned clip
     is converted from 24 kHz last (resample).  The `true_peak` ceiling is enforced at 24 kHz, before that conversion: down-conversion
-    removes content and can move the peak; the sample peaks of the converted clips are left in `resample_info`."""
+    removes content and can move the peak; the sample peaks of the converted clips are left in `resample_info`; `trim_silence` (True: at
+    most 0.05 s of silence before and 0.1 s after the speech; or a dict of trim_many's options; None or False: off) and `max_pause`
+    (seconds; every longer pause is shortened to it; None: off) - after the rate and the pitch and before the level (trim, csrc/silence.hip
+    - DESIGN.md 5.28; the defaults were chosen from the code, nobody has run a trained checkpoint's audio through them; status and seconds
+    removed are left in `silence_info`)."""
 
     redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
@@ -917,8 +1001,8 @@ class TextToSpeech(_Common):
             self._redact_s = 0.0
             wavs = self._redact_clips(wavs, redact)
             self.timings["redact_s"] = self._redact_s
-        # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> level -> output sample rate
-        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate)
+        # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> pauses -> level -> output sample rate
+        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate, o.pauses)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -936,12 +1020,14 @@ class TextToSpeech(_Common):
         speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
         loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
         pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
-        96000) converts every clip last, in ONE call."""
+        96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
+        pitch and before the level, in ONE call (trim_many)."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
+        pauses = sil.options(kwargs)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
-        return self._voiced(out, rate, pitch, level, sample_rate)
+        return self._voiced(out, rate, pitch, level, sample_rate, pauses)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
@@ -1030,6 +1116,7 @@ class TextToSpeech(_Common):
         noise = hf.pop("noise_override", None) or {}
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
         pitch, sample_rate = rs.options(hf, speaking_rate)
+        pauses = sil.options(hf)
         plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
@@ -1040,7 +1127,7 @@ class TextToSpeech(_Common):
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
             solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
-            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate)
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

@@ -35,6 +35,7 @@ from . import engine as E
 from . import stages
 from . import loudness as loud
 from . import resample as rs
+from . import silence as sil
 from . import solver as fastsolver
 from . import stretch as tsm
 from . import weights as W
@@ -193,6 +194,7 @@ class TextToSpeech(_Common):
         self._single("tts")
         speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
         pitch, sample_rate = rs.options(hf_generate_kwargs, speaking_rate)
+        pauses = sil.options(hf_generate_kwargs)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -202,7 +204,7 @@ class TextToSpeech(_Common):
         self.last_codes = codes
         latents = self.ar.latents(cond, text_tokens, codes)          # api_fast.py:510-514 (return_latent=True)
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
-        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate)[0]  # (speaking rate and pitch -> level -> sample rate)
+        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate, pauses)[0]  # (rate and pitch -> pauses -> level -> sample rate)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
@@ -213,11 +215,13 @@ class TextToSpeech(_Common):
         speaking_rate= (0.5 .. 2.0): every clip is time-stretched at the same pitch, all of them in ONE stretch_many call.
         loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
         pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
-        96000) converts every clip last, in ONE call."""
+        96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
+        pitch and before the level, in ONE call (trim_many)."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
+        pauses = sil.options(kwargs)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
-        return self._voiced(out, rate, pitch, level, sample_rate)
+        return self._voiced(out, rate, pitch, level, sample_rate, pauses)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs):
@@ -336,6 +340,7 @@ class TextToSpeech(_Common):
         tsm.refuse_streaming(hf_generate_kwargs, "tts_stream")
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
@@ -384,6 +389,7 @@ class TextToSpeech(_Common):
         tsm.refuse_streaming(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
+        sil.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
@@ -520,6 +526,7 @@ class TextToSpeech(_Common):
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
+        sil.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):

@@ -425,6 +425,22 @@ RS_PITCH_ONE = 65536
 RS_MAX_TERM, RS_MAX_RATIO = 1048576, 8
 RS_MAX_SAMPLES, RS_MAX_CLIPS = 8388608, 64
 RS_OK, RS_EMPTY, RS_REFUSED = 0, 1, 2
+# include/tortoise_mi355x_sil.h: speech regions, edge trimming and pause capping of rendered clips (its own header and version)
+_SIL_PROTOS = {
+    "tt_sil_abi_version": (_i, []),
+    "tt_sil_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_sil_destroy": (None, [vp]),
+    "tt_sil_frames": (_i, [_i]),
+    "tt_sil_max_regions": (_i, [_i]),
+    "tt_sil_find": (_i, [vp, _i] + [vp] * 12),
+    "tt_sil_trim": (_i, [vp, _i] + [vp] * 15),
+}
+SIL_ABI_VERSION = 1
+SIL_SLOT, SIL_HOP, SIL_FRAME, SIL_FADE = 120, 240, 480, 120  # TT_SIL_SLOT, TT_SIL_HOP, TT_SIL_FRAME, TT_SIL_FADE
+SIL_SAMPLE_RATE = 24000
+SIL_MAX_SAMPLES, SIL_MAX_CLIPS = 8388608, 64
+SIL_MAX_FRAMES_PARAM = 6000
+SIL_OK, SIL_UNCHANGED, SIL_SILENT, SIL_EMPTY, SIL_REFUSED = 0, 1, 2, 3, 4
 # include/tortoise_mi355x_solver.h: DDIM / DPM-Solver++(2M) on a tt_diff handle (its own header and version, same library)
 _SOLVER_PROTOS = {
     "tt_solver_abi_version": (_i, []),
@@ -508,7 +524,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -544,6 +560,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
     if lib.tt_rs_abi_version() != RS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
+    if lib.tt_sil_abi_version() != SIL_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_solver.h is version %d in the library, %d in Python" % (lib.tt_solver_abi_version(), SOLVER_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):

@@ -39,7 +39,7 @@ def merge_alignments(alignments, clip_samples):
 
 
 def read_long_form(tts, text, preset="standard", conditioning_latents=None, voice_samples=None, seed=None, texts_are_chunks=False,
-                   return_timings=False, **tts_kwargs):
+                   return_timings=False, pause=None, **tts_kwargs):
     """tts: a TextToSpeech built with candidate_sharding=False (one complete engine per rank), or a fast-path
     tortoise_tts_amd.api_fast.TextToSpeech (the reference's read_fast.py): each rank then renders its chunks with one tts_many call -
     tts()'s defaults plus tts_kwargs, the agreed seed for every chunk - and `preset` does not apply (read_fast.py passes none; the fast
@@ -54,13 +54,19 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     loudness_scope='whole' one gain for the concatenation.
     pitch= goes to the chunks' calls with speaking_rate=.  sample_rate= (Hz, 8000 .. 96000) is applied here, last: every chunk is converted
     from 24 kHz in one call, after the level and after the alignment, whose positions then count samples of the returned audio (the
-    Alignment carries that rate)."""
+    Alignment carries that rate).
+    trim_silence= / max_pause= go to the chunks' calls.  pause= (seconds; None: off) sets the silence between two chunks: every chunk is cut
+    to its speech at both ends (lead = trail = 0; its own trim_silence= / max_pause= still shape the inside) and `pause` seconds of zeros
+    are appended to every part but the last, after the per-chunk level and before the alignment, so the gap between the last speech
+    region of one chunk and the first of the next is exactly round(pause * 24000) samples and the full audio is still the parts joined."""
     from . import loudness as loud
     from . import resample as rs
+    from . import silence as sil
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
     scope, level = loud.scope_option(tts_kwargs), loud.level_options(tts_kwargs)  # (applied here, to what the chunks' calls return)
     sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (here too, after the level)
+    gap = None if pause is None else sil.for_long_form(tts_kwargs, pause)  # (the chunks' calls get lead = trail = 0)
     if getattr(tts, "world", 1) != 1:
         raise ValueError("read_long_form spreads chunks over the ranks: build TextToSpeech(candidate_sharding=False)")
     if texts_are_chunks:
@@ -102,6 +108,8 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     if parts is None:
         return None, None
     clips = [parts[j] for j in range(len(texts))]
+    if gap:  # the chosen pause after every chunk but the last
+        clips = [torch.cat([c, c.new_zeros(c.shape[:-1] + (gap,))], dim=-1) for c in clips[:-1]] + clips[-1:]
     full = torch.cat([c.squeeze(0) for c in clips], dim=-1)  # read.py:74, 87
     if level is not None and scope == "whole":  # one gain (and one limiter pass) for the concatenation; the parts are its pieces
         full = tts._at_level([full], level)[0]

@@ -632,6 +632,92 @@ class ResampleStage(_Handle):
         return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
 
 
+class SilenceStage(_Handle):
+    """Speech regions, edge trimming and pause capping (csrc/silence.hip, include/tortoise_mi355x_sil.h): ragged batches, each clip with its
+    own parameters (silence.Params), one tt_sil_find / tt_sil_trim call per max_clips clips, every clip's result bit-identical to running it
+    alone."""
+
+    api = "tt_sil"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        self._create(self.max_samples, self.max_clips)
+
+    def _check(self, clips, params):
+        if len(clips) != len(params):
+            raise ValueError(f"{len(clips)} clips with {len(params)} parameter sets")
+        for i, x in enumerate(clips):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the silence stage's capacity ({self.max_samples})")
+
+    def find_many(self, clips, params, energies=False):
+        """clips f32 [n_i] (device or host) and a silence.Params each -> one dict per clip: status (E.SIL_OK / SIL_SILENT), regions
+        [(a, b)] in samples, peak (E, the largest frame energy) and, for energies=True, energies (f64 [F] on the host)."""
+        self._check(clips, params)
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], False, energies)
+        return out
+
+    def trim_many(self, clips, params):
+        """clips f32 [n_i] and a silence.Params each -> one (y f32 [n_out_i] on the stage's device, dict) per clip; the dict holds status
+        (E.SIL_OK / SIL_UNCHANGED / SIL_SILENT), regions [(a, b)] of the input, segments [(o, i, l)] (silence.map_sample) and peak."""
+        self._check(clips, params)
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], True, False)
+        return out
+
+    def _group(self, clips, params, trim, energies):
+        n, dev = len(clips), self.device
+        lens = [x.shape[0] for x in clips]
+        io = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
+        ro = np.concatenate(([0], np.cumsum([self.lib.tt_sil_max_regions(m) for m in lens]))).astype(np.int32)  # (regions and segments alike)
+        fo = np.concatenate(([0], np.cumsum([self.lib.tt_sil_frames(m) for m in lens]))).astype(np.int32)
+        par = np.asarray([[p.min_sil, p.pad, p.lead, p.trail, p.max_pause][:5 if trim else 2] for p in params], dtype=np.int32).reshape(-1)
+        thr = torch.tensor([[p.rel, p.floor_e] for p in params], dtype=torch.float64).to(dev)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, ro, fo, par])).to(dev)
+        R = int(ro[-1])
+        res = torch.zeros(4 * n + 5 * R + 1, device=dev, dtype=torch.int32)  # n_out | n_regions | n_segments | status | regions | segments
+        peak = torch.zeros(n, device=dev, dtype=torch.float64)
+        hp, rp = host.data_ptr(), res.data_ptr()
+        p_io, p_ro, p_fo, p_par = hp, hp + 4 * (n + 1), hp + 8 * (n + 1), hp + 12 * (n + 1)
+        p_nout, p_nreg, p_nseg, p_st, p_reg, p_seg = rp, rp + 4 * n, rp + 8 * n, rp + 12 * n, rp + 16 * n, rp + 16 * n + 8 * R
+        en = y = None
+        if trim:
+            y = torch.zeros(int(io[-1]) + 1, device=dev, dtype=torch.float32)
+            E.check(self.lib.tt_sil_trim(self.h, n, audio.data_ptr(), p_io, thr.data_ptr(), p_par, p_ro, p_ro, y.data_ptr(), p_nout, p_nreg,
+                                         p_reg, p_nseg, p_seg, peak.data_ptr(), p_st, E.stream_ptr()))
+        else:
+            en = torch.zeros(int(fo[-1]) + 1, device=dev, dtype=torch.float64) if energies else None
+            E.check(self.lib.tt_sil_find(self.h, n, audio.data_ptr(), p_io, thr.data_ptr(), p_par, p_ro, p_fo if energies else None, p_nreg,
+                                         p_reg, peak.data_ptr(), en.data_ptr() if energies else None, p_st, E.stream_ptr()))
+        res = res.cpu().numpy()
+        status = res[3 * n:4 * n].tolist()
+        if any(st in (E.SIL_EMPTY, E.SIL_REFUSED) for st in status):
+            raise RuntimeError(f"silence: the device stage refused clips it was handed (status {status})")
+        peaks = peak.cpu().tolist()
+        regs = res[4 * n:4 * n + 2 * R].reshape(-1, 2)
+        segs = res[4 * n + 2 * R:4 * n + 5 * R].reshape(-1, 3)
+        en = en.cpu() if en is not None else None
+        out = []
+        for i in range(n):
+            d = dict(status=status[i], peak=peaks[i], regions=[(int(a), int(b)) for a, b in regs[ro[i]:ro[i] + res[n + i]]])
+            if trim:
+                d["segments"] = [(int(o), int(s), int(m)) for o, s, m in segs[ro[i]:ro[i] + res[2 * n + i]]]
+                out.append((y[io[i]:io[i] + int(res[i])], d))
+            else:
+                if en is not None:
+                    d["energies"] = en[fo[i]:fo[i + 1]].clone()
+                out.append(d)
+        return out
+
+
 class LoudnessStage(_Handle):
     """Integrated loudness, true peak and the gain to a target under a ceiling (csrc/loudness.hip, include/tortoise_mi355x_loud.h): ragged
     batches, each clip with its own target and ceiling, one tt_loud_measure / tt_loud_normalize call per group of at most max_clips clips and
