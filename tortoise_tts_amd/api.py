@@ -213,6 +213,47 @@ ORIG_ALIGNER_SECONDS = 30  # the longest clip the aligner of a path without its 
 LOUDNESS_STAGE_SAMPLES = 16 * 30 * E.LOUD_SAMPLE_RATE  # samples of one call the loudness stage is first built for: sixteen clips of 30 s
 
 
+class StreamResampler:
+    """One stream of a stages.StreamResampleStage (_Common.open_resampler): f32 chunks in, f32 tensors on the device out (possibly
+    empty).  An output appears once the H + 1 input samples after its position are in (latency_seconds); finish() ends the stream as
+    the clip's end and frees the slot.  A context manager: leaving it closes the stream."""
+
+    def __init__(self, stage, P, Q, from_rate=rs.SAMPLE_RATE):
+        self.stage, self.P, self.Q = stage, P, Q
+        self.slot = stage.open(P, Q)
+        self.n_in = self.n_out = 0
+        self.latency_seconds = rs.stream_latency(P, Q) / float(from_rate)
+
+    def _push(self, chunk, flush):
+        if self.slot is None:
+            raise ValueError("this resampling stream is closed")
+        chunk = torch.as_tensor(chunk, dtype=torch.float32).reshape(-1)
+        y = self.stage.push_many([(self.slot, chunk, flush)])[0]
+        self.n_in += chunk.shape[0]
+        self.n_out += y.shape[0]
+        return y
+
+    def push(self, chunk):
+        return self._push(chunk, False)
+
+    def finish(self, chunk=None):
+        """The outputs still due (after an optional last chunk); the stream is over and its slot free."""
+        y = self._push(torch.zeros(0) if chunk is None else chunk, True)
+        self.close()
+        return y
+
+    def close(self):
+        if self.slot is not None:
+            self.stage.close(self.slot)
+            self.slot = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class _Common:
     """What this module's TextToSpeech and api_fast.TextToSpeech share: the lazy tokenizer, the seed, the text front-end."""
     world = 1  # processes that share one utterance's work (TextToSpeech with candidate sharding sets its own)
@@ -529,6 +570,20 @@ class _Common:
     def resample(self, audio, to_rate, from_rate=rs.SAMPLE_RATE):
         """resample_many of one clip -> the clip at to_rate."""
         return self.resample_many([audio], to_rate, from_rate)[0]
+
+    stream_resampler = None
+
+    def load_stream_resample(self, max_streams=16):
+        """The streaming resampler of open_resampler (stages.StreamResampleStage), built on first use."""
+        if self.stream_resampler is None:
+            self.stream_resampler = stages.StreamResampleStage(max_streams, device=self.device)
+        return self.stream_resampler
+
+    def open_resampler(self, to_rate, from_rate=rs.SAMPLE_RATE):
+        """A StreamResampler for audio that arrives in chunks: push(chunk) returns the samples at to_rate that became ready, finish() the
+        rest; their concatenation is resample(whole clip, to_rate, from_rate) to the bit, whatever the chunking.  Up to 16 may be open."""
+        P, Q = rs.ratio(from_rate, to_rate)
+        return StreamResampler(self.load_stream_resample(), P, Q, int(from_rate))
 
     @torch.no_grad()
     def shift_pitch_many(self, audios, semitones, return_info=False):

@@ -60,6 +60,7 @@ class _Session:
     threshold: int = 0
     wav_gen_prev: Any = None
     wav_overlap: Any = None
+    rs_slot: Any = None   # stream_sample_rate=: the session's slot on the streaming resampler
 
 
 class TextToSpeech(_Common):
@@ -342,6 +343,7 @@ class TextToSpeech(_Common):
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        stream_rate = rs.stream_options(hf_generate_kwargs)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -351,28 +353,43 @@ class TextToSpeech(_Common):
         wav_gen_prev, wav_overlap = None, None
         emitted = 0          # (token, latent) pairs already decoded into an emitted chunk
         threshold = first    # pairs the reference buffers before the next decode (api_fast.py:412)
-        for codes, done in self.ar.generate_stream(1, max_mel_tokens, chunk, first_chunk=first, temperature=temperature, top_p=top_p,
-                                                   repetition_penalty=float(repetition_penalty), top_k=top_k, seed=seed,
-                                                   typical_mass=typical_mass):
-            if done and codes.shape[1] > 0 and int(codes[0, -1]) == self.stop_mel_token:
-                codes = codes[:, :-1]  # the reference's generator stops BEFORE yielding the stop token's pair
-            if codes.shape[1] == 0:
-                break
-            self.last_codes = codes
-            latents = self._stream_latents(cond, text_tokens, codes)
-            wav_gen = self.hifi_decoder.inference(latents, cond).reshape(-1)
-            wav_chunk, wav_gen_prev, wav_overlap = self.handle_chunks(wav_gen, wav_gen_prev, wav_overlap, overlap_wav_len)
-            yield wav_chunk
-            if done:
+        # stream_sample_rate=: every piece goes through one slot of the streaming resampler, the stream's last piece with flush
+        rs_slot = None if stream_rate is None else self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
+        try:
+            for codes, done in self.ar.generate_stream(1, max_mel_tokens, chunk, first_chunk=first, temperature=temperature, top_p=top_p,
+                                                       repetition_penalty=float(repetition_penalty), top_k=top_k, seed=seed,
+                                                       typical_mass=typical_mass):
+                if done and codes.shape[1] > 0 and int(codes[0, -1]) == self.stop_mel_token:
+                    codes = codes[:, :-1]  # the reference's generator stops BEFORE yielding the stop token's pair
+                if codes.shape[1] == 0:
+                    break
+                self.last_codes = codes
+                latents = self._stream_latents(cond, text_tokens, codes)
+                wav_gen = self.hifi_decoder.inference(latents, cond).reshape(-1)
+                wav_chunk, wav_gen_prev, wav_overlap = self.handle_chunks(wav_gen, wav_gen_prev, wav_overlap, overlap_wav_len)
                 # The reference decodes once per filled buffer AND once more when its generator raises StopIteration
                 # (api_fast.py:405-420).  When the sequence ends exactly on a buffer boundary that last pass sees the same latents
                 # again and handle_chunks hands out the withheld overlap tail: mirror it.
-                if stream_chunk_size > 0 and codes.shape[1] - emitted == threshold:
-                    wav_chunk, wav_gen_prev, wav_overlap = self.handle_chunks(wav_gen, wav_gen_prev, wav_overlap, overlap_wav_len)
-                    yield wav_chunk
-                break
-            emitted = codes.shape[1]
-            threshold = chunk
+                extra = done and stream_chunk_size > 0 and codes.shape[1] - emitted == threshold
+                yield wav_chunk if rs_slot is None else self._stream_rs().push_many([(rs_slot, wav_chunk, done and not extra)])[0]
+                if done:
+                    if extra:
+                        wav_chunk, wav_gen_prev, wav_overlap = self.handle_chunks(wav_gen, wav_gen_prev, wav_overlap, overlap_wav_len)
+                        yield wav_chunk if rs_slot is None else self._stream_rs().push_many([(rs_slot, wav_chunk, True)])[0]
+                    break
+                emitted = codes.shape[1]
+                threshold = chunk
+        finally:
+            if rs_slot is not None:
+                self._stream_rs().close(rs_slot)
+
+    _stream_stage = None
+
+    def _stream_rs(self):
+        """The streaming resampler of stream_sample_rate= (stages.StreamResampleStage, one slot per session), built on first use."""
+        if self._stream_stage is None:
+            self._stream_stage = stages.StreamResampleStage(self.max_streams, device=self.device)
+        return self._stream_stage
 
     # ------------------------------------------------------------------ several streams in one decode batch (max_streams > 1)
     def _single(self, name):
@@ -385,12 +402,18 @@ class TextToSpeech(_Common):
         """Admit one streaming session (max_streams > 1) and return its id.  Takes tts_stream's arguments; the session's pieces come out
         of stream_pieces() on exactly tts_stream's schedule.  May be called at any time, also between pieces of other sessions.  Raises
         when every slot is busy or when the sampling settings differ from those of the running sessions (they share one sampler) -
-        with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken."""
+        with per_session_sampling any valid settings are taken, and invalid ones raise ValueError before a slot is taken.
+        stream_sample_rate=R (also on tts_stream): the session's pieces come at R Hz instead of 24 kHz - the same number of pieces with
+        the same done flags, each holding the samples that became ready (possibly none), through one slot of the streaming resampler
+        (stages.StreamResampleStage; all pieces due in a round of stream_pieces in ONE push).  Their concatenation is bit for bit
+        resample() of the 24 kHz stream; the audio lags by resample.stream_latency input samples (1.5 ms; 4.5 ms to 8 kHz) until the
+        last piece flushes it.  None or 24000: nothing is built, today's bits."""
         tsm.refuse_streaming(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
+        stream_rate = rs.stream_options(kwargs)  # (validated before a slot is taken)
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -424,6 +447,8 @@ class TextToSpeech(_Common):
         first = max(chunk, 60) if size > 0 else max_mel_tokens  # first_buffer = 60 (api_fast.py:401, 412)
         sess = _Session(self._next_sid, slot, cond, text_tokens, max_mel_tokens, chunk, size, a["overlap_wav_len"], min(first, max_mel_tokens),
                         threshold=first)
+        if stream_rate is not None:
+            sess.rs_slot = self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
         self._next_sid += 1
         self._sessions[slot] = sess
         self._session_settings = settings
@@ -436,8 +461,30 @@ class TextToSpeech(_Common):
             if sess.sid == sid:
                 del self._sessions[slot]
                 self.ar.close(slot)
+                self._close_rs(sess)
                 return
         raise KeyError(f"close_stream: no open session {sid}")
+
+    def _close_rs(self, sess):
+        if sess.rs_slot is not None:
+            self._stream_rs().close(sess.rs_slot)
+            sess.rs_slot = None
+
+    def _resample_due(self, due, vocoded):
+        """stream_sample_rate=: the pieces of this round's sessions that stream at another rate, all resampled in ONE push_many (a
+        session's extra last piece in a second one): slot -> [(chunk at the session's rate, done)].  The last piece of a session is
+        pushed with flush.  {} when no session of the round has a rate."""
+        pieces = {slot: self._session_piece(sess, n, fin, vocoded.get(slot)) for slot, sess, n, fin in due if sess.rs_slot is not None}
+        if not pieces:
+            return {}
+        rs_slots = {slot: sess.rs_slot for slot, sess, _, _ in due}
+        out = {slot: [] for slot in pieces}
+        for k in range(max(len(p) for p in pieces.values())):
+            todo = [slot for slot, p in pieces.items() if len(p) > k]
+            res = self._stream_rs().push_many([(rs_slots[slot], pieces[slot][k][0], pieces[slot][k][1]) for slot in todo])
+            for slot, y in zip(todo, res):
+                out[slot].append((y, pieces[slot][k][1]))
+        return out
 
     def _session_latents(self, sess, n, finished):
         """The first half of tts_stream's loop body for a session whose token count reached its piece boundary (or its end):
@@ -505,16 +552,19 @@ class TextToSpeech(_Common):
             # every session whose piece is due is vocoded in one batched call before the first yield of the round
             vocoded = self._vocode_due([(slot, sess, n_total[slot], finished[slot]) for slot, sess in batch
                                         if finished[slot] or n_total[slot] >= sess.target])
+            due = [(slot, sess, n_total[slot], finished[slot]) for slot, sess in batch if finished[slot] or n_total[slot] >= sess.target]
+            resampled = self._resample_due(due, vocoded) if any(sess.rs_slot is not None for _, sess, _, _ in due) else {}
             for slot, sess in batch:
                 if self._sessions.get(slot) is not sess:  # closed while an earlier piece of this round was out
                     continue
                 sess.n = n_total[slot]
-                if not (finished[slot] or n_total[slot] >= sess.target):
+                if slot not in resampled and not (finished[slot] or n_total[slot] >= sess.target):
                     continue
-                pieces = self._session_piece(sess, n_total[slot], finished[slot], vocoded.get(slot))
+                pieces = resampled[slot] if slot in resampled else self._session_piece(sess, n_total[slot], finished[slot], vocoded.get(slot))
                 if pieces[-1][1]:  # the session is over: its row is free for the next admission
                     del self._sessions[slot]
                     self.ar.close(slot)
+                    self._close_rs(sess)
                 for wav_chunk, done in pieces:
                     yield sess.sid, wav_chunk, done
 
@@ -522,7 +572,8 @@ class TextToSpeech(_Common):
         """Stream several texts at once (max_streams > 1): a generator of (index into texts, wav_chunk, done).  kwargs are tts_stream's,
         shared by all texts; use_deterministic_seed may be a list with one seed per text, and so may temperature, top_p,
         repetition_penalty, top_k, typical_sampling and typical_mass on an instance with per_session_sampling.  Texts beyond the free
-        slots are admitted as earlier sessions end."""
+        slots are admitted as earlier sessions end.  stream_sample_rate= (Hz, 8000 .. 96000; one value or a list with one per text,
+        None allowed): that text's pieces at another rate than 24 kHz, see open_stream."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
@@ -532,6 +583,12 @@ class TextToSpeech(_Common):
         if not isinstance(seeds, (list, tuple)):
             seeds = [seeds] * len(texts)
         per_text = {}
+        if isinstance(kwargs.get("stream_sample_rate"), (list, tuple)):  # one rate per text, None allowed
+            if len(kwargs["stream_sample_rate"]) != len(texts):
+                raise ValueError(f"tts_stream_many: {len(kwargs['stream_sample_rate'])} stream_sample_rate values for {len(texts)} texts")
+            per_text["stream_sample_rate"] = kwargs.pop("stream_sample_rate")
+        for r in per_text.get("stream_sample_rate", [kwargs.get("stream_sample_rate")]):
+            rs.stream_options({"stream_sample_rate": r})  # (every rate is validated before the first session opens)
         for name in ("temperature", "top_p", "repetition_penalty", "top_k", "typical_sampling", "typical_mass"):
             if isinstance(kwargs.get(name), (list, tuple)):
                 if not self.per_session_sampling:

@@ -13,7 +13,8 @@
 //     thread             owns kRsPer consecutive outputs: ONE in the product (1024 threads, four waves per SIMD, whose other waves cover a
 //                        wave's wait for its gather), four in the form built first (256 threads, one wave per SIMD: 2 .. 2.7 times as slow,
 //                        profiles/r20_resample.txt).  (i, r) of the first come from one 64-bit division, further ones by adding
-//                        (P / Q, P % Q) with carry.  The header's per-tap division is not executed: with f = floor(r cq / Q) and
+//                        (P / Q, P % Q) with carry.  The output itself is rs_output of resample_steps.h, which the streaming kernels
+//                        (resample_stream.hip) share.  The header's per-tap division is not executed: with f = floor(r cq / Q) and
 //                        g = ceil(r cq / Q) (one 64-bit division per output), u = |d| cq + f for d = j - i <= 0 and u = d cq - g for
 //                        d >= 1, exactly, so u walks down and up again by cq.
 //     gather             a tap reads tab[k] and tab[k + 1] (neighbours: one ds_read2_b32) and one span value.  Lanes hold neighbouring outputs,
@@ -25,44 +26,19 @@
 #include <math.h>
 #include <vector>
 #include "runtime.h"
-#include "../../include/tortoise_mi355x_rs.h"
+#include "resample_steps.h"
 
 namespace tt {
 
-constexpr int kRsTab = TT_RS_ZEROS * TT_RS_PER_ZERO;  // Z L = 16384: taps with k >= kRsTab are zero
 #ifndef TT_RS_THREADS
 #define TT_RS_THREADS 1024  // threads of a workgroup and consecutive outputs of a thread: 1024 x 1 (16 waves on the CU hide the gather's LDS latency)
 #define TT_RS_PER 1         // against 256 x 4 (one wave per SIMD), measured in profiles/r20_resample.txt; -D both for an A/B build (build.py variants)
 #endif
 constexpr int kRsThreads = TT_RS_THREADS, kRsPer = TT_RS_PER, kRsTile = kRsThreads * kRsPer;
 static_assert(kRsTile == 1024 && kRsThreads % 64 == 0 && kRsThreads >= TT_RS_MAX_CLIPS, "a tile is 1024 outputs");
-constexpr long long kRsOne = (long long)kRsTab << 16;                                               // Z L 65536
-constexpr long long kRsCqNum = (long long)TT_RS_RHO_NUM * TT_RS_PER_ZERO * 65536;                   // 9 L 65536
-constexpr int kRsCqMin = (int)(kRsCqNum / ((long long)TT_RS_RHO_DEN * TT_RS_MAX_RATIO));            // cq at P / Q = 8
-constexpr int kRsHMax = (int)((kRsOne + kRsCqMin - 1) / kRsCqMin);                                  // 285
 constexpr int kRsSpan = ((kRsTile - 1) * TT_RS_MAX_RATIO + 1 + 2 * kRsHMax + 1 + 15) / 16 * 16;     // samples of LDS for a tile's inputs
 constexpr size_t kRsLds = (size_t)(TT_RS_TABLE + 3 + kRsSpan) * sizeof(float);                      // (the table padded to 16388 floats)
-static_assert(TT_RS_TABLE == kRsTab + 1 && kRsHMax == 285 && kRsLds <= 160 * 1024, "rs_resample_kernel's LDS plan");
-static_assert(kRsOne + 2 * (kRsCqNum / TT_RS_RHO_DEN) < (1ll << 32), "u <= (H + 1) cq < Z L 65536 + 2 cq fits 32 bits");
-
-__host__ __device__ static inline int rs_gcd(int a, int b) {
-  while (b) {
-    const int t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-__host__ __device__ static inline bool rs_ratio_ok(int P, int Q) {
-  if (P < 1 || Q < 1 || P > TT_RS_MAX_TERM || Q > TT_RS_MAX_TERM) return false;
-  if ((long long)P > (long long)TT_RS_MAX_RATIO * Q || (long long)Q > (long long)TT_RS_MAX_RATIO * P) return false;
-  return Q == TT_RS_PITCH_ONE || rs_gcd(P, Q) == 1;
-}
-__host__ __device__ static inline int rs_out_samples(int n, int P, int Q) { return (int)(((long long)n * Q + P - 1) / P); }
-__host__ __device__ static inline unsigned rs_cq(int P, int Q) {
-  return P > Q ? (unsigned)(kRsCqNum * Q / ((long long)TT_RS_RHO_DEN * P)) : (unsigned)(kRsCqNum / TT_RS_RHO_DEN);
-}
-__host__ __device__ static inline int rs_half_width(unsigned cq) { return (int)((kRsOne + cq - 1) / cq); }
+static_assert(kRsLds <= 160 * 1024, "rs_resample_kernel's LDS plan");
 
 // the status of clip c, and for an OK clip its length and output length
 __device__ static inline int rs_clip(const int* __restrict__ in_off, const int* __restrict__ Ps, const int* __restrict__ Qs,
@@ -125,7 +101,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_resample_kernel(int n_clips, co
     float* y = out + out_off[c];
     const unsigned cq = rs_cq(P, Q);
     const int H = rs_half_width(cq);
-    const float c32 = (float)(0.9 * (P > Q ? (double)Q / (double)P : 1.0));
+    const float c32 = rs_c32(P, Q);
     const int m0 = (g - first) * kRsTile, m1 = min(m0 + kRsTile, n_out);  // this tile's outputs
     const int j0 = (int)((long long)m0 * P / Q) - H;                      // the first input it touches
     const int span = (int)((long long)(m1 - 1) * P / Q) + H + 1 - j0 + 1;
@@ -143,22 +119,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_resample_kernel(int n_clips, co
       const int di = P / Q, dr = P % Q;
 #pragma unroll 1
       for (int e = 0; e < kRsPer && m < m1; ++e, ++m) {
-        const unsigned long long rc = (unsigned long long)r * cq;
-        const unsigned f = (unsigned)(rc / (unsigned)Q), g_up = f + (rc % (unsigned)Q != 0);
-        const float* xs = span_s + (i - H - j0);  // x[i - H ..]
-        float acc = 0.f;
-        auto tap = [&](unsigned u, float xv) {
-          const unsigned k = u >> 16;
-          const unsigned kc = k < (unsigned)kRsTab ? k : (unsigned)kRsTab - 1;
-          const float a = (float)(u & 65535u) * (1.f / 65536.f);
-          const float t0 = tab_s[kc], t1 = tab_s[kc + 1];
-          const float h = k < (unsigned)kRsTab ? c32 * fmaf(a, t1 - t0, t0) : 0.f;
-          acc = fmaf(h, xv, acc);
-        };
-        unsigned u = (unsigned)H * cq + f;  // d = -H .. 0: u = |d| cq + f
-        for (int d = 0; d <= H; ++d, u -= cq) tap(u, xs[d]);
-        u = cq - g_up;                      // d = 1 .. H + 1: u = d cq - g
-        for (int d = 1; d <= H + 1; ++d, u += cq) tap(u, xs[H + d]);
+        const float acc = rs_output(tab_s, span_s + (i - H - j0), H, cq, Q, r, c32);  // x[i - H ..]: the steps of resample_steps.h
         y[m] = acc;
         pk = fmaxf(pk, fabsf(acc));
         i += di;
@@ -180,19 +141,6 @@ __global__ __launch_bounds__(kRsThreads) void rs_resample_kernel(int n_clips, co
       }
     }
   }
-}
-
-// I0 by its power series, sum_k ((x / 2)^k / k!)^2: the same double operations in the same order as tests/resample_reference.py
-static double rs_i0(double x) {
-  const double y = x / 2;
-  double term = 1, sum = 1;
-  for (int k = 1; k < 500; ++k) {
-    const double f = y / k;
-    term *= f * f;
-    sum += term;
-    if (term < 1e-17 * sum) break;
-  }
-  return sum;
 }
 
 }  // namespace tt
@@ -220,12 +168,7 @@ int tt_rs_create(int max_samples, int max_clips, tt_rs** out) {
   if (!rc) rc = e->arena.alloc_t(&e->table, TT_RS_TABLE, false);
   if (!rc) {
     std::vector<float> tab(TT_RS_TABLE);
-    const double i0b = rs_i0((double)TT_RS_BETA);
-    for (int t = 0; t <= kRsTab; ++t) {
-      const double x = (double)t / TT_RS_PER_ZERO, q = (double)t / kRsTab;
-      const double s = t ? sin(M_PI * x) / (M_PI * x) : 1.0;
-      tab[t] = (float)(s * rs_i0(TT_RS_BETA * sqrt(1.0 - q * q)) / i0b);
-    }
+    rs_fill_table(tab.data());
     int dev = 0, cus = 0;
     if (hipMemcpy(e->table, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||

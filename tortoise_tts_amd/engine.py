@@ -425,6 +425,21 @@ RS_PITCH_ONE = 65536
 RS_MAX_TERM, RS_MAX_RATIO = 1048576, 8
 RS_MAX_SAMPLES, RS_MAX_CLIPS = 8388608, 64
 RS_OK, RS_EMPTY, RS_REFUSED = 0, 1, 2
+# include/tortoise_mi355x_rss.h: the resampler fed in chunks, for streams at another sample rate (its own header and version)
+_ip = C.POINTER(_i)
+_RSS_PROTOS = {
+    "tt_rss_abi_version": (_i, []),
+    "tt_rss_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_rss_destroy": (None, [vp]),
+    "tt_rss_open": (_i, [vp, _i, _i, _i, vp]),
+    "tt_rss_close": (_i, [vp, _i]),
+    "tt_rss_state": (_i, [vp, _i, _ip, _ip, _ip, _ip]),
+    "tt_rss_ready": (_i, [_i, _i, _i, _i, _i]),
+    "tt_rss_push": (_i, [vp, _i, _ip, _ip, _ip, vp, vp, vp]),
+}
+RSS_ABI_VERSION = 1
+RSS_HIST, RSS_MAX_STREAMS, RSS_BANK_MAX, RSS_AUTO_MAX_Q = 576, 64, 16384, 16  # TT_RSS_HIST, TT_RSS_MAX_STREAMS, TT_RSS_BANK_MAX, TT_RSS_AUTO_MAX_Q
+RSS_AUTO, RSS_TABLE, RSS_BANK = 0, 1, 2
 # include/tortoise_mi355x_sil.h: speech regions, edge trimming and pause capping of rendered clips (its own header and version)
 _SIL_PROTOS = {
     "tt_sil_abi_version": (_i, []),
@@ -524,7 +539,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -560,6 +575,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
     if lib.tt_rs_abi_version() != RS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
+    if lib.tt_rss_abi_version() != RSS_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_rss.h is version %d in the library, %d in Python" % (lib.tt_rss_abi_version(), RSS_ABI_VERSION))
     if lib.tt_sil_abi_version() != SIL_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:

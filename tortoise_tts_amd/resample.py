@@ -90,6 +90,47 @@ def options(kwargs, speaking_rate=None):
     return s, sr
 
 
+def half_width(P, Q):
+    """H of the header: ceil(Z L 65536 / cq), cq = floor(9 L 65536 Qc / (10 Pc)) with (Pc, Qc) = (P, Q) for P > Q, else (1, 1)."""
+    num = E.RS_RHO_NUM * E.RS_PER_ZERO * 65536
+    cq = num * int(Q) // (E.RS_RHO_DEN * int(P)) if P > Q else num // E.RS_RHO_DEN
+    return -((-(E.RS_ZEROS * E.RS_PER_ZERO * 65536)) // cq)
+
+
+def stream_latency(P, Q):
+    """Input samples a streamed output waits for beyond its own position: H + 1 (include/tortoise_mi355x_rss.h)."""
+    return half_width(P, Q) + 1
+
+
+def _ready_total(n, P, Q, flush):
+    have = n if flush else n - stream_latency(P, Q)
+    return -((-have * int(Q)) // int(P)) if have > 0 else 0
+
+
+def stream_ready(n_before, n_chunk, P, Q, flush):
+    """The Python mirror of tt_rss_ready: the outputs a push of n_chunk samples emits on a stream that holds n_before, given it has
+    emitted ready(n_before) = ceil((n_before - H - 1) Q / P) (0 until n_before > H + 1); a flush brings the total to ceil(n Q / P).
+    ValueError for what the library answers with -1."""
+    n_before, n_chunk = int(n_before), int(n_chunk)
+    P, Q = check_ratio(P, Q)
+    if n_before < 0 or n_chunk < 0 or n_before + n_chunk > E.RS_MAX_SAMPLES:
+        raise ValueError(f"a stream of {n_before} + {n_chunk} samples: non-negative counts, at most {E.RS_MAX_SAMPLES} in all")
+    return _ready_total(n_before + n_chunk, P, Q, bool(flush)) - _ready_total(n_before, P, Q, False)
+
+
+def stream_options(kwargs):
+    """Takes `stream_sample_rate` out of a streaming call's **kwargs -> the rate in Hz, or None (absent, None or 24000: nothing is built,
+    nothing changes).  ValueError as for sample_rate=."""
+    sr = kwargs.pop("stream_sample_rate", None)
+    if sr is None:
+        return None
+    try:
+        sr = sample_rate(sr)
+    except ValueError as err:
+        raise ValueError("stream_" + str(err)) from None
+    return None if sr == SAMPLE_RATE else sr
+
+
 def refuse_streaming(kwargs, who):
     for k in ("pitch", "sample_rate"):
         if k in kwargs:

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from . import engine as E
 from . import pack
+from . import resample as rs
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig
 from .schedule import Schedule
 
@@ -630,6 +631,72 @@ class ResampleStage(_Handle):
             raise RuntimeError(f"resample: the device stage refused clips it was handed (status {status})")
         peaks = res[:n].view(torch.float32).tolist()
         return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
+
+
+class StreamResampleStage(_Handle):
+    """The resampler fed in chunks (csrc/resample_stream.hip, include/tortoise_mi355x_rss.h): up to max_streams streams, each with its own
+    (P, Q); whatever the chunking, what a stream emits is bit for bit ResampleStage's result for the whole clip.  form: "auto" (a phase
+    bank for the few-phase ratios, the table otherwise), "table" or "bank"."""
+
+    api = "tt_rss"
+    FORMS = {"auto": E.RSS_AUTO, "table": E.RSS_TABLE, "bank": E.RSS_BANK}
+
+    def __init__(self, max_streams=16, form="auto", device="cuda"):
+        if form not in self.FORMS:
+            raise ValueError(f"form={form!r}: one of {sorted(self.FORMS)}")
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_streams, self.form = int(max_streams), form
+        self.slots = {}  # open slot -> [P, Q, samples pushed, finished]
+        self._create(self.max_streams, self.FORMS[form])
+
+    def open(self, P, Q):
+        """A free slot opened at ratio (P, Q) (resample.ratio) -> its number.  ValueError for a ratio the device refuses (before a slot is
+        taken), RuntimeError when every slot is taken."""
+        P, Q = rs.check_ratio(P, Q)
+        free = [s for s in range(self.max_streams) if s not in self.slots]
+        if not free:
+            raise RuntimeError(f"all {self.max_streams} resampling streams are open")
+        E.check(self.lib.tt_rss_open(self.h, free[0], P, Q, E.stream_ptr()))
+        self.slots[free[0]] = [P, Q, 0, False]
+        return free[0]
+
+    def close(self, slot=None):
+        """close(slot): the slot is free again (whatever it still held is dropped).  close(): the stage."""
+        if slot is None:
+            self.slots = {}
+            return super().close()
+        if self.slots.pop(slot, None) is not None and self.h:
+            E.check(self.lib.tt_rss_close(self.h, int(slot)))
+
+    def push_many(self, items):
+        """items = [(slot, chunk f32 [n] (device or host, n >= 0), flush)], distinct open slots -> what each emits (f32 on the stage's
+        device, possibly empty): ONE tt_rss_push, no synchronisation.  A flushed slot is finished: close() it to free it."""
+        n = len(items)
+        if not 1 <= n <= self.max_streams or len({s for s, _, _ in items}) != n:
+            raise ValueError(f"push_many: {n} chunks for {len({s for s, _, _ in items})} slots (1 .. {self.max_streams} distinct slots)")
+        counts = []
+        for slot, x, flush in items:
+            st = self.slots.get(slot)
+            if st is None or st[3]:
+                raise ValueError(f"push_many: slot {slot} is not open" if st is None else f"push_many: slot {slot} is finished")
+            if x.dim() != 1:
+                raise ValueError(f"push_many: slot {slot}: a chunk of shape {tuple(x.shape)}, expected [samples]")
+            counts.append(rs.stream_ready(st[2], x.shape[0], st[0], st[1], flush))
+        dev = self.device
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for _, x, _ in items] + [torch.zeros(1, device=dev)])
+        y = torch.empty(sum(counts) + 1, device=dev, dtype=torch.float32)
+        arr = C.c_int * n
+        E.check(self.lib.tt_rss_push(self.h, n, arr(*[int(s) for s, _, _ in items]), arr(*[int(x.shape[0]) for _, x, _ in items]),
+                                     arr(*[int(bool(f)) for _, _, f in items]), audio.data_ptr(), y.data_ptr(), E.stream_ptr()))
+        out, o = [], 0
+        for (slot, x, flush), c in zip(items, counts):
+            st = self.slots[slot]
+            st[2] += x.shape[0]
+            st[3] = bool(flush)
+            out.append(y[o:o + c])
+            o += c
+        return out
 
 
 class SilenceStage(_Handle):
