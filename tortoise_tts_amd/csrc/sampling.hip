@@ -9,7 +9,7 @@
 // multinomial(p, 1) is realised as argmax(p / q), q ~ Exp(1): q is either an injected tensor
 // (parity runs share the oracle's draws) or Philox4x32-10 keyed by (seed; global row, step, token),
 // which makes the sampled codes independent of how candidates are sharded over GPUs.
-#include "ops.h"
+#include "sample_steps.h"
 
 namespace tt {
 
@@ -22,41 +22,6 @@ __device__ unsigned long long g_sample_stamps[16];
 #else
 #define TT_STAMP(i)
 #endif
-
-__device__ __forceinline__ unsigned f2key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                               unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// Strictly sequential (left to right) sum of x[0 .. n) in LDS, computed redundantly by every lane of ONE wave: the values are read 64
-// at a time into a register per lane and handed out with v_readlane (a few cycles each) instead of one dependent LDS round trip
-// (~100 cycles at one wave per SIMD) per element.  Same additions in the same order as `for (i) acc += x[i]`.
-__device__ __forceinline__ float seq_sum_lds(const float* x, int n, int lane) {
-  float acc = 0.f;
-  for (int base = 0; base < n; base += 64) {
-    const float v = base + lane < n ? x[base + lane] : 0.f;
-    const int cnt = min(64, n - base);
-    for (int j = 0; j < cnt; ++j) acc += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-  }
-  return acc;
-}
 
 // one thread: finished rows emit the stop token (stream_generator.py:980-996), bookkeeping of the sampled token; returns it
 __device__ __forceinline__ int sample_commit(const SampleArgs& a, int b, int step, int best_i, unsigned* seen) {
@@ -78,13 +43,7 @@ __device__ __forceinline__ int sample_commit(const SampleArgs& a, int b, int ste
 __device__ __forceinline__ void sample_embed(const SampleArgs& a, int b, int step, const int* tok_s, int tid, int nthreads) {
   if (a.embed_x && step + a.pos_offset < a.pos_len) {
     __syncthreads();
-    const int tok = tok_s[0];
-    const int pos = step + a.pos_offset;
-    for (int c = tid * 4; c < a.D; c += nthreads * 4) {
-      const float4 e = *(const float4*)(a.tok_emb + (size_t)tok * a.D + c);
-      const float4 p = *(const float4*)(a.pos_emb + (size_t)pos * a.D + c);
-      *(float4*)(a.embed_x + (size_t)b * a.D + c) = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
-    }
+    embed_row(a.embed_x + (size_t)b * a.D, a.tok_emb + (size_t)tok_s[0] * a.D, a.pos_emb + (size_t)(step + a.pos_offset) * a.D, a.D, tid, nthreads);
   }
 }
 
@@ -92,37 +51,8 @@ __device__ __forceinline__ void sample_embed(const SampleArgs& a, int b, int ste
 // step instead, so that the rows the batch carries along stay finite
 __device__ __forceinline__ bool sess_idle(const SampleArgs& a, int b, int tid, int nthreads) {
   if (!a.sess || a.sess[SESS_RUN * a.B + b] == SESS_RUNNING) return false;
-  if (a.embed_x)
-    for (int c = tid * 4; c < a.D; c += nthreads * 4) *(float4*)(a.embed_x + (size_t)b * a.D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.embed_x) zero_row(a.embed_x + (size_t)b * a.D, a.D, tid, nthreads);
   return true;
-}
-// the row's step (Philox counter, codes column), logits row, Philox key and candidate index (block-uniform)
-__device__ __forceinline__ int sample_step(const SampleArgs& a, int b) { return a.sess ? a.sess[SESS_N * a.B + b] : a.state[0]; }
-__device__ __forceinline__ const float* sample_logits(const SampleArgs& a, int b, int grp, int step) {
-  if (a.sess) return (step == 0 && a.pre_logits ? a.pre_logits : a.logits) + (size_t)b * a.ldl;  // token 0: the row's admission prefill
-  return a.logits + (a.ldl ? (size_t)b * a.ldl : (size_t)grp * (a.ldg ? a.ldg : a.V));
-}
-__device__ __forceinline__ unsigned long long sample_key(const SampleArgs& a, int b, int grp) {
-  // from device memory when the caller replays a cached step graph (the seed of a call is then data, not a baked-in kernel argument),
-  // else from the argument block; a session row has its own key
-  return a.keys_dev ? a.keys_dev[a.sess ? b : grp] : (a.ngroups > 1 ? a.group_seeds[grp] : a.seed);
-}
-// the row's sampling scalars: its own entry on a session handle with per-row scalars (block-uniform, read once), else the argument block
-__device__ __forceinline__ SampleScalars sample_scalars(const SampleArgs& a, int b) {
-  if (a.rows) return a.rows[b];
-  SampleScalars sc;
-  sc.rep_penalty = a.rep_penalty; sc.temperature = a.temperature; sc.top_p = a.top_p; sc.top_k = a.top_k; sc.typical_mass = a.typical_mass;
-  return sc;
-}
-// per-row scalars: a typical row reads the mask's output row, the others their own source (sample_launch switches `logits` for the
-// whole launch otherwise)
-__device__ __forceinline__ const float* sample_row_logits(const SampleArgs& a, const SampleScalars& sc, int b, int grp, int step) {
-  if (a.rows && sc.typical_mass != 0.f) return a.typical_out + (size_t)b * a.ldl;
-  return sample_logits(a, b, grp, step);
-}
-__device__ __forceinline__ int sample_cand(const SampleArgs& a, int b, int grp, int row_offset) {
-  // global index of the candidate: within its utterance (the draw does not depend on the batching); a session row is candidate 0
-  return a.sess ? 0 : row_offset + (a.ngroups > 1 ? b - grp * a.group_size : b);
 }
 
 // PER: vocabulary entries per thread (V <= 256 PER): 33 covers the model's 8194 mel codes, 40 anything up to 10240 - every unrolled loop below is PER long
@@ -148,12 +78,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
   if (sess_idle(a, b, tid, 256)) return;
   const SampleScalars sc = sample_scalars(a, b);
   if (a.rows && !sample_fast_k(sc.top_k)) return;  // (a row of the full-sort sampler)
-  const int step = sample_step(a, b);
-  const int grp = a.ngroups > 1 ? b / a.group_size : 0;  // utterance of this row (block-uniform)
-  const unsigned long long philox_key = sample_key(a, b, grp);  // Philox key of this row's utterance (block-uniform, read once)
-  const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;  // (block-uniform scalar load)
-  const float* lg = sample_row_logits(a, sc, b, grp, step);
-  unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
+  const SampleRow row = sample_row(a, sc, b);
   float val[PER];
   bool bad = false;  // NaN / +inf logits: an operand overflowed somewhere upstream (-inf is legitimate: a suppressed token)
   {
@@ -164,8 +89,8 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int tc = min(tid + 256 * j, V - 1);
-      raw[j] = lg[tc];
-      sw[j] = seen[tc >> 5];
+      raw[j] = row.lg[tc];
+      sw[j] = row.seen[tc >> 5];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -174,9 +99,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       float s = raw[j];
       const bool live = t < V;
       bad = bad || (live && (s != s || s == INFINITY));
-      if (sc.rep_penalty != 1.0f && ((sw[j] >> (t & 31)) & 1u)) s = s < 0.f ? s * sc.rep_penalty : s / sc.rep_penalty;
-      if (sc.temperature != 1.0f) s = s / sc.temperature;
-      if (__float_as_uint(s) == 0x80000000u) s = 0.f;  // -0.0 ties with +0.0 in the reference's float comparisons: one zero, so that key order == float order
+      s = sample_score(s, (sw[j] >> (t & 31)) & 1u, sc);
       val[j] = live ? s : -INFINITY;
     }
   }
@@ -408,108 +331,44 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
       const float sl = in ? sorted_v[tid] : -INFINITY;
       const int id = in ? sorted_i[tid] : 0x7fffffff;
       const float m = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sl), 0));
-      const float e = in ? __expf(sl - m) : 0.f;
-      const int eb = __builtin_bit_cast(int, e);
-      float total = 0.f;
-#pragma unroll
-      for (int j = 0; j < 64; ++j) total += __builtin_bit_cast(float, __builtin_amdgcn_readlane(eb, j));
+      const float e = in ? softmax_e(sl, m) : 0.f;
+      const float total = seq_sum_wave(e);
       TT_STAMP(6);
       TT_STAMP(7);
       int keep = n;
       if (sc.top_p < 1.0f) {
         // ascending cumulative probability of element r == sum of the probabilities of elements n-1 .. r; the partial sums never decrease,
         // so "the first r (from the top) whose sum exceeds 1 - top_p" is 1 + the number of r in [1, n) whose sum does
-        const int pb = __builtin_bit_cast(int, e / total);
+        const float pl = e / total;
         const float thr = 1.0f - sc.top_p;
         float tail = 0.f;
         int over = 0;
 #pragma unroll
         for (int r = 63; r >= 1; --r) {
-          tail += __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, r));
+          tail += lane_value(pl, r);
           over += tail > thr ? 1 : 0;
         }
         keep = over + 1;
       }
-      const int kb = __builtin_bit_cast(int, tid < keep ? e : 0.f);
-      float kt = 0.f;
-#pragma unroll
-      for (int j = 0; j < 64; ++j) kt += __builtin_bit_cast(float, __builtin_amdgcn_readlane(kb, j));
+      const float kt = seq_sum_wave(tid < keep ? e : 0.f);
       TT_STAMP(8);
-      // multinomial == argmax(p / q)
-      float best = -1.f;
-      int best_i = 0x7fffffff;
-      if (tid < keep) {
-        const float p = e / kt;
-        float q;
-        if (a.exp_noise) {
-          q = a.exp_noise[((size_t)step * a.B + b) * V + id];
-        } else {
-          unsigned r[4];
-          const unsigned long long key = philox_key;
-          const int cand = sample_cand(a, b, grp, row_offset);  // index within the utterance: the draw does not depend on the batching
-          philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)key, (unsigned)(key >> 32), r);
-          const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-          q = -__logf(u);
-        }
-        const float sc = p / q;
-        if (sc > best || (sc == best && id < best_i)) {
-          best = sc;
-          best_i = id;
-        }
-      }
+      Best best;
+      if (in && tid < keep) best.take(sample_draw(a, row, id, e / kt), id);  // (in: a row without a survivor still has keep == 1)
       TT_STAMP(9);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(best_i, o, 64);
-        if (ov > best || (ov == best && oi < best_i)) {
-          best = ov;
-          best_i = oi;
-        }
-      }
-      if (tid == 0) red_i[0] = sample_commit(a, b, step, best_i, seen);
+      best = best_wave(best);
+      if (tid == 0) red_i[0] = sample_commit(a, b, row.step, best.i, row.seen);
     }
   } else {
-    // (a tie plateau: the exponentials by all threads through the LDS, the sums by wave 0)
-    for (int i = tid; i < n; i += 256) sv[i] = __expf(sorted_v[i] - sorted_v[0]);  // sv is free after the rank sort
+    // (a tie plateau: the exponentials by all threads through the LDS, the sums by wave 0, every lane redundantly)
+    const float m = sorted_v[0];
+    for (int i = tid; i < n; i += 256) sv[i] = softmax_e(sorted_v[i], m);  // sv is free after the rank sort
     __syncthreads();
-    if (tid < 64) {  // (wave 0; every lane gets the same sum)
-      const float total = seq_sum_lds(sv, n, tid);
-      if (tid == 0) kept_total = total;  // (parked here for the parallel divisions below; overwritten with the kept sum afterwards)
-    }
-    __syncthreads();
-    TT_STAMP(6);
-    {  // the probabilities sv[r] / total, by all threads (the same IEEE division one thread did serially in round 3); si is free
-      const float total = kept_total;
-      float* pr = (float*)si;
-      for (int i = tid; i < n; i += 256) pr[i] = sv[i] / total;
-    }
-    __syncthreads();
-    TT_STAMP(7);
-    if (tid < 64) {  // wave 0, every lane redundantly: the same sequential arithmetic as one thread walking the arrays
-      const float* pr = (const float*)si;
-      int keep = n;
-      if (sc.top_p < 1.0f) {
-        float tail = 0.f;
-        keep = 1;
-        const float thr = 1.0f - sc.top_p;
-        // ascending cumulative probability of element r == sum of probabilities of elements r..n-1
-        bool done = false;
-        for (int hi = n - 1; hi >= 1 && !done; hi -= 64) {  // elements hi, hi - 1, ... in chunks of 64 (lane j holds element hi - j)
-          const int r_l = hi - tid;
-          const float v = r_l >= 1 ? pr[r_l] : 0.f;
-          const int cnt = min(64, hi);
-          for (int j = 0; j < cnt; ++j) {
-            tail += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
-            if (tail > thr) {
-              keep = hi - j + 1;
-              done = true;
-              break;
-            }
-          }
-        }
-      }
-      const float kt = seq_sum_lds(sv, keep, tid);
+    if (tid < 64) {
+      const float total = seq_sum_lds<1>(sv, n, tid);
+      TT_STAMP(6);
+      TT_STAMP(7);
+      const int keep = top_p_keep_lds<1>(sv, n, total, sc.top_p, tid);
+      const float kt = seq_sum_lds<1>(sv, keep, tid);
       if (tid == 0) {
         kept = keep;
         kept_total = kt;
@@ -517,58 +376,15 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     }
     __syncthreads();
     TT_STAMP(8);
-    // ---- multinomial == argmax(p / q)
     const int keep = kept;
-    const float m = sorted_v[0];
-    float best = -1.f;
-    int best_i = 0x7fffffff;
-    for (int i = tid; i < keep; i += 256) {
-      const int id = sorted_i[i];
-      const float p = __expf(sorted_v[i] - m) / kept_total;
-      float q;
-      if (a.exp_noise) {
-        q = a.exp_noise[((size_t)step * a.B + b) * V + id];
-      } else {
-        unsigned r[4];
-        const unsigned long long key = philox_key;
-        const int cand = sample_cand(a, b, grp, row_offset);  // index within the utterance: the draw does not depend on the batching
-        philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)key, (unsigned)(key >> 32), r);
-        const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-        q = -__logf(u);
-      }
-      const float sc = p / q;
-      if (sc > best || (sc == best && id < best_i)) {
-        best = sc;
-        best_i = id;
-      }
-    }
+    Best best;
+    for (int i = tid; i < keep; i += 256) best.take(sample_draw(a, row, sorted_i[i], softmax_e(sorted_v[i], m) / kept_total), sorted_i[i]);
     TT_STAMP(9);
-    // block argmax (value desc, index asc)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(best_i, o, 64);
-      if (ov > best || (ov == best && oi < best_i)) {
-        best = ov;
-        best_i = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      red_v[tid >> 6] = best;
-      red_i[tid >> 6] = best_i;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w)
-        if (red_v[w] > best || (red_v[w] == best && red_i[w] < best_i)) {
-          best = red_v[w];
-          best_i = red_i[w];
-        }
-      red_i[0] = sample_commit(a, b, step, best_i, seen);
-    }
+    best = best_block<4>(best, red_v, red_i, tid);
+    if (tid == 0) red_i[0] = sample_commit(a, b, row.step, best.i, row.seen);
   }
   TT_STAMP(10);
-  sample_embed(a, b, step, red_i, tid, 256);
+  sample_embed(a, b, row.step, red_i, tid, 256);
   TT_STAMP(11);
 }
 
@@ -581,10 +397,6 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
 // A correct path for every k, not a fast one: the reference's own default (k = 50) and the benchmark take the kernel above.
 constexpr int WIDE_N = 16384;
 constexpr int WIDE_V = 10240;
-__device__ __forceinline__ float key2f(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-  return __uint_as_float(u);
-}
 
 __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wide[];
@@ -604,21 +416,10 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   } else if (sess_idle(a, b, tid, 1024)) {
     return;
   }
-  const int step = sample_step(a, b);
-  const int grp = a.ngroups > 1 ? b / a.group_size : 0;
-  const unsigned long long philox_key = sample_key(a, b, grp);
-  const int row_offset = a.row_offset_dev ? *a.row_offset_dev : a.row_offset;
-  const float* lg = sample_row_logits(a, sc, b, grp, step);
-  unsigned* seen = a.seen + (size_t)b * ((V + 31) / 32);
+  const SampleRow row = sample_row(a, sc, b);
   for (int t = tid; t < WIDE_N; t += 1024) {
-    unsigned kk = 0u;  // padding slots sort behind every real score (f2key(-inf) = 0x007FFFFF > 0)
-    if (t < V) {
-      float s = lg[t];
-      if (sc.rep_penalty != 1.0f && ((seen[t >> 5] >> (t & 31)) & 1u)) s = s < 0.f ? s * sc.rep_penalty : s / sc.rep_penalty;
-      if (sc.temperature != 1.0f) s = s / sc.temperature;
-      kk = f2key(s);
-    }
-    key[t] = kk;
+    // padding slots sort behind every real score (f2key(-inf) = 0x007FFFFF > 0)
+    key[t] = t < V ? f2key(sample_score(row.lg[t], (row.seen[t >> 5] >> (t & 31)) & 1u, sc)) : 0u;
     tok[t] = (unsigned short)(t < V ? t : 0xFFFF);
   }
   // bitonic sort: final order = descending key, ascending token on equal keys
@@ -647,76 +448,24 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(SampleArgs a) {
   __syncthreads();
   const int n = n_s;
   const float v0 = key2f(key[0]);
-  for (int i = tid; i < n; i += 1024) ef[i] = __expf(key2f(key[i]) - v0);
+  for (int i = tid; i < n; i += 1024) ef[i] = softmax_e(key2f(key[i]), v0);
   __syncthreads();
-  if (tid == 0) {  // same sequential arithmetic as sample_kernel
-    float total = 0.f;
-    for (int i = 0; i < n; ++i) total += ef[i];
-    int keep = n;
-    if (sc.top_p < 1.0f) {
-      float tail = 0.f;
-      keep = 1;
-      const float thr = 1.0f - sc.top_p;
-      for (int r = n - 1; r >= 1; --r) {
-        tail += ef[r] / total;
-        if (tail > thr) {
-          keep = r + 1;
-          break;
-        }
-      }
+  if (tid < 64) {  // wave 0, every lane redundantly: the same sequential arithmetic as sample_kernel
+    const float total = seq_sum_lds<64>(ef, n, tid);
+    const int keep = top_p_keep_lds<64>(ef, n, total, sc.top_p, tid);
+    const float kt = seq_sum_lds<64>(ef, keep, tid);
+    if (tid == 0) {
+      kept = keep;
+      kept_total = kt;
     }
-    float kt = 0.f;
-    for (int i = 0; i < keep; ++i) kt += ef[i];
-    kept = keep;
-    kept_total = kt;
   }
   __syncthreads();
   const int keep = kept;
-  float best = -1.f;
-  int best_i = 0x7fffffff;
-  for (int i = tid; i < keep; i += 1024) {
-    const int id = tok[i];
-    const float p = __expf(key2f(key[i]) - v0) / kept_total;
-    float q;
-    if (a.exp_noise) {
-      q = a.exp_noise[((size_t)step * a.B + b) * V + id];
-    } else {
-      unsigned r[4];
-      const unsigned long long pk = philox_key;
-      const int cand = sample_cand(a, b, grp, row_offset);
-      philox4x32_10((unsigned)id, (unsigned)step, (unsigned)cand, 0u, (unsigned)pk, (unsigned)(pk >> 32), r);
-      const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      q = -__logf(u);
-    }
-    const float sc = p / q;
-    if (sc > best || (sc == best && id < best_i)) {
-      best = sc;
-      best_i = id;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(best_i, o, 64);
-    if (ov > best || (ov == best && oi < best_i)) {
-      best = ov;
-      best_i = oi;
-    }
-  }
-  if ((tid & 63) == 0) {
-    red_v[tid >> 6] = best;
-    red_i[tid >> 6] = best_i;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 16; ++w)
-      if (red_v[w] > best || (red_v[w] == best && red_i[w] < best_i)) {
-        best = red_v[w];
-        best_i = red_i[w];
-      }
-    red_i[0] = sample_commit(a, b, step, best_i, seen);
-  }
-  sample_embed(a, b, step, red_i, tid, 1024);
+  Best best;
+  for (int i = tid; i < keep; i += 1024) best.take(sample_draw(a, row, tok[i], softmax_e(key2f(key[i]), v0) / kept_total), tok[i]);
+  best = best_block<16>(best, red_v, red_i, tid);
+  if (tid == 0) red_i[0] = sample_commit(a, b, row.step, best.i, row.seen);
+  sample_embed(a, b, row.step, red_i, tid, 1024);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -765,9 +514,7 @@ __global__ __launch_bounds__(1024) void typical_mask_kernel(SampleArgs a) {
     const int t = tid + 1024 * j;
     const int tc = min(t, V - 1);
     raw[j] = lg[tc];
-    float x = raw[j];
-    if (sc.rep_penalty != 1.0f && ((seen[tc >> 5] >> (tc & 31)) & 1u)) x = x < 0.f ? x * sc.rep_penalty : x / sc.rep_penalty;
-    s[j] = t < V ? x : -INFINITY;
+    s[j] = t < V ? sample_penalty(raw[j], (seen[tc >> 5] >> (tc & 31)) & 1u, sc.rep_penalty) : -INFINITY;
     m = fmaxf(m, s[j]);
   }
   m = wave_max(m);
@@ -894,23 +641,9 @@ extern "C" int ttx_sample_stamps(unsigned long long* out16) {
 namespace tt {
 #endif
 
-// Last kernel of a step.  state[0] = tokens sampled so far, state[1] = slot / index of the newest token (the one the next decode
-// step feeds), state[2] = index of the first token after which every row had stopped (-1: none yet).  With `progress` (pinned
-// host memory) the two host-visible words are published with system-scope stores: the host paces and ends its launch loop on
-// them without draining the queue (tt_ar_generate).
+// Last kernel of a step (ar_publish_step: the state and progress words)
 __global__ void ar_advance_kernel(int* state, const int* unfinished_count, int* progress) {
-  if (threadIdx.x == 0) {
-    const int step = state[0];  // index of the token the sampler just produced
-    state[0] = step + 1;
-    state[1] = step;
-    if (progress) {
-      if (unfinished_count && unfinished_count[step] == 0 && state[2] < 0) {
-        state[2] = step;
-        __hip_atomic_store(progress + 1, step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      __hip_atomic_store(progress, step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  if (threadIdx.x == 0) ar_publish_step(state, unfinished_count, progress);
 }
 int ar_state_advance_launch(int* state, const int* unfinished_count, int* progress, hipStream_t stream) {
   ar_advance_kernel<<<1, 64, 0, stream>>>(state, unfinished_count, progress);
@@ -933,16 +666,7 @@ __global__ void ar_sess_advance_kernel(int* state, int* sess, int B, const int* 
         sess[SESS_RUN * B + r] = SESS_FINISHED;
       }
     }
-    const int step = state[0];
-    state[0] = step + 1;
-    state[1] = step;
-    if (progress) {
-      if (unfinished_count[step] == 0 && state[2] < 0) {
-        state[2] = step;
-        __hip_atomic_store(progress + 1, step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      __hip_atomic_store(progress, step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    ar_publish_step(state, unfinished_count, progress);
   }
 }
 int ar_sess_advance_launch(int* state, int* sess, int B, const int* unfinished, const int* unfinished_count, int* progress, hipStream_t stream) {
@@ -953,12 +677,7 @@ int ar_sess_advance_launch(int* state, int* sess, int B, const int* unfinished, 
 
 __global__ void ar_sess_admit_kernel(int* sess, int B, int row, int P1, unsigned* seen, int* unfinished, int V, int start_token) {
   const int words = (V + 31) / 32;
-  for (int w = threadIdx.x; w < words; w += blockDim.x) {
-    unsigned v = 0u;
-    if (w == 0) v |= 1u << 1;  // fake_inputs = [1] * P + [start_mel_token], as ar_begin_kernel
-    if (w == (start_token >> 5)) v |= 1u << (start_token & 31);
-    seen[(size_t)row * words + w] = v;
-  }
+  for (int w = threadIdx.x; w < words; w += blockDim.x) seen[(size_t)row * words + w] = seen_init_word(w, start_token);
   if (threadIdx.x == 0) {
     unfinished[row] = 1;
     sess[SESS_N * B + row] = 0;
@@ -990,14 +709,7 @@ __global__ void ar_begin_kernel(int* state, unsigned* seen, int* unfinished, int
                                 int start_token) {
   const int words = (V + 31) / 32;
   const int total = B * words;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int w = i % words;
-    unsigned v = 0u;
-    // fake_inputs = [1] * P + [start_mel_token] (autoregressive.py:546-548): ids 1 and start are "seen"
-    if (w == 0) v |= 1u << 1;
-    if (w == (start_token >> 5)) v |= 1u << (start_token & 31);
-    seen[i] = v;
-  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) seen[i] = seen_init_word(i % words, start_token);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B; i += gridDim.x * blockDim.x) unfinished[i] = 1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < max_steps; i += gridDim.x * blockDim.x) unfinished_count[i] = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1016,27 +728,14 @@ int ar_begin_launch(int* state, unsigned* seen, int* unfinished, int* unfinished
 __global__ __launch_bounds__(256) void ar_embed_kernel(const int* tok, const int* state, const float* tok_emb, const float* pos_emb,
                                                        float* x, int D, int pos_offset) {
   const int b = blockIdx.x;
-  const int t = tok[b];
-  const int pos = state[1] + pos_offset;
-  for (int c = threadIdx.x * 4; c < D; c += 1024) {
-    const float4 e = *(const float4*)(tok_emb + (size_t)t * D + c);
-    const float4 p = *(const float4*)(pos_emb + (size_t)pos * D + c);
-    *(float4*)(x + (size_t)b * D + c) = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
-  }
+  embed_row(x + (size_t)b * D, tok_emb + (size_t)tok[b] * D, pos_emb + (size_t)(state[1] + pos_offset) * D, D, threadIdx.x, 256);
 }
 __global__ __launch_bounds__(256) void ar_embed_rows_kernel(const int* tok, const int* row_slot, const float* tok_emb, const float* pos_emb,
                                                             float* x, int D, int pos_offset) {
   const int b = blockIdx.x;
   const int sl = row_slot[b];
-  for (int c = threadIdx.x * 4; c < D; c += 1024) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sl >= 0) {
-      const float4 e = *(const float4*)(tok_emb + (size_t)tok[b] * D + c);
-      const float4 p = *(const float4*)(pos_emb + (size_t)(sl + pos_offset) * D + c);
-      v = make_float4(e.x + p.x, e.y + p.y, e.z + p.z, e.w + p.w);
-    }
-    *(float4*)(x + (size_t)b * D + c) = v;
-  }
+  if (sl >= 0) embed_row(x + (size_t)b * D, tok_emb + (size_t)tok[b] * D, pos_emb + (size_t)(sl + pos_offset) * D, D, threadIdx.x, 256);
+  else zero_row(x + (size_t)b * D, D, threadIdx.x, 256);
 }
 int ar_embed_rows_launch(const int* tok, const int* row_slot, const float* tok_emb, const float* pos_emb, float* x, int B, int D, int pos_offset,
                          hipStream_t stream) {
