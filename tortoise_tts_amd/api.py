@@ -254,6 +254,81 @@ class StreamResampler:
         self.close()
 
 
+class StreamStretcher:
+    """One stream at another speaking rate and / or pitch (_Common.open_stretcher): f32 chunks at 24 kHz in, f32 tensors on the device out
+    (possibly empty) - a slot of a stages.StreamStretchStage at rq_eff, then, for a pitch, a slot of a stages.StreamResampleStage at
+    (pq, 65536).  An output appears once the 1407 input samples behind the start of its hop's frame are in (latency_seconds; the pitch
+    resampler adds its H + 1); finish() ends the stream as the clip's end and frees the slots.  A context manager: leaving it closes the
+    stream."""
+
+    def __init__(self, stretch_stage, pitch_stage, rq_eff, pq, keep_map=False):
+        self.stretch_stage, self.pitch_stage, self.rq, self.pq = stretch_stage, pitch_stage, int(rq_eff), int(pq)
+        self.slot = self.pitch_slot = None
+        self.closed = False
+        self._offsets = [] if keep_map else None
+        try:
+            if stretch_stage is not None:
+                self.slot = stretch_stage.open(self.rq)
+            if pitch_stage is not None:
+                self.pitch_slot = pitch_stage.open(self.pq, E.RS_PITCH_ONE)
+        except Exception:
+            self.close()
+            raise
+        self.n_in = self.n_out = 0
+        late = tsm.stream_latency() if stretch_stage is not None else 0.0
+        if pitch_stage is not None:
+            late += rs.stream_latency(self.pq, E.RS_PITCH_ONE) * self.rq / E.TSM_RATE_ONE
+        self.latency_seconds = late / float(E.TSM_SAMPLE_RATE)
+
+    def _push(self, chunk, flush):
+        if self.closed:
+            raise ValueError("this time-stretch stream is closed")
+        y = torch.as_tensor(chunk, dtype=torch.float32).reshape(-1)
+        self.n_in += y.shape[0]
+        if self.slot is not None:
+            if self._offsets is None:
+                y = self.stretch_stage.push_many([(self.slot, y, flush)])[0]
+            else:
+                (y,), (off,) = self.stretch_stage.push_many([(self.slot, y, flush)], return_offsets=True)
+                self._offsets.append(off)
+        if self.pitch_slot is not None:
+            y = self.pitch_stage.push_many([(self.pitch_slot, y, flush)])[0]
+        self.n_out += y.shape[0]
+        return y
+
+    def push(self, chunk):
+        return self._push(chunk, False)
+
+    def finish(self, chunk=None):
+        """The outputs still due (after an optional last chunk); the stream is over and its slots free."""
+        y = self._push(torch.zeros(0) if chunk is None else chunk, True)
+        self.close()
+        return y
+
+    def anchors(self):
+        """keep_map=True: int64 [frames so far, 2] anchors (output sample of the time-stretch, input sample) of the frames that have run
+        (stretch.anchors; after finish() they are stretch_many(return_map=True)'s).  Synchronises."""
+        if self._offsets is None:
+            raise ValueError("anchors(): open the stretcher with keep_map=True")
+        off = torch.cat([o.cpu() for o in self._offsets]) if self._offsets else torch.zeros(0, dtype=torch.int32)
+        return tsm.anchors(self.rq, off) if off.numel() else torch.zeros(0, 2, dtype=torch.int64)
+
+    def close(self):
+        self.closed = True
+        if self.slot is not None:
+            self.stretch_stage.close(self.slot)
+            self.slot = None
+        if self.pitch_slot is not None:
+            self.pitch_stage.close(self.pitch_slot)
+            self.pitch_slot = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class _Common:
     """What this module's TextToSpeech and api_fast.TextToSpeech share: the lazy tokenizer, the seed, the text front-end."""
     world = 1  # processes that share one utterance's work (TextToSpeech with candidate sharding sets its own)
@@ -438,6 +513,36 @@ class _Common:
     def stretch(self, audio, rate=None, duration=None):
         """stretch_many of one clip -> the stretched clip."""
         return self.stretch_many([audio], rates=rate, durations=duration)[0]
+
+    stream_stretcher = None
+    stream_pitch_resampler = None
+
+    def load_stream_stretch(self, max_streams=16):
+        """The streaming time-stretch of open_stretcher (stages.StreamStretchStage), built on first use."""
+        if self.stream_stretcher is None:
+            self.stream_stretcher = stages.StreamStretchStage(max_streams, device=self.device)
+        return self.stream_stretcher
+
+    def load_stream_pitch(self, max_streams=16):
+        """The streaming resampler behind open_stretcher's pitch (a stages.StreamResampleStage of its own), built on first use."""
+        if self.stream_pitch_resampler is None:
+            self.stream_pitch_resampler = stages.StreamResampleStage(max_streams, device=self.device)
+        return self.stream_pitch_resampler
+
+    def open_stretcher(self, rate=None, pitch=None, keep_map=False):
+        """A StreamStretcher for 24 kHz audio that arrives in chunks: push(chunk) returns the samples that became ready, finish() the rest;
+        their concatenation is stretch(whole clip, rate) - with a pitch, the time-stretch and the resampling shift_pitch / tts(pitch=)
+        make - to the bit, whatever the chunking.  rate (0.5 .. 2.0) and pitch (semitones, +-12) are validated as speaking_rate= and
+        pitch= of tts() are.  keep_map=True: anchors() gives stretch_many(return_map=True)'s anchors.  Up to 16 may be open."""
+        if rate is not None:
+            tsm.rate_q(rate)
+        pq, rq_eff = rs.pitch(0.0 if pitch is None else pitch, rate)
+        if rq_eff == E.TSM_RATE_ONE and pq == E.RS_PITCH_ONE:
+            raise ValueError("open_stretcher: give a rate other than 1.0 or a pitch other than 0 semitones")
+        if keep_map and rq_eff == E.TSM_RATE_ONE:
+            raise ValueError("open_stretcher: keep_map=True needs a time-stretch (this rate and pitch need none)")
+        return StreamStretcher(self.load_stream_stretch() if rq_eff != E.TSM_RATE_ONE else None,
+                               self.load_stream_pitch() if pq != E.RS_PITCH_ONE else None, rq_eff, pq, keep_map)
 
     def _at_rate(self, clips, rate):
         """The clips a tts call is about to return ({winner: clip} or a list), at speaking_rate `rate`: one stretch_many call for all of

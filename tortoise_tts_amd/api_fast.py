@@ -61,6 +61,8 @@ class _Session:
     wav_gen_prev: Any = None
     wav_overlap: Any = None
     rs_slot: Any = None   # stream_sample_rate=: the session's slot on the streaming resampler
+    ts_slot: Any = None   # stream_speaking_rate= / stream_pitch=: its slot on the streaming time-stretch
+    pitch_slot: Any = None  # stream_pitch=: its slot on the pitch resampler behind the time-stretch
 
 
 class TextToSpeech(_Common):
@@ -344,6 +346,7 @@ class TextToSpeech(_Common):
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         stream_rate = rs.stream_options(hf_generate_kwargs)
+        stream_voice = tsm.stream_options(hf_generate_kwargs)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -353,8 +356,9 @@ class TextToSpeech(_Common):
         wav_gen_prev, wav_overlap = None, None
         emitted = 0          # (token, latent) pairs already decoded into an emitted chunk
         threshold = first    # pairs the reference buffers before the next decode (api_fast.py:412)
-        # stream_sample_rate=: every piece goes through one slot of the streaming resampler, the stream's last piece with flush
-        rs_slot = None if stream_rate is None else self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
+        # stream_speaking_rate= / stream_pitch= / stream_sample_rate=: every piece goes through the session's slots of the streaming
+        # time-stretch, the pitch resampler and the rate resampler, in this order; the stream's last piece with flush
+        chain = self._open_chain(stream_voice, stream_rate)
         try:
             for codes, done in self.ar.generate_stream(1, max_mel_tokens, chunk, first_chunk=first, temperature=temperature, top_p=top_p,
                                                        repetition_penalty=float(repetition_penalty), top_k=top_k, seed=seed,
@@ -371,25 +375,80 @@ class TextToSpeech(_Common):
                 # (api_fast.py:405-420).  When the sequence ends exactly on a buffer boundary that last pass sees the same latents
                 # again and handle_chunks hands out the withheld overlap tail: mirror it.
                 extra = done and stream_chunk_size > 0 and codes.shape[1] - emitted == threshold
-                yield wav_chunk if rs_slot is None else self._stream_rs().push_many([(rs_slot, wav_chunk, done and not extra)])[0]
+                yield wav_chunk if chain is None else self._chain_push([(chain, wav_chunk, done and not extra)])[0]
                 if done:
                     if extra:
                         wav_chunk, wav_gen_prev, wav_overlap = self.handle_chunks(wav_gen, wav_gen_prev, wav_overlap, overlap_wav_len)
-                        yield wav_chunk if rs_slot is None else self._stream_rs().push_many([(rs_slot, wav_chunk, True)])[0]
+                        yield wav_chunk if chain is None else self._chain_push([(chain, wav_chunk, True)])[0]
                     break
                 emitted = codes.shape[1]
                 threshold = chunk
         finally:
-            if rs_slot is not None:
-                self._stream_rs().close(rs_slot)
+            self._close_chain(chain)
 
     _stream_stage = None
+    _stretch_stage = None
+    _pitch_stage = None
 
     def _stream_rs(self):
         """The streaming resampler of stream_sample_rate= (stages.StreamResampleStage, one slot per session), built on first use."""
         if self._stream_stage is None:
             self._stream_stage = stages.StreamResampleStage(self.max_streams, device=self.device)
         return self._stream_stage
+
+    def _stream_ts(self):
+        """The streaming time-stretch of stream_speaking_rate= / stream_pitch= (stages.StreamStretchStage, one slot per session), built on
+        first use."""
+        if self._stretch_stage is None:
+            self._stretch_stage = stages.StreamStretchStage(self.max_streams, device=self.device)
+        return self._stretch_stage
+
+    def _stream_pitch(self):
+        """The resampler behind the time-stretch of stream_pitch= (a second stages.StreamResampleStage: the first one's slots belong to
+        stream_sample_rate=), built on first use."""
+        if self._pitch_stage is None:
+            self._pitch_stage = stages.StreamResampleStage(self.max_streams, device=self.device)
+        return self._pitch_stage
+
+    def _open_chain(self, stream_voice, stream_rate):
+        """The slots one stream's pieces go through: (time-stretch slot at rq_eff, pitch slot at (pq, 65536), rate slot), None where a
+        stage is not needed - or None when none is.  stream_voice: stretch.stream_options' (rq_eff, pq); stream_rate: Hz.  A rate of
+        exactly 1 is no time-stretch and a ratio of 1 no resampling, as in the whole-clip calls.  An open that fails frees the others."""
+        if stream_voice is None and stream_rate is None:
+            return None
+        chain = [None, None, None]
+        try:
+            if stream_voice is not None and stream_voice[0] != E.TSM_RATE_ONE:
+                chain[0] = self._stream_ts().open(stream_voice[0])
+            if stream_voice is not None and stream_voice[1] != E.RS_PITCH_ONE:
+                chain[1] = self._stream_pitch().open(stream_voice[1], E.RS_PITCH_ONE)
+            if stream_rate is not None:
+                chain[2] = self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
+        except Exception:
+            self._close_chain(tuple(chain))
+            raise
+        return tuple(chain) if any(c is not None for c in chain) else None
+
+    def _close_chain(self, chain):
+        for slot, stage in zip(chain or (), (self._stream_ts, self._stream_pitch, self._stream_rs)):
+            if slot is not None:
+                stage().close(slot)
+
+    def _chain_push(self, items):
+        """items = [(chain, piece, flush)] of distinct streams -> what each emits at the end of its chain: ONE push_many per stage for all of
+        them (the time-stretch, then the pitch resampler, then the rate resampler; a stream without a slot on a stage passes it by)."""
+        pieces = [x for _, x, _ in items]
+        for which, stage in enumerate((self._stream_ts, self._stream_pitch, self._stream_rs)):
+            todo = [i for i, (chain, _, _) in enumerate(items) if chain[which] is not None]
+            if todo:
+                for i, y in zip(todo, stage().push_many([(items[i][0][which], pieces[i], items[i][2]) for i in todo])):
+                    pieces[i] = y
+        return pieces
+
+    @staticmethod
+    def _chain_of(sess):
+        chain = (sess.ts_slot, sess.pitch_slot, sess.rs_slot)
+        return chain if any(c is not None for c in chain) else None
 
     # ------------------------------------------------------------------ several streams in one decode batch (max_streams > 1)
     def _single(self, name):
@@ -407,13 +466,20 @@ class TextToSpeech(_Common):
         the same done flags, each holding the samples that became ready (possibly none), through one slot of the streaming resampler
         (stages.StreamResampleStage; all pieces due in a round of stream_pieces in ONE push).  Their concatenation is bit for bit
         resample() of the 24 kHz stream; the audio lags by resample.stream_latency input samples (1.5 ms; 4.5 ms to 8 kHz) until the
-        last piece flushes it.  None or 24000: nothing is built, today's bits."""
+        last piece flushes it.  None or 24000: nothing is built, today's bits.
+        stream_speaking_rate=r (0.5 .. 2.0) and stream_pitch=s (semitones, +-12), also on tts_stream: the session's pieces at another
+        speaking rate and pitch, validated as speaking_rate= and pitch= of tts() are - through one slot of the streaming time-stretch
+        (stages.StreamStretchStage) at rate r / 2^(s/12) and, for a pitch, one slot of a second streaming resampler at 2^(s/12), in front
+        of the stream_sample_rate slot; every stage is ONE push per round of stream_pieces.  The concatenation is bit for bit the
+        whole-clip chain (stretch / shift_pitch, then resample) of the 24 kHz stream; the audio lags by 1407 samples (58.6 ms) until the
+        last piece flushes it, so early pieces may be short or empty.  None, 1.0 and 0: nothing is built, today's bits."""
         tsm.refuse_streaming(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
         stream_rate = rs.stream_options(kwargs)  # (validated before a slot is taken)
+        stream_voice = tsm.stream_options(kwargs)
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -438,17 +504,22 @@ class TextToSpeech(_Common):
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
         slot = free[0]
-        if self.per_session_sampling:
-            self.ar.admit(slot, cond, text_tokens, seed, **dict(zip(("temperature", "top_p", "repetition_penalty", "top_k", "typical_mass"), settings)))
-        else:
-            self.ar.admit(slot, cond, text_tokens, seed)
+        chain = self._open_chain(stream_voice, stream_rate)  # (before the row is taken: a refusal here leaves no session behind)
+        try:
+            if self.per_session_sampling:
+                self.ar.admit(slot, cond, text_tokens, seed, **dict(zip(("temperature", "top_p", "repetition_penalty", "top_k", "typical_mass"), settings)))
+            else:
+                self.ar.admit(slot, cond, text_tokens, seed)
+        except Exception:
+            self._close_chain(chain)
+            raise
         size = a["stream_chunk_size"]
         chunk = size if size > 0 else max_mel_tokens
         first = max(chunk, 60) if size > 0 else max_mel_tokens  # first_buffer = 60 (api_fast.py:401, 412)
         sess = _Session(self._next_sid, slot, cond, text_tokens, max_mel_tokens, chunk, size, a["overlap_wav_len"], min(first, max_mel_tokens),
                         threshold=first)
-        if stream_rate is not None:
-            sess.rs_slot = self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
+        if chain is not None:
+            sess.ts_slot, sess.pitch_slot, sess.rs_slot = chain
         self._next_sid += 1
         self._sessions[slot] = sess
         self._session_settings = settings
@@ -466,22 +537,22 @@ class TextToSpeech(_Common):
         raise KeyError(f"close_stream: no open session {sid}")
 
     def _close_rs(self, sess):
-        if sess.rs_slot is not None:
-            self._stream_rs().close(sess.rs_slot)
-            sess.rs_slot = None
+        """Frees every slot of the session's chain."""
+        self._close_chain(self._chain_of(sess))
+        sess.ts_slot = sess.pitch_slot = sess.rs_slot = None
 
     def _resample_due(self, due, vocoded):
-        """stream_sample_rate=: the pieces of this round's sessions that stream at another rate, all resampled in ONE push_many (a
-        session's extra last piece in a second one): slot -> [(chunk at the session's rate, done)].  The last piece of a session is
-        pushed with flush.  {} when no session of the round has a rate."""
-        pieces = {slot: self._session_piece(sess, n, fin, vocoded.get(slot)) for slot, sess, n, fin in due if sess.rs_slot is not None}
+        """stream_speaking_rate= / stream_pitch= / stream_sample_rate=: the pieces of this round's sessions that have a chain, all of them
+        through ONE push_many per stage (a session's extra last piece in a second one): slot -> [(chunk at the end of the session's
+        chain, done)].  The last piece of a session is pushed with flush.  {} when no session of the round has a chain."""
+        pieces = {slot: self._session_piece(sess, n, fin, vocoded.get(slot)) for slot, sess, n, fin in due if self._chain_of(sess) is not None}
         if not pieces:
             return {}
-        rs_slots = {slot: sess.rs_slot for slot, sess, _, _ in due}
+        chains = {slot: self._chain_of(sess) for slot, sess, _, _ in due}
         out = {slot: [] for slot in pieces}
         for k in range(max(len(p) for p in pieces.values())):
             todo = [slot for slot, p in pieces.items() if len(p) > k]
-            res = self._stream_rs().push_many([(rs_slots[slot], pieces[slot][k][0], pieces[slot][k][1]) for slot in todo])
+            res = self._chain_push([(chains[slot], pieces[slot][k][0], pieces[slot][k][1]) for slot in todo])
             for slot, y in zip(todo, res):
                 out[slot].append((y, pieces[slot][k][1]))
         return out
@@ -553,7 +624,7 @@ class TextToSpeech(_Common):
             vocoded = self._vocode_due([(slot, sess, n_total[slot], finished[slot]) for slot, sess in batch
                                         if finished[slot] or n_total[slot] >= sess.target])
             due = [(slot, sess, n_total[slot], finished[slot]) for slot, sess in batch if finished[slot] or n_total[slot] >= sess.target]
-            resampled = self._resample_due(due, vocoded) if any(sess.rs_slot is not None for _, sess, _, _ in due) else {}
+            resampled = self._resample_due(due, vocoded) if any(self._chain_of(sess) is not None for _, sess, _, _ in due) else {}
             for slot, sess in batch:
                 if self._sessions.get(slot) is not sess:  # closed while an earlier piece of this round was out
                     continue
@@ -573,7 +644,8 @@ class TextToSpeech(_Common):
         shared by all texts; use_deterministic_seed may be a list with one seed per text, and so may temperature, top_p,
         repetition_penalty, top_k, typical_sampling and typical_mass on an instance with per_session_sampling.  Texts beyond the free
         slots are admitted as earlier sessions end.  stream_sample_rate= (Hz, 8000 .. 96000; one value or a list with one per text,
-        None allowed): that text's pieces at another rate than 24 kHz, see open_stream."""
+        None allowed): that text's pieces at another rate than 24 kHz, see open_stream.  stream_speaking_rate= and stream_pitch= (one value
+        or a list with one per text, None allowed): that text's pieces at another speaking rate and pitch, see open_stream."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
@@ -589,6 +661,13 @@ class TextToSpeech(_Common):
             per_text["stream_sample_rate"] = kwargs.pop("stream_sample_rate")
         for r in per_text.get("stream_sample_rate", [kwargs.get("stream_sample_rate")]):
             rs.stream_options({"stream_sample_rate": r})  # (every rate is validated before the first session opens)
+        for name in ("stream_speaking_rate", "stream_pitch"):
+            if isinstance(kwargs.get(name), (list, tuple)):
+                if len(kwargs[name]) != len(texts):
+                    raise ValueError(f"tts_stream_many: {len(kwargs[name])} {name} values for {len(texts)} texts")
+                per_text[name] = kwargs.pop(name)
+        for i in range(len(texts)):  # (every text's rate and pitch are validated together before the first session opens)
+            tsm.stream_options({name: per_text[name][i] if name in per_text else kwargs.get(name) for name in ("stream_speaking_rate", "stream_pitch")})
         for name in ("temperature", "top_p", "repetition_penalty", "top_k", "typical_sampling", "typical_mass"):
             if isinstance(kwargs.get(name), (list, tuple)):
                 if not self.per_session_sampling:

@@ -5,7 +5,8 @@
 //     region             the nominal position a_k does not depend on the path: the 1663 samples x[a_k - 256 ..) that frame k can touch (512
 //                        candidate windows of 768, and the 768 behind any choice + Hs: the NEXT template) are fetched into registers a
 //                        frame ahead, while the current frame's search runs, and written to LDS when the search is done.  No global load
-//                        sits on the chain.
+//                        sits on the chain.  A region that lies inside the clip - every frame's but the first and the last few - is
+//                        fetched from one uniform base without a bounds test per sample (tsm_fetch_inside).
 //     template           copied LDS -> LDS from the region at the chosen offset (16-byte aligned again, so its reads are ds_read_b128 broadcasts).
 //     search             thread (half, u) owns the adjacent candidates 4u .. 4u + 3 over j in [384 half, 384 half + 384): its region reads
 //                        are 16-byte aligned ds_read_b128, consecutive over the lanes (no bank conflict), each value feeds all four
@@ -19,54 +20,19 @@
 //     overlap-add        y of hop k - 1 needs frame k - 1 (the template's first half) and frame k (the region at the chosen offset): both
 //                        are in LDS; one coalesced store per sample.
 //   Nothing a clip computes depends on where it stands in the batch.
+//   The steps are csrc/tsm_steps.h's, shared with the chunked kernel of tsm_stream.hip.
 #include <math.h>
 #include "runtime.h"
-#include "../../include/tortoise_mi355x_tsm.h"
+#include "tsm_steps.h"
 
 namespace tt {
-
-constexpr int kTsmW = TT_TSM_WINDOW, kTsmHs = TT_TSM_HOP, kTsmS = TT_TSM_SEARCH;
-constexpr int kTsmThreads = 256;                           // 128 x four candidates, x the two halves of j
-constexpr int kTsmRegion = 2 * kTsmS - 1 + kTsmHs + kTsmW;  // 1663 samples from a_k - kTsmS
-constexpr int kTsmRegionPad = 1664;
-constexpr int kTsmPre = (kTsmRegion + kTsmThreads - 1) / kTsmThreads;  // region samples a thread holds of the next frame (7)
-static_assert(4 * (kTsmThreads / 2) == 2 * kTsmS && kTsmW == 2 * kTsmHs && kTsmW % 8 == 0 && kTsmW == 3 * kTsmThreads, "tsm_stretch_kernel's thread mapping");
-
-typedef float tsm_f2 __attribute__((ext_vector_type(2)));  // (8- and 16-byte aligned: ds_read_b64 / ds_read_b128)
-typedef float tsm_f4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ static inline bool tsm_rate_ok(int rq) { return rq >= TT_TSM_RATE_MIN && rq <= TT_TSM_RATE_MAX; }
-__host__ __device__ static inline int tsm_out_samples(int n, int rq) {
-  const long long v = ((long long)n * TT_TSM_RATE_ONE + rq / 2) / rq;
-  return v < 1 ? 1 : (int)v;
-}
-__host__ __device__ static inline int tsm_frames(int n_out) { return (n_out + kTsmHs - 1) / kTsmHs + 1; }
-__host__ __device__ static inline int tsm_nominal(int k, int rq) { return (int)(((long long)(k - 1) * kTsmHs * rq + 32768) >> 16); }
-
-// (score, tie order) as one unsigned key: a greater score wins; among equal scores the smaller |d|, and of +-d the negative one
-__device__ __forceinline__ unsigned long long tsm_key(float s, int cand) {
-  s += 0.f;  // (-0 -> +0: equal scores have equal bits)
-  unsigned u = __float_as_uint(s);
-  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
-  const int d = cand - kTsmS;
-  const unsigned pos = d < 0 ? (unsigned)(-2 * d - 1) : (unsigned)(2 * d);  // 0, -1, 1, -2, 2, ... -> 0, 1, 2, 3, 4, ...
-  return ((unsigned long long)u << 32) | (unsigned)(2 * kTsmS - 1 - pos);
-}
-__device__ __forceinline__ int tsm_key_cand(unsigned long long key) {
-  const int pos = 2 * kTsmS - 1 - (int)(key & (2 * kTsmS - 1));
-  return kTsmS + ((pos & 1) ? -((pos + 1) >> 1) : (pos >> 1));
-}
 
 __global__ __launch_bounds__(kTsmThreads) void tsm_stretch_kernel(const float* __restrict__ audio, const int* __restrict__ in_off,
                                                                   const int* __restrict__ rqs, const float* __restrict__ window, int max_samples,
                                                                   float* __restrict__ out, const int* __restrict__ out_off,
                                                                   int* __restrict__ offsets, const int* __restrict__ frame_off,
                                                                   int* __restrict__ status) {
-  __shared__ __align__(16) float reg_s[kTsmRegionPad];
-  __shared__ __align__(16) float sh_s[kTsmRegionPad];  // reg_s one sample on: sh_s[i] = reg_s[i + 1]
-  __shared__ __align__(16) float tpl_s[kTsmW];
-  __shared__ float part_s[8 * kTsmThreads / 2];  // c and E of the upper half of j, [4 + 4][128]
-  __shared__ unsigned long long best_s[kTsmThreads / 64];
+  TT_TSM_LDS;
   const int c = blockIdx.x, t = threadIdx.x, u = t & (kTsmThreads / 2 - 1), half = t / (kTsmThreads / 2);
   const int i0 = in_off[c], n = in_off[c + 1] - i0, rq = rqs[c];
   const int o0 = out_off[c], f0 = frame_off[c];
@@ -92,10 +58,7 @@ __global__ __launch_bounds__(kTsmThreads) void tsm_stretch_kernel(const float* _
   auto sample = [&](int i) { return i >= 0 && i < n ? x[i] : 0.f; };
   float* y = out + o0;
   int* off = offsets + f0;
-  // the window values of this thread's output samples t and t + 256 of every hop: first half (the entering frame), second half (the leaving one)
-  const bool two = t + kTsmThreads < kTsmHs;
-  const float w_in0 = window[t], w_out0 = window[t + kTsmHs];
-  const float w_in1 = two ? window[t + kTsmThreads] : 0.f, w_out1 = two ? window[t + kTsmThreads + kTsmHs] : 0.f;
+  const TsmWin w = tsm_window(window, t);
   // frame 0 sits at p_0 = -Hs: frame 1's template is x[0 .. W)
 #pragma unroll
   for (int e = 0; e < kTsmW / kTsmThreads; ++e) tpl_s[e * kTsmThreads + t] = sample(e * kTsmThreads + t);
@@ -103,84 +66,23 @@ __global__ __launch_bounds__(kTsmThreads) void tsm_stretch_kernel(const float* _
   float pre[kTsmPre];
   auto fetch = [&](int k) {
     const int base = tsm_nominal(k, rq) - kTsmS;
-#pragma unroll
-    for (int e = 0; e < kTsmPre; ++e) {
-      const int i = e * kTsmThreads + t;
-      pre[e] = i < kTsmRegion ? sample(base + i) : 0.f;
-    }
+    if (base >= 0 && base + kTsmRegion <= n)  // (uniform over the workgroup) all but the first and the last few frames of a clip
+      tsm_fetch_inside(pre, x + base, t);
+    else
+      tsm_fetch(pre, k, rq, t, sample);
   };
   fetch(1);
   for (int k = 1; k < K; ++k) {
-    // (the previous frame's reads of reg_s ended before its last barrier)
-#pragma unroll
-    for (int e = 0; e < kTsmPre; ++e) {
-      const int i = e * kTsmThreads + t;
-      if (i < kTsmRegionPad) reg_s[i] = pre[e];
-      if (i >= 1 && i < kTsmRegionPad) sh_s[i - 1] = pre[e];
-    }
+    tsm_store_region(reg_s, sh_s, pre, t);
     if (k + 1 < K) fetch(k + 1);  // in flight while this frame is searched
     __syncthreads();
-    // candidates 4u .. 4u + 3 over this thread's half of j: the window reg_s[4u + j ..] is 16-byte aligned for every j = 0 mod 4
-    const tsm_f4* r4 = (const tsm_f4*)reg_s + u + half * (kTsmW / 8);
-    const tsm_f4* s4 = (const tsm_f4*)sh_s + u + half * (kTsmW / 8);
-    const tsm_f4* t4 = (const tsm_f4*)tpl_s + half * (kTsmW / 8);
-    tsm_f2 c01 = {0.f, 0.f}, c23 = {0.f, 0.f}, e01 = {0.f, 0.f}, e23 = {0.f, 0.f};  // (c, E) of candidates 4u + (0, 1) and 4u + (2, 3)
-    auto step = [&](float tj, tsm_f2 a, tsm_f2 b) {  // one j: the window values of candidates (0, 1) and (2, 3), register pairs as read
-      c01 = __builtin_elementwise_fma(tsm_f2{tj, tj}, a, c01);
-      c23 = __builtin_elementwise_fma(tsm_f2{tj, tj}, b, c23);
-      e01 = __builtin_elementwise_fma(a, a, e01);
-      e23 = __builtin_elementwise_fma(b, b, e23);
-    };
-    // x0 = region[4u + j .. + 3], x1 = the same one sample on (the shifted copy): every pair a step needs is an aligned half of a read
-    tsm_f4 tv = t4[0], x0 = r4[0], x1 = s4[0];
-#pragma unroll 4
-    for (int q = 0; q < kTsmW / 8; ++q) {
-      const tsm_f4 y0 = r4[q + 1], y1 = s4[q + 1], tn = t4[q + 1 < kTsmW / 8 ? q + 1 : q];  // the next j's reads, in flight over this j's FMAs
-      step(tv.x, x0.xy, x0.zw);  // ascending j
-      step(tv.y, x1.xy, x1.zw);
-      step(tv.z, x0.zw, y0.xy);
-      step(tv.w, x1.zw, y1.xy);
-      tv = tn; x0 = y0; x1 = y1;
-    }
-    const float cc[4] = {c01.x, c01.y, c23.x, c23.y}, ee[4] = {e01.x, e01.y, e23.x, e23.y};
-    if (half) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        part_s[g * kTsmThreads / 2 + u] = cc[g];
-        part_s[(4 + g) * kTsmThreads / 2 + u] = ee[g];
-      }
-    }
-    __syncthreads();
-    unsigned long long key = 0;  // (below every candidate's key)
-    if (!half) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float cg = cc[g] + part_s[g * kTsmThreads / 2 + u], eg = ee[g] + part_s[(4 + g) * kTsmThreads / 2 + u];
-        const unsigned long long kg = tsm_key(cg / sqrtf(eg + 1e-20f), 4 * u + g);
-        key = kg > key ? kg : key;
-      }
-    }
-    for (int m = 32; m >= 1; m >>= 1) {
-      const unsigned long long o = __shfl_xor(key, m);
-      key = o > key ? o : key;
-    }
-    if ((t & 63) == 0) best_s[t >> 6] = key;
-    __syncthreads();
-#pragma unroll
-    for (int wv = 0; wv < kTsmThreads / 64; ++wv) key = best_s[wv] > key ? best_s[wv] : key;
-    const int cs = tsm_key_cand(key);  // 0 .. 511, the same in every thread
-    // hop k - 1 of the output: frame k - 1 leaves (the template's first half), frame k enters (the region at the chosen offset)
-    const int m0 = (k - 1) * kTsmHs + t;
-    if (m0 < n_out) y[m0] = fmaf(w_in0, reg_s[cs + t], w_out0 * tpl_s[t]);
-    if (two && m0 + kTsmThreads < n_out) y[m0 + kTsmThreads] = fmaf(w_in1, reg_s[cs + t + kTsmThreads], w_out1 * tpl_s[t + kTsmThreads]);
+    float cc[4], ee[4];
+    tsm_search(reg_s, sh_s, tpl_s, u, half, cc, ee);
+    const int cs = tsm_argmax(cc, ee, part_s, best_s, t, u, half);
+    // hop k - 1 of the output
+    tsm_overlap_add(w, reg_s, tpl_s, cs, t, y, (k - 1) * kTsmHs + t, n_out);
     if (t == 0) off[k] = cs - kTsmS;
-    // the next template: what follows this frame's choice, x[p_k + Hs + j]
-    float nt[kTsmW / kTsmThreads];
-#pragma unroll
-    for (int e = 0; e < kTsmW / kTsmThreads; ++e) nt[e] = reg_s[cs + kTsmHs + e * kTsmThreads + t];
-    __syncthreads();  // every read of tpl_s, reg_s and best_s of this frame is done
-#pragma unroll
-    for (int e = 0; e < kTsmW / kTsmThreads; ++e) tpl_s[e * kTsmThreads + t] = nt[e];
+    tsm_next_template(reg_s, tpl_s, cs, t);
   }
   if (t == 0) status[c] = TT_TSM_OK;
 }

@@ -440,6 +440,21 @@ _RSS_PROTOS = {
 RSS_ABI_VERSION = 1
 RSS_HIST, RSS_MAX_STREAMS, RSS_BANK_MAX, RSS_AUTO_MAX_Q = 576, 64, 16384, 16  # TT_RSS_HIST, TT_RSS_MAX_STREAMS, TT_RSS_BANK_MAX, TT_RSS_AUTO_MAX_Q
 RSS_AUTO, RSS_TABLE, RSS_BANK = 0, 1, 2
+
+# include/tortoise_mi355x_tss.h: the time-stretch fed in chunks, for streams at another speaking rate and pitch (its own header and version)
+_TSS_PROTOS = {
+    "tt_tss_abi_version": (_i, []),
+    "tt_tss_create": (_i, [_i, C.POINTER(vp)]),
+    "tt_tss_destroy": (None, [vp]),
+    "tt_tss_open": (_i, [vp, _i, _i]),
+    "tt_tss_close": (_i, [vp, _i]),
+    "tt_tss_state": (_i, [vp, _i, _ip, _ip, _ip, _ip]),
+    "tt_tss_frames_done": (_i, [_i, _i]),
+    "tt_tss_ready": (_i, [_i, _i, _i, _i]),
+    "tt_tss_push": (_i, [vp, _i, _ip, _ip, _ip, vp, vp, vp, vp]),
+}
+TSS_ABI_VERSION = 1
+TSS_LOOK, TSS_HIST, TSS_MAX_STREAMS = 1407, 1664, 64  # TT_TSS_LOOK, TT_TSS_HIST, TT_TSS_MAX_STREAMS
 # include/tortoise_mi355x_sil.h: speech regions, edge trimming and pause capping of rendered clips (its own header and version)
 _SIL_PROTOS = {
     "tt_sil_abi_version": (_i, []),
@@ -539,7 +554,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -577,6 +592,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
     if lib.tt_rss_abi_version() != RSS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rss.h is version %d in the library, %d in Python" % (lib.tt_rss_abi_version(), RSS_ABI_VERSION))
+    if lib.tt_tss_abi_version() != TSS_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_tss.h is version %d in the library, %d in Python" % (lib.tt_tss_abi_version(), TSS_ABI_VERSION))
     if lib.tt_sil_abi_version() != SIL_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:

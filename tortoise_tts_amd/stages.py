@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from . import engine as E
 from . import pack
 from . import resample as rs
+from . import stretch as tsm
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig
 from .schedule import Schedule
 
@@ -697,6 +698,79 @@ class StreamResampleStage(_Handle):
             out.append(y[o:o + c])
             o += c
         return out
+
+
+class StreamStretchStage(_Handle):
+    """The WSOLA time-stretch fed in chunks (csrc/tsm_stream.hip, include/tortoise_mi355x_tss.h): up to max_streams streams, each with its
+    own rate; whatever the chunking, what a stream emits - samples and chosen offsets - is bit for bit TimeStretchStage's result for the
+    whole clip, 1407 input samples late until the flush."""
+
+    api = "tt_tss"
+
+    def __init__(self, max_streams=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_streams = int(max_streams)
+        self.slots = {}  # open slot -> [rq, samples pushed, finished]
+        self._create(self.max_streams)
+
+    def open(self, rq):
+        """A free slot opened at the 16.16 rate rq (stretch.rate_q) -> its number.  ValueError for a rate outside [0.5, 2.0] (before a slot
+        is taken), RuntimeError when every slot is taken."""
+        rq = int(rq)
+        if not E.TSM_RATE_MIN <= rq <= E.TSM_RATE_MAX:
+            raise ValueError(f"rate {rq} / 65536 is outside the supported range [0.5, 2.0]")
+        free = [s for s in range(self.max_streams) if s not in self.slots]
+        if not free:
+            raise RuntimeError(f"all {self.max_streams} time-stretch streams are open")
+        E.check(self.lib.tt_tss_open(self.h, free[0], rq))
+        self.slots[free[0]] = [rq, 0, False]
+        return free[0]
+
+    def close(self, slot=None):
+        """close(slot): the slot is free again (whatever it still held is dropped).  close(): the stage."""
+        if slot is None:
+            self.slots = {}
+            return super().close()
+        if self.slots.pop(slot, None) is not None and self.h:
+            E.check(self.lib.tt_tss_close(self.h, int(slot)))
+
+    def push_many(self, items, return_offsets=False):
+        """items = [(slot, chunk f32 [n] (device or host, n >= 0), flush)], distinct open slots -> what each emits (f32 on the stage's
+        device, possibly empty): ONE tt_tss_push, no synchronisation.  return_offsets=True: (outputs, offsets) with the chosen d_k of the
+        frames each slot ran as int32 tensors on the device (stretch.stream_offsets of them).  A flushed slot is finished: close() it to
+        free it."""
+        n = len(items)
+        if not 1 <= n <= self.max_streams or len({s for s, _, _ in items}) != n:
+            raise ValueError(f"push_many: {n} chunks for {len({s for s, _, _ in items})} slots (1 .. {self.max_streams} distinct slots)")
+        counts, frames = [], []
+        for slot, x, flush in items:
+            st = self.slots.get(slot)
+            if st is None or st[2]:
+                raise ValueError(f"push_many: slot {slot} is not open" if st is None else f"push_many: slot {slot} is finished")
+            if x.dim() != 1:
+                raise ValueError(f"push_many: slot {slot}: a chunk of shape {tuple(x.shape)}, expected [samples]")
+            counts.append(tsm.stream_ready(st[1], x.shape[0], st[0], flush))
+            frames.append(tsm.stream_offsets(st[1], x.shape[0], st[0], flush) if return_offsets else 0)
+        dev = self.device
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for _, x, _ in items] + [torch.zeros(1, device=dev)])
+        y = torch.empty(sum(counts) + 1, device=dev, dtype=torch.float32)
+        off = torch.empty(sum(frames) + 1, device=dev, dtype=torch.int32) if return_offsets else None
+        arr = C.c_int * n
+        E.check(self.lib.tt_tss_push(self.h, n, arr(*[int(s) for s, _, _ in items]), arr(*[int(x.shape[0]) for _, x, _ in items]),
+                                     arr(*[int(bool(f)) for _, _, f in items]), audio.data_ptr(), y.data_ptr(),
+                                     off.data_ptr() if return_offsets else None, E.stream_ptr()))
+        out, offs, o, f = [], [], 0, 0
+        for (slot, x, flush), c, k in zip(items, counts, frames):
+            st = self.slots[slot]
+            st[1] += x.shape[0]
+            st[2] = bool(flush)
+            out.append(y[o:o + c])
+            o += c
+            if return_offsets:
+                offs.append(off[f:f + k])
+                f += k
+        return (out, offs) if return_offsets else out
 
 
 class SilenceStage(_Handle):
