@@ -453,12 +453,20 @@ class _Common:
         """tts(text, **tts_kwargs) and where its words are -> (what tts returns, align.Alignment - a list of k of them for k > 1; None where
         tts returns no audio, i.e. on the other ranks of a sharded job).  The text is aligned as spoken (see align_many).  With sample_rate=
         the clip is aligned at 24 kHz and converted afterwards; the Alignment then counts samples of the returned audio and carries its
-        rate (.seconds() and .to_srt() use it)."""
+        rate (.seconds() and .to_srt() use it).
+        word_rates= (a list with one speaking rate per word of the text as spoken, None for a word left alone; or a dict {word index:
+        rate}; each in [0.5, 2.0]): single words or phrases slower or faster, SSML's <prosody rate>.  It goes with speaking_rate= (the rate
+        of everything else: the other words and the pauses) and pitch=.  The clip is rendered without post-processing and aligned at
+        24 kHz, which costs ONE EXTRA ALIGNER PASS; the words' spans become a stretch.RateMap (from_words; left in self.rate_maps), and the
+        usual chain runs with ONE time-stretch along that map, the pitch folded into every segment's rate: redaction -> stretch and the
+        one resampling -> pauses -> loudness -> sample rate.  The returned timings are those of the returned audio, aligned as always.
+        Single-rank instances only.  How natural a jump between neighbouring words sounds nobody has judged on a trained checkpoint."""
         if not isinstance(text, str):
             raise TypeError("tts_with_timings aligns the text with the audio: pass it as a str, not as token ids")
         self.load_aligner()  # (missing files are reported before anything renders)
         sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (the aligner reads 24 kHz: converted after it)
-        res = self.tts(text, **tts_kwargs)
+        word_rates = tsm.word_rates(tts_kwargs)
+        res = self.tts(text, **tts_kwargs) if word_rates is None else self._tts_at_word_rates(text, word_rates, tts_kwargs)
         out = res[0] if tts_kwargs.get("return_deterministic_state") else res
         if out is None:
             return res, None
@@ -471,8 +479,38 @@ class _Common:
             res = (out,) + tuple(res[1:]) if tts_kwargs.get("return_deterministic_state") else out
         return res, (als if isinstance(out, (list, tuple)) else als[0])
 
+    def _tts_at_word_rates(self, text, word_rates, tts_kwargs):
+        """tts(text, **tts_kwargs) with its post-processing run along a rate map of the words -> what tts returns."""
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("tts_with_timings: word_rates is not available on a sharded job (the ranks that return no audio have nothing to "
+                             "align); build a single-rank instance")
+        kw = dict(tts_kwargs)
+        rate, level = tsm.speaking_rate(kw), loud.level_options(kw)
+        pitch = rs.options(kw, rate)[0]
+        pauses = sil.options(kw)
+        res = self.tts(text, **kw)  # (rendered and redacted, nothing else)
+        state = bool(kw.get("return_deterministic_state"))
+        out = res[0] if state else res
+        clips = list(out) if isinstance(out, (list, tuple)) else [out]
+        als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
+        self.rate_maps = [tsm.RateMap.from_words(al, word_rates, base=1.0 if rate is None else rate) for al in als]
+        clips = self._voiced(self._at_map(clips, self.rate_maps, pitch), None, None, level, None, pauses)
+        out = clips if isinstance(out, (list, tuple)) else clips[0]
+        return (out,) + tuple(res[1:]) if state else out
+
     # ------------------------------------------------------------------ speaking rate: WSOLA time-stretch of finished clips
     stretcher = None
+    warp_stretcher = None
+
+    def load_warp_stretch(self, max_samples=0):
+        """The time-stretch along a rate map (stages.WarpStretchStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.TSM_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the time-stretch can take ({E.TSM_MAX_SAMPLES})")
+        if self.warp_stretcher is None or self.warp_stretcher.max_samples < max_samples:
+            if self.warp_stretcher is not None:
+                self.warp_stretcher.close()
+            self.warp_stretcher = stages.WarpStretchStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE), device=self.device)
+        return self.warp_stretcher
 
     def load_stretch(self, max_samples=0):
         """The time-stretch stage (stages.TimeStretchStage), built on first use for clips of 30 s and rebuilt for a longer one."""
@@ -485,15 +523,22 @@ class _Common:
         return self.stretcher
 
     @torch.no_grad()
-    def stretch_many(self, audios, rates=None, durations=None, return_map=False):
+    def stretch_many(self, audios, rates=None, durations=None, return_map=False, rate_maps=None):
         """The same speech at another speed and the same pitch: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> the stretched
         clips, each in the shape and on the device it came in.  Give exactly one of `rates` (2.0: twice as fast; one value or one per clip,
         each in [0.5, 2.0]) and `durations` (seconds the clip shall last: rate = n / (duration * 24000)).  All clips go through ONE device
         call per 16.  return_map=True: also, per clip, int64 [K, 2] anchors (output sample, input sample) of the frames the output was
-        assembled from (stretch.anchors), with which a time in the original clip is carried over to the stretched one."""
+        assembled from (stretch.anchors), with which a time in the original clip is carried over to the stretched one.
+        rate_maps=[...] instead of rates / durations: a speaking rate that changes inside the clip - per clip a stretch.RateMap
+        (from_segments, from_anchors, from_words) or a list of (start_seconds, rate); ONE device call per 16 again (csrc/tsm_warp.hip), and
+        a map of one segment gives the bits of `rates`."""
         audios = list(audios)
+        if rate_maps is not None:
+            if rates is not None or durations is not None:
+                raise ValueError("stretch: give exactly one of rate, duration and rate_map")
+            return self._stretch_maps(audios, rate_maps, return_map)
         if (rates is None) == (durations is None):
-            raise ValueError("stretch: give exactly one of rate and duration")
+            raise ValueError("stretch: give exactly one of rate, duration and rate_map")
         given = rates if durations is None else durations
         given = list(given) if isinstance(given, (list, tuple)) else [given] * len(audios)
         if len(given) != len(audios):
@@ -510,9 +555,79 @@ class _Common:
         self._stretch_s = time.perf_counter() - t0
         return (out, [tsm.anchors(rq, off) for rq, (_, off) in zip(rqs, res)]) if return_map else out
 
-    def stretch(self, audio, rate=None, duration=None):
+    def stretch(self, audio, rate=None, duration=None, rate_map=None):
         """stretch_many of one clip -> the stretched clip."""
-        return self.stretch_many([audio], rates=rate, durations=duration)[0]
+        return self.stretch_many([audio], rates=rate, durations=duration, rate_maps=None if rate_map is None else [rate_map])[0]
+
+    def _stretch_maps(self, audios, rate_maps, return_map):
+        """stretch_many along rate maps."""
+        rate_maps = list(rate_maps)
+        if len(rate_maps) != len(audios):
+            raise ValueError(f"stretch: {len(audios)} clips with {len(rate_maps)} rate maps")
+        for i, a in enumerate(audios):
+            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
+                raise ValueError(f"stretch: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+        maps = [tsm.rate_map(a.shape[-1], m) for a, m in zip(audios, rate_maps)]
+        if not audios:
+            return ([], []) if return_map else []
+        t0 = time.perf_counter()
+        res = self.load_warp_stretch(max(a.shape[-1] for a in audios)).stretch_many([a.reshape(-1) for a in audios], [m.table for m in maps])
+        out = [y.to(a.device).reshape(a.shape[:-1] + (-1,)) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
+        self._stretch_s = time.perf_counter() - t0
+        return (out, [m.anchors(off) for m, (_, off) in zip(maps, res)]) if return_map else out
+
+    @torch.no_grad()
+    def retime_many(self, audios, anchors, durations=None, return_map=False):
+        """The dubbing call: every clip stretched so that given moments of it sound at given times.  audios as in stretch_many; anchors: per
+        clip a list of (src_seconds, dst_seconds) - what is at src in the clip is to sound at dst in the result, both increasing, (0, 0)
+        implied; durations (None, one value or one per clip; seconds): the final anchor (the clip's end, duration).  Between two anchors
+        the rate is constant and must lie in [0.5, 2.0] (ValueError names the pair); behind a last anchor inside the clip the rest runs
+        at rate 1.0.  The plan lands within (dst_(i+1) - m_i) / 65536 + 1 samples of every dst (stretch.RateMap.from_anchors); the audio itself
+        sits where WSOLA puts it, within its search range (+-256 samples, 10.7 ms) of that, as for a constant rate.  ONE device call per
+        16 clips.  return_map=True: also the anchors of the frames, as in stretch_many."""
+        audios, anchors = list(audios), list(anchors)
+        if len(anchors) != len(audios):
+            raise ValueError(f"retime: {len(audios)} clips with {len(anchors)} anchor lists")
+        durations = list(durations) if isinstance(durations, (list, tuple)) else [durations] * len(audios)
+        if len(durations) != len(audios):
+            raise ValueError(f"retime: {len(audios)} clips with {len(durations)} durations")
+        to_s = lambda t: int(round(float(t) * E.TSM_SAMPLE_RATE))
+        maps = []
+        for i, (a, pts, d) in enumerate(zip(audios, anchors, durations)):
+            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
+                raise ValueError(f"retime: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+            pts = [(to_s(s_), to_s(t)) for s_, t in (pts or [])]
+            if d is not None:
+                if not float(d) > 0:
+                    raise ValueError(f"retime: duration={d} must be positive (seconds)")
+                pts.append((a.shape[-1], to_s(d)))
+            if not pts:
+                raise ValueError(f"retime: clip {i}: give anchors, a duration or both")
+            maps.append(tsm.RateMap.from_anchors(a.shape[-1], pts))
+        return self._stretch_maps(audios, maps, return_map)
+
+    def retime(self, audio, anchors=None, duration=None, return_map=False):
+        """retime_many of one clip -> the retimed clip (return_map=True: and its anchors)."""
+        res = self.retime_many([audio], [anchors], durations=duration, return_map=return_map)
+        return (res[0][0], res[1][0]) if return_map else res[0]
+
+    def _at_map(self, clips, maps, semitones):
+        """The clips of a tts call (a list) along their rate maps (speaking rates) at pitch `semitones` (None: 0): ONE stretch for all of
+        them along the maps with the pitch folded into every segment, rq_i -> round(rq_i 65536 / pq), and ONE resampling by (pq, 65536);
+        their time in timings['stretch_s'] / ['pitch_s'].  A clip whose map is rate 1.0 throughout is not stretched."""
+        pq = E.RS_PITCH_ONE if semitones is None else rs.pitch(semitones)[0]
+        maps = [m.with_pitch(pq) for m in maps]
+        self._stretch_s = 0.0
+        seq = list(clips)
+        todo = [i for i, m in enumerate(maps) if m.rqs != [E.TSM_RATE_ONE]]
+        if todo:
+            for i, y in zip(todo, self.stretch_many([seq[i] for i in todo], rate_maps=[maps[i] for i in todo])):
+                seq[i] = y
+            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+        if pq != E.RS_PITCH_ONE:
+            seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE)] * len(seq), False)
+            self.timings = dict(getattr(self, "timings", None) or {}, pitch_s=self._resample_s)
+        return seq
 
     stream_stretcher = None
     stream_pitch_resampler = None

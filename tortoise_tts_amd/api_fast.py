@@ -341,6 +341,7 @@ class TextToSpeech(_Common):
                    **hf_generate_kwargs):
         self._single("tts_stream")
         tsm.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        tsm.refuse_word_rates(hf_generate_kwargs, "tts_stream")
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
@@ -474,6 +475,7 @@ class TextToSpeech(_Common):
         whole-clip chain (stretch / shift_pitch, then resample) of the 24 kHz stream; the audio lags by 1407 samples (58.6 ms) until the
         last piece flushes it, so early pieces may be short or empty.  None, 1.0 and 0: nothing is built, today's bits."""
         tsm.refuse_streaming(kwargs, "open_stream")
+        tsm.refuse_word_rates(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
@@ -647,6 +649,7 @@ class TextToSpeech(_Common):
         None allowed): that text's pieces at another rate than 24 kHz, see open_stream.  stream_speaking_rate= and stream_pitch= (one value
         or a list with one per text, None allowed): that text's pieces at another speaking rate and pitch, see open_stream."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
+        tsm.refuse_word_rates(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
         sil.refuse_streaming(kwargs, "tts_stream_many")

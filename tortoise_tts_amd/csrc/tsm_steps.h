@@ -97,6 +97,16 @@ __device__ __forceinline__ void tsm_fetch(float (&pre)[kTsmPre], int k, int rq, 
   }
 }
 
+// region from a base the kernel computed itself (a rate map's nominal position, tsm_warp.hip): the samples x[base ..), read through `sample`
+template <class Sample>
+__device__ __forceinline__ void tsm_fetch_at(float (&pre)[kTsmPre], int base, int t, Sample sample) {
+#pragma unroll
+  for (int e = 0; e < kTsmPre; ++e) {
+    const int i = e * kTsmThreads + t;
+    pre[e] = i < kTsmRegion ? sample(base + i) : 0.f;
+  }
+}
+
 // region, the common case: the whole region lies inside the input, at p[0 .. kTsmRegion) - one base that is uniform over the workgroup and
 // seven plain loads, no bounds test per sample (the tests of tsm_fetch cost the chain some 0.3 us per frame).  The pad entry 1663 repeats
 // the last sample instead of holding 0: no step reads it (the search reads reg_s / sh_s below 1280, the overlap-add and the template

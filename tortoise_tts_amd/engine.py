@@ -455,6 +455,19 @@ _TSS_PROTOS = {
 }
 TSS_ABI_VERSION = 1
 TSS_LOOK, TSS_HIST, TSS_MAX_STREAMS = 1407, 1664, 64  # TT_TSS_LOOK, TT_TSS_HIST, TT_TSS_MAX_STREAMS
+# include/tortoise_mi355x_tsw.h: the time-stretch along a rate map, a speaking rate that changes inside the clip (its own header and version)
+_TSW_PROTOS = {
+    "tt_tsw_abi_version": (_i, []),
+    "tt_tsw_plan": (_i, [_i, _i, _ip, _ip, _ip]),
+    "tt_tsw_out_samples": (_i, [_i, _i, _ip]),
+    "tt_tsw_frames": (_i, [_i, _i, _ip]),
+    "tt_tsw_create": (_i, [_i, _i, _i, C.POINTER(vp)]),
+    "tt_tsw_destroy": (None, [vp]),
+    "tt_tsw_stretch": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+TSW_ABI_VERSION = 1
+TSW_MAX_SEGMENTS, TSW_MIN_SEGMENT = 64, 2  # TT_TSW_MAX_SEGMENTS, TT_TSW_MIN_SEGMENT
+TSW_OK, TSW_EMPTY, TSW_REFUSED = 0, 1, 2
 # include/tortoise_mi355x_sil.h: speech regions, edge trimming and pause capping of rendered clips (its own header and version)
 _SIL_PROTOS = {
     "tt_sil_abi_version": (_i, []),
@@ -554,7 +567,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -594,6 +607,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_rss.h is version %d in the library, %d in Python" % (lib.tt_rss_abi_version(), RSS_ABI_VERSION))
     if lib.tt_tss_abi_version() != TSS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_tss.h is version %d in the library, %d in Python" % (lib.tt_tss_abi_version(), TSS_ABI_VERSION))
+    if lib.tt_tsw_abi_version() != TSW_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_tsw.h is version %d in the library, %d in Python" % (lib.tt_tsw_abi_version(), TSW_ABI_VERSION))
     if lib.tt_sil_abi_version() != SIL_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:

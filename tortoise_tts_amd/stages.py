@@ -583,6 +583,59 @@ class TimeStretchStage(_Handle):
         return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
 
 
+class WarpStretchStage(_Handle):
+    """WSOLA time-stretch along a rate map (csrc/tsm_warp.hip, include/tortoise_mi355x_tsw.h): ragged batches, each clip with its own table
+    of segments (stretch.RateMap.table), one tt_tsw_stretch call per max_clips clips, every clip's result bit-identical to stretching it
+    alone; the table (0, 0, rq) gives TimeStretchStage's bits."""
+
+    api = "tt_tsw"
+
+    def __init__(self, max_samples, max_clips=16, max_segments=E.TSW_MAX_SEGMENTS, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips, self.max_segments = int(max_samples), int(max_clips), int(max_segments)
+        self._create(self.max_samples, self.max_clips, self.max_segments)
+
+    def stretch_many(self, clips, tables):
+        """clips f32 [n_i] (device or host) and the table [(m, a, rq), ...] of each -> one (y f32 [n_out_i] on the stage's device, chosen
+        offsets int32 [K_i] on the host) per clip.  ValueError for an empty clip, a clip beyond the handle or a table that breaks a rule."""
+        if len(clips) != len(tables):
+            raise ValueError(f"{len(clips)} clips with {len(tables)} rate maps")
+        for i, (x, tb) in enumerate(zip(clips, tables)):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the time-stretch stage's capacity ({self.max_samples})")
+            if not 1 <= len(tb) <= self.max_segments:
+                raise ValueError(f"clip {i}: a rate map of {len(tb)} segments (1 .. {self.max_segments})")
+            if not tsm.table_out_samples(x.shape[0], tb):
+                raise ValueError(f"clip {i}: the rate map's table breaks a rule of include/tortoise_mi355x_tsw.h for a clip of {x.shape[0]} samples")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], tables[g:g + self.max_clips])
+        return out
+
+    def _group(self, clips, tables):
+        n, dev = len(clips), self.device
+        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
+        so = np.concatenate(([0], np.cumsum([len(tb) for tb in tables]))).astype(np.int32)
+        oo = np.concatenate(([0], np.cumsum([tsm.table_out_samples(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
+        fo = np.concatenate(([0], np.cumsum([tsm.table_frames(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
+        seg = np.asarray([v for tb in tables for row in tb for v in row], dtype=np.int32)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, so, oo, fo, seg])).to(dev)
+        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
+        ri = torch.zeros(int(fo[-1]) + n, device=dev, dtype=torch.int32)  # (offsets | status): one copy back
+        hp, ip, w = host.data_ptr(), ri.data_ptr(), 4 * (n + 1)
+        E.check(self.lib.tt_tsw_stretch(self.h, n, audio.data_ptr(), hp, hp + 4 * w, hp + w, y.data_ptr(), hp + 2 * w, ip, hp + 3 * w,
+                                        ip + 4 * int(fo[-1]), E.stream_ptr()))
+        ri = ri.cpu()
+        status = ri[int(fo[-1]):].tolist()
+        if any(st != E.TSW_OK for st in status):
+            raise RuntimeError(f"time-stretch along a rate map: the device stage refused clips it was handed (status {status})")
+        return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
+
+
 class ResampleStage(_Handle):
     """Band-limited resampling at an arbitrary ratio (csrc/resample.hip, include/tortoise_mi355x_rs.h): ragged batches, each clip with its own
     (P, Q) input samples per output sample, one tt_rs_resample call per max_clips clips, every clip's result bit-identical to resampling it
