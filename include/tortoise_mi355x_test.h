@@ -238,6 +238,15 @@ int tt_op_cls_conv(int dtype, int cin, int cout, int stride, const float* x, int
 int tt_op_cls_attention(int dtype, const float* qkv, int n, int nq, void* out, void* stream);
 int tt_op_cls_head(const float* x, const float* w, const float* b, float* logits, float* emb, void* stream);
 
+/* Formant correction staged (csrc/formant.hip, include/tortoise_mi355x_fmt.h; `h` is a tt_fmt handle).  tt_op_fmt_run is tt_fmt_run with three
+ * optional outputs, each clip's at stage_offsets[c] (host array, in units of one frame's gains: a multiple of 4): spectrum f32 [T][2 * bins_pad]
+ * (re, im interleaved, at spectrum + 2 * stage_offsets[c]), logmag f32 [T][bins_pad] (step 2), gains f32 [T][bins_pad] (step 4, clamped).
+ * tt_op_fmt_synth runs steps 5 to 7 alone from a given spectrum and given gains in those layouts. */
+int tt_op_fmt_run(void* h, const float* wav, const long long* clip_offsets, const int* clip_lengths, const int* warp_index, int n_clips, float* out,
+                  const long long* out_offsets, float* spectrum, float* logmag, float* gains, const long long* stage_offsets, void* stream);
+int tt_op_fmt_synth(void* h, const float* spectrum, const float* gains, const long long* stage_offsets, const int* clip_lengths, int n_clips,
+                    float* out, const long long* out_offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ from . import align
 from . import dist as tdist
 from . import engine as E
 from . import stages
+from . import formant as fmt
 from . import loudness as loud
 from . import resample as rs
 from . import silence as sil
@@ -459,7 +460,7 @@ class _Common:
         of everything else: the other words and the pauses) and pitch=.  The clip is rendered without post-processing and aligned at
         24 kHz, which costs ONE EXTRA ALIGNER PASS; the words' spans become a stretch.RateMap (from_words; left in self.rate_maps), and the
         usual chain runs with ONE time-stretch along that map, the pitch folded into every segment's rate: redaction -> stretch and the
-        one resampling -> pauses -> loudness -> sample rate.  The returned timings are those of the returned audio, aligned as always.
+        one resampling -> formants -> pauses -> loudness -> sample rate.  The returned timings are those of the returned audio, aligned as always.
         Single-rank instances only.  How natural a jump between neighbouring words sounds nobody has judged on a trained checkpoint."""
         if not isinstance(text, str):
             raise TypeError("tts_with_timings aligns the text with the audio: pass it as a str, not as token ids")
@@ -487,14 +488,14 @@ class _Common:
         kw = dict(tts_kwargs)
         rate, level = tsm.speaking_rate(kw), loud.level_options(kw)
         pitch = rs.options(kw, rate)[0]
-        pauses = sil.options(kw)
+        pauses, formants = sil.options(kw), fmt.options(kw, pitch)
         res = self.tts(text, **kw)  # (rendered and redacted, nothing else)
         state = bool(kw.get("return_deterministic_state"))
         out = res[0] if state else res
         clips = list(out) if isinstance(out, (list, tuple)) else [out]
         als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
         self.rate_maps = [tsm.RateMap.from_words(al, word_rates, base=1.0 if rate is None else rate) for al in als]
-        clips = self._voiced(self._at_map(clips, self.rate_maps, pitch), None, None, level, None, pauses)
+        clips = self._voiced(self._at_map(clips, self.rate_maps, pitch), None, None, level, None, pauses, formants)
         out = clips if isinstance(out, (list, tuple)) else clips[0]
         return (out,) + tuple(res[1:]) if state else out
 
@@ -806,18 +807,26 @@ class _Common:
         return StreamResampler(self.load_stream_resample(), P, Q, int(from_rate))
 
     @torch.no_grad()
-    def shift_pitch_many(self, audios, semitones, return_info=False):
+    def shift_pitch_many(self, audios, semitones, return_info=False, formants=None, formant_lifter_ms=None, formant_max_gain_db=None):
         """The same speech at another pitch and the same duration: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), semitones
         (+: up; one value or one per clip, each within +-12) -> the shifted clips.  Two batched device calls: a time-stretch at rate
         65536^2 / pq (rounded; pq = round(2^(s/12) 65536)), then a resampling by (pq, 65536), which undoes the stretch's change of duration
         (to within the rounding of the two lengths) and moves every frequency by 2^(s/12).  Pitch by resampling moves the formants with
         the pitch: it stays natural for a few semitones, and nobody has rendered a trained checkpoint through it.  0 semitones returns the
-        clip as it is.  return_info=True: also the sample peak of every returned clip."""
+        clip as it is.  return_info=True: also the sample peak of every returned clip.  formants='keep': a third batched call, the cepstral
+        envelope correction at warp 2^(s/12) (shift_formants_many's kernel and options), puts the formants back where they were; the peaks
+        of return_info are then those of the corrected clips.  None or 'follow': the two calls alone."""
         audios = self._level_clips(audios, "shift_pitch")
         semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
         if len(semis) != len(audios):
             raise ValueError(f"shift_pitch: {len(audios)} clips with {len(semis)} pitches")
         plans = [rs.pitch(s_) for s_ in semis]
+        keep = fmt.mode(formants)
+        corr = [fmt.params(s_, keep, None, formant_lifter_ms, formant_max_gain_db) for s_ in semis]
+        if any(p is not None for p in corr):
+            out = self.shift_pitch_many(audios, semis)
+            out = self._correct_formants(out, corr)
+            return (out, [float(a.abs().max()) for a in out]) if return_info else out
         t0 = time.perf_counter()
         todo = [i for i, (pq, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
         mid = list(audios)
@@ -828,9 +837,72 @@ class _Common:
         self._resample_s = time.perf_counter() - t0
         return res
 
-    def shift_pitch(self, audio, semitones):
-        """shift_pitch_many of one clip -> the shifted clip."""
-        return self.shift_pitch_many([audio], semitones)[0]
+    def shift_pitch(self, audio, semitones, formants=None, **options):
+        """shift_pitch_many of one clip -> the shifted clip (options: formant_lifter_ms, formant_max_gain_db)."""
+        return self.shift_pitch_many([audio], semitones, formants=formants, **options)[0]
+
+    # ------------------------------------------------------------------ formants: the cepstral envelope correction
+    formant_stage = None
+
+    def load_formant(self, max_samples=0, q=None, max_gain_db=None, clips=1):
+        """The formant stage (stages.FormantStage), sized from the batch it is first asked for: the longest clip rounded up to whole
+        seconds and min(clips, 16) clips per call, 13,056 bytes of intermediates per frame (94 frames a second) and clip slot - 12 MB for
+        one clip of 10 s, 196 MB for sixteen.  It is rebuilt, never smaller, for a longer clip, a larger batch or another lifter or clamp."""
+        q = fmt.lifter_q() if q is None else int(q)
+        g = fmt.max_gain_db() if max_gain_db is None else float(max_gain_db)
+        need = max(-(-int(max_samples) // fmt.SAMPLE_RATE), 1) * fmt.SAMPLE_RATE
+        slots = max(1, min(int(clips), E.FMT_MAX_CLIPS))
+        st = self.formant_stage
+        if st is None or st.max_samples < need or st.max_clips < slots or st.q != q or st.max_gain_db != g:
+            if st is not None:
+                need, slots = max(need, st.max_samples), max(slots, st.max_clips)
+                st.close()
+            self.formant_stage = stages.FormantStage(need, q, g, max_clips=slots, device=self.device)
+        return self.formant_stage
+
+    def _correct_formants(self, audios, plans):
+        """audios (validated) with one fmt.Params or None each -> the clips, each in the shape and on the device it came in; the clips of
+        one (lifter, clamp) go through ONE device call per 16.  None is no call: the clip is returned as it is."""
+        t0 = time.perf_counter()
+        out = list(audios)
+        for key in sorted({(p.q, p.max_gain_db) for p in plans if p is not None}):
+            todo = [i for i, p in enumerate(plans) if p is not None and (p.q, p.max_gain_db) == key]
+            for i in todo:
+                if audios[i].shape[-1] < fmt.MIN_SAMPLES:
+                    raise ValueError(f"formants: clip {i} has {audios[i].shape[-1]} samples; the correction needs at least {fmt.MIN_SAMPLES}")
+            stage = self.load_formant(max(audios[i].shape[-1] for i in todo), *key, clips=len(todo))
+            res = stage.correct_many([audios[i].reshape(-1) for i in todo], [plans[i].alpha for i in todo])
+            for i, y in zip(todo, res):
+                out[i] = y.to(audios[i].device).reshape(audios[i].shape)
+        self._formant_s = time.perf_counter() - t0
+        return out
+
+    @torch.no_grad()
+    def shift_formants_many(self, audios, semitones, formant_lifter_ms=None, formant_max_gain_db=None):
+        """The same speech at the same pitch and duration with its formants moved: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device,
+        n >= 513), semitones (+: up, a smaller speaker; one value or one per clip, each within +-12) -> the clips, each in the shape and on
+        the device it came in.  The spectral envelope (the first formant_lifter_ms of the cepstrum, 2 ms by default) of every frame is read
+        at 2^(-f / 12) times each frequency and the frame's spectrum gets the difference as a gain of at most formant_max_gain_db (24 dB);
+        the harmonics stay where they are (csrc/formant.hip - DESIGN.md 5.32).  All clips go through ONE device call per 16.  0 semitones
+        returns the clip as it is.  Nobody has listened to a trained checkpoint through it."""
+        audios = self._level_clips(audios, "shift_formants")
+        semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
+        if len(semis) != len(audios):
+            raise ValueError(f"shift_formants: {len(audios)} clips with {len(semis)} shifts")
+        return self._correct_formants(audios, [fmt.params(None, False, f, formant_lifter_ms, formant_max_gain_db) for f in semis])
+
+    def shift_formants(self, audio, semitones, **options):
+        """shift_formants_many of one clip -> the clip with its formants moved."""
+        return self.shift_formants_many([audio], semitones, **options)[0]
+
+    def _at_formants(self, clips, params):
+        """The clips a tts call is about to return ({winner: clip} or a list) corrected with `params` (formant.Params): one call for all of
+        them, its time in timings['formant_s']."""
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        seq = self._correct_formants(seq, [params] * len(seq))
+        self.timings = dict(getattr(self, "timings", None) or {}, formant_s=self._formant_s)
+        return dict(zip(keys, seq)) if keys is not None else seq
 
     def _at_pitch(self, clips, rate, semitones):
         """The clips a tts call is about to return ({winner: clip} or a list) at speaking_rate `rate` (None: 1.0) and pitch `semitones`: ONE
@@ -932,13 +1004,16 @@ class _Common:
         self.timings = dict(getattr(self, "timings", None) or {}, silence_s=self._silence_s)
         return dict(zip(keys, seq)) if keys is not None else seq
 
-    def _voiced(self, clips, rate, pitch, level, sample_rate, pauses=None):
-        """The chain behind redaction: speaking rate and pitch together, then the pauses (silence.Params: durations are then delivered
-        seconds), then the level (at 24 kHz: the loudness gate sees the final content), then the output sample rate."""
+    def _voiced(self, clips, rate, pitch, level, sample_rate, pauses=None, formants=None):
+        """The chain behind redaction: speaking rate and pitch together, then the formants (formant.Params), then the pauses
+        (silence.Params: durations are then delivered seconds), then the level (at 24 kHz: the loudness gate sees the final content), then
+        the output sample rate."""
         if pitch is not None:
             clips = self._at_pitch(clips, rate, pitch)
         elif rate is not None:
             clips = self._at_rate(clips, rate)
+        if formants is not None:
+            clips = self._at_formants(clips, formants)
         if pauses is not None:
             clips = self._at_pauses(clips, pauses)
         if level is not None:
@@ -970,7 +1045,11 @@ class TextToSpeech(_Common):
     most 0.05 s of silence before and 0.1 s after the speech; or a dict of trim_many's options; None or False: off) and `max_pause`
     (seconds; every longer pause is shortened to it; None: off) - after the rate and the pitch and before the level (trim, csrc/silence.hip
     - DESIGN.md 5.28; the defaults were chosen from the code, nobody has run a trained checkpoint's audio through them; status and seconds
-    removed are left in `silence_info`)."""
+    removed are left in `silence_info`); `formants` ('keep': after a `pitch` the formants are put back where they were; None or 'follow':
+    they move with the pitch) and `formant_shift` (semitones, +-12: the formants alone move up, with or without a pitch; the combined
+    envelope warp 2^((pitch - formant_shift) / 12) must stay in 0.5 .. 2), with the options `formant_lifter_ms` (2) and
+    `formant_max_gain_db` (24) - after the rate and the pitch and before the pauses (shift_formants, csrc/formant.hip - DESIGN.md 5.32;
+    downward shifts are corrected less, and nobody has listened to a trained checkpoint through it)."""
 
     redacts_brackets = True  # tts() cuts [bracketed] passages out of its clips (enable_redaction)
 
@@ -1276,8 +1355,8 @@ class TextToSpeech(_Common):
             self._redact_s = 0.0
             wavs = self._redact_clips(wavs, redact)
             self.timings["redact_s"] = self._redact_s
-        # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> pauses -> level -> output sample rate
-        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate, o.pauses)
+        # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> formants -> pauses -> level -> output sample rate
+        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate, o.pauses, o.formants)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -1296,13 +1375,14 @@ class TextToSpeech(_Common):
         loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
         pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
         96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
-        pitch and before the level, in ONE call (trim_many)."""
+        pitch and before the level, in ONE call (trim_many).  formants= / formant_shift= correct every clip's spectral envelope after the
+        pitch and before the pauses, in ONE call (shift_formants_many)."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
-        pauses = sil.options(kwargs)
+        pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
-        return self._voiced(out, rate, pitch, level, sample_rate, pauses)
+        return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, verbose=False, **kwargs):
@@ -1391,7 +1471,7 @@ class TextToSpeech(_Common):
         noise = hf.pop("noise_override", None) or {}
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
         pitch, sample_rate = rs.options(hf, speaking_rate)
-        pauses = sil.options(hf)
+        pauses, formants = sil.options(hf), fmt.options(hf, pitch)
         plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
         if not 0 <= args["cvvp_amount"] <= 1:
@@ -1402,7 +1482,7 @@ class TextToSpeech(_Common):
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
             solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
-            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses)
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses, formants=formants)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

@@ -33,6 +33,7 @@ import torch
 
 from . import engine as E
 from . import stages
+from . import formant as fmt
 from . import loudness as loud
 from . import resample as rs
 from . import silence as sil
@@ -197,7 +198,7 @@ class TextToSpeech(_Common):
         self._single("tts")
         speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
         pitch, sample_rate = rs.options(hf_generate_kwargs, speaking_rate)
-        pauses = sil.options(hf_generate_kwargs)
+        pauses, formants = sil.options(hf_generate_kwargs), fmt.options(hf_generate_kwargs, pitch)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -207,7 +208,7 @@ class TextToSpeech(_Common):
         self.last_codes = codes
         latents = self.ar.latents(cond, text_tokens, codes)          # api_fast.py:510-514 (return_latent=True)
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
-        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate, pauses)[0]  # (rate and pitch -> pauses -> level -> sample rate)
+        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate, pauses, formants)[0]  # (rate and pitch -> formants -> pauses -> level -> sample rate)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
@@ -219,12 +220,13 @@ class TextToSpeech(_Common):
         loudness= (LUFS; with true_peak= and limit=): after that, every clip is brought to the target, all of them in ONE normalize_many call.
         pitch= (semitones, +-12) goes with the speaking rate - ONE stretch and ONE resampling for all clips - and sample_rate= (Hz, 8000 ..
         96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
-        pitch and before the level, in ONE call (trim_many)."""
+        pitch and before the level, in ONE call (trim_many).  formants= / formant_shift= correct every clip's spectral envelope after the
+        pitch and before the pauses, in ONE call (shift_formants_many)."""
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
-        pauses = sil.options(kwargs)
+        pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
-        return self._voiced(out, rate, pitch, level, sample_rate, pauses)
+        return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()
     def _tts_many(self, texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs):
@@ -345,6 +347,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        fmt.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         stream_rate = rs.stream_options(hf_generate_kwargs)
         stream_voice = tsm.stream_options(hf_generate_kwargs)
@@ -479,6 +482,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
+        fmt.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
         stream_rate = rs.stream_options(kwargs)  # (validated before a slot is taken)
         stream_voice = tsm.stream_options(kwargs)
@@ -653,6 +657,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
         sil.refuse_streaming(kwargs, "tts_stream_many")
+        fmt.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):

@@ -216,6 +216,22 @@ class MelTables(C.Structure):
 # include/tortoise_mi355x_mel.h, order == tt_mel_struct_size(which)
 MEL_STRUCTS = [MelConfig, MelTables]
 
+FMT_MAX_CLIPS, FMT_MAX_WARPS, FMT_Q_PAD = 16, 16, 64  # TT_FMT_MAX_CLIPS, TT_FMT_MAX_WARPS, TT_FMT_Q_PAD
+
+
+class FmtConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_fft", "hop", "bins_pad", "q")] + [("max_gain_db", C.c_float)] + [
+        (n, C.c_int) for n in ("max_samples", "max_clips", "n_warps")]
+
+
+class FmtTables(C.Structure):
+    _fields_ = [(n, vp) for n in ("basis", "inverse", "cepstrum", "warps")]
+
+
+# include/tortoise_mi355x_fmt.h, order == tt_fmt_struct_size(which)
+FMT_STRUCTS = [FmtConfig, FmtTables]
+FMT_ABI_VERSION = 1
+
 class GemmDesc(C.Structure):
     """tt_op_gemm_desc (include/tortoise_mi355x_test.h): every GEMM form of the operator-level test entry tt_op_gemm_ex."""
     _fields_ = [("A", vp), ("W", vp), ("A2", vp), ("a2_slot", vp), ("a2_slot_stride", C.c_size_t)] + [
@@ -484,6 +500,15 @@ SIL_SAMPLE_RATE = 24000
 SIL_MAX_SAMPLES, SIL_MAX_CLIPS = 8388608, 64
 SIL_MAX_FRAMES_PARAM = 6000
 SIL_OK, SIL_UNCHANGED, SIL_SILENT, SIL_EMPTY, SIL_REFUSED = 0, 1, 2, 3, 4
+# include/tortoise_mi355x_fmt.h: formant-preserving pitch, the cepstral envelope correction (its own header and version, same library)
+_FMT_PROTOS = {
+    "tt_fmt_abi_version": (_i, []),
+    "tt_fmt_struct_size": (_sz, [_i]),
+    "tt_fmt_create": (_i, [C.POINTER(FmtConfig), C.POINTER(FmtTables), C.POINTER(vp)]),
+    "tt_fmt_destroy": (None, [vp]),
+    "tt_fmt_frames": (_i, [vp, _i]),
+    "tt_fmt_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
+}
 # include/tortoise_mi355x_solver.h: DDIM / DPM-Solver++(2M) on a tt_diff handle (its own header and version, same library)
 _SOLVER_PROTOS = {
     "tt_solver_abi_version": (_i, []),
@@ -548,6 +573,8 @@ _TEST_PROTOS = {
     "tt_op_cls_conv": (_i, [_i, _i, _i, _i, vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "tt_op_cls_attention": (_i, [_i, vp, _i, _i, vp, vp]),
     "tt_op_cls_head": (_i, [vp, vp, vp, vp, vp, vp]),
+    "tt_op_fmt_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp, vp, vp, C.POINTER(_ll), vp]),
+    "tt_op_fmt_synth": (_i, [vp, vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
 }
 
 _lib = None
@@ -567,7 +594,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -595,6 +622,12 @@ def load_library():
         want = lib.tt_mel_struct_size(i)
         if C.sizeof(st) != want:
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    for i, st in enumerate(FMT_STRUCTS):
+        want = lib.tt_fmt_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    if lib.tt_fmt_abi_version() != FMT_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_fmt.h is version %d in the library, %d in Python" % (lib.tt_fmt_abi_version(), FMT_ABI_VERSION))
     if lib.tt_ctc_abi_version() != CTC_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_ctc.h is version %d in the library, %d in Python" % (lib.tt_ctc_abi_version(), CTC_ABI_VERSION))
     if lib.tt_tsm_abi_version() != TSM_ABI_VERSION:

@@ -52,7 +52,8 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     loudness= (LUFS; with true_peak= and limit=, see TextToSpeech.normalize_many) brings the reading to a level: loudness_scope='chunk' (the
     default) every chunk to the target, in one normalize_many call per rank - the level no longer moves from chunk to chunk;
     loudness_scope='whole' one gain for the concatenation.
-    pitch= goes to the chunks' calls with speaking_rate=.  sample_rate= (Hz, 8000 .. 96000) is applied here, last: every chunk is converted
+    pitch= goes to the chunks' calls with speaking_rate=, and so do formants= ('keep') / formant_shift= with their options: every chunk's
+    spectral envelope is corrected after its pitch shift and before its pauses, with the same warp for all chunks.  sample_rate= (Hz, 8000 .. 96000) is applied here, last: every chunk is converted
     from 24 kHz in one call, after the level and after the alignment, whose positions then count samples of the returned audio (the
     Alignment carries that rate).
     trim_silence= / max_pause= go to the chunks' calls.  pause= (seconds; None: off) sets the silence between two chunks: every chunk is cut

@@ -912,6 +912,87 @@ class SilenceStage(_Handle):
         return out
 
 
+class FormantStage(_Handle):
+    """Formant-preserving pitch: the cepstral envelope correction of finished clips at 24 kHz (csrc/formant.hip,
+    include/tortoise_mi355x_fmt.h): ragged batches, each clip with its own warp alpha, one tt_fmt_run call per max_clips clips, every clip's
+    result bit-identical to correcting it alone.  The handle's `warps` table has 16 slots; the stage keeps one D per distinct warp in it and
+    replaces the least recently used one when a new warp arrives (a copy on the current stream, ordered before the run that reads it)."""
+
+    api = "tt_fmt"
+
+    def __init__(self, max_samples, q=None, max_gain_db=None, max_clips=E.FMT_MAX_CLIPS, device="cuda"):
+        from . import formant as fmt
+        self.fmt = fmt
+        self.q = fmt.lifter_q() if q is None else int(q)
+        self.max_gain_db = fmt.max_gain_db() if max_gain_db is None else fmt.max_gain_db(max_gain_db)
+        if not fmt.Q_RANGE[0] <= self.q <= fmt.Q_RANGE[1]:
+            raise ValueError(f"{self.q} cepstral coefficients; the stage takes {fmt.Q_RANGE[0]} .. {fmt.Q_RANGE[1]}")
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        t = fmt.tables(self.q, [1.0])
+        self.t = {k: t[k].to(self.device).contiguous() for k in ("basis", "inverse", "cepstrum")}
+        self.t["warps"] = torch.zeros(E.FMT_MAX_WARPS, E.FMT_Q_PAD, fmt.BINS_PAD, device=self.device, dtype=torch.float32)
+        self.slots, self.clock = {}, 0  # alpha -> [slot, last use]
+        c = E.FmtConfig()
+        c.n_fft, c.hop, c.bins_pad, c.q, c.max_gain_db = fmt.N_FFT, fmt.HOP, fmt.BINS_PAD, self.q, self.max_gain_db
+        c.max_samples, c.max_clips, c.n_warps = self.max_samples, self.max_clips, E.FMT_MAX_WARPS
+        tb = E.FmtTables()
+        tb.basis, tb.inverse, tb.cepstrum, tb.warps = (E.ptr(self.t[k]) for k in ("basis", "inverse", "cepstrum", "warps"))
+        self._create(C.byref(c), C.byref(tb))
+
+    def _slot(self, alpha, busy):
+        """The slot of `warps` that holds D(alpha), filled on first use; `busy`: slots this call already relies on."""
+        self.clock += 1
+        if alpha in self.slots:
+            self.slots[alpha][1] = self.clock
+            return self.slots[alpha][0]
+        if len(self.slots) < E.FMT_MAX_WARPS:
+            slot = len(self.slots)
+        else:
+            old = min((a for a in self.slots if self.slots[a][0] not in busy), key=lambda a: self.slots[a][1])
+            slot = self.slots.pop(old)[0]
+        self.t["warps"][slot].copy_(self.fmt.warp_table(alpha, self.q).float())
+        self.slots[alpha] = [slot, self.clock]
+        return slot
+
+    def correct_many(self, clips, alphas):
+        """clips f32 [n] (device or host, n >= 513) and the warp alpha of each (0.5 .. 2) -> the corrected clips f32 [n] on the stage's
+        device.  ValueError for a clip the handle does not take or a warp outside the range."""
+        if len(clips) != len(alphas):
+            raise ValueError(f"{len(clips)} clips with {len(alphas)} warps")
+        alphas = [float(a) for a in alphas]
+        for i, (x, a) in enumerate(zip(clips, alphas)):
+            if x.dim() != 1 or x.shape[0] < self.fmt.MIN_SAMPLES:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least {self.fmt.MIN_SAMPLES} samples "
+                                 f"(the frames are centred with reflect padding)")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the formant stage's capacity ({self.max_samples})")
+            if not self.fmt.WARP_RANGE[0] <= a <= self.fmt.WARP_RANGE[1]:
+                raise ValueError(f"clip {i}: warp {a!r} is outside {self.fmt.WARP_RANGE}")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], alphas[g:g + self.max_clips])
+        return out
+
+    def _group(self, clips, alphas):
+        k, dev = len(clips), self.device
+        busy, idx = set(), []
+        for a in alphas:
+            idx.append(self._slot(a, busy))
+            busy.add(idx[-1])
+        lens = [int(x.shape[0]) for x in clips]
+        offs = [0] * k
+        for i in range(1, k):
+            offs[i] = offs[i - 1] + lens[i - 1]
+        parts = [x.to(device=dev, dtype=torch.float32) for x in clips]
+        wav = (torch.cat(parts) if k > 1 else parts[0]).contiguous()
+        y = torch.empty(sum(lens), device=dev, dtype=torch.float32)
+        ll, ii = (C.c_longlong * k)(*offs), (C.c_int * k)(*lens)
+        E.check(self.lib.tt_fmt_run(self.h, E.ptr(wav), ll, ii, (C.c_int * k)(*idx), k, E.ptr(y), ll, E.stream_ptr()))
+        return [y[o:o + n] for o, n in zip(offs, lens)]
+
+
 class LoudnessStage(_Handle):
     """Integrated loudness, true peak and the gain to a target under a ceiling (csrc/loudness.hip, include/tortoise_mi355x_loud.h): ragged
     batches, each clip with its own target and ceiling, one tt_loud_measure / tt_loud_normalize call per group of at most max_clips clips and
