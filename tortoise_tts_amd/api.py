@@ -461,13 +461,22 @@ class _Common:
         24 kHz, which costs ONE EXTRA ALIGNER PASS; the words' spans become a stretch.RateMap (from_words; left in self.rate_maps), and the
         usual chain runs with ONE time-stretch along that map, the pitch folded into every segment's rate: redaction -> stretch and the
         one resampling -> formants -> pauses -> loudness -> sample rate.  The returned timings are those of the returned audio, aligned as always.
-        Single-rank instances only.  How natural a jump between neighbouring words sounds nobody has judged on a trained checkpoint."""
+        Single-rank instances only.  How natural a jump between neighbouring words sounds nobody has judged on a trained checkpoint.
+        word_pitches= (a list with one pitch in semitones per word, None for a word left alone; or a dict {word index: semitones}; each
+        within +-12): single words higher or lower, SSML's <prosody pitch>.  It goes with pitch= (the pitch of everything else), word_rates=
+        and speaking_rate=; the one aligner pass serves both maps, the segments are the union of their word borders (at most 64 together),
+        and the chain runs ONE time-stretch and ONE resampling along them with every word's duration kept (_tts_at_word_pitches; the maps
+        are left in self.pitch_maps).  formants='keep' / formant_shift= are refused with it.  Pitch steps between neighbouring words,
+        without formant correction, nobody has judged either."""
         if not isinstance(text, str):
             raise TypeError("tts_with_timings aligns the text with the audio: pass it as a str, not as token ids")
         self.load_aligner()  # (missing files are reported before anything renders)
         sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (the aligner reads 24 kHz: converted after it)
-        word_rates = tsm.word_rates(tts_kwargs)
-        res = self.tts(text, **tts_kwargs) if word_rates is None else self._tts_at_word_rates(text, word_rates, tts_kwargs)
+        word_rates, word_pitches = tsm.word_rates(tts_kwargs), rs.word_pitches(tts_kwargs)
+        if word_pitches is not None:
+            res = self._tts_at_word_pitches(text, word_rates, word_pitches, tts_kwargs)
+        else:
+            res = self.tts(text, **tts_kwargs) if word_rates is None else self._tts_at_word_rates(text, word_rates, tts_kwargs)
         out = res[0] if tts_kwargs.get("return_deterministic_state") else res
         if out is None:
             return res, None
@@ -496,6 +505,44 @@ class _Common:
         als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
         self.rate_maps = [tsm.RateMap.from_words(al, word_rates, base=1.0 if rate is None else rate) for al in als]
         clips = self._voiced(self._at_map(clips, self.rate_maps, pitch), None, None, level, None, pauses, formants)
+        out = clips if isinstance(out, (list, tuple)) else clips[0]
+        return (out,) + tuple(res[1:]) if state else out
+
+    def _tts_at_word_pitches(self, text, word_rates, word_pitches, tts_kwargs):
+        """tts(text, **tts_kwargs) with its post-processing run along a pitch map of the words (and a rate map, with word_rates) -> what
+        tts returns.  ONE aligner pass on the plain clip serves both maps; the segments are taken over the union of their word borders
+        (at most 64 together); ONE time-stretch at stretch_rq(rq_i, pq_i) per segment and ONE resampling at pq_i along the stretch's own
+        borders keep every word's duration len_i / rate_i (resample.WarpChain, resample.duration_bound); then pauses and level as always.
+        The maps are left in self.pitch_maps (and self.rate_maps)."""
+        if getattr(self, "world", 1) > 1:
+            raise ValueError("tts_with_timings: word_pitches is not available on a sharded job (the ranks that return no audio have nothing to "
+                             "align); build a single-rank instance")
+        kw = dict(tts_kwargs)
+        rs.refuse_formants(kw.get("formants"), kw.get("formant_shift"), "tts_with_timings(word_pitches=)")
+        rate, level = tsm.speaking_rate(kw), loud.level_options(kw)
+        pitch = rs.options(kw, rate)[0]
+        pauses = sil.options(kw)
+        fmt.options(kw, None)  # (takes the formant keywords out; 'follow' and the lifter options change nothing)
+        base_rate, base_pitch = 1.0 if rate is None else rate, 0.0 if pitch is None else pitch
+        res = self.tts(text, **kw)  # (rendered and redacted, nothing else)
+        state = bool(kw.get("return_deterministic_state"))
+        out = res[0] if state else res
+        clips = list(out) if isinstance(out, (list, tuple)) else [out]
+        als = self.align_many(clips, [self._spoken_text(text)] * len(clips))
+        self.pitch_maps = [rs.PitchMap.from_words(al, word_pitches, base=base_pitch) for al in als]
+        self.rate_maps = [tsm.RateMap.from_words(al, {} if word_rates is None else word_rates, base=base_rate) for al in als]
+        chains = []
+        for al, rm, pm in zip(als, self.rate_maps, self.pitch_maps):
+            def name(i, b, al=al):
+                at = [f"word {k} ({w!r})" for k, (w, a, _, _) in enumerate(al.words) if int(a) == b]
+                return f"tts_with_timings: {at[0] if at else 'the segment at sample %d' % b}"
+            chains.append(rs.WarpChain(al.samples, *rs.merge_maps(al.samples, list(zip(rm.starts, rm.rqs)), list(zip(pm.starts, pm.pqs)), name)))
+        clips = self._at_chains(clips, chains)
+        if any(c.stretch is not None for c in chains):
+            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+        if any(set(c.pqs) != {E.RS_PITCH_ONE} for c in chains):
+            self.timings = dict(getattr(self, "timings", None) or {}, pitch_s=self._resample_s)
+        clips = self._voiced(clips, None, None, level, None, pauses, None)
         out = clips if isinstance(out, (list, tuple)) else clips[0]
         return (out,) + tuple(res[1:]) if state else out
 
@@ -807,7 +854,8 @@ class _Common:
         return StreamResampler(self.load_stream_resample(), P, Q, int(from_rate))
 
     @torch.no_grad()
-    def shift_pitch_many(self, audios, semitones, return_info=False, formants=None, formant_lifter_ms=None, formant_max_gain_db=None):
+    def shift_pitch_many(self, audios, semitones=None, return_info=False, formants=None, formant_lifter_ms=None, formant_max_gain_db=None,
+                         pitch_maps=None, return_map=False):
         """The same speech at another pitch and the same duration: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), semitones
         (+: up; one value or one per clip, each within +-12) -> the shifted clips.  Two batched device calls: a time-stretch at rate
         65536^2 / pq (rounded; pq = round(2^(s/12) 65536)), then a resampling by (pq, 65536), which undoes the stretch's change of duration
@@ -815,8 +863,23 @@ class _Common:
         the pitch: it stays natural for a few semitones, and nobody has rendered a trained checkpoint through it.  0 semitones returns the
         clip as it is.  return_info=True: also the sample peak of every returned clip.  formants='keep': a third batched call, the cepstral
         envelope correction at warp 2^(s/12) (shift_formants_many's kernel and options), puts the formants back where they were; the peaks
-        of return_info are then those of the corrected clips.  None or 'follow': the two calls alone."""
+        of return_info are then those of the corrected clips.  None or 'follow': the two calls alone.
+        pitch_maps=[...] instead of semitones: a pitch that changes inside the clip, SSML's <prosody pitch> - per clip a resample.PitchMap
+        (from_segments, from_words) or a list of (start_seconds, semitones).  Every segment keeps its duration: ONE time-stretch along
+        the map at rate 65536^2 / pq_i per segment (csrc/tsm_warp.hip), then ONE resampling along it (csrc/resample_warp.hip) whose borders
+        are where the stretch put them; the position is continuous across a border, the low-pass changes there.  Every border and the end
+        land within resample.duration_bound of where they were.  A map of 0 semitones throughout returns the clip as it is, a map of one
+        segment takes the path of `semitones`.  return_map=True: also, per clip, int64 [S + 1, 2] anchors (input sample, output sample) of
+        every border and of the end.  The formants move with each segment's pitch: formants='keep' is refused with a map.  Nobody has
+        listened to pitch steps between neighbouring words on a trained checkpoint."""
         audios = self._level_clips(audios, "shift_pitch")
+        if (semitones is None) == (pitch_maps is None):
+            raise ValueError("shift_pitch: give exactly one of semitones and pitch_map")
+        if pitch_maps is not None:
+            rs.refuse_formants(formants, None, "shift_pitch(pitch_map=)")
+            return self._shift_maps(audios, pitch_maps, return_info, return_map)
+        if return_map:
+            raise ValueError("shift_pitch: return_map=True goes with pitch_map")
         semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
         if len(semis) != len(audios):
             raise ValueError(f"shift_pitch: {len(audios)} clips with {len(semis)} pitches")
@@ -837,9 +900,80 @@ class _Common:
         self._resample_s = time.perf_counter() - t0
         return res
 
-    def shift_pitch(self, audio, semitones, formants=None, **options):
-        """shift_pitch_many of one clip -> the shifted clip (options: formant_lifter_ms, formant_max_gain_db)."""
-        return self.shift_pitch_many([audio], semitones, formants=formants, **options)[0]
+    def shift_pitch(self, audio, semitones=None, formants=None, pitch_map=None, return_map=False, **options):
+        """shift_pitch_many of one clip -> the shifted clip (options: formant_lifter_ms, formant_max_gain_db); pitch_map= instead of
+        semitones: a pitch that changes inside the clip (return_map=True: and its anchors)."""
+        if pitch_map is None and not return_map:
+            return self.shift_pitch_many([audio], semitones, formants=formants, **options)[0]
+        res = self.shift_pitch_many([audio], semitones, formants=formants, pitch_maps=None if pitch_map is None else [pitch_map],
+                                    return_map=return_map, **options)
+        return (res[0][0], res[1][0]) if return_map else res[0]
+
+    warp_resampler = None
+
+    def load_warp_resample(self, max_samples=0):
+        """The resampling along a pitch map (stages.WarpResampleStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.RS_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the resampler can take ({E.RS_MAX_SAMPLES})")
+        if self.warp_resampler is None or self.warp_resampler.max_samples < max_samples:
+            if self.warp_resampler is not None:
+                self.warp_resampler.close()
+            self.warp_resampler = stages.WarpResampleStage(max(int(max_samples), 2 * ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE), device=self.device)
+        return self.warp_resampler
+
+    def _shift_maps(self, audios, pitch_maps, return_info, return_map):
+        """shift_pitch_many along pitch maps."""
+        pitch_maps = list(pitch_maps)
+        if len(pitch_maps) != len(audios):
+            raise ValueError(f"shift_pitch: {len(audios)} clips with {len(pitch_maps)} pitch maps")
+        maps = [rs.pitch_map(a.shape[-1], m) for a, m in zip(audios, pitch_maps)]
+        self.pitch_maps = maps
+        chains = []
+        for m in maps:  # (neighbours at one pitch are one segment: a map that says 3 semitones twice takes the constant path)
+            segs = [(b, p) for i, (b, p) in enumerate(zip(m.starts, m.pqs)) if i == 0 or p != m.pqs[i - 1]]
+            chains.append(rs.WarpChain(m.n, [b for b, _ in segs], [E.TSM_RATE_ONE] * len(segs), [p for _, p in segs]))
+        out = self._at_chains(audios, chains)
+        res = (out,)
+        if return_info:
+            res += ([float(a.abs().max()) for a in out],)
+        if return_map:
+            res += ([c.anchors for c in chains],)
+        return res if len(res) > 1 else out
+
+    def _at_chains(self, audios, chains):
+        """audios (validated) each along its resample.WarpChain -> the clips, each in the shape and on the device it came in: ONE
+        time-stretch call per 16 for the clips whose speaking rate or pitch changes inside them, and ONE resampling call.  What is
+        constant over a clip takes the constant kernels (their bits: a table of one segment gives them anyway), and what is 1.0
+        throughout runs nothing; their time in self._stretch_s / self._resample_s."""
+        seq = list(audios)
+        self._stretch_s = 0.0
+        const = [i for i, c in enumerate(chains) if c.stretch is not None and len(c.stretch) == 1]
+        warp = [i for i, c in enumerate(chains) if c.stretch is not None and len(c.stretch) > 1]
+        spent = 0.0
+        if const:
+            for i, y in zip(const, self.stretch_many([seq[i] for i in const], rates=[chains[i].rq_effs[0] / E.TSM_RATE_ONE for i in const])):
+                seq[i] = y
+            spent += self._stretch_s
+        if warp:
+            for i, y in zip(warp, self.stretch_many([seq[i] for i in warp], rate_maps=[tsm.RateMap(chains[i].n, chains[i].starts, chains[i].rq_effs)
+                                                                                          for i in warp])):
+                seq[i] = y
+            spent += self._stretch_s
+        self._stretch_s = spent
+        t0 = time.perf_counter()
+        flat = [i for i, c in enumerate(chains) if len(set(c.pqs)) == 1]
+        bent = [i for i, c in enumerate(chains) if len(set(c.pqs)) > 1]
+        if flat:
+            for i, y in zip(flat, self._resample_ratios([seq[i] for i in flat], [(chains[i].pqs[0], E.RS_PITCH_ONE) for i in flat], False)):
+                seq[i] = y
+        if bent:
+            res = self.load_warp_resample(max(seq[i].shape[-1] for i in bent)).resample_many([seq[i].reshape(-1) for i in bent],
+                                                                                            [chains[i].resample for i in bent])
+            for i, (y, _) in zip(bent, res):  # (the peaks' copy back has synchronised)
+                seq[i] = y.to(audios[i].device).reshape(audios[i].shape[:-1] + (-1,))
+        self._resample_s = time.perf_counter() - t0
+        assert all(y.shape[-1] == c.n_out for y, c in zip(seq, chains)), "the chain's plans and the stages agree on every length"
+        return seq
 
     # ------------------------------------------------------------------ formants: the cepstral envelope correction
     formant_stage = None
@@ -1377,6 +1511,7 @@ class TextToSpeech(_Common):
         96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
         pitch and before the level, in ONE call (trim_many).  formants= / formant_shift= correct every clip's spectral envelope after the
         pitch and before the pauses, in ONE call (shift_formants_many)."""
+        rs.refuse_word_pitches(kwargs, "tts_many")
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)

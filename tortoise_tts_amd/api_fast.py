@@ -222,6 +222,7 @@ class TextToSpeech(_Common):
         96000) converts every clip last, in ONE call.  trim_silence= / max_pause= shape the pauses of every clip after the rate and the
         pitch and before the level, in ONE call (trim_many).  formants= / formant_shift= correct every clip's spectral envelope after the
         pitch and before the pauses, in ONE call (shift_formants_many)."""
+        rs.refuse_word_pitches(kwargs, "tts_many")
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
@@ -346,6 +347,7 @@ class TextToSpeech(_Common):
         tsm.refuse_word_rates(hf_generate_kwargs, "tts_stream")
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        rs.refuse_word_pitches(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fmt.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
@@ -481,6 +483,7 @@ class TextToSpeech(_Common):
         tsm.refuse_word_rates(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
+        rs.refuse_word_pitches(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
         fmt.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
@@ -656,6 +659,7 @@ class TextToSpeech(_Common):
         tsm.refuse_word_rates(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
+        rs.refuse_word_pitches(kwargs, "tts_stream_many")
         sil.refuse_streaming(kwargs, "tts_stream_many")
         fmt.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")

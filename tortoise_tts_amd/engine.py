@@ -456,6 +456,19 @@ _RSS_PROTOS = {
 RSS_ABI_VERSION = 1
 RSS_HIST, RSS_MAX_STREAMS, RSS_BANK_MAX, RSS_AUTO_MAX_Q = 576, 64, 16384, 16  # TT_RSS_HIST, TT_RSS_MAX_STREAMS, TT_RSS_BANK_MAX, TT_RSS_AUTO_MAX_Q
 RSS_AUTO, RSS_TABLE, RSS_BANK = 0, 1, 2
+# include/tortoise_mi355x_rsw.h: the resampler along a pitch map, a pitch that changes inside the clip (its own header and version)
+_RSW_PROTOS = {
+    "tt_rsw_abi_version": (_i, []),
+    "tt_rsw_plan": (_i, [_i, _i, _ip, _ip, _ip]),
+    "tt_rsw_out_samples": (_i, [_i, _i, _ip]),
+    "tt_rsw_create": (_i, [_i, _i, _i, C.POINTER(vp)]),
+    "tt_rsw_destroy": (None, [vp]),
+    "tt_rsw_resample": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+RSW_ABI_VERSION = 1
+RSW_MAX_SEGMENTS, RSW_MIN_SEGMENT = 64, 2  # TT_RSW_MAX_SEGMENTS, TT_RSW_MIN_SEGMENT
+RSW_P_MIN, RSW_P_MAX = 32768, 131072       # TT_RSW_P_MIN, TT_RSW_P_MAX
+RSW_OK, RSW_EMPTY, RSW_REFUSED = 0, 1, 2
 
 # include/tortoise_mi355x_tss.h: the time-stretch fed in chunks, for streams at another speaking rate and pitch (its own header and version)
 _TSS_PROTOS = {
@@ -594,7 +607,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -638,6 +651,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
     if lib.tt_rss_abi_version() != RSS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rss.h is version %d in the library, %d in Python" % (lib.tt_rss_abi_version(), RSS_ABI_VERSION))
+    if lib.tt_rsw_abi_version() != RSW_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_rsw.h is version %d in the library, %d in Python" % (lib.tt_rsw_abi_version(), RSW_ABI_VERSION))
     if lib.tt_tss_abi_version() != TSS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_tss.h is version %d in the library, %d in Python" % (lib.tt_tss_abi_version(), TSS_ABI_VERSION))
     if lib.tt_tsw_abi_version() != TSW_ABI_VERSION:

@@ -65,6 +65,7 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     from . import silence as sil
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
+    rs.refuse_word_pitches(tts_kwargs, "read_long_form")
     scope, level = loud.scope_option(tts_kwargs), loud.level_options(tts_kwargs)  # (applied here, to what the chunks' calls return)
     sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (here too, after the level)
     gap = None if pause is None else sil.for_long_form(tts_kwargs, pause)  # (the chunks' calls get lead = trail = 0)

@@ -1,5 +1,7 @@
 """Host side of the resampler (include/tortoise_mi355x_rs.h, csrc/resample.hip, stages.ResampleStage): the options of a tts() call, the
-integer ratios of a rate conversion and of a pitch shift, and the integers that carry a position across."""
+integer ratios of a rate conversion and of a pitch shift, and the integers that carry a position across; and of a pitch that changes
+inside the clip (include/tortoise_mi355x_rsw.h, csrc/resample_warp.hip, stages.WarpResampleStage): the table of segments, its plan from
+segments or word timings (PitchMap), and the chain that keeps every word's duration (warp_chain)."""
 import math
 
 from . import engine as E
@@ -136,3 +138,267 @@ def refuse_streaming(kwargs, who):
         if k in kwargs:
             raise ValueError(f"{who}: {k} is not available for streamed audio (the resampler filters across the pieces' borders, and they are "
                              f"cross-faded as they are made); use tts() / tts_many(), or shift_pitch() / resample() the collected clip")
+
+
+# ----------------------------------------------------------------------------------------------- a pitch that changes inside the clip
+# include/tortoise_mi355x_rsw.h, csrc/resample_warp.hip, stages.WarpResampleStage.  A table is a list of segments (m_i, thi_i, tlo_i, P_i):
+# from output sample m_i on, where the input stands at t_i = thi_i 65536 + tlo_i (1 / 65536 sample), the clip is read at P_i / 65536 input
+# samples per output sample.  Everything here is integers that host and device agree on; the functions mirror the library's
+# (csrc/resample_warp_host.h).
+MIN_WORD_SPAN = 4  # samples a word's span or a gap needs to own a segment of a PitchMap.from_words; derived there
+
+
+def map_out_samples(n, table):
+    """The Python mirror of tt_rsw_out_samples: n_out of a clip of n samples along `table`, 0 for a table that breaks a rule ((0, 0) start,
+    0 <= tlo < 65536, m strictly increasing, ratios in range, continuity, t_(S-1) < n 65536)."""
+    n, S = int(n), len(table)
+    if n < 1 or n > E.RS_MAX_SAMPLES or S < 1 or S > E.RSW_MAX_SEGMENTS:
+        return 0
+    if tuple(table[0][:3]) != (0, 0, 0):
+        return 0
+    for i, (m, hi, lo, P) in enumerate(table):
+        if not E.RSW_P_MIN <= P <= E.RSW_P_MAX or hi < 0 or not 0 <= lo <= 65535:
+            return 0
+        if i + 1 < S:
+            m1, hi1, lo1, _ = table[i + 1]
+            if m1 <= m or hi * 65536 + lo + (m1 - m) * P != hi1 * 65536 + lo1:
+                return 0
+    m, hi, lo, P = table[-1]
+    t = hi * 65536 + lo
+    if t >= n * 65536:
+        return 0
+    return m + -((t - n * 65536) // P)
+
+
+def map_position(m, table):
+    """(input index, phase) of output sample m along `table`: pos = t_i + (m - m_i) P_i, i the last segment with m_i <= m -> (pos >> 16,
+    pos & 65535)."""
+    i = 0
+    while i + 1 < len(table) and table[i + 1][0] <= m:
+        i += 1
+    pos = table[i][1] * 65536 + table[i][2] + (m - table[i][0]) * table[i][3]
+    return pos >> 16, pos & 65535
+
+
+def map_plan(n, starts, pqs):
+    """The Python mirror of tt_rsw_plan: input-domain segments (b_i, P_i), b_0 = 0 < b_1 < .. < b_S = n, each of at least 2 samples -> the
+    table.  Every length is measured from the achieved t_i: 0 <= t_i - 65536 b_i < P_(i-1).  ValueError for what the library answers
+    with -1."""
+    n, S = int(n), len(starts)
+    if len(pqs) != S:
+        raise ValueError(f"pitch map: {S} segment starts with {len(pqs)} ratios")
+    if n < 1 or n > E.RS_MAX_SAMPLES:
+        raise ValueError(f"pitch map: a clip of {n} samples (1 .. {E.RS_MAX_SAMPLES})")
+    if S < 1 or S > E.RSW_MAX_SEGMENTS:
+        raise ValueError(f"pitch map: {S} segments (1 .. {E.RSW_MAX_SEGMENTS})")
+    starts, pqs = [int(b) for b in starts], [int(p) for p in pqs]
+    if starts[0] != 0:
+        raise ValueError(f"pitch map: segment 0 starts at sample {starts[0]}, not at 0")
+    for i in range(S):
+        end = starts[i + 1] if i + 1 < S else n
+        if end - starts[i] < E.RSW_MIN_SEGMENT:
+            raise ValueError(f"pitch map: segment {i} starts at sample {starts[i]} and ends at {end}: the starts increase, and a segment covers "
+                             f"at least {E.RSW_MIN_SEGMENT} samples")
+        if not E.RSW_P_MIN <= pqs[i] <= E.RSW_P_MAX:
+            raise ValueError(f"pitch map: segment {i}: ratio {pqs[i]} / 65536 is outside the supported range [0.5, 2.0] (+-12 semitones)")
+    table, m, t = [], 0, 0
+    for i in range(S):
+        table.append((m, t >> 16, t & 65535, pqs[i]))
+        if i + 1 < S:
+            L = max(1, -((t - starts[i + 1] * 65536) // pqs[i]))
+            m, t = m + L, t + L * pqs[i]
+    return table
+
+
+def _semitones_q(s, what):
+    try:
+        s = float(s)
+        ok = PITCH_RANGE[0] <= s <= PITCH_RANGE[1]  # (NaN fails too)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or isinstance(s, bool):
+        raise ValueError(f"{what}: pitch {s!r} semitones is outside the supported range [{PITCH_RANGE[0]}, {PITCH_RANGE[1]}]")
+    return pitch_ratio(s)[0]
+
+
+class PitchMap:
+    """The pitch of a clip of n samples (24 kHz) as it changes inside the clip: input-domain segments (start sample b_i, ratio pq_i =
+    round(2^(s_i / 12) 65536)), and the integer table planned from them.  .table [(m_i, thi_i, tlo_i, P_i)] and .n_out are what the device
+    computes with when THIS clip is resampled along the map (which changes every segment's duration by 65536 / pq_i); .starts and .pqs
+    what they were planned from.  shift_pitch(pitch_map=) keeps the durations: it plans a time-stretch and a resampling from .starts and
+    .pqs (warp_chain).  Build one with from_segments or from_words."""
+
+    def __init__(self, n, starts, pqs):
+        self.n, self.starts, self.pqs = int(n), [int(b) for b in starts], [int(p) for p in pqs]
+        self.table = map_plan(self.n, self.starts, self.pqs)
+        self.n_out = map_out_samples(self.n, self.table)
+        assert self.n_out > 0, "a planned table obeys the table's rules"
+
+    def __repr__(self):
+        return f"PitchMap(n={self.n}, segments={[(b, round(12 * math.log2(p / E.RS_PITCH_ONE), 3)) for b, p in zip(self.starts, self.pqs)]})"
+
+    @classmethod
+    def from_segments(cls, n, segments):
+        """[(start_sample, semitones), ...]: from start_sample on (the first one 0) the clip sounds `semitones` higher (+-12), up to the next
+        start or the clip's end.  ValueError names the segment for a pitch outside the range, starts that do not increase, a segment under
+        2 samples and more than 64 segments."""
+        segments = list(segments)
+        pqs = [_semitones_q(s, f"pitch map: segment {i}") for i, (_, s) in enumerate(segments)]
+        return cls(n, [int(b) for b, _ in segments], pqs)
+
+    @classmethod
+    def from_words(cls, alignment, semitones, base=0.0):
+        """One pitch per word of an align.Alignment (24 kHz): `semitones` is a list with one entry per word (None: the base) or a dict
+        {word index: semitones}.  A word's span is its start to its end; everything else - the pauses, the words without a pitch - sounds
+        at `base`.  Neighbours at the same pitch are one segment.  The rules are RateMap.from_words' with one difference: a span or a gap
+        under MIN_WORD_SPAN = 4 samples owns no segment (it joins the one before it).  Why 4: the map's segments are first time-stretched,
+        at a rate of up to 2.0 (65536 / pq for a pitch alone, rq / pq with word_rates, both held to [0.5, 2.0]), and the resampler's plan
+        needs 2 samples of every STRETCHED segment.  The stretch's plan measures a segment from the position it achieved, within one
+        sample of the border (|a_i - b_i| <= 1), so a span of 4 counts as at least 3 there and comes out as
+        (3 * 65536 + 131072 / 2) / 131072 = 2 samples at rate 2.0; a span of 3 could come out as 1."""
+        words = alignment.words
+        if getattr(alignment, "rate", SAMPLE_RATE) != SAMPLE_RATE:
+            raise ValueError(f"word_pitches: the alignment counts samples at {alignment.rate} Hz; the pitch map runs at {SAMPLE_RATE}")
+        if isinstance(semitones, dict):
+            for i in semitones:
+                if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(words):
+                    raise ValueError(f"word_pitches: word index {i!r} (the text has {len(words)} words: 0 .. {len(words) - 1})")
+            per = [semitones.get(i) for i in range(len(words))]
+        else:
+            per = list(semitones)
+            if len(per) != len(words):
+                raise ValueError(f"word_pitches: {len(per)} pitches for the {len(words)} words of the text")
+        base_q = _semitones_q(base, "word_pitches: the base")
+        raw, at = [(0, base_q)], 0
+        for i, ((w, a, b, _), s) in enumerate(zip(words, per)):
+            if s is None:
+                continue
+            q = _semitones_q(s, f"word_pitches: word {i} ({w!r})")
+            a = max(int(a), at)
+            if int(b) - a < MIN_WORD_SPAN:
+                continue
+            raw += [(a, q), (int(b), base_q)]
+            at = int(b)
+        segs = []
+        for j, (s_, q) in enumerate(raw):
+            end = raw[j + 1][0] if j + 1 < len(raw) else alignment.samples
+            if end - s_ < MIN_WORD_SPAN or (segs and segs[-1][1] == q):
+                continue
+            segs.append((s_ if segs else 0, q))
+        segs = segs or [(0, base_q)]
+        return cls(alignment.samples, [b for b, _ in segs], [q for _, q in segs])
+
+
+def pitch_map(n, given):
+    """What shift_pitch(pitch_map=) takes -> a PitchMap of a clip of n samples: a PitchMap (its n must be the clip's), or a list of
+    (start_seconds, semitones)."""
+    if isinstance(given, PitchMap):
+        if given.n != int(n):
+            raise ValueError(f"shift_pitch: the pitch map was made for a clip of {given.n} samples, this one has {int(n)}")
+        return given
+    try:
+        segs = [(int(round(float(t) * SAMPLE_RATE)), s) for t, s in given]
+    except (TypeError, ValueError):
+        raise ValueError(f"shift_pitch: pitch_map={given!r}: a PitchMap, or a list of (start_seconds, semitones)") from None
+    return PitchMap.from_segments(n, segs)
+
+
+def word_pitches(kwargs):
+    """Takes `word_pitches` out of a tts_with_timings call's **kwargs -> None (absent or None) or the list / dict."""
+    given = kwargs.pop("word_pitches", None)
+    if given is not None and not isinstance(given, (list, tuple, dict)):
+        raise ValueError(f"word_pitches={given!r}: a list with one pitch in semitones per word (None: the base pitch), or a dict "
+                         f"{{word index: semitones}}")
+    return given
+
+
+def refuse_word_pitches(kwargs, who):
+    if "word_pitches" in kwargs:
+        raise ValueError(f"{who}: word_pitches is not available here (it needs the finished clip and its word timings); use tts_with_timings()")
+
+
+def refuse_formants(formants, formant_shift, who):
+    if formants not in (None, "follow") or formant_shift is not None:
+        raise ValueError(f"{who}: formants='keep' / formant_shift= do not go with a pitch that changes inside the clip (the formant stage takes "
+                         f"one warp per clip; a warp per segment is not built)")
+
+
+def merge_maps(n, rate_segments, pitch_segments, name=lambda i, b: f"segment {i}"):
+    """Segments over the union of the borders of a rate map and a pitch map of the same clip of n samples: rate_segments [(b, rq)] and
+    pitch_segments [(b, pq)], both starting at 0 -> (starts, rqs, pqs), neighbours with the same (rq, pq) joined.  Where the two maps'
+    borders leave a piece under MIN_WORD_SPAN samples between them, it owns no segment and joins the one before it (from_words' rule).
+    ValueError for more than 64 segments in all and, naming the segment through name(its index, its start sample), for a combination
+    whose time-stretch rate stretch_rq(rq_i, pq_i) leaves [0.5, 2.0]."""
+    cuts = sorted({int(b) for b, _ in rate_segments} | {int(b) for b, _ in pitch_segments})
+    at = lambda segs, b: [v for s_, v in segs if int(s_) <= b][-1]
+    merged = []
+    for b in cuts:
+        rq, pq = int(at(rate_segments, b)), int(at(pitch_segments, b))
+        if int(n) - b < MIN_WORD_SPAN and merged:
+            continue
+        if merged and b - merged[-1][0] < MIN_WORD_SPAN:  # the piece before this border is too short to own a segment
+            if len(merged) == 1:
+                continue
+            merged.pop()
+        if merged and merged[-1][1:] == (rq, pq):
+            continue
+        merged.append((b, rq, pq))
+    if len(merged) > E.RSW_MAX_SEGMENTS:
+        raise ValueError(f"word_rates and word_pitches together make {len(merged)} segments over the union of their word borders; "
+                         f"at most {E.RSW_MAX_SEGMENTS} fit one clip")
+    for i, (b, rq, pq) in enumerate(merged):
+        eff = stretch_rq(rq, pq)
+        if not E.TSM_RATE_MIN <= eff <= E.TSM_RATE_MAX:
+            raise ValueError(f"{name(i, b)}: speaking rate {rq / E.TSM_RATE_ONE:.4f} at pitch ratio {pq / E.RS_PITCH_ONE:.4f} needs a "
+                             f"time-stretch at rate {eff / E.TSM_RATE_ONE:.4f}, outside the supported range [0.5, 2.0]")
+    return [b for b, _, _ in merged], [rq for _, rq, _ in merged], [pq for _, _, pq in merged]
+
+
+class WarpChain:
+    """The two plans that give a clip of n samples the speaking rates rqs and the pitch ratios pqs over the segments `starts`, every
+    segment's duration len_i 65536 / rq_i kept: .stretch, the table of ONE tt_tsw_stretch at rq_eff_i = stretch_rq(rq_i, pq_i) (None
+    when every rq_eff is 1.0: nothing is stretched), and .resample, the table of ONE tt_rsw_resample whose input-domain borders are the
+    stretch table's m_i, at pq_i.  .n_mid and .n_out are the lengths after either; .anchors int64 [S + 1, 2]: (input sample, output
+    sample) of every border and of the end."""
+
+    def __init__(self, n, starts, rqs, pqs):
+        from . import stretch as tsm
+        self.n, self.starts, self.rqs, self.pqs = int(n), [int(b) for b in starts], [int(r) for r in rqs], [int(p) for p in pqs]
+        self.rq_effs = [stretch_rq(rq, pq) for rq, pq in zip(self.rqs, self.pqs)]
+        for i, (b, e) in enumerate(zip(self.starts, self.starts[1:] + [self.n])):
+            if len(self.starts) > 1 and e - b < MIN_WORD_SPAN:
+                raise ValueError(f"pitch map: segment {i} starts at sample {b} and ends at {e}: with the durations kept, a segment covers at "
+                                 f"least {MIN_WORD_SPAN} samples (PitchMap.from_words)")
+        rm = tsm.RateMap(self.n, self.starts, self.rq_effs)
+        self.stretch = None if all(r == E.TSM_RATE_ONE for r in self.rq_effs) else rm.table
+        self.frames, self.n_mid = rm.frames, rm.n_out
+        self.mid_starts = [row[0] for row in rm.table]  # (rate 1.0 throughout: m_i = a_i = b_i, the table is the identity)
+        self.resample = map_plan(self.n_mid, self.mid_starts, self.pqs)
+        self.n_out = map_out_samples(self.n_mid, self.resample)
+        assert self.n_out > 0, "a planned table obeys the table's rules"
+
+    @property
+    def anchors(self):
+        import torch
+        return torch.tensor([(b, row[0]) for b, row in zip(self.starts, self.resample)] + [(self.n, self.n_out)], dtype=torch.int64)
+
+    def ideal(self, i):
+        """sum_(j < i) len_j 65536 / rq_j: where border i (i = S: the end) would stand with no rounding, in samples."""
+        ends = self.starts[1:] + [self.n]
+        return sum((e - b) * E.TSM_RATE_ONE / rq for b, e, rq in list(zip(self.starts, ends, self.rqs))[:i])
+
+
+def duration_bound(i, ideal):
+    """How far border i >= 1 of a WarpChain (i = S: the clip's end) can stand from ideal = sum_(j < i) len_j 65536 / rq_j, in samples:
+    ideal / 16384 + 8.01 i + 1.  From the two plans' roundings, with g_j = 65536^2 / (rq_eff_j pq_j) the achieved gain of segment j:
+      N_j = (len_j + d_(j+1) - d_j - s_j) g_j + (e_(j+1) - e_j) / pq_j   output samples of segment j, exactly, where
+      d_j = a_j - b_j, |d_j| <= 1       the stretch plan's offset at border j (tortoise_mi355x_tsw.h)
+      |s_j| <= 1/2                      the rounding of the stretch's advance (or of its last length)
+      0 <= e_j < pq_(j-1)               the resampler plan's offset at border j (tortoise_mi355x_rsw.h), e_0 = 0
+    - g_j differs from 65536 / rq_j by the rounding of rq_eff_j = round(rq_j 65536 / pq_j): relatively at most
+      pq_j / (2 rq_j 65536) / (1 - ...) <= 2^-15 (1 + 2^-14) < 2^-14 for pq / rq <= 4: ideal / 16384 in all, the only term that grows with
+      the clip (7 samples in 5 s; a constant pitch=, whose one segment rounds the same way, has it too)
+    - (|d_(j+1)| + |d_j| + 1/2) g_j <= 2.5 * 2 (1 + 2^-14) < 5.01 per segment
+    - sum_j (e_(j+1) - e_j) / pq_j = e_i / pq_(i-1) + sum_(0 < j < i) e_j (1 / pq_(j-1) - 1 / pq_j): below 1 + 3 (i - 1), as
+      e_j / pq_(j-1) < 1 and pq_(j-1) / pq_j <= 4."""
+    return ideal / 16384.0 + 8.01 * i + 1.0

@@ -687,6 +687,59 @@ class ResampleStage(_Handle):
         return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
 
 
+class WarpResampleStage(_Handle):
+    """Band-limited resampling along a pitch map (csrc/resample_warp.hip, include/tortoise_mi355x_rsw.h): ragged batches, each clip with its
+    own table of segments (resample.map_plan), one tt_rsw_resample call per max_clips clips, every clip's result bit-identical to resampling
+    it alone; the table (0, 0, 0, P) gives ResampleStage's bits at (P, 65536)."""
+
+    api = "tt_rsw"
+
+    def __init__(self, max_samples, max_clips=16, max_segments=E.RSW_MAX_SEGMENTS, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips, self.max_segments = int(max_samples), int(max_clips), int(max_segments)
+        self._create(self.max_samples, self.max_clips, self.max_segments)
+
+    def resample_many(self, clips, tables):
+        """clips f32 [n_i] (device or host) and the table [(m, thi, tlo, P), ...] of each -> one (y f32 [n_out_i] on the stage's device,
+        max |y| as a float) per clip.  ValueError for an empty clip, a clip beyond the handle or a table that breaks a rule."""
+        if len(clips) != len(tables):
+            raise ValueError(f"{len(clips)} clips with {len(tables)} pitch maps")
+        for i, (x, tb) in enumerate(zip(clips, tables)):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the resampling stage's capacity ({self.max_samples})")
+            if not 1 <= len(tb) <= self.max_segments:
+                raise ValueError(f"clip {i}: a pitch map of {len(tb)} segments (1 .. {self.max_segments})")
+            if not rs.map_out_samples(x.shape[0], tb):
+                raise ValueError(f"clip {i}: the pitch map's table breaks a rule of include/tortoise_mi355x_rsw.h for a clip of {x.shape[0]} samples")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], tables[g:g + self.max_clips])
+        return out
+
+    def _group(self, clips, tables):
+        n, dev = len(clips), self.device
+        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
+        so = np.concatenate(([0], np.cumsum([len(tb) for tb in tables]))).astype(np.int32)
+        oo = np.concatenate(([0], np.cumsum([rs.map_out_samples(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
+        seg = np.asarray([v for tb in tables for row in tb for v in row], dtype=np.int32)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, so, oo, seg])).to(dev)
+        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
+        res = torch.zeros(2 * n, device=dev, dtype=torch.int32)  # (peak as f32 bits | status): one copy back
+        hp, rp, w = host.data_ptr(), res.data_ptr(), 4 * (n + 1)
+        E.check(self.lib.tt_rsw_resample(self.h, n, audio.data_ptr(), hp, hp + 3 * w, hp + w, y.data_ptr(), hp + 2 * w, rp, rp + 4 * n,
+                                         E.stream_ptr()))
+        res = res.cpu()
+        status = res[n:].tolist()
+        if any(st != E.RSW_OK for st in status):
+            raise RuntimeError(f"resample along a pitch map: the device stage refused clips it was handed (status {status})")
+        peaks = res[:n].view(torch.float32).tolist()
+        return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
+
+
 class StreamResampleStage(_Handle):
     """The resampler fed in chunks (csrc/resample_stream.hip, include/tortoise_mi355x_rss.h): up to max_streams streams, each with its own
     (P, Q); whatever the chunking, what a stream emits is bit for bit ResampleStage's result for the whole clip.  form: "auto" (a phase
