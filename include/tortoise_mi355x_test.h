@@ -247,6 +247,13 @@ int tt_op_fmt_run(void* h, const float* wav, const long long* clip_offsets, cons
 int tt_op_fmt_synth(void* h, const float* spectrum, const float* gains, const long long* stage_offsets, const int* clip_lengths, int n_clips,
                     float* out, const long long* out_offsets, void* stream);
 
+/* F0 tracker staged (csrc/f0.hip, include/tortoise_mi355x_f0.h; `h` is a tt_f0 handle).  tt_op_f0_track is tt_f0_track with one more output:
+ * dprime f64 [frm_off[n_clips]][TT_F0_LAG_MAX + 1], the normalised difference d'(0 .. T) of every frame, sliced by frm_off like lag.
+ * tt_op_f0_group: the frames a workgroup of the kernel owns (the sizes at which a clip begins another group). */
+int tt_op_f0_track(void* h, int n_clips, const float* audio, const int* in_off, const int* par, const double* thr, const int* frm_off, int* lag,
+                   float* f0, float* aper, int* n_voiced, int* status, double* dprime, void* stream);
+int tt_op_f0_group(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ from . import engine as E
 from . import stages
 from . import formant as fmt
 from . import loudness as loud
+from . import pitch as f0m
 from . import resample as rs
 from . import silence as sil
 from . import solver as fastsolver
@@ -473,6 +474,8 @@ class _Common:
         self.load_aligner()  # (missing files are reported before anything renders)
         sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (the aligner reads 24 kHz: converted after it)
         word_rates, word_pitches = tsm.word_rates(tts_kwargs), rs.word_pitches(tts_kwargs)
+        if tts_kwargs.get("pitch_hz") is not None:  # (refused before anything renders; the inner tts() call measures and shifts)
+            f0m.options(dict(pitch_hz=tts_kwargs["pitch_hz"], word_pitches=word_pitches), tts_kwargs.get("pitch") or None, "tts_with_timings")
         if word_pitches is not None:
             res = self._tts_at_word_pitches(text, word_rates, word_pitches, tts_kwargs)
         else:
@@ -855,7 +858,7 @@ class _Common:
 
     @torch.no_grad()
     def shift_pitch_many(self, audios, semitones=None, return_info=False, formants=None, formant_lifter_ms=None, formant_max_gain_db=None,
-                         pitch_maps=None, return_map=False):
+                         pitch_maps=None, return_map=False, to_hz=None):
         """The same speech at another pitch and the same duration: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), semitones
         (+: up; one value or one per clip, each within +-12) -> the shifted clips.  Two batched device calls: a time-stretch at rate
         65536^2 / pq (rounded; pq = round(2^(s/12) 65536)), then a resampling by (pq, 65536), which undoes the stretch's change of duration
@@ -871,10 +874,24 @@ class _Common:
         land within resample.duration_bound of where they were.  A map of 0 semitones throughout returns the clip as it is, a map of one
         segment takes the path of `semitones`.  return_map=True: also, per clip, int64 [S + 1, 2] anchors (input sample, output sample) of
         every border and of the end.  The formants move with each segment's pitch: formants='keep' is refused with a map.  Nobody has
-        listened to pitch steps between neighbouring words on a trained checkpoint."""
+        listened to pitch steps between neighbouring words on a trained checkpoint.
+        to_hz=H (one value or one per clip, 50 .. 1000 Hz) instead of semitones: an absolute pitch, SSML's <prosody pitch="180Hz">.  ONE
+        f0_many call measures the clips (csrc/f0.hip), and every clip is shifted by 12 log2(H / its median F0) through the calls above, a
+        ratio per clip; formants='keep' stays allowed.  A shift beyond +-12 semitones is clamped and a clip with fewer than 10 voiced
+        frames is returned bit for bit, each with a warning.  return_info=True then gives, per clip, a dict measured_hz (None: no
+        median), semitones, clamped and peak; the readings are also left in self.pitch_info."""
         audios = self._level_clips(audios, "shift_pitch")
-        if (semitones is None) == (pitch_maps is None):
-            raise ValueError("shift_pitch: give exactly one of semitones and pitch_map")
+        if (semitones is None) + (pitch_maps is None) + (to_hz is None) != 2:
+            raise ValueError("shift_pitch: give exactly one of semitones and pitch_map, or to_hz")
+        if to_hz is not None:
+            if return_map:
+                raise ValueError("shift_pitch: return_map=True goes with pitch_map")
+            fmt.mode(formants)
+            semis, info = self._shifts_to(audios, to_hz, "shift_pitch")
+            out, peaks = self.shift_pitch_many(audios, semis, True, formants, formant_lifter_ms, formant_max_gain_db) if audios else ([], [])
+            for d, pk in zip(info, peaks):
+                d["peak"] = pk
+            return (out, info) if return_info else out
         if pitch_maps is not None:
             rs.refuse_formants(formants, None, "shift_pitch(pitch_map=)")
             return self._shift_maps(audios, pitch_maps, return_info, return_map)
@@ -900,9 +917,15 @@ class _Common:
         self._resample_s = time.perf_counter() - t0
         return res
 
-    def shift_pitch(self, audio, semitones=None, formants=None, pitch_map=None, return_map=False, **options):
+    def shift_pitch(self, audio, semitones=None, formants=None, pitch_map=None, return_map=False, to_hz=None, **options):
         """shift_pitch_many of one clip -> the shifted clip (options: formant_lifter_ms, formant_max_gain_db); pitch_map= instead of
-        semitones: a pitch that changes inside the clip (return_map=True: and its anchors)."""
+        semitones: a pitch that changes inside the clip (return_map=True: and its anchors); to_hz= instead of either: the clip with its
+        median F0 moved to that many Hz (return_info=True: and its reading)."""
+        if to_hz is not None:
+            info = options.pop("return_info", False)
+            res = self.shift_pitch_many([audio], semitones, info, formants, pitch_maps=None if pitch_map is None else [pitch_map],
+                                        return_map=return_map, to_hz=to_hz, **options)
+            return (res[0][0], res[1][0]) if info else res[0]
         if pitch_map is None and not return_map:
             return self.shift_pitch_many([audio], semitones, formants=formants, **options)[0]
         res = self.shift_pitch_many([audio], semitones, formants=formants, pitch_maps=None if pitch_map is None else [pitch_map],
@@ -975,6 +998,73 @@ class _Common:
         assert all(y.shape[-1] == c.n_out for y, c in zip(seq, chains)), "the chain's plans and the stages agree on every length"
         return seq
 
+    # ------------------------------------------------------------------ F0: the YIN tracker
+    f0_stage = None
+    pitch_info = None
+
+    def load_f0(self, max_samples=0):
+        """The F0 stage (stages.F0Stage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        if max_samples > E.F0_MAX_SAMPLES:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the F0 tracker can take ({E.F0_MAX_SAMPLES})")
+        if self.f0_stage is None or self.f0_stage.max_samples < max_samples:
+            if self.f0_stage is not None:
+                self.f0_stage.close()
+            self.f0_stage = stages.F0Stage(max(int(max_samples), ORIG_ALIGNER_SECONDS * f0m.SAMPLE_RATE), device=self.device)
+        return self.f0_stage
+
+    @torch.no_grad()
+    def f0_many(self, audios, fmin=f0m.DEFAULTS["fmin"], fmax=f0m.DEFAULTS["fmax"], threshold=f0m.DEFAULTS["threshold"],
+                floor_db=f0m.DEFAULTS["floor_db"]):
+        """The fundamental frequency of every clip: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> [pitch.F0Track], a frame
+        every 10 ms (hz 0 where unvoiced, aperiodicity, voiced, times(), median_hz(), semitones(ref), range_semitones(), at(seconds),
+        for_words(alignment)).  YIN (de Cheveigne & Kawahara 2002) over a 40 ms window: the first dip of the normalised difference
+        below `threshold` among the periods of fmin .. fmax Hz (within 50 .. 1000), refined by a parabola; a frame without such a dip, or
+        with its power below floor_db dBFS, is unvoiced.  No smoothing over frames: an octave jump in one frame stays in the track (the
+        median does not see it).  All clips go through ONE device call per 16 (csrc/f0.hip).  The defaults were chosen from the paper
+        and the code: nobody has tuned them on a trained checkpoint's audio."""
+        audios = self._level_clips(audios, "f0")
+        p = f0m.params(fmin, fmax, threshold, floor_db)
+        if not audios:
+            return []
+        res = self.load_f0(max(a.shape[-1] for a in audios)).track_many([a.reshape(-1) for a in audios], [p] * len(audios))
+        return [f0m.track_of(r, a.shape[-1]) for r, a in zip(res, audios)]
+
+    def f0(self, audio, **options):
+        """f0_many of one clip -> pitch.F0Track."""
+        return self.f0_many([audio], **options)[0]
+
+    def _shifts_to(self, audios, to_hz, who):
+        """audios (validated) and the pitch to land on (Hz: one value or one per clip) -> (semitones per clip, [dict(measured_hz, semitones,
+        clamped)]): ONE f0_many call, then pitch.shift_to per clip.  The readings are left in self.pitch_info."""
+        hzs = list(to_hz) if isinstance(to_hz, (list, tuple)) else [to_hz] * len(audios)
+        if len(hzs) != len(audios):
+            raise ValueError(f"{who}: {len(audios)} clips with {len(hzs)} target pitches")
+        hzs = [f0m.target_hz("to_hz" if who == "shift_pitch" else "pitch_hz", h) for h in hzs]
+        t0 = time.perf_counter()
+        tracks = self.f0_many(audios)
+        semis, info = [], []
+        for i, (tr, h) in enumerate(zip(tracks, hzs)):
+            med = tr.median_hz()
+            s, clamped = f0m.shift_to(med, h, who, i if len(audios) > 1 else None)
+            semis.append(s)
+            info.append(dict(measured_hz=med, semitones=s, clamped=clamped))
+        self.pitch_info = info
+        self._f0_s = time.perf_counter() - t0
+        return semis, info
+
+    def _pitch_hz_plan(self, clips, hz, formant_kw, who="tts"):
+        """pitch_hz= of a tts call: the clips it is about to return ({winner: clip} or a list), measured in ONE device call -> (semitones
+        per clip in the clips' order, formant.Params or None per clip: formants='keep' takes every clip's own shift back)."""
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        semis, _ = self._shifts_to(self._level_clips(seq, who), hz, who)
+        self.timings = dict(getattr(self, "timings", None) or {}, f0_s=self._f0_s)
+        kw = dict(formant_kw or {})
+        keep = fmt.mode(kw.get("formants"))
+        plans = [fmt.params(s_ if s_ != 0.0 else None, keep, kw.get("formant_shift"), kw.get("formant_lifter_ms"), kw.get("formant_max_gain_db"))
+                 for s_ in semis]
+        return semis, plans
+
     # ------------------------------------------------------------------ formants: the cepstral envelope correction
     formant_stage = None
 
@@ -1034,7 +1124,7 @@ class _Common:
         them, its time in timings['formant_s']."""
         keys = sorted(clips) if isinstance(clips, dict) else None
         seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        seq = self._correct_formants(seq, [params] * len(seq))
+        seq = self._correct_formants(seq, list(params) if isinstance(params, list) else [params] * len(seq))  # (a list: one per clip, None allowed)
         self.timings = dict(getattr(self, "timings", None) or {}, formant_s=self._formant_s)
         return dict(zip(keys, seq)) if keys is not None else seq
 
@@ -1042,10 +1132,19 @@ class _Common:
         """The clips a tts call is about to return ({winner: clip} or a list) at speaking_rate `rate` (None: 1.0) and pitch `semitones`: ONE
         stretch_many call at rq_eff = round(rq 65536 / pq) and ONE resampling by (pq, 65536) for all of them; their time in
         timings['stretch_s'] / ['pitch_s']."""
-        pq, rq_eff = rs.pitch(semitones, rate)
         self._stretch_s = 0.0
         keys = sorted(clips) if isinstance(clips, dict) else None
         seq = [clips[i] for i in keys] if keys is not None else list(clips)
+        if isinstance(semitones, list):  # one pitch per clip (pitch_hz=), in the clips' order: still ONE stretch and ONE resampling
+            plans = [rs.pitch(s_, rate) for s_ in semitones]
+            todo = [i for i, (_, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
+            if todo:
+                for i, y in zip(todo, self.stretch_many([seq[i] for i in todo], rates=[plans[i][1] / E.TSM_RATE_ONE for i in todo])):
+                    seq[i] = y
+            seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE) for pq, _ in plans], False)
+            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s, pitch_s=self._resample_s)
+            return dict(zip(keys, seq)) if keys is not None else seq
+        pq, rq_eff = rs.pitch(semitones, rate)
         if rq_eff != E.TSM_RATE_ONE:
             seq = self.stretch_many(seq, rates=rq_eff / E.TSM_RATE_ONE)  # (rq_eff / 65536 is exact: stretch.rate_q returns rq_eff)
         seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE)] * len(seq), False)
@@ -1146,7 +1245,7 @@ class _Common:
             clips = self._at_pitch(clips, rate, pitch)
         elif rate is not None:
             clips = self._at_rate(clips, rate)
-        if formants is not None:
+        if formants is not None and not (isinstance(formants, list) and all(p is None for p in formants)):
             clips = self._at_formants(clips, formants)
         if pauses is not None:
             clips = self._at_pauses(clips, pauses)
@@ -1471,6 +1570,8 @@ class TextToSpeech(_Common):
             # diffusion generation parameters follow
             diffusion_iterations=100, cond_free=True, cond_free_k=2, diffusion_temperature=1.0,
             **hf_generate_kwargs):
+        if self.world > 1:
+            f0m.refuse_sharded(hf_generate_kwargs, "tts")
         o = self._settings(locals())  # (the arguments above, by name)
         redact = self._redaction_text(text)
         tokens = self._text_tokens(text, max_mel_tokens)
@@ -1490,7 +1591,10 @@ class TextToSpeech(_Common):
             wavs = self._redact_clips(wavs, redact)
             self.timings["redact_s"] = self._redact_s
         # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> formants -> pauses -> level -> output sample rate
-        wavs = self._voiced(wavs, o.speaking_rate, o.pitch, o.level, o.sample_rate, o.pauses, o.formants)
+        pitch, formants = o.pitch, o.formants
+        if o.pitch_hz is not None:  # measured after redaction, ONE device call for all clips: a shift per clip
+            pitch, formants = self._pitch_hz_plan(wavs, o.pitch_hz, o.formant_kw)
+        wavs = self._voiced(wavs, o.speaking_rate, pitch, o.level, o.sample_rate, o.pauses, formants)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
             wavs = tdist.collect_on_rank0(wavs, k)
@@ -1514,9 +1618,12 @@ class TextToSpeech(_Common):
         rs.refuse_word_pitches(kwargs, "tts_many")
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
+        pitch_hz, formant_kw = f0m.options(kwargs, pitch, "tts_many"), f0m.formant_keywords(kwargs)
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
+        if pitch_hz is not None:  # pitch_hz= (Hz): every clip's median F0 measured in ONE call, then a shift per clip through the same chain
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many")
         return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()
@@ -1606,6 +1713,7 @@ class TextToSpeech(_Common):
         noise = hf.pop("noise_override", None) or {}
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
         pitch, sample_rate = rs.options(hf, speaking_rate)
+        pitch_hz, formant_kw = f0m.options(hf, pitch), f0m.formant_keywords(hf)
         pauses, formants = sil.options(hf), fmt.options(hf, pitch)
         plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
@@ -1617,7 +1725,8 @@ class TextToSpeech(_Common):
                           typical_mass=typical_mass),
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
             solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
-            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses, formants=formants)
+            diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses, formants=formants,
+            pitch_hz=pitch_hz, formant_kw=formant_kw)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

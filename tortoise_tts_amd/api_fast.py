@@ -35,6 +35,7 @@ from . import engine as E
 from . import stages
 from . import formant as fmt
 from . import loudness as loud
+from . import pitch as f0m
 from . import resample as rs
 from . import silence as sil
 from . import solver as fastsolver
@@ -198,6 +199,7 @@ class TextToSpeech(_Common):
         self._single("tts")
         speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
         pitch, sample_rate = rs.options(hf_generate_kwargs, speaking_rate)
+        pitch_hz, formant_kw = f0m.options(hf_generate_kwargs, pitch), f0m.formant_keywords(hf_generate_kwargs)
         pauses, formants = sil.options(hf_generate_kwargs), fmt.options(hf_generate_kwargs, pitch)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
@@ -208,7 +210,10 @@ class TextToSpeech(_Common):
         self.last_codes = codes
         latents = self.ar.latents(cond, text_tokens, codes)          # api_fast.py:510-514 (return_latent=True)
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
-        return self._voiced([wav.cpu()], speaking_rate, pitch, level, sample_rate, pauses, formants)[0]  # (rate and pitch -> formants -> pauses -> level -> sample rate)
+        out = [wav.cpu()]
+        if pitch_hz is not None:  # pitch_hz= (Hz): the clip's median F0 measured, then the shift that lands on it
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw)
+        return self._voiced(out, speaking_rate, pitch, level, sample_rate, pauses, formants)[0]  # (rate and pitch -> formants -> pauses -> level -> sample rate)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
         """Several texts, one clip each: the result equals [tts(t, ...) for t in texts] on a max_streams=1 instance started from the same
@@ -225,8 +230,11 @@ class TextToSpeech(_Common):
         rs.refuse_word_pitches(kwargs, "tts_many")
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
+        pitch_hz, formant_kw = f0m.options(kwargs, pitch, "tts_many"), f0m.formant_keywords(kwargs)
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
+        if pitch_hz is not None:  # pitch_hz= (Hz): every clip's median F0 measured in ONE call, then a shift per clip
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many")
         return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()
@@ -348,6 +356,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_streaming(hf_generate_kwargs, "tts_stream")
         rs.refuse_word_pitches(hf_generate_kwargs, "tts_stream")
+        f0m.refuse_streaming(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fmt.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
@@ -484,6 +493,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(kwargs, "open_stream")
         rs.refuse_streaming(kwargs, "open_stream")
         rs.refuse_word_pitches(kwargs, "open_stream")
+        f0m.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
         fmt.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
@@ -660,6 +670,7 @@ class TextToSpeech(_Common):
         loud.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_streaming(kwargs, "tts_stream_many")
         rs.refuse_word_pitches(kwargs, "tts_stream_many")
+        f0m.refuse_streaming(kwargs, "tts_stream_many")
         sil.refuse_streaming(kwargs, "tts_stream_many")
         fmt.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")

@@ -513,6 +513,20 @@ SIL_SAMPLE_RATE = 24000
 SIL_MAX_SAMPLES, SIL_MAX_CLIPS = 8388608, 64
 SIL_MAX_FRAMES_PARAM = 6000
 SIL_OK, SIL_UNCHANGED, SIL_SILENT, SIL_EMPTY, SIL_REFUSED = 0, 1, 2, 3, 4
+# include/tortoise_mi355x_f0.h: the YIN fundamental-frequency tracker over ragged batches (its own header and version)
+_F0_PROTOS = {
+    "tt_f0_abi_version": (_i, []),
+    "tt_f0_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_f0_destroy": (None, [vp]),
+    "tt_f0_frames": (_i, [_i]),
+    "tt_f0_lags": (_i, [C.c_double, C.c_double, _ip, _ip]),
+    "tt_f0_track": (_i, [vp, _i] + [vp] * 11),
+}
+F0_ABI_VERSION = 1
+F0_HOP, F0_WINDOW, F0_LEAD, F0_LAG_MIN, F0_LAG_MAX = 240, 960, 720, 24, 480  # TT_F0_HOP, TT_F0_WINDOW, TT_F0_LEAD, TT_F0_LAG_MIN, TT_F0_LAG_MAX
+F0_SAMPLE_RATE = 24000
+F0_MAX_SAMPLES, F0_MAX_CLIPS = 8388608, 64
+F0_OK, F0_EMPTY, F0_REFUSED = 0, 1, 2
 # include/tortoise_mi355x_fmt.h: formant-preserving pitch, the cepstral envelope correction (its own header and version, same library)
 _FMT_PROTOS = {
     "tt_fmt_abi_version": (_i, []),
@@ -588,6 +602,8 @@ _TEST_PROTOS = {
     "tt_op_cls_head": (_i, [vp, vp, vp, vp, vp, vp]),
     "tt_op_fmt_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp, vp, vp, C.POINTER(_ll), vp]),
     "tt_op_fmt_synth": (_i, [vp, vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
+    "tt_op_f0_track": (_i, [vp, _i] + [vp] * 12),
+    "tt_op_f0_group": (_i, []),
 }
 
 _lib = None
@@ -607,7 +623,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -659,6 +675,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_tsw.h is version %d in the library, %d in Python" % (lib.tt_tsw_abi_version(), TSW_ABI_VERSION))
     if lib.tt_sil_abi_version() != SIL_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
+    if lib.tt_f0_abi_version() != F0_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_f0.h is version %d in the library, %d in Python" % (lib.tt_f0_abi_version(), F0_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_solver.h is version %d in the library, %d in Python" % (lib.tt_solver_abi_version(), SOLVER_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):

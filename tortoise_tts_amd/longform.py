@@ -61,11 +61,13 @@ def read_long_form(tts, text, preset="standard", conditioning_latents=None, voic
     are appended to every part but the last, after the per-chunk level and before the alignment, so the gap between the last speech
     region of one chunk and the first of the next is exactly round(pause * 24000) samples and the full audio is still the parts joined."""
     from . import loudness as loud
+    from . import pitch as f0m
     from . import resample as rs
     from . import silence as sil
     from .api_fast import TextToSpeech as FastTextToSpeech
     fast = isinstance(tts, FastTextToSpeech)
     rs.refuse_word_pitches(tts_kwargs, "read_long_form")
+    f0m.refuse_long_form(tts_kwargs)
     scope, level = loud.scope_option(tts_kwargs), loud.level_options(tts_kwargs)  # (applied here, to what the chunks' calls return)
     sample_rate = rs.options(dict(sample_rate=tts_kwargs.pop("sample_rate", None)))[1]  # (here too, after the level)
     gap = None if pause is None else sil.for_long_form(tts_kwargs, pause)  # (the chunks' calls get lead = trail = 0)

@@ -965,6 +965,68 @@ class SilenceStage(_Handle):
         return out
 
 
+class F0Stage(_Handle):
+    """The YIN fundamental-frequency tracker (csrc/f0.hip, include/tortoise_mi355x_f0.h): ragged batches, each clip with its own parameters
+    (pitch.Params), one tt_f0_track call per max_clips clips, every clip's result bit-identical to running it alone."""
+
+    api = "tt_f0"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        self._create(self.max_samples, self.max_clips)
+
+    def track_many(self, clips, params, dprime=False):
+        """clips f32 [n_i] (device or host) and a pitch.Params each -> one dict per clip: lag (i32 [F]), f0 (f32 [F], 0 where unvoiced), aper
+        (f32 [F]) on the host, n_voiced; dprime=True: also dprime (f64 [F, 481], through the test entry tt_op_f0_track)."""
+        if len(clips) != len(params):
+            raise ValueError(f"{len(clips)} clips with {len(params)} parameter sets")
+        for i, x in enumerate(clips):
+            if x.dim() != 1 or x.shape[0] < 1:
+                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
+            if x.shape[0] > self.max_samples:
+                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the F0 stage's capacity ({self.max_samples})")
+        out = []
+        for g in range(0, len(clips), self.max_clips):
+            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], dprime)
+        return out
+
+    def _group(self, clips, params, dprime):
+        n, dev = len(clips), self.device
+        lens = [x.shape[0] for x in clips]
+        io = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
+        fo = np.concatenate(([0], np.cumsum([self.lib.tt_f0_frames(m) for m in lens]))).astype(np.int32)
+        par = np.asarray([[p.lag_lo, p.lag_hi] for p in params], dtype=np.int32).reshape(-1)
+        thr = torch.tensor([[p.thr, p.floor_e] for p in params], dtype=torch.float64).to(dev)
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
+        host = torch.from_numpy(np.concatenate([io, fo, par])).to(dev)
+        Fs = int(fo[-1])
+        res = torch.zeros(2 * n + Fs + 1, device=dev, dtype=torch.int32)  # n_voiced | status | lag
+        vals = torch.zeros(2 * Fs + 1, device=dev, dtype=torch.float32)  # f0 | aper
+        hp, rp, vp_ = host.data_ptr(), res.data_ptr(), vals.data_ptr()
+        args = (self.h, n, audio.data_ptr(), hp, hp + 8 * (n + 1), thr.data_ptr(), hp + 4 * (n + 1), rp + 8 * n, vp_, vp_ + 4 * Fs, rp, rp + 4 * n)
+        dpr = None
+        if dprime:
+            dpr = torch.zeros(Fs * (E.F0_LAG_MAX + 1) + 1, device=dev, dtype=torch.float64)
+            E.check(self.lib.tt_op_f0_track(*args, dpr.data_ptr(), E.stream_ptr()))
+        else:
+            E.check(self.lib.tt_f0_track(*args, E.stream_ptr()))
+        res, vals = res.cpu().numpy(), vals.cpu().numpy()
+        status = res[n:2 * n].tolist()
+        if any(st != E.F0_OK for st in status):
+            raise RuntimeError(f"f0: the device stage refused clips it was handed (status {status})")
+        dpr = dpr.cpu().numpy()[:-1].reshape(Fs, E.F0_LAG_MAX + 1) if dprime else None
+        out = []
+        for i in range(n):
+            a, b = int(fo[i]), int(fo[i + 1])
+            d = dict(lag=res[2 * n + a:2 * n + b].copy(), f0=vals[a:b].copy(), aper=vals[Fs + a:Fs + b].copy(), n_voiced=int(res[i]))
+            if dprime:
+                d["dprime"] = dpr[a:b].copy()
+            out.append(d)
+        return out
+
+
 class FormantStage(_Handle):
     """Formant-preserving pitch: the cepstral envelope correction of finished clips at 24 kHz (csrc/formant.hip,
     include/tortoise_mi355x_fmt.h): ragged batches, each clip with its own warp alpha, one tt_fmt_run call per max_clips clips, every clip's
