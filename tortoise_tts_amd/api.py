@@ -542,12 +542,72 @@ class _Common:
             chains.append(rs.WarpChain(al.samples, *rs.merge_maps(al.samples, list(zip(rm.starts, rm.rqs)), list(zip(pm.starts, pm.pqs)), name)))
         clips = self._at_chains(clips, chains)
         if any(c.stretch is not None for c in chains):
-            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+            self._note(stretch_s=self._stretch_s)
         if any(set(c.pqs) != {E.RS_PITCH_ONE} for c in chains):
-            self.timings = dict(getattr(self, "timings", None) or {}, pitch_s=self._resample_s)
+            self._note(pitch_s=self._resample_s)
         clips = self._voiced(clips, None, None, level, None, pauses, None)
         out = clips if isinstance(out, (list, tuple)) else clips[0]
         return (out,) + tuple(res[1:]) if state else out
+
+    # ------------------------------------------------------------------ what the clip-level calls below share
+    def _clip_stage(self, attr, name, max_samples, cap, what, floor):
+        """The stages.<name> kept in self.<attr>: refused above `cap` samples (what the library takes), built on first use for clips of at
+        least `floor` samples, closed and rebuilt for a longer clip."""
+        if max_samples > cap:
+            raise ValueError(f"a clip of {max_samples} samples exceeds what the {what} can take ({cap})")
+        st = getattr(self, attr)
+        if st is None or (st.max_total_samples if hasattr(st, "max_total_samples") else st.max_samples) < max_samples:
+            if st is not None:
+                st.close()
+            setattr(self, attr, getattr(stages, name)(max(int(max_samples), floor), device=self.device))
+        return getattr(self, attr)
+
+    def _streaming_stage(self, attr, name, max_streams):
+        """The streaming stages.<name> kept in self.<attr>, built on first use."""
+        if getattr(self, attr) is None:
+            setattr(self, attr, getattr(stages, name)(max_streams, device=self.device))
+        return getattr(self, attr)
+
+    @staticmethod
+    def _clip(i, a, who):
+        """Clip i of a call is [n], [1, n] or [1, 1, n]; ValueError in the name of `who`."""
+        if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
+            raise ValueError(f"{who}: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+
+    def _clips(self, audios, who):
+        """The clips of a call as a list, every one checked (_clip)."""
+        audios = list(audios)
+        for i, a in enumerate(audios):
+            self._clip(i, a, who)
+        return audios
+
+    @staticmethod
+    def _per_clip(v, n):
+        """One value for all n clips, or one per clip."""
+        return list(v) if isinstance(v, (list, tuple)) else [v] * n
+
+    @staticmethod
+    def _like(a, y):
+        """The stage's result y in the shape and on the device of the clip a it was made from."""
+        return y.to(a.device).reshape(a.shape[:-1] + (-1,))
+
+    @staticmethod
+    def _winners(clips, step):
+        """What a tts call is about to return, {winner: clip} or a list, through step(list of clips) -> list; given back as it came."""
+        keys = sorted(clips) if isinstance(clips, dict) else None
+        seq = step([clips[i] for i in keys] if keys is not None else list(clips))
+        return dict(zip(keys, seq)) if keys is not None else seq
+
+    def _note(self, **seconds):
+        self.timings = dict(getattr(self, "timings", None) or {}, **seconds)
+
+    @staticmethod
+    def _subset(seq, todo, fn):
+        """fn(the clips of `seq` at the indices `todo`) -> as many clips, put back in their places; no call where `todo` is empty."""
+        if todo:
+            for i, y in zip(todo, fn([seq[i] for i in todo])):
+                seq[i] = y
+        return seq
 
     # ------------------------------------------------------------------ speaking rate: WSOLA time-stretch of finished clips
     stretcher = None
@@ -555,23 +615,13 @@ class _Common:
 
     def load_warp_stretch(self, max_samples=0):
         """The time-stretch along a rate map (stages.WarpStretchStage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.TSM_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the time-stretch can take ({E.TSM_MAX_SAMPLES})")
-        if self.warp_stretcher is None or self.warp_stretcher.max_samples < max_samples:
-            if self.warp_stretcher is not None:
-                self.warp_stretcher.close()
-            self.warp_stretcher = stages.WarpStretchStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE), device=self.device)
-        return self.warp_stretcher
+        return self._clip_stage("warp_stretcher", "WarpStretchStage", max_samples, E.TSM_MAX_SAMPLES, "time-stretch",
+                                ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE)
 
     def load_stretch(self, max_samples=0):
         """The time-stretch stage (stages.TimeStretchStage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.TSM_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the time-stretch can take ({E.TSM_MAX_SAMPLES})")
-        if self.stretcher is None or self.stretcher.max_samples < max_samples:
-            if self.stretcher is not None:
-                self.stretcher.close()
-            self.stretcher = stages.TimeStretchStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE), device=self.device)
-        return self.stretcher
+        return self._clip_stage("stretcher", "TimeStretchStage", max_samples, E.TSM_MAX_SAMPLES, "time-stretch",
+                                ORIG_ALIGNER_SECONDS * E.TSM_SAMPLE_RATE)
 
     @torch.no_grad()
     def stretch_many(self, audios, rates=None, durations=None, return_map=False, rate_maps=None):
@@ -591,18 +641,16 @@ class _Common:
         if (rates is None) == (durations is None):
             raise ValueError("stretch: give exactly one of rate, duration and rate_map")
         given = rates if durations is None else durations
-        given = list(given) if isinstance(given, (list, tuple)) else [given] * len(audios)
+        given = self._per_clip(given, len(audios))
         if len(given) != len(audios):
             raise ValueError(f"stretch: {len(audios)} clips with {len(given)} {'rates' if durations is None else 'durations'}")
-        for i, a in enumerate(audios):
-            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
-                raise ValueError(f"stretch: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+        self._clips(audios, "stretch")
         rqs = [tsm.rate_q(v if durations is None else tsm.rate_for_duration(a.shape[-1], v)) for a, v in zip(audios, given)]
         if not audios:
             return ([], []) if return_map else []
         t0 = time.perf_counter()
         res = self.load_stretch(max(a.shape[-1] for a in audios)).stretch_many([a.reshape(-1) for a in audios], rqs)
-        out = [y.to(a.device).reshape(a.shape[:-1] + (-1,)) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
+        out = [self._like(a, y) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
         self._stretch_s = time.perf_counter() - t0
         return (out, [tsm.anchors(rq, off) for rq, (_, off) in zip(rqs, res)]) if return_map else out
 
@@ -615,15 +663,13 @@ class _Common:
         rate_maps = list(rate_maps)
         if len(rate_maps) != len(audios):
             raise ValueError(f"stretch: {len(audios)} clips with {len(rate_maps)} rate maps")
-        for i, a in enumerate(audios):
-            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
-                raise ValueError(f"stretch: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+        self._clips(audios, "stretch")
         maps = [tsm.rate_map(a.shape[-1], m) for a, m in zip(audios, rate_maps)]
         if not audios:
             return ([], []) if return_map else []
         t0 = time.perf_counter()
         res = self.load_warp_stretch(max(a.shape[-1] for a in audios)).stretch_many([a.reshape(-1) for a in audios], [m.table for m in maps])
-        out = [y.to(a.device).reshape(a.shape[:-1] + (-1,)) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
+        out = [self._like(a, y) for a, (y, _) in zip(audios, res)]  # (the offsets' copy back has synchronised)
         self._stretch_s = time.perf_counter() - t0
         return (out, [m.anchors(off) for m, (_, off) in zip(maps, res)]) if return_map else out
 
@@ -639,14 +685,13 @@ class _Common:
         audios, anchors = list(audios), list(anchors)
         if len(anchors) != len(audios):
             raise ValueError(f"retime: {len(audios)} clips with {len(anchors)} anchor lists")
-        durations = list(durations) if isinstance(durations, (list, tuple)) else [durations] * len(audios)
+        durations = self._per_clip(durations, len(audios))
         if len(durations) != len(audios):
             raise ValueError(f"retime: {len(audios)} clips with {len(durations)} durations")
         to_s = lambda t: int(round(float(t) * E.TSM_SAMPLE_RATE))
         maps = []
         for i, (a, pts, d) in enumerate(zip(audios, anchors, durations)):
-            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
-                raise ValueError(f"retime: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
+            self._clip(i, a, "retime")
             pts = [(to_s(s_), to_s(t)) for s_, t in (pts or [])]
             if d is not None:
                 if not float(d) > 0:
@@ -672,12 +717,11 @@ class _Common:
         seq = list(clips)
         todo = [i for i, m in enumerate(maps) if m.rqs != [E.TSM_RATE_ONE]]
         if todo:
-            for i, y in zip(todo, self.stretch_many([seq[i] for i in todo], rate_maps=[maps[i] for i in todo])):
-                seq[i] = y
-            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+            self._subset(seq, todo, lambda sub: self.stretch_many(sub, rate_maps=[maps[i] for i in todo]))
+            self._note(stretch_s=self._stretch_s)
         if pq != E.RS_PITCH_ONE:
             seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE)] * len(seq), False)
-            self.timings = dict(getattr(self, "timings", None) or {}, pitch_s=self._resample_s)
+            self._note(pitch_s=self._resample_s)
         return seq
 
     stream_stretcher = None
@@ -685,15 +729,11 @@ class _Common:
 
     def load_stream_stretch(self, max_streams=16):
         """The streaming time-stretch of open_stretcher (stages.StreamStretchStage), built on first use."""
-        if self.stream_stretcher is None:
-            self.stream_stretcher = stages.StreamStretchStage(max_streams, device=self.device)
-        return self.stream_stretcher
+        return self._streaming_stage("stream_stretcher", "StreamStretchStage", max_streams)
 
     def load_stream_pitch(self, max_streams=16):
         """The streaming resampler behind open_stretcher's pitch (a stages.StreamResampleStage of its own), built on first use."""
-        if self.stream_pitch_resampler is None:
-            self.stream_pitch_resampler = stages.StreamResampleStage(max_streams, device=self.device)
-        return self.stream_pitch_resampler
+        return self._streaming_stage("stream_pitch_resampler", "StreamResampleStage", max_streams)
 
     def open_stretcher(self, rate=None, pitch=None, keep_map=False):
         """A StreamStretcher for 24 kHz audio that arrives in chunks: push(chunk) returns the samples that became ready, finish() the rest;
@@ -714,12 +754,8 @@ class _Common:
         """The clips a tts call is about to return ({winner: clip} or a list), at speaking_rate `rate`: one stretch_many call for all of
         them, its time in timings['stretch_s']."""
         self._stretch_s = 0.0
-        if isinstance(clips, dict):
-            keys = sorted(clips)
-            out = dict(zip(keys, self.stretch_many([clips[i] for i in keys], rates=rate)))
-        else:
-            out = self.stretch_many(clips, rates=rate)
-        self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s)
+        out = self._winners(clips, lambda seq: self.stretch_many(seq, rates=rate))
+        self._note(stretch_s=self._stretch_s)
         return out
 
     # ------------------------------------------------------------------ level: integrated loudness, true peak, gain under a ceiling
@@ -727,27 +763,13 @@ class _Common:
 
     def load_loudness(self, max_samples=0):
         """The loudness stage (stages.LoudnessStage), built on first use for sixteen clips of 30 s and rebuilt for a longer clip."""
-        if max_samples > E.LOUD_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the loudness stage can take ({E.LOUD_MAX_SAMPLES})")
-        if self.leveller is None or self.leveller.max_total_samples < max_samples:
-            if self.leveller is not None:
-                self.leveller.close()
-            self.leveller = stages.LoudnessStage(max(int(max_samples), LOUDNESS_STAGE_SAMPLES), device=self.device)
-        return self.leveller
-
-    @staticmethod
-    def _level_clips(audios, who):
-        audios = list(audios)
-        for i, a in enumerate(audios):
-            if not 1 <= a.dim() <= 3 or a.numel() != a.shape[-1] or a.numel() == 0:
-                raise ValueError(f"{who}: clip {i} of shape {tuple(a.shape)}, expected [n], [1, n] or [1, 1, n] with n >= 1")
-        return audios
+        return self._clip_stage("leveller", "LoudnessStage", max_samples, E.LOUD_MAX_SAMPLES, "loudness stage", LOUDNESS_STAGE_SAMPLES)
 
     @torch.no_grad()
     def loudness_many(self, audios):
         """Integrated loudness (ITU-R BS.1770-4 / EBU R 128, gated) and 4x oversampled true peak of every clip: audios f32 [n] / [1, n] /
         [1, 1, n] at 24 kHz (any device) -> [loudness.Loudness], all clips in ONE device call per 16."""
-        audios = self._level_clips(audios, "loudness")
+        audios = self._clips(audios, "loudness")
         if not audios:
             return []
         res = self.load_loudness(max(a.shape[-1] for a in audios)).measure_many([a.reshape(-1) for a in audios])
@@ -764,9 +786,8 @@ class _Common:
         'scale' (the gain is lowered until the ceiling holds; the shortfall is reported), 'lookahead' (a 5 ms look-ahead limiter takes the
         peaks down instead) or 'none'.  A clip shorter than 400 ms or without a block above -70 LUFS is returned unchanged.
         return_info=True: also [loudness.Loudness]."""
-        audios = self._level_clips(audios, "normalize")
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(audios)
-        targets, peaks = per(loudness), per(true_peak)
+        audios = self._clips(audios, "normalize")
+        targets, peaks = self._per_clip(loudness, len(audios)), self._per_clip(true_peak, len(audios))
         if len(targets) != len(audios) or len(peaks) != len(audios):
             raise ValueError(f"normalize: {len(audios)} clips with {len(targets)} targets and {len(peaks)} ceilings")
         levels = [loud.level(T, p, limit) for T, p in zip(targets, peaks)]
@@ -775,7 +796,7 @@ class _Common:
         t0 = time.perf_counter()
         res = self.load_loudness(max(a.shape[-1] for a in audios)).normalize_many(
             [a.reshape(-1) for a in audios], [lv.loudness for lv in levels], [lv.ceiling for lv in levels], loud.MODES[limit or "scale"])
-        out = [y.to(a.device).reshape(a.shape) for a, (y, _) in zip(audios, res)]  # (the readings' copy back has synchronised)
+        out = [self._like(a, y) for a, (y, _) in zip(audios, res)]  # (the readings' copy back has synchronised)
         self._level_s = time.perf_counter() - t0
         return (out, [loud.reading(r, lv.loudness) for (_, r), lv in zip(res, levels)]) if return_info else out
 
@@ -787,26 +808,20 @@ class _Common:
         """The clips a tts call is about to return ({winner: clip} or a list), at `level` (loudness.Level): one normalize_many call for all
         of them, its time in timings['level_s'], the readings in self.loudness_info."""
         self._level_s = 0.0
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        out, info = self.normalize_many([clips[i] for i in keys] if keys is not None else clips, level.loudness, level.true_peak, level.limit,
-                                        return_info=True)
-        self.loudness_info = info
-        self.timings = dict(getattr(self, "timings", None) or {}, level_s=self._level_s)
-        return dict(zip(keys, out)) if keys is not None else out
 
+        def step(seq):
+            out, self.loudness_info = self.normalize_many(seq, level.loudness, level.true_peak, level.limit, return_info=True)
+            return out
+        out = self._winners(clips, step)
+        self._note(level_s=self._level_s)
+        return out
 
     # ------------------------------------------------------------------ pitch and output sample rate: the arbitrary-ratio resampler
     resampler = None
 
     def load_resample(self, max_samples=0):
         """The resampling stage (stages.ResampleStage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.RS_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the resampler can take ({E.RS_MAX_SAMPLES})")
-        if self.resampler is None or self.resampler.max_samples < max_samples:
-            if self.resampler is not None:
-                self.resampler.close()
-            self.resampler = stages.ResampleStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE), device=self.device)
-        return self.resampler
+        return self._clip_stage("resampler", "ResampleStage", max_samples, E.RS_MAX_SAMPLES, "resampler", ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE)
 
     def _resample_ratios(self, audios, ratios, return_info):
         """audios (validated) at (P, Q) each -> the clips, each in the shape and on the device it came in; all of them through ONE device
@@ -818,7 +833,7 @@ class _Common:
             res = self.load_resample(max(audios[i].shape[-1] for i in todo)).resample_many([audios[i].reshape(-1) for i in todo],
                                                                                           [ratios[i] for i in todo])
             for i, (y, pk) in zip(todo, res):  # (the peaks' copy back has synchronised)
-                out[i], peaks[i] = y.to(audios[i].device).reshape(audios[i].shape[:-1] + (-1,)), pk
+                out[i], peaks[i] = self._like(audios[i], y), pk
         if return_info:
             peaks = [float(a.abs().max()) if pk is None else pk for a, pk in zip(audios, peaks)]
         self._resample_s = time.perf_counter() - t0
@@ -831,9 +846,8 @@ class _Common:
         terms up to 2^20 and lies in 1/8 .. 8 (24000 -> 8000 / 16000 / 44100 / 48000, or a 44100 Hz voice clip -> 22050).  A Kaiser-windowed
         sinc with its cutoff at 0.9 of the narrower Nyquist frequency (csrc/resample.hip): pass-band within 0.001 dB, everything else below
         -100 dB.  All clips go through ONE device call per 16.  return_info=True: also the sample peak max |y| of every returned clip."""
-        audios = self._level_clips(audios, "resample")
-        per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(audios)
-        to_rates, from_rates = per(to_rates), per(from_rates)
+        audios = self._clips(audios, "resample")
+        to_rates, from_rates = self._per_clip(to_rates, len(audios)), self._per_clip(from_rates, len(audios))
         if len(to_rates) != len(audios) or len(from_rates) != len(audios):
             raise ValueError(f"resample: {len(audios)} clips with {len(to_rates)} target rates and {len(from_rates)} source rates")
         return self._resample_ratios(audios, [rs.ratio(f, t) for f, t in zip(from_rates, to_rates)], return_info)
@@ -846,9 +860,7 @@ class _Common:
 
     def load_stream_resample(self, max_streams=16):
         """The streaming resampler of open_resampler (stages.StreamResampleStage), built on first use."""
-        if self.stream_resampler is None:
-            self.stream_resampler = stages.StreamResampleStage(max_streams, device=self.device)
-        return self.stream_resampler
+        return self._streaming_stage("stream_resampler", "StreamResampleStage", max_streams)
 
     def open_resampler(self, to_rate, from_rate=rs.SAMPLE_RATE):
         """A StreamResampler for audio that arrives in chunks: push(chunk) returns the samples at to_rate that became ready, finish() the
@@ -880,7 +892,7 @@ class _Common:
         ratio per clip; formants='keep' stays allowed.  A shift beyond +-12 semitones is clamped and a clip with fewer than 10 voiced
         frames is returned bit for bit, each with a warning.  return_info=True then gives, per clip, a dict measured_hz (None: no
         median), semitones, clamped and peak; the readings are also left in self.pitch_info."""
-        audios = self._level_clips(audios, "shift_pitch")
+        audios = self._clips(audios, "shift_pitch")
         if (semitones is None) + (pitch_maps is None) + (to_hz is None) != 2:
             raise ValueError("shift_pitch: give exactly one of semitones and pitch_map, or to_hz")
         if to_hz is not None:
@@ -897,7 +909,7 @@ class _Common:
             return self._shift_maps(audios, pitch_maps, return_info, return_map)
         if return_map:
             raise ValueError("shift_pitch: return_map=True goes with pitch_map")
-        semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
+        semis = self._per_clip(semitones, len(audios))
         if len(semis) != len(audios):
             raise ValueError(f"shift_pitch: {len(audios)} clips with {len(semis)} pitches")
         plans = [rs.pitch(s_) for s_ in semis]
@@ -908,12 +920,7 @@ class _Common:
             out = self._correct_formants(out, corr)
             return (out, [float(a.abs().max()) for a in out]) if return_info else out
         t0 = time.perf_counter()
-        todo = [i for i, (pq, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
-        mid = list(audios)
-        if todo:  # (rate 1.0 is the input itself: not stretched)
-            for i, y in zip(todo, self.stretch_many([audios[i] for i in todo], rates=[plans[i][1] / E.TSM_RATE_ONE for i in todo])):
-                mid[i] = y
-        res = self._resample_ratios(mid, [(pq, E.RS_PITCH_ONE) for pq, _ in plans], return_info)
+        res = self._resample_ratios(self._stretched(list(audios), plans), [(pq, E.RS_PITCH_ONE) for pq, _ in plans], return_info)
         self._resample_s = time.perf_counter() - t0
         return res
 
@@ -936,13 +943,8 @@ class _Common:
 
     def load_warp_resample(self, max_samples=0):
         """The resampling along a pitch map (stages.WarpResampleStage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.RS_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the resampler can take ({E.RS_MAX_SAMPLES})")
-        if self.warp_resampler is None or self.warp_resampler.max_samples < max_samples:
-            if self.warp_resampler is not None:
-                self.warp_resampler.close()
-            self.warp_resampler = stages.WarpResampleStage(max(int(max_samples), 2 * ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE), device=self.device)
-        return self.warp_resampler
+        return self._clip_stage("warp_resampler", "WarpResampleStage", max_samples, E.RS_MAX_SAMPLES, "resampler",
+                                2 * ORIG_ALIGNER_SECONDS * rs.SAMPLE_RATE)
 
     def _shift_maps(self, audios, pitch_maps, return_info, return_map):
         """shift_pitch_many along pitch maps."""
@@ -963,6 +965,12 @@ class _Common:
             res += ([c.anchors for c in chains],)
         return res if len(res) > 1 else out
 
+    def _stretched(self, seq, plans):
+        """The list `seq` with every clip whose plan (pq, rq_eff) has a rate other than 1.0 time-stretched at it, in ONE stretch_many call
+        (rate 1.0 is the input itself: not stretched)."""
+        todo = [i for i, (_, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
+        return self._subset(seq, todo, lambda sub: self.stretch_many(sub, rates=[plans[i][1] / E.TSM_RATE_ONE for i in todo]))
+
     def _at_chains(self, audios, chains):
         """audios (validated) each along its resample.WarpChain -> the clips, each in the shape and on the device it came in: ONE
         time-stretch call per 16 for the clips whose speaking rate or pitch changes inside them, and ONE resampling call.  What is
@@ -972,28 +980,21 @@ class _Common:
         self._stretch_s = 0.0
         const = [i for i, c in enumerate(chains) if c.stretch is not None and len(c.stretch) == 1]
         warp = [i for i, c in enumerate(chains) if c.stretch is not None and len(c.stretch) > 1]
-        spent = 0.0
-        if const:
-            for i, y in zip(const, self.stretch_many([seq[i] for i in const], rates=[chains[i].rq_effs[0] / E.TSM_RATE_ONE for i in const])):
-                seq[i] = y
-            spent += self._stretch_s
-        if warp:
-            for i, y in zip(warp, self.stretch_many([seq[i] for i in warp], rate_maps=[tsm.RateMap(chains[i].n, chains[i].starts, chains[i].rq_effs)
-                                                                                          for i in warp])):
-                seq[i] = y
-            spent += self._stretch_s
-        self._stretch_s = spent
+        self._subset(seq, const, lambda sub: self.stretch_many(sub, rates=[chains[i].rq_effs[0] / E.TSM_RATE_ONE for i in const]))
+        spent = self._stretch_s  # (still 0.0 where no clip took that call)
+        maps = [tsm.RateMap(chains[i].n, chains[i].starts, chains[i].rq_effs) for i in warp]
+        self._subset(seq, warp, lambda sub: self.stretch_many(sub, rate_maps=maps))
+        self._stretch_s = spent + self._stretch_s if warp else spent
         t0 = time.perf_counter()
         flat = [i for i, c in enumerate(chains) if len(set(c.pqs)) == 1]
         bent = [i for i, c in enumerate(chains) if len(set(c.pqs)) > 1]
-        if flat:
-            for i, y in zip(flat, self._resample_ratios([seq[i] for i in flat], [(chains[i].pqs[0], E.RS_PITCH_ONE) for i in flat], False)):
-                seq[i] = y
-        if bent:
-            res = self.load_warp_resample(max(seq[i].shape[-1] for i in bent)).resample_many([seq[i].reshape(-1) for i in bent],
-                                                                                            [chains[i].resample for i in bent])
-            for i, (y, _) in zip(bent, res):  # (the peaks' copy back has synchronised)
-                seq[i] = y.to(audios[i].device).reshape(audios[i].shape[:-1] + (-1,))
+        self._subset(seq, flat, lambda sub: self._resample_ratios(sub, [(chains[i].pqs[0], E.RS_PITCH_ONE) for i in flat], False))
+
+        def along(sub):  # (the peaks' copy back has synchronised)
+            stage = self.load_warp_resample(max(a.shape[-1] for a in sub))
+            res = stage.resample_many([a.reshape(-1) for a in sub], [chains[i].resample for i in bent])
+            return [self._like(a, y) for a, (y, _) in zip(sub, res)]
+        self._subset(seq, bent, along)
         self._resample_s = time.perf_counter() - t0
         assert all(y.shape[-1] == c.n_out for y, c in zip(seq, chains)), "the chain's plans and the stages agree on every length"
         return seq
@@ -1004,13 +1005,7 @@ class _Common:
 
     def load_f0(self, max_samples=0):
         """The F0 stage (stages.F0Stage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.F0_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the F0 tracker can take ({E.F0_MAX_SAMPLES})")
-        if self.f0_stage is None or self.f0_stage.max_samples < max_samples:
-            if self.f0_stage is not None:
-                self.f0_stage.close()
-            self.f0_stage = stages.F0Stage(max(int(max_samples), ORIG_ALIGNER_SECONDS * f0m.SAMPLE_RATE), device=self.device)
-        return self.f0_stage
+        return self._clip_stage("f0_stage", "F0Stage", max_samples, E.F0_MAX_SAMPLES, "F0 tracker", ORIG_ALIGNER_SECONDS * f0m.SAMPLE_RATE)
 
     @torch.no_grad()
     def f0_many(self, audios, fmin=f0m.DEFAULTS["fmin"], fmax=f0m.DEFAULTS["fmax"], threshold=f0m.DEFAULTS["threshold"],
@@ -1022,7 +1017,7 @@ class _Common:
         with its power below floor_db dBFS, is unvoiced.  No smoothing over frames: an octave jump in one frame stays in the track (the
         median does not see it).  All clips go through ONE device call per 16 (csrc/f0.hip).  The defaults were chosen from the paper
         and the code: nobody has tuned them on a trained checkpoint's audio."""
-        audios = self._level_clips(audios, "f0")
+        audios = self._clips(audios, "f0")
         p = f0m.params(fmin, fmax, threshold, floor_db)
         if not audios:
             return []
@@ -1036,7 +1031,7 @@ class _Common:
     def _shifts_to(self, audios, to_hz, who):
         """audios (validated) and the pitch to land on (Hz: one value or one per clip) -> (semitones per clip, [dict(measured_hz, semitones,
         clamped)]): ONE f0_many call, then pitch.shift_to per clip.  The readings are left in self.pitch_info."""
-        hzs = list(to_hz) if isinstance(to_hz, (list, tuple)) else [to_hz] * len(audios)
+        hzs = self._per_clip(to_hz, len(audios))
         if len(hzs) != len(audios):
             raise ValueError(f"{who}: {len(audios)} clips with {len(hzs)} target pitches")
         hzs = [f0m.target_hz("to_hz" if who == "shift_pitch" else "pitch_hz", h) for h in hzs]
@@ -1055,10 +1050,9 @@ class _Common:
     def _pitch_hz_plan(self, clips, hz, formant_kw, who="tts"):
         """pitch_hz= of a tts call: the clips it is about to return ({winner: clip} or a list), measured in ONE device call -> (semitones
         per clip in the clips' order, formant.Params or None per clip: formants='keep' takes every clip's own shift back)."""
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        semis, _ = self._shifts_to(self._level_clips(seq, who), hz, who)
-        self.timings = dict(getattr(self, "timings", None) or {}, f0_s=self._f0_s)
+        seq = [clips[i] for i in sorted(clips)] if isinstance(clips, dict) else clips
+        semis, _ = self._shifts_to(self._clips(seq, who), hz, who)
+        self._note(f0_s=self._f0_s)
         kw = dict(formant_kw or {})
         keep = fmt.mode(kw.get("formants"))
         plans = [fmt.params(s_ if s_ != 0.0 else None, keep, kw.get("formant_shift"), kw.get("formant_lifter_ms"), kw.get("formant_max_gain_db"))
@@ -1097,7 +1091,7 @@ class _Common:
             stage = self.load_formant(max(audios[i].shape[-1] for i in todo), *key, clips=len(todo))
             res = stage.correct_many([audios[i].reshape(-1) for i in todo], [plans[i].alpha for i in todo])
             for i, y in zip(todo, res):
-                out[i] = y.to(audios[i].device).reshape(audios[i].shape)
+                out[i] = self._like(audios[i], y)
         self._formant_s = time.perf_counter() - t0
         return out
 
@@ -1109,8 +1103,8 @@ class _Common:
         at 2^(-f / 12) times each frequency and the frame's spectrum gets the difference as a gain of at most formant_max_gain_db (24 dB);
         the harmonics stay where they are (csrc/formant.hip - DESIGN.md 5.32).  All clips go through ONE device call per 16.  0 semitones
         returns the clip as it is.  Nobody has listened to a trained checkpoint through it."""
-        audios = self._level_clips(audios, "shift_formants")
-        semis = list(semitones) if isinstance(semitones, (list, tuple)) else [semitones] * len(audios)
+        audios = self._clips(audios, "shift_formants")
+        semis = self._per_clip(semitones, len(audios))
         if len(semis) != len(audios):
             raise ValueError(f"shift_formants: {len(audios)} clips with {len(semis)} shifts")
         return self._correct_formants(audios, [fmt.params(None, False, f, formant_lifter_ms, formant_max_gain_db) for f in semis])
@@ -1122,57 +1116,42 @@ class _Common:
     def _at_formants(self, clips, params):
         """The clips a tts call is about to return ({winner: clip} or a list) corrected with `params` (formant.Params): one call for all of
         them, its time in timings['formant_s']."""
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        seq = self._correct_formants(seq, list(params) if isinstance(params, list) else [params] * len(seq))  # (a list: one per clip, None allowed)
-        self.timings = dict(getattr(self, "timings", None) or {}, formant_s=self._formant_s)
-        return dict(zip(keys, seq)) if keys is not None else seq
+        # (params as a list: one per clip, None allowed)
+        out = self._winners(clips, lambda seq: self._correct_formants(seq, list(params) if isinstance(params, list) else [params] * len(seq)))
+        self._note(formant_s=self._formant_s)
+        return out
 
     def _at_pitch(self, clips, rate, semitones):
         """The clips a tts call is about to return ({winner: clip} or a list) at speaking_rate `rate` (None: 1.0) and pitch `semitones`: ONE
         stretch_many call at rq_eff = round(rq 65536 / pq) and ONE resampling by (pq, 65536) for all of them; their time in
         timings['stretch_s'] / ['pitch_s']."""
         self._stretch_s = 0.0
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        if isinstance(semitones, list):  # one pitch per clip (pitch_hz=), in the clips' order: still ONE stretch and ONE resampling
-            plans = [rs.pitch(s_, rate) for s_ in semitones]
-            todo = [i for i, (_, rq) in enumerate(plans) if rq != E.TSM_RATE_ONE]
-            if todo:
-                for i, y in zip(todo, self.stretch_many([seq[i] for i in todo], rates=[plans[i][1] / E.TSM_RATE_ONE for i in todo])):
-                    seq[i] = y
-            seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE) for pq, _ in plans], False)
-            self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s, pitch_s=self._resample_s)
-            return dict(zip(keys, seq)) if keys is not None else seq
-        pq, rq_eff = rs.pitch(semitones, rate)
-        if rq_eff != E.TSM_RATE_ONE:
-            seq = self.stretch_many(seq, rates=rq_eff / E.TSM_RATE_ONE)  # (rq_eff / 65536 is exact: stretch.rate_q returns rq_eff)
-        seq = self._resample_ratios(seq, [(pq, E.RS_PITCH_ONE)] * len(seq), False)
-        self.timings = dict(getattr(self, "timings", None) or {}, stretch_s=self._stretch_s, pitch_s=self._resample_s)
-        return dict(zip(keys, seq)) if keys is not None else seq
+
+        def step(seq):
+            # a list: one pitch per clip (pitch_hz=), in the clips' order: still ONE stretch and ONE resampling.  rq_eff / 65536 is exact:
+            # stretch.rate_q returns rq_eff
+            plans = [rs.pitch(s_, rate) for s_ in semitones] if isinstance(semitones, list) else [rs.pitch(semitones, rate)] * len(seq)
+            return self._resample_ratios(self._stretched(seq, plans), [(pq, E.RS_PITCH_ONE) for pq, _ in plans], False)
+        out = self._winners(clips, step)
+        self._note(stretch_s=self._stretch_s, pitch_s=self._resample_s)
+        return out
 
     def _at_sample_rate(self, clips, sample_rate):
         """The clips a tts call is about to return ({winner: clip} or a list) converted from 24 kHz to `sample_rate`: the last step, one
         call for all of them, its time in timings['resample_s'], the sample peaks of the returned clips in self.resample_info."""
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        seq, peaks = self._resample_ratios(seq, [rs.ratio(rs.SAMPLE_RATE, sample_rate)] * len(seq), True)
-        self.resample_info = peaks
-        self.timings = dict(getattr(self, "timings", None) or {}, resample_s=self._resample_s)
-        return dict(zip(keys, seq)) if keys is not None else seq
+        def step(seq):
+            seq, self.resample_info = self._resample_ratios(seq, [rs.ratio(rs.SAMPLE_RATE, sample_rate)] * len(seq), True)
+            return seq
+        out = self._winners(clips, step)
+        self._note(resample_s=self._resample_s)
+        return out
 
     # ------------------------------------------------------------------ pauses and silence: speech regions, edge trimming, pause capping
     silencer = None
 
     def load_silence(self, max_samples=0):
         """The silence stage (stages.SilenceStage), built on first use for clips of 30 s and rebuilt for a longer one."""
-        if max_samples > E.SIL_MAX_SAMPLES:
-            raise ValueError(f"a clip of {max_samples} samples exceeds what the silence stage can take ({E.SIL_MAX_SAMPLES})")
-        if self.silencer is None or self.silencer.max_samples < max_samples:
-            if self.silencer is not None:
-                self.silencer.close()
-            self.silencer = stages.SilenceStage(max(int(max_samples), ORIG_ALIGNER_SECONDS * sil.SAMPLE_RATE), device=self.device)
-        return self.silencer
+        return self._clip_stage("silencer", "SilenceStage", max_samples, E.SIL_MAX_SAMPLES, "silence stage", ORIG_ALIGNER_SECONDS * sil.SAMPLE_RATE)
 
     @torch.no_grad()
     def speech_regions_many(self, audios, top_db=sil.DEFAULTS["top_db"], floor_db=sil.DEFAULTS["floor_db"],
@@ -1182,7 +1161,7 @@ class _Common:
         first and after the last region is not listed).  A 10 ms frame is active when its energy is within top_db of the clip's loudest
         frame and above floor_db dBFS; pauses shorter than min_silence seconds are bridged and every region is padded by `pad` seconds.
         All clips go through ONE device call per 16.  A clip without an active frame has no region."""
-        audios = self._level_clips(audios, "speech_regions")
+        audios = self._clips(audios, "speech_regions")
         p = sil.params(lead=None, trail=None, max_pause=None, top_db=top_db, floor_db=floor_db, min_silence=min_silence, pad=pad)
         if not audios:
             return []
@@ -1201,7 +1180,7 @@ class _Common:
         if audios:
             res = self.load_silence(max(a.shape[-1] for a in audios)).trim_many([a.reshape(-1) for a in audios], params)
             for a, (y, d) in zip(audios, res):  # (the results' copy back has synchronised)
-                out.append(y.to(a.device).reshape(a.shape[:-1] + (-1,)))
+                out.append(self._like(a, y))
                 maps.append(d["segments"])
                 info.append(dict(status=sil.STATUS[d["status"]], removed_s=(a.shape[-1] - y.shape[-1]) / sil.SAMPLE_RATE, regions=d["regions"]))
         self.silence_info = info
@@ -1220,7 +1199,7 @@ class _Common:
         found and edited without a round trip in between.  The defaults were chosen from the code: nobody has run a trained checkpoint's
         audio through them.  return_map=True: also, per clip, the segment list [(output start, input start, length)], with which
         silence.map_sample carries a time in the original clip over to the trimmed one.  Status and seconds removed: self.silence_info."""
-        audios = self._level_clips(audios, "trim")
+        audios = self._clips(audios, "trim")
         p = sil.params(lead=lead, trail=trail, max_pause=max_pause, top_db=top_db, floor_db=floor_db, min_silence=min_silence, pad=pad)
         return self._trim_params(audios, [p] * len(audios), return_map)
 
@@ -1231,11 +1210,9 @@ class _Common:
     def _at_pauses(self, clips, params):
         """The clips a tts call is about to return ({winner: clip} or a list) with their pauses shaped by `params` (silence.Params): one
         call for all of them, its time in timings['silence_s'], status and seconds removed in self.silence_info."""
-        keys = sorted(clips) if isinstance(clips, dict) else None
-        seq = [clips[i] for i in keys] if keys is not None else list(clips)
-        seq = self._trim_params(seq, [params] * len(seq), False)
-        self.timings = dict(getattr(self, "timings", None) or {}, silence_s=self._silence_s)
-        return dict(zip(keys, seq)) if keys is not None else seq
+        out = self._winners(clips, lambda seq: self._trim_params(seq, [params] * len(seq), False))
+        self._note(silence_s=self._silence_s)
+        return out
 
     def _voiced(self, clips, rate, pitch, level, sample_rate, pauses=None, formants=None):
         """The chain behind redaction: speaking rate and pitch together, then the formants (formant.Params), then the pauses

@@ -4,6 +4,7 @@ call on the caller's current torch stream.  No model arithmetic happens here bey
 gathers for the once-per-utterance prefix (plumbing).
 """
 import ctypes as C
+import itertools
 import math
 import os
 
@@ -12,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import engine as E
+from . import formant as fmt
 from . import pack
 from . import resample as rs
 from . import stretch as tsm
@@ -473,16 +475,114 @@ class AlignerStage(_GuardedHandle):
         return self.run(audio).cpu().tolist()
 
 
-class CtcAlignStage(_Handle):
+class _Tables:
+    """Named flat lists of one dtype laid end to end in one host buffer and copied to the device in one go: p(name) is the device address
+    of an array, whatever stands before it."""
+
+    def __init__(self, device, dtype=torch.int32, **arrays):
+        self.at, flat = {}, []
+        for name, v in arrays.items():
+            self.at[name] = len(flat)
+            flat += v
+        self.t = torch.tensor(flat, dtype=dtype).to(device)
+
+    def p(self, name):
+        return self.t.data_ptr() + self.at[name] * self.t.element_size()
+
+
+class _Results:
+    """Result arrays from named sizes, <torch dtype name>=dict(name=elements): one zero-filled device tensor per dtype, its arrays end to
+    end and one pad element behind them (an empty array still has an address).  p(name) is an array's device address for the call; after
+    cpu(), one copy back per dtype, [name] is the array on the host, a numpy view of that copy."""
+
+    def __init__(self, device, **dtypes):
+        self.at, self.buf = {}, {}
+        for dt, sizes in dtypes.items():
+            o = 0
+            for name, k in sizes.items():
+                self.at[name] = (dt, o, int(k))
+                o += int(k)
+            self.buf[dt] = torch.zeros(o + 1, device=device, dtype=getattr(torch, dt))
+
+    def p(self, name):
+        dt, o, _ = self.at[name]
+        return self.buf[dt].data_ptr() + o * self.buf[dt].element_size()
+
+    def cpu(self):
+        self.buf = {dt: b.cpu().numpy() for dt, b in self.buf.items()}
+
+    def __getitem__(self, name):
+        dt, o, k = self.at[name]
+        return self.buf[dt][o:o + k]
+
+
+class _ClipStage(_Handle):
+    """A stage over ragged batches of clips: every public call checks its clips, splits them into groups the handle takes in one call
+    (_groups) and hands each group to the stage's _group, which packs its tables (_Tables), makes ONE library call on the current stream
+    and cuts every clip's result out of the result buffers (_Results).  The wording of the shared errors comes from class attributes."""
+
+    noun = None               # "... exceed the <noun> capacity"
+    what = None               # "<what>: the device stage refused clips it was handed"
+    capacity = "max_samples"  # the attribute that bounds a clip
+    least, least_text = 1, "one sample"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda", extra=()):
+        """extra: what <api>_create takes after (capacity, max_clips); None: the stage calls _create itself."""
+        self.lib = E.init()
+        self.device = torch.device(device)
+        setattr(self, self.capacity, int(max_samples))
+        self.max_clips = int(max_clips)
+        if extra is not None:
+            self._create(int(max_samples), self.max_clips, *extra)
+
+    def _check_clip(self, i, x):
+        if x.dim() != 1 or x.shape[0] < self.least:
+            raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least {self.least_text}")
+        if x.shape[0] > getattr(self, self.capacity):
+            raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the {self.noun} capacity ({getattr(self, self.capacity)})")
+
+    def _groups(self, clips):
+        """[(first, end)] of the runs of clips that go into one call each."""
+        return [(g, min(g + self.max_clips, len(clips))) for g in range(0, len(clips), self.max_clips)]
+
+    def _run(self, clips, *per_clip, **options):
+        """_group over every group of `clips` and the matching slices of the per-clip lists (None stays None) -> the results in order."""
+        out = []
+        for a, b in self._groups(clips):
+            out += self._group(clips[a:b], *[None if v is None else v[a:b] for v in per_clip], **options)
+        return out
+
+    @staticmethod
+    def _offsets(counts):
+        """Per-clip counts -> a list of n + 1: where each clip's slice starts and the last one ends."""
+        return list(itertools.accumulate(counts, initial=0))
+
+    def _audio(self, clips):
+        """The clips end to end on the device, one pad element behind them."""
+        return torch.cat([x.to(device=self.device, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=self.device)])
+
+    @staticmethod
+    def _host(a):
+        """A slice of a result array as a host tensor of its own."""
+        return torch.from_numpy(a.copy())
+
+    def _accepted(self, status, ok):
+        """The per-clip status as a list; RuntimeError unless every one is in `ok`."""
+        status = status.tolist()
+        if any(st not in ok for st in status):
+            raise RuntimeError(f"{self.what}: the device stage refused clips it was handed (status {status})")
+        return status
+
+
+class CtcAlignStage(_ClipStage):
     """CTC forced alignment of known targets with the aligner's logits (csrc/ctc_align.hip, include/tortoise_mi355x_ctc.h): ragged batches,
     one tt_ctc_align call per max_clips clips, every clip's result bit-identical to aligning it alone."""
 
-    api = "tt_ctc"
+    api, capacity = "tt_ctc", "max_frames"
 
     def __init__(self, vocab, blank, max_frames, max_tokens=E.CTC_MAX_TOKENS, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.vocab, self.blank, self.max_frames, self.max_tokens, self.max_clips = int(vocab), int(blank), int(max_frames), int(max_tokens), int(max_clips)
+        self.vocab, self.blank, self.max_tokens = int(vocab), int(blank), int(max_tokens)
+        super().__init__(max_frames, max_clips, device, extra=None)
         self._create(self.max_frames, self.max_tokens, self.max_clips, self.vocab, self.blank)
 
     @classmethod
@@ -505,47 +605,32 @@ class CtcAlignStage(_Handle):
                 raise ValueError(f"clip {i}: logits of shape {tuple(lg.shape)}, expected [frames, {self.vocab}]")
             if lg.shape[0] > self.max_frames:
                 raise ValueError(f"clip {i}: {lg.shape[0]} frames exceed the forced alignment's capacity ({self.max_frames})")
-        out = []
-        for g in range(0, len(logits_list), self.max_clips):
-            out += self._group(logits_list[g:g + self.max_clips], targets_list[g:g + self.max_clips])
-        return out
+        return self._run(logits_list, targets_list)
 
     def _group(self, logits_list, targets_list):
         n, dev = len(logits_list), self.device
-        fo = np.concatenate(([0], np.cumsum([lg.shape[0] for lg in logits_list]))).astype(np.int32)
-        to = np.concatenate(([0], np.cumsum([len(tg) for tg in targets_list]))).astype(np.int32)
-        F_, L_ = int(fo[-1]), int(to[-1])
+        fo, to = self._offsets(lg.shape[0] for lg in logits_list), self._offsets(len(tg) for tg in targets_list)
         lg = torch.cat([x.to(device=dev, dtype=torch.float32).reshape(-1, self.vocab) for x in logits_list] + [torch.zeros(1, self.vocab, device=dev)])
-        host = torch.from_numpy(np.concatenate([fo, to, np.asarray([t for tg in targets_list for t in tg] + [0], dtype=np.int32)])).to(dev)
-        # one int32 result buffer (path | spans | status) and one f32 (conf | score): two copies back
-        ri = torch.zeros(F_ + 2 * L_ + n, device=dev, dtype=torch.int32)
-        rf = torch.zeros(L_ + n, device=dev, dtype=torch.float32)
-        hp, ip, fp = host.data_ptr(), ri.data_ptr(), rf.data_ptr()  # (pointer arithmetic: an empty slice has no data_ptr)
-        E.check(self.lib.tt_ctc_align(self.h, n, lg.data_ptr(), hp, hp + 4 * (2 * n + 2), hp + 4 * (n + 1), ip, ip + 4 * F_, fp, fp + 4 * L_,
-                                      ip + 4 * (F_ + 2 * L_), E.stream_ptr()))
-        ri, rf = ri.cpu(), rf.cpu()
+        t = _Tables(dev, fo=fo, to=to, targets=[t for tg in targets_list for t in tg] + [0])
+        r = _Results(dev, int32=dict(path=fo[-1], spans=2 * to[-1], status=n), float32=dict(conf=to[-1], score=n))  # two copies back
+        E.check(self.lib.tt_ctc_align(self.h, n, lg.data_ptr(), t.p("fo"), t.p("targets"), t.p("to"), r.p("path"), r.p("spans"), r.p("conf"),
+                                      r.p("score"), r.p("status"), E.stream_ptr()))
+        r.cpu()
+        path, spans, conf, score = r["path"], r["spans"].reshape(-1, 2), r["conf"], r["score"].tolist()
         out = []
-        for i in range(n):
-            st = int(ri[F_ + 2 * L_ + i])
-            r = {"status": st}
+        for i, st in enumerate(r["status"].tolist()):
+            d = {"status": st}
             if st == E.CTC_OK:
-                r.update(path=ri[fo[i]:fo[i + 1]].clone(), spans=ri[F_ + 2 * to[i]:F_ + 2 * to[i + 1]].reshape(-1, 2).clone(),
-                         conf=rf[to[i]:to[i + 1]].clone(), score=float(rf[L_ + i]))
-            out.append(r)
+                d.update(path=self._host(path[fo[i]:fo[i + 1]]), spans=self._host(spans[to[i]:to[i + 1]]), conf=self._host(conf[to[i]:to[i + 1]]), score=score[i])
+            out.append(d)
         return out
 
 
-class TimeStretchStage(_Handle):
+class TimeStretchStage(_ClipStage):
     """WSOLA time-stretch of 24 kHz clips (csrc/tsm.hip, include/tortoise_mi355x_tsm.h): ragged batches, each clip with its own rate, one
     tt_tsm_stretch call per max_clips clips, every clip's result bit-identical to stretching it alone."""
 
-    api = "tt_tsm"
-
-    def __init__(self, max_samples, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
-        self._create(self.max_samples, self.max_clips)
+    api, noun, what = "tt_tsm", "time-stretch stage's", "time-stretch"
 
     def stretch_many(self, clips, rqs):
         """clips f32 [n_i] (device or host) and the 16.16 rate of each (stretch.rate_q) -> one (y f32 [n_out_i] on the stage's device, chosen
@@ -553,48 +638,41 @@ class TimeStretchStage(_Handle):
         if len(clips) != len(rqs):
             raise ValueError(f"{len(clips)} clips with {len(rqs)} rates")
         for i, (x, rq) in enumerate(zip(clips, rqs)):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the time-stretch stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
             if not E.TSM_RATE_MIN <= int(rq) <= E.TSM_RATE_MAX:
                 raise ValueError(f"clip {i}: rate {int(rq)} / 65536 is outside the supported range [0.5, 2.0]")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], [int(r) for r in rqs[g:g + self.max_clips]])
-        return out
+        return self._run(clips, [int(r) for r in rqs])
 
     def _group(self, clips, rqs):
-        n, dev = len(clips), self.device
-        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
-        oo = np.concatenate(([0], np.cumsum([self.lib.tt_tsm_out_samples(x.shape[0], r) for x, r in zip(clips, rqs)]))).astype(np.int32)
-        fo = np.concatenate(([0], np.cumsum([self.lib.tt_tsm_frames(x.shape[0], r) for x, r in zip(clips, rqs)]))).astype(np.int32)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, oo, fo, np.asarray(rqs, dtype=np.int32)])).to(dev)
-        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
-        ri = torch.zeros(int(fo[-1]) + n, device=dev, dtype=torch.int32)  # (offsets | status): one copy back
-        hp, ip = host.data_ptr(), ri.data_ptr()
-        E.check(self.lib.tt_tsm_stretch(self.h, n, audio.data_ptr(), hp, hp + 4 * 3 * (n + 1), y.data_ptr(), hp + 4 * (n + 1), ip,
-                                        hp + 4 * 2 * (n + 1), ip + 4 * int(fo[-1]), E.stream_ptr()))
-        ri = ri.cpu()
-        status = ri[int(fo[-1]):].tolist()
-        if any(st != E.TSM_OK for st in status):
-            raise RuntimeError(f"time-stretch: the device stage refused clips it was handed (status {status})")
-        return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
+        lens = [x.shape[0] for x in clips]
+        oo = self._offsets(self.lib.tt_tsm_out_samples(m, r) for m, r in zip(lens, rqs))
+        fo = self._offsets(self.lib.tt_tsm_frames(m, r) for m, r in zip(lens, rqs))
+        return self._stretch(self.lib.tt_tsm_stretch, clips, oo, fo, _Tables(self.device, io=self._offsets(lens), oo=oo, fo=fo, rq=rqs), ("rq",))
+
+    def _stretch(self, entry, clips, oo, fo, t, own):
+        """The call of the two time-stretch stages, which differ in the tables `own` between in_off and out: -> (y, offsets) per clip."""
+        n = len(clips)
+        audio = self._audio(clips)
+        y = torch.zeros(oo[-1] + 1, device=self.device, dtype=torch.float32)
+        r = _Results(self.device, int32=dict(offsets=fo[-1], status=n))  # one copy back
+        E.check(entry(self.h, n, audio.data_ptr(), t.p("io"), *[t.p(k) for k in own], y.data_ptr(), t.p("oo"), r.p("offsets"), t.p("fo"),
+                      r.p("status"), E.stream_ptr()))
+        r.cpu()
+        self._accepted(r["status"], (E.TSM_OK,))  # (E.TSW_OK is the same 0)
+        offsets = r["offsets"]
+        return [(y[oo[i]:oo[i + 1]], self._host(offsets[fo[i]:fo[i + 1]])) for i in range(n)]
 
 
-class WarpStretchStage(_Handle):
+class WarpStretchStage(TimeStretchStage):
     """WSOLA time-stretch along a rate map (csrc/tsm_warp.hip, include/tortoise_mi355x_tsw.h): ragged batches, each clip with its own table
     of segments (stretch.RateMap.table), one tt_tsw_stretch call per max_clips clips, every clip's result bit-identical to stretching it
     alone; the table (0, 0, rq) gives TimeStretchStage's bits."""
 
-    api = "tt_tsw"
+    api, what = "tt_tsw", "time-stretch along a rate map"
 
     def __init__(self, max_samples, max_clips=16, max_segments=E.TSW_MAX_SEGMENTS, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips, self.max_segments = int(max_samples), int(max_clips), int(max_segments)
-        self._create(self.max_samples, self.max_clips, self.max_segments)
+        self.max_segments = int(max_segments)
+        super().__init__(max_samples, max_clips, device, (self.max_segments,))
 
     def stretch_many(self, clips, tables):
         """clips f32 [n_i] (device or host) and the table [(m, a, rq), ...] of each -> one (y f32 [n_out_i] on the stage's device, chosen
@@ -602,52 +680,28 @@ class WarpStretchStage(_Handle):
         if len(clips) != len(tables):
             raise ValueError(f"{len(clips)} clips with {len(tables)} rate maps")
         for i, (x, tb) in enumerate(zip(clips, tables)):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the time-stretch stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
             if not 1 <= len(tb) <= self.max_segments:
                 raise ValueError(f"clip {i}: a rate map of {len(tb)} segments (1 .. {self.max_segments})")
             if not tsm.table_out_samples(x.shape[0], tb):
                 raise ValueError(f"clip {i}: the rate map's table breaks a rule of include/tortoise_mi355x_tsw.h for a clip of {x.shape[0]} samples")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], tables[g:g + self.max_clips])
-        return out
+        return self._run(clips, tables)
 
     def _group(self, clips, tables):
-        n, dev = len(clips), self.device
-        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
-        so = np.concatenate(([0], np.cumsum([len(tb) for tb in tables]))).astype(np.int32)
-        oo = np.concatenate(([0], np.cumsum([tsm.table_out_samples(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
-        fo = np.concatenate(([0], np.cumsum([tsm.table_frames(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
-        seg = np.asarray([v for tb in tables for row in tb for v in row], dtype=np.int32)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, so, oo, fo, seg])).to(dev)
-        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
-        ri = torch.zeros(int(fo[-1]) + n, device=dev, dtype=torch.int32)  # (offsets | status): one copy back
-        hp, ip, w = host.data_ptr(), ri.data_ptr(), 4 * (n + 1)
-        E.check(self.lib.tt_tsw_stretch(self.h, n, audio.data_ptr(), hp, hp + 4 * w, hp + w, y.data_ptr(), hp + 2 * w, ip, hp + 3 * w,
-                                        ip + 4 * int(fo[-1]), E.stream_ptr()))
-        ri = ri.cpu()
-        status = ri[int(fo[-1]):].tolist()
-        if any(st != E.TSW_OK for st in status):
-            raise RuntimeError(f"time-stretch along a rate map: the device stage refused clips it was handed (status {status})")
-        return [(y[oo[i]:oo[i + 1]], ri[fo[i]:fo[i + 1]].clone()) for i in range(n)]
+        lens = [x.shape[0] for x in clips]
+        oo = self._offsets(tsm.table_out_samples(m, tb) for m, tb in zip(lens, tables))
+        fo = self._offsets(tsm.table_frames(m, tb) for m, tb in zip(lens, tables))
+        t = _Tables(self.device, io=self._offsets(lens), so=self._offsets(len(tb) for tb in tables), oo=oo, fo=fo,
+                    seg=[v for tb in tables for row in tb for v in row])
+        return self._stretch(self.lib.tt_tsw_stretch, clips, oo, fo, t, ("seg", "so"))
 
 
-class ResampleStage(_Handle):
+class ResampleStage(_ClipStage):
     """Band-limited resampling at an arbitrary ratio (csrc/resample.hip, include/tortoise_mi355x_rs.h): ragged batches, each clip with its own
     (P, Q) input samples per output sample, one tt_rs_resample call per max_clips clips, every clip's result bit-identical to resampling it
     alone."""
 
-    api = "tt_rs"
-
-    def __init__(self, max_samples, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
-        self._create(self.max_samples, self.max_clips)
+    api, noun, what = "tt_rs", "resampling stage's", "resample"
 
     def resample_many(self, clips, ratios):
         """clips f32 [n_i] (device or host) and the (P, Q) of each (resample.ratio / pitch_ratio) -> one (y f32 [n_out_i] on the stage's
@@ -655,50 +709,42 @@ class ResampleStage(_Handle):
         if len(clips) != len(ratios):
             raise ValueError(f"{len(clips)} clips with {len(ratios)} ratios")
         for i, (x, (P, Q)) in enumerate(zip(clips, ratios)):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the resampling stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
             if not self.lib.tt_rs_out_samples(x.shape[0], int(P), int(Q)):
                 raise ValueError(f"clip {i}: ratio {int(P)}/{int(Q)} is outside what the resampler takes (terms up to {E.RS_MAX_TERM}, "
                                  f"1/{E.RS_MAX_RATIO} .. {E.RS_MAX_RATIO}, reduced unless Q = {E.RS_PITCH_ONE})")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], [(int(P), int(Q)) for P, Q in ratios[g:g + self.max_clips]])
-        return out
+        return self._run(clips, [(int(P), int(Q)) for P, Q in ratios])
 
     def _group(self, clips, ratios):
-        n, dev = len(clips), self.device
-        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
-        oo = np.concatenate(([0], np.cumsum([self.lib.tt_rs_out_samples(x.shape[0], P, Q) for x, (P, Q) in zip(clips, ratios)]))).astype(np.int32)
-        pq = np.asarray([[P for P, _ in ratios], [Q for _, Q in ratios]], dtype=np.int32).reshape(-1)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, oo, pq])).to(dev)
-        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
-        res = torch.zeros(2 * n, device=dev, dtype=torch.int32)  # (peak as f32 bits | status): one copy back
-        hp, rp = host.data_ptr(), res.data_ptr()
-        E.check(self.lib.tt_rs_resample(self.h, n, audio.data_ptr(), hp, hp + 4 * 2 * (n + 1), hp + 4 * (2 * (n + 1) + n), y.data_ptr(),
-                                        hp + 4 * (n + 1), rp, rp + 4 * n, E.stream_ptr()))
-        res = res.cpu()
-        status = res[n:].tolist()
-        if any(st != E.RS_OK for st in status):
-            raise RuntimeError(f"resample: the device stage refused clips it was handed (status {status})")
-        peaks = res[:n].view(torch.float32).tolist()
+        lens = [x.shape[0] for x in clips]
+        oo = self._offsets(self.lib.tt_rs_out_samples(m, P, Q) for m, (P, Q) in zip(lens, ratios))
+        t = _Tables(self.device, io=self._offsets(lens), oo=oo, P=[P for P, _ in ratios], Q=[Q for _, Q in ratios])
+        return self._resample(self.lib.tt_rs_resample, clips, oo, t, ("P", "Q"))
+
+    def _resample(self, entry, clips, oo, t, own):
+        """The call of the two resampling stages, which differ in the tables `own` between in_off and out: -> (y, peak) per clip."""
+        n = len(clips)
+        audio = self._audio(clips)
+        y = torch.zeros(oo[-1] + 1, device=self.device, dtype=torch.float32)
+        r = _Results(self.device, int32=dict(peak=n, status=n))  # (the peaks as f32 bits: one copy back)
+        E.check(entry(self.h, n, audio.data_ptr(), t.p("io"), *[t.p(k) for k in own], y.data_ptr(), t.p("oo"), r.p("peak"), r.p("status"),
+                      E.stream_ptr()))
+        r.cpu()
+        self._accepted(r["status"], (E.RS_OK,))  # (E.RSW_OK is the same 0)
+        peaks = r["peak"].view(np.float32).tolist()
         return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
 
 
-class WarpResampleStage(_Handle):
+class WarpResampleStage(ResampleStage):
     """Band-limited resampling along a pitch map (csrc/resample_warp.hip, include/tortoise_mi355x_rsw.h): ragged batches, each clip with its
     own table of segments (resample.map_plan), one tt_rsw_resample call per max_clips clips, every clip's result bit-identical to resampling
     it alone; the table (0, 0, 0, P) gives ResampleStage's bits at (P, 65536)."""
 
-    api = "tt_rsw"
+    api, what = "tt_rsw", "resample along a pitch map"
 
     def __init__(self, max_samples, max_clips=16, max_segments=E.RSW_MAX_SEGMENTS, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips, self.max_segments = int(max_samples), int(max_clips), int(max_segments)
-        self._create(self.max_samples, self.max_clips, self.max_segments)
+        self.max_segments = int(max_segments)
+        super().__init__(max_samples, max_clips, device, (self.max_segments,))
 
     def resample_many(self, clips, tables):
         """clips f32 [n_i] (device or host) and the table [(m, thi, tlo, P), ...] of each -> one (y f32 [n_out_i] on the stage's device,
@@ -706,38 +752,19 @@ class WarpResampleStage(_Handle):
         if len(clips) != len(tables):
             raise ValueError(f"{len(clips)} clips with {len(tables)} pitch maps")
         for i, (x, tb) in enumerate(zip(clips, tables)):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the resampling stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
             if not 1 <= len(tb) <= self.max_segments:
                 raise ValueError(f"clip {i}: a pitch map of {len(tb)} segments (1 .. {self.max_segments})")
             if not rs.map_out_samples(x.shape[0], tb):
                 raise ValueError(f"clip {i}: the pitch map's table breaks a rule of include/tortoise_mi355x_rsw.h for a clip of {x.shape[0]} samples")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], tables[g:g + self.max_clips])
-        return out
+        return self._run(clips, tables)
 
     def _group(self, clips, tables):
-        n, dev = len(clips), self.device
-        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
-        so = np.concatenate(([0], np.cumsum([len(tb) for tb in tables]))).astype(np.int32)
-        oo = np.concatenate(([0], np.cumsum([rs.map_out_samples(x.shape[0], tb) for x, tb in zip(clips, tables)]))).astype(np.int32)
-        seg = np.asarray([v for tb in tables for row in tb for v in row], dtype=np.int32)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, so, oo, seg])).to(dev)
-        y = torch.zeros(int(oo[-1]) + 1, device=dev, dtype=torch.float32)
-        res = torch.zeros(2 * n, device=dev, dtype=torch.int32)  # (peak as f32 bits | status): one copy back
-        hp, rp, w = host.data_ptr(), res.data_ptr(), 4 * (n + 1)
-        E.check(self.lib.tt_rsw_resample(self.h, n, audio.data_ptr(), hp, hp + 3 * w, hp + w, y.data_ptr(), hp + 2 * w, rp, rp + 4 * n,
-                                         E.stream_ptr()))
-        res = res.cpu()
-        status = res[n:].tolist()
-        if any(st != E.RSW_OK for st in status):
-            raise RuntimeError(f"resample along a pitch map: the device stage refused clips it was handed (status {status})")
-        peaks = res[:n].view(torch.float32).tolist()
-        return [(y[oo[i]:oo[i + 1]], float(peaks[i])) for i in range(n)]
+        lens = [x.shape[0] for x in clips]
+        oo = self._offsets(rs.map_out_samples(m, tb) for m, tb in zip(lens, tables))
+        t = _Tables(self.device, io=self._offsets(lens), so=self._offsets(len(tb) for tb in tables), oo=oo,
+                    seg=[v for tb in tables for row in tb for v in row])
+        return self._resample(self.lib.tt_rsw_resample, clips, oo, t, ("seg", "so"))
 
 
 class StreamResampleStage(_Handle):
@@ -879,85 +906,63 @@ class StreamStretchStage(_Handle):
         return (out, offs) if return_offsets else out
 
 
-class SilenceStage(_Handle):
+class SilenceStage(_ClipStage):
     """Speech regions, edge trimming and pause capping (csrc/silence.hip, include/tortoise_mi355x_sil.h): ragged batches, each clip with its
     own parameters (silence.Params), one tt_sil_find / tt_sil_trim call per max_clips clips, every clip's result bit-identical to running it
     alone."""
 
-    api = "tt_sil"
-
-    def __init__(self, max_samples, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
-        self._create(self.max_samples, self.max_clips)
+    api, noun, what = "tt_sil", "silence stage's", "silence"
 
     def _check(self, clips, params):
         if len(clips) != len(params):
             raise ValueError(f"{len(clips)} clips with {len(params)} parameter sets")
         for i, x in enumerate(clips):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the silence stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
 
     def find_many(self, clips, params, energies=False):
         """clips f32 [n_i] (device or host) and a silence.Params each -> one dict per clip: status (E.SIL_OK / SIL_SILENT), regions
         [(a, b)] in samples, peak (E, the largest frame energy) and, for energies=True, energies (f64 [F] on the host)."""
         self._check(clips, params)
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], False, energies)
-        return out
+        return self._run(clips, params, trim=False, energies=energies)
 
     def trim_many(self, clips, params):
         """clips f32 [n_i] and a silence.Params each -> one (y f32 [n_out_i] on the stage's device, dict) per clip; the dict holds status
         (E.SIL_OK / SIL_UNCHANGED / SIL_SILENT), regions [(a, b)] of the input, segments [(o, i, l)] (silence.map_sample) and peak."""
         self._check(clips, params)
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], True, False)
-        return out
+        return self._run(clips, params, trim=True, energies=False)
 
     def _group(self, clips, params, trim, energies):
         n, dev = len(clips), self.device
         lens = [x.shape[0] for x in clips]
-        io = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
-        ro = np.concatenate(([0], np.cumsum([self.lib.tt_sil_max_regions(m) for m in lens]))).astype(np.int32)  # (regions and segments alike)
-        fo = np.concatenate(([0], np.cumsum([self.lib.tt_sil_frames(m) for m in lens]))).astype(np.int32)
-        par = np.asarray([[p.min_sil, p.pad, p.lead, p.trail, p.max_pause][:5 if trim else 2] for p in params], dtype=np.int32).reshape(-1)
+        io, fo = self._offsets(lens), self._offsets(self.lib.tt_sil_frames(m) for m in lens)
+        ro = self._offsets(self.lib.tt_sil_max_regions(m) for m in lens)  # (regions and segments alike)
         thr = torch.tensor([[p.rel, p.floor_e] for p in params], dtype=torch.float64).to(dev)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, ro, fo, par])).to(dev)
-        R = int(ro[-1])
-        res = torch.zeros(4 * n + 5 * R + 1, device=dev, dtype=torch.int32)  # n_out | n_regions | n_segments | status | regions | segments
-        peak = torch.zeros(n, device=dev, dtype=torch.float64)
-        hp, rp = host.data_ptr(), res.data_ptr()
-        p_io, p_ro, p_fo, p_par = hp, hp + 4 * (n + 1), hp + 8 * (n + 1), hp + 12 * (n + 1)
-        p_nout, p_nreg, p_nseg, p_st, p_reg, p_seg = rp, rp + 4 * n, rp + 8 * n, rp + 12 * n, rp + 16 * n, rp + 16 * n + 8 * R
+        audio = self._audio(clips)
+        t = _Tables(dev, io=io, ro=ro, fo=fo, par=[v for p in params for v in (p.min_sil, p.pad, p.lead, p.trail, p.max_pause)[:5 if trim else 2]])
+        r = _Results(dev, int32=dict(n_out=n, n_regions=n, n_segments=n, status=n, regions=2 * ro[-1], segments=3 * ro[-1]), float64=dict(peak=n))
         en = y = None
         if trim:
-            y = torch.zeros(int(io[-1]) + 1, device=dev, dtype=torch.float32)
-            E.check(self.lib.tt_sil_trim(self.h, n, audio.data_ptr(), p_io, thr.data_ptr(), p_par, p_ro, p_ro, y.data_ptr(), p_nout, p_nreg,
-                                         p_reg, p_nseg, p_seg, peak.data_ptr(), p_st, E.stream_ptr()))
+            y = torch.zeros(io[-1] + 1, device=dev, dtype=torch.float32)
+            E.check(self.lib.tt_sil_trim(self.h, n, audio.data_ptr(), t.p("io"), thr.data_ptr(), t.p("par"), t.p("ro"), t.p("ro"), y.data_ptr(),
+                                         r.p("n_out"), r.p("n_regions"), r.p("regions"), r.p("n_segments"), r.p("segments"), r.p("peak"),
+                                         r.p("status"), E.stream_ptr()))
         else:
-            en = torch.zeros(int(fo[-1]) + 1, device=dev, dtype=torch.float64) if energies else None
-            E.check(self.lib.tt_sil_find(self.h, n, audio.data_ptr(), p_io, thr.data_ptr(), p_par, p_ro, p_fo if energies else None, p_nreg,
-                                         p_reg, peak.data_ptr(), en.data_ptr() if energies else None, p_st, E.stream_ptr()))
-        res = res.cpu().numpy()
-        status = res[3 * n:4 * n].tolist()
-        if any(st in (E.SIL_EMPTY, E.SIL_REFUSED) for st in status):
-            raise RuntimeError(f"silence: the device stage refused clips it was handed (status {status})")
-        peaks = peak.cpu().tolist()
-        regs = res[4 * n:4 * n + 2 * R].reshape(-1, 2)
-        segs = res[4 * n + 2 * R:4 * n + 5 * R].reshape(-1, 3)
+            en = torch.zeros(fo[-1] + 1, device=dev, dtype=torch.float64) if energies else None
+            E.check(self.lib.tt_sil_find(self.h, n, audio.data_ptr(), t.p("io"), thr.data_ptr(), t.p("par"), t.p("ro"), t.p("fo") if energies else None,
+                                         r.p("n_regions"), r.p("regions"), r.p("peak"), en.data_ptr() if energies else None, r.p("status"),
+                                         E.stream_ptr()))
+        r.cpu()
+        status = self._accepted(r["status"], (E.SIL_OK, E.SIL_UNCHANGED, E.SIL_SILENT))
+        peaks = r["peak"].tolist()
+        n_out, n_reg, n_seg = (r[k].tolist() for k in ("n_out", "n_regions", "n_segments"))
+        regs, segs = r["regions"].reshape(-1, 2), r["segments"].reshape(-1, 3)
         en = en.cpu() if en is not None else None
         out = []
         for i in range(n):
-            d = dict(status=status[i], peak=peaks[i], regions=[(int(a), int(b)) for a, b in regs[ro[i]:ro[i] + res[n + i]]])
+            d = dict(status=status[i], peak=peaks[i], regions=[(int(a), int(b)) for a, b in regs[ro[i]:ro[i] + n_reg[i]]])
             if trim:
-                d["segments"] = [(int(o), int(s), int(m)) for o, s, m in segs[ro[i]:ro[i] + res[2 * n + i]]]
-                out.append((y[io[i]:io[i] + int(res[i])], d))
+                d["segments"] = [(int(o), int(s), int(m)) for o, s, m in segs[ro[i]:ro[i] + n_seg[i]]]
+                out.append((y[io[i]:io[i] + n_out[i]], d))
             else:
                 if en is not None:
                     d["energies"] = en[fo[i]:fo[i + 1]].clone()
@@ -965,17 +970,11 @@ class SilenceStage(_Handle):
         return out
 
 
-class F0Stage(_Handle):
+class F0Stage(_ClipStage):
     """The YIN fundamental-frequency tracker (csrc/f0.hip, include/tortoise_mi355x_f0.h): ragged batches, each clip with its own parameters
     (pitch.Params), one tt_f0_track call per max_clips clips, every clip's result bit-identical to running it alone."""
 
-    api = "tt_f0"
-
-    def __init__(self, max_samples, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
-        self._create(self.max_samples, self.max_clips)
+    api, noun, what = "tt_f0", "F0 stage's", "f0"
 
     def track_many(self, clips, params, dprime=False):
         """clips f32 [n_i] (device or host) and a pitch.Params each -> one dict per clip: lag (i32 [F]), f0 (f32 [F], 0 where unvoiced), aper
@@ -983,68 +982,55 @@ class F0Stage(_Handle):
         if len(clips) != len(params):
             raise ValueError(f"{len(clips)} clips with {len(params)} parameter sets")
         for i, x in enumerate(clips):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the F0 stage's capacity ({self.max_samples})")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], params[g:g + self.max_clips], dprime)
-        return out
+            self._check_clip(i, x)
+        return self._run(clips, params, dprime=dprime)
 
     def _group(self, clips, params, dprime):
         n, dev = len(clips), self.device
         lens = [x.shape[0] for x in clips]
-        io = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
-        fo = np.concatenate(([0], np.cumsum([self.lib.tt_f0_frames(m) for m in lens]))).astype(np.int32)
-        par = np.asarray([[p.lag_lo, p.lag_hi] for p in params], dtype=np.int32).reshape(-1)
+        fo = self._offsets(self.lib.tt_f0_frames(m) for m in lens)
+        Fs = fo[-1]
         thr = torch.tensor([[p.thr, p.floor_e] for p in params], dtype=torch.float64).to(dev)
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, fo, par])).to(dev)
-        Fs = int(fo[-1])
-        res = torch.zeros(2 * n + Fs + 1, device=dev, dtype=torch.int32)  # n_voiced | status | lag
-        vals = torch.zeros(2 * Fs + 1, device=dev, dtype=torch.float32)  # f0 | aper
-        hp, rp, vp_ = host.data_ptr(), res.data_ptr(), vals.data_ptr()
-        args = (self.h, n, audio.data_ptr(), hp, hp + 8 * (n + 1), thr.data_ptr(), hp + 4 * (n + 1), rp + 8 * n, vp_, vp_ + 4 * Fs, rp, rp + 4 * n)
+        audio = self._audio(clips)
+        t = _Tables(dev, io=self._offsets(lens), fo=fo, par=[v for p in params for v in (p.lag_lo, p.lag_hi)])
+        r = _Results(dev, int32=dict(n_voiced=n, status=n, lag=Fs), float32=dict(f0=Fs, aper=Fs))
+        args = (self.h, n, audio.data_ptr(), t.p("io"), t.p("par"), thr.data_ptr(), t.p("fo"), r.p("lag"), r.p("f0"), r.p("aper"), r.p("n_voiced"),
+                r.p("status"))
         dpr = None
         if dprime:
             dpr = torch.zeros(Fs * (E.F0_LAG_MAX + 1) + 1, device=dev, dtype=torch.float64)
             E.check(self.lib.tt_op_f0_track(*args, dpr.data_ptr(), E.stream_ptr()))
         else:
             E.check(self.lib.tt_f0_track(*args, E.stream_ptr()))
-        res, vals = res.cpu().numpy(), vals.cpu().numpy()
-        status = res[n:2 * n].tolist()
-        if any(st != E.F0_OK for st in status):
-            raise RuntimeError(f"f0: the device stage refused clips it was handed (status {status})")
+        r.cpu()
+        self._accepted(r["status"], (E.F0_OK,))
+        lag, f0, aper, voiced = r["lag"], r["f0"], r["aper"], r["n_voiced"].tolist()
         dpr = dpr.cpu().numpy()[:-1].reshape(Fs, E.F0_LAG_MAX + 1) if dprime else None
         out = []
         for i in range(n):
-            a, b = int(fo[i]), int(fo[i + 1])
-            d = dict(lag=res[2 * n + a:2 * n + b].copy(), f0=vals[a:b].copy(), aper=vals[Fs + a:Fs + b].copy(), n_voiced=int(res[i]))
+            a, b = fo[i], fo[i + 1]
+            d = dict(lag=lag[a:b].copy(), f0=f0[a:b].copy(), aper=aper[a:b].copy(), n_voiced=voiced[i])
             if dprime:
                 d["dprime"] = dpr[a:b].copy()
             out.append(d)
         return out
 
 
-class FormantStage(_Handle):
+class FormantStage(_ClipStage):
     """Formant-preserving pitch: the cepstral envelope correction of finished clips at 24 kHz (csrc/formant.hip,
     include/tortoise_mi355x_fmt.h): ragged batches, each clip with its own warp alpha, one tt_fmt_run call per max_clips clips, every clip's
     result bit-identical to correcting it alone.  The handle's `warps` table has 16 slots; the stage keeps one D per distinct warp in it and
     replaces the least recently used one when a new warp arrives (a copy on the current stream, ordered before the run that reads it)."""
 
-    api = "tt_fmt"
+    api, noun, fmt = "tt_fmt", "formant stage's", fmt
+    least, least_text = fmt.MIN_SAMPLES, f"{fmt.MIN_SAMPLES} samples (the frames are centred with reflect padding)"
 
     def __init__(self, max_samples, q=None, max_gain_db=None, max_clips=E.FMT_MAX_CLIPS, device="cuda"):
-        from . import formant as fmt
-        self.fmt = fmt
         self.q = fmt.lifter_q() if q is None else int(q)
         self.max_gain_db = fmt.max_gain_db() if max_gain_db is None else fmt.max_gain_db(max_gain_db)
         if not fmt.Q_RANGE[0] <= self.q <= fmt.Q_RANGE[1]:
             raise ValueError(f"{self.q} cepstral coefficients; the stage takes {fmt.Q_RANGE[0]} .. {fmt.Q_RANGE[1]}")
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_samples, self.max_clips = int(max_samples), int(max_clips)
+        super().__init__(max_samples, max_clips, device, extra=None)
         t = fmt.tables(self.q, [1.0])
         self.t = {k: t[k].to(self.device).contiguous() for k in ("basis", "inverse", "cepstrum")}
         self.t["warps"] = torch.zeros(E.FMT_MAX_WARPS, E.FMT_Q_PAD, fmt.BINS_PAD, device=self.device, dtype=torch.float32)
@@ -1078,17 +1064,10 @@ class FormantStage(_Handle):
             raise ValueError(f"{len(clips)} clips with {len(alphas)} warps")
         alphas = [float(a) for a in alphas]
         for i, (x, a) in enumerate(zip(clips, alphas)):
-            if x.dim() != 1 or x.shape[0] < self.fmt.MIN_SAMPLES:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least {self.fmt.MIN_SAMPLES} samples "
-                                 f"(the frames are centred with reflect padding)")
-            if x.shape[0] > self.max_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the formant stage's capacity ({self.max_samples})")
+            self._check_clip(i, x)
             if not self.fmt.WARP_RANGE[0] <= a <= self.fmt.WARP_RANGE[1]:
                 raise ValueError(f"clip {i}: warp {a!r} is outside {self.fmt.WARP_RANGE}")
-        out = []
-        for g in range(0, len(clips), self.max_clips):
-            out += self._group(clips[g:g + self.max_clips], alphas[g:g + self.max_clips])
-        return out
+        return self._run(clips, alphas)
 
     def _group(self, clips, alphas):
         k, dev = len(clips), self.device
@@ -1108,18 +1087,15 @@ class FormantStage(_Handle):
         return [y[o:o + n] for o, n in zip(offs, lens)]
 
 
-class LoudnessStage(_Handle):
+class LoudnessStage(_ClipStage):
     """Integrated loudness, true peak and the gain to a target under a ceiling (csrc/loudness.hip, include/tortoise_mi355x_loud.h): ragged
     batches, each clip with its own target and ceiling, one tt_loud_measure / tt_loud_normalize call per group of at most max_clips clips and
     max_total_samples samples, every clip's result bit-identical to running it alone."""
 
-    api = "tt_loud"
+    api, noun, what, capacity = "tt_loud", "loudness stage's", "loudness", "max_total_samples"
 
     def __init__(self, max_total_samples, max_clips=16, device="cuda"):
-        self.lib = E.init()
-        self.device = torch.device(device)
-        self.max_total_samples, self.max_clips = int(max_total_samples), int(max_clips)
-        self._create(self.max_total_samples, self.max_clips)
+        super().__init__(max_total_samples, max_clips, device)
 
     def measure_many(self, clips):
         """clips f32 [n_i] (device or host) -> one dict per clip: status (E.LOUD_OK / SHORT / SILENT), lufs, true_peak (linear), blocks_abs,
@@ -1140,51 +1116,49 @@ class LoudnessStage(_Handle):
 
     def _many(self, clips, targets, ceilings, mode):
         for i, x in enumerate(clips):
-            if x.dim() != 1 or x.shape[0] < 1:
-                raise ValueError(f"clip {i}: audio of shape {tuple(x.shape)}, expected [samples] with at least one sample")
-            if x.shape[0] > self.max_total_samples:
-                raise ValueError(f"clip {i}: {x.shape[0]} samples exceed the loudness stage's capacity ({self.max_total_samples})")
-        out, g0 = [], 0
-        while g0 < len(clips):  # the longest run of clips the handle takes in one call
+            self._check_clip(i, x)
+        return self._run(clips, targets, ceilings, mode=mode)
+
+    def _groups(self, clips):
+        """The longest runs of clips the handle takes in one call: at most max_clips clips and max_total_samples samples."""
+        runs, g0 = [], 0
+        while g0 < len(clips):
             g1, total = g0, 0
             while g1 < len(clips) and g1 - g0 < self.max_clips and total + clips[g1].shape[0] <= self.max_total_samples:
                 total += clips[g1].shape[0]
                 g1 += 1
-            out += self._group(clips[g0:g1], targets and targets[g0:g1], ceilings and ceilings[g0:g1], mode)
+            runs.append((g0, g1))
             g0 = g1
-        return out
+        return runs
 
     def _group(self, clips, targets, ceilings, mode):
         n, dev = len(clips), self.device
-        io = np.concatenate(([0], np.cumsum([x.shape[0] for x in clips]))).astype(np.int32)
-        ho = np.concatenate(([0], np.cumsum([self.lib.tt_loud_hops(x.shape[0]) for x in clips]))).astype(np.int32)
-        N, Hn = int(io[-1]), int(ho[-1])
-        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for x in clips] + [torch.zeros(1, device=dev)])
-        host = torch.from_numpy(np.concatenate([io, ho])).to(dev)
-        rd = torch.zeros(n + Hn, device=dev, dtype=torch.float64)   # (lufs | hop_energy)
-        rf = torch.zeros(3 * n, device=dev, dtype=torch.float32)    # (true_peak | gain | out_true_peak)
-        ri = torch.zeros(3 * n, device=dev, dtype=torch.int32)      # (blocks_abs | blocks_rel | status)
-        hp, dp, fp, ip = host.data_ptr(), rd.data_ptr(), rf.data_ptr(), ri.data_ptr()
+        io, ho = self._offsets(x.shape[0] for x in clips), self._offsets(self.lib.tt_loud_hops(x.shape[0]) for x in clips)
+        audio = self._audio(clips)
+        t = _Tables(dev, io=io, ho=ho)
+        r = _Results(dev, float64=dict(lufs=n, hop_energy=ho[-1]), float32=dict(true_peak=n, gain=n, out_true_peak=n),
+                     int32=dict(blocks_abs=n, blocks_rel=n, status=n))
+        head = (self.h, n, audio.data_ptr(), t.p("io"), t.p("ho"))
+        measured = (r.p("lufs"), r.p("true_peak"), r.p("blocks_abs"), r.p("blocks_rel"), r.p("hop_energy"))
         y = None
         if targets is None:
-            E.check(self.lib.tt_loud_measure(self.h, n, audio.data_ptr(), hp, hp + 4 * (n + 1), dp, fp, ip, ip + 4 * n, dp + 8 * n, ip + 8 * n,
-                                             E.stream_ptr()))
+            E.check(self.lib.tt_loud_measure(*head, *measured, r.p("status"), E.stream_ptr()))
         else:
-            tc = torch.tensor(list(targets) + list(ceilings), dtype=torch.float32).to(dev)
-            y = torch.zeros(N + 1, device=dev, dtype=torch.float32)
-            E.check(self.lib.tt_loud_normalize(self.h, n, audio.data_ptr(), hp, hp + 4 * (n + 1), tc.data_ptr(), tc.data_ptr() + 4 * n, int(mode),
-                                               y.data_ptr(), dp, fp, ip, ip + 4 * n, dp + 8 * n, fp + 4 * n, fp + 8 * n, ip + 8 * n, E.stream_ptr()))
-        rd, rf, ri = rd.cpu(), rf.cpu(), ri.cpu()
-        status = ri[2 * n:].tolist()
-        if any(st not in (E.LOUD_OK, E.LOUD_SHORT, E.LOUD_SILENT) for st in status):
-            raise RuntimeError(f"loudness: the device stage refused clips it was handed (status {status})")
-        out = []
+            tc = _Tables(dev, torch.float32, target=targets, ceiling=ceilings)
+            y = torch.zeros(io[-1] + 1, device=dev, dtype=torch.float32)
+            E.check(self.lib.tt_loud_normalize(*head, tc.p("target"), tc.p("ceiling"), int(mode), y.data_ptr(), *measured, r.p("gain"),
+                                               r.p("out_true_peak"), r.p("status"), E.stream_ptr()))
+        r.cpu()
+        status = self._accepted(r["status"], (E.LOUD_OK, E.LOUD_SHORT, E.LOUD_SILENT))
+        lufs, true_peak, blocks_abs, blocks_rel, gain, out_true_peak = (
+            r[k].tolist() for k in ("lufs", "true_peak", "blocks_abs", "blocks_rel", "gain", "out_true_peak"))
+        hop_energy, out = r["hop_energy"], []
         for i in range(n):
-            r = dict(status=status[i], lufs=float(rd[i]), true_peak=float(rf[i]), blocks_abs=int(ri[i]), blocks_rel=int(ri[n + i]),
-                     hop_energy=rd[n + ho[i]:n + ho[i + 1]].clone())
+            d = dict(status=status[i], lufs=lufs[i], true_peak=true_peak[i], blocks_abs=blocks_abs[i], blocks_rel=blocks_rel[i],
+                     hop_energy=self._host(hop_energy[ho[i]:ho[i + 1]]))
             if y is not None:
-                r.update(gain=float(rf[n + i]), out_true_peak=float(rf[2 * n + i]))
-            out.append((None if y is None else y[io[i]:io[i + 1]], r))
+                d.update(gain=gain[i], out_true_peak=out_true_peak[i])
+            out.append((None if y is None else y[io[i]:io[i + 1]], d))
         return out
 
 
