@@ -671,7 +671,7 @@ def F_pad_text(ids):
 
 @torch.no_grad()
 def test_ar_step_graph_is_kept_between_calls_and_seeds_are_data():
-    """The captured decode step is kept on the handle between tt_ar_generate calls (csrc/gpt2.hip step_key): the Philox keys live in
+    """The captured decode step is kept on the handle between tt_ar_generate calls (csrc/gpt2.hip ar_step_key): the Philox keys live in
     device memory, so a second call with another seed replays the SAME graph and must sample what eager launches sample for that seed;
     a call that changes what the graph bakes in (batch, prefix length, sampling scalars) must re-capture."""
     cfg = ARConfig(**G.AR_CFG)

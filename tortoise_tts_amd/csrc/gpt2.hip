@@ -13,6 +13,8 @@
 //                was built and measured 0.7 - 10 % slower at every batch size from 16 to 256: profiles/r05_ab_ar_five_launch_step.txt,
 //                profiles/r06_ab_small_batch_decode.txt; it is not in the library.)
 //   * latents:   teacher-forced full pass for the CLVP winners (autoregressive.py:454-506).
+// The host side of a step is argument builders (each launch described once), two layer forms (ar_layer_mfma, ar_layer_gemv), one step
+// runner (ar_run_steps) and one finish (ar_finish): DESIGN.md 4, "How a decode step is assembled and paced".
 #include "runtime.h"
 #include <unistd.h>
 #include <chrono>
@@ -138,31 +140,117 @@ namespace tt { int g_ar_gemv = 2; }  // ttx_kernel_variant(TTX_AR_GEMV), read at
 
 static const int MAX_SPLIT = 8;
 
-static inline GemmArgs ar_gemm(const tt_ar* e, const void* A, int lda, const void* W, int ldw, int M, int N, int K) {
-  return gemm_args(A, lda, W, ldw, M, N, K);
-}
+// ------------------------------------------------------------------------------ argument builders: each launch is described once
+// LayerNorm weights of a trunk row norm; g2 / b2: the second norm lm_head applies on top (final_norm over ln_f)
+struct LnW { const float* g1; const float* b1; const float* g2 = nullptr; const float* b2 = nullptr; };
+static inline LnW ar_head_ln(const tt_ar* e) { return LnW{e->w.lnf_g, e->w.lnf_b, e->w.final_norm_g, e->w.final_norm_b}; }
+// What a split-K projection leaves for the next row norm to add into the residual stream: its bias and `nslab` slabs of e->slabs
+struct Pending { const float* bias = nullptr; int nslab = 0; };
 
-// x [M][D] rows (+ pending bias / split-K slabs of the GEMM before) -> LayerNorm -> h_out [M][D] T.  slabs: [nslab][slab_rows][D]
-static int ar_rownorm_rows(tt_ar* e, float* x, void* h_out, int M, const float* g1, const float* b1, const float* add_bias, const float* slabs,
-                           int nslab, int slab_rows, hipStream_t s) {
+// x [M][D] rows (+ the pending bias / slabs [nslab][slab_rows][D]) -> LayerNorm (-> second LayerNorm) -> h_out [M][D] T.  One workgroup
+// per row; a caller that wants the f32 copy of the normalised rows sets out_f32 itself or files it as a latent (ar_file_latent).
+static RowNormArgs ar_norm_args(const tt_ar* e, float* x, void* h_out, int M, const LnW& w, const Pending& pend = Pending(), int slab_rows = 0) {
   RowNormArgs a;
   memset(&a, 0, sizeof(a));
   a.x = x; a.ldx = e->D; a.M = M; a.D = e->D;
-  a.add_bias = add_bias;
-  a.add_slabs = nslab ? slabs : nullptr;
-  a.nslab = nslab; a.slab_stride = (size_t)slab_rows * e->D; a.ldslab = e->D;
-  a.write_x = (add_bias || nslab) ? 1 : 0;
+  a.add_bias = pend.bias;
+  a.add_slabs = pend.nslab ? e->slabs : nullptr;
+  a.nslab = pend.nslab; a.slab_stride = (size_t)slab_rows * e->D; a.ldslab = e->D;  // (the stride is read per slab: unread without slabs)
+  a.write_x = (pend.bias || pend.nslab) ? 1 : 0;
   a.mode = NORM_LAYER;
-  a.g1 = g1; a.b1 = b1; a.eps1 = 1e-5f;
+  a.g1 = w.g1; a.b1 = w.b1; a.eps1 = 1e-5f;
+  a.g2 = w.g2; a.b2 = w.b2; a.eps2 = w.g2 ? 1e-5f : 0.f;
   a.out_t = h_out; a.ldot = e->D;
   a.row_blocks = 1;
   a.guard = e->guard.dev;
+  return a;
+}
+// The f32 copy of lm_head's normalised rows is the reference's per-step latent.  lat_index >= 0 files the row(s) as that latent of
+// sequence lat_row (prefill: 0); -1: under the device-side step counter (the decode step feeding token i - 1 produces latent i; a
+// session row under its own counter); -2, or a handle / batch without latent capture: nothing
+static void ar_file_latent(const tt_ar* e, RowNormArgs* a, int lat_index, int lat_row) {
+  if (!e->lat || lat_index == -2 || a->M > e->lat_batch) return;
+  a->out_f32 = e->lat; a->ldo32 = e->D;
+  a->f32_slot_stride = (size_t)e->lat_batch * e->D;
+  if (lat_index >= 0) a->out_f32 += (size_t)lat_index * a->f32_slot_stride + (size_t)lat_row * e->D;
+  else if (e->sessions) { a->f32_row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; a->f32_slot_base = 1; }  // every row its own index
+  else { a->f32_slot = e->state + 1; a->f32_slot_base = 1; }
+}
+static int ar_norm(tt_ar* e, float* x, int M, const LnW& w, const Pending& pend, int slab_rows, hipStream_t s) {
+  return rownorm_launch(e->cfg.dtype, ar_norm_args(e, x, e->h, M, w, pend, slab_rows), s);
+}
+// lm_head = Sequential(final_norm, mel_head) applied to ln_f(x) (autoregressive.py:42, 174): its input norm
+static int ar_head_norm(tt_ar* e, float* x, int M, const Pending& pend, int slab_rows, hipStream_t s, int lat_index = -2, int lat_row = 0) {
+  RowNormArgs a = ar_norm_args(e, x, e->h, M, ar_head_ln(e), pend, slab_rows);
+  ar_file_latent(e, &a, lat_index, lat_row);
   return rownorm_launch(e->cfg.dtype, a, s);
 }
-static int ar_rownorm(tt_ar* e, float* x, int M, const float* g1, const float* b1, const float* g2, const float* b2,
-                      const float* add_bias, int nslab, int slab_rows, hipStream_t s) {
-  (void)g2; (void)b2;
-  return ar_rownorm_rows(e, x, e->h, M, g1, b1, add_bias, e->slabs, nslab, slab_rows, s);
+// row P of e->x = the start token's input row: mel_embedding[start] + mel_pos_embedding[0]  (autoregressive.py:137-141)
+static int ar_start_row(tt_ar* e, int P, hipStream_t s) {
+  RowNormArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = e->x + (size_t)P * e->D; a.ldx = e->D; a.M = 1; a.D = e->D;
+  a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * e->D; a.ldxin = e->D;
+  a.add_bias = e->w.mel_pos;  // row 0
+  a.write_x = 1; a.mode = NORM_NONE;
+  return rownorm_launch(e->cfg.dtype, a, s);
+}
+
+// A GEMV-shaped launch over the decode step's e->B rows (a wide session handle: its live rows): [M][N] = A [M][K] W[N][K]^T + bias.
+// The caller adds the fields of its epilogue.
+static GemvArgs ar_gemv_args(const tt_ar* e, const void* A, int lda, const void* W, int ldw, int N, int K, const float* bias, int epi) {
+  GemvArgs v;
+  memset(&v, 0, sizeof(v));
+  v.A = A; v.lda = lda; v.W = W; v.ldw = ldw; v.M = e->B; v.N = N; v.K = K; v.bias = bias; v.epi = epi;
+  v.row_live = ar_gemv_live(e);
+  return v;
+}
+// the LayerNorm of the rows of x in front of the product (gemv == 2), instead of a launch of its own
+static void ar_gemv_ln(const tt_ar* e, GemvArgs* v, const float* g, const float* b) {
+  v->ln_x = e->x; v->ldx = e->D; v->ln_g = g; v->ln_b = b; v->ln_eps = 1e-5f; v->guard = e->guard.dev;
+}
+
+static inline void* ar_kc(const tt_ar* e, int l) { return offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es); }
+static inline void* ar_vc(const tt_ar* e, int l) { return offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es); }
+
+// Decode attention of layer l over the e->B rows: one shared prefix, one prefix per utterance group, or (session handles) one per row
+static DecodeAttnArgs ar_attn_args(const tt_ar* e, int l) {
+  DecodeAttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = e->q;
+  a.kp = offset_t(e->kp, (size_t)l * e->prefix_layer_elems, e->es);
+  a.vp = offset_t(e->vp, (size_t)l * e->prefix_layer_elems, e->es);
+  a.P1 = e->P1; a.kc = ar_kc(e, l); a.vc = ar_vc(e, l); a.tmax = e->tmax; a.step = e->state + 1;
+  a.out = e->attn; a.B = e->B; a.heads = e->H; a.host_tgen = e->host_slot + 1;
+  if (e->G > 1) {
+    a.ngroups = e->G; a.group_size = e->B / e->G;
+    a.prefix_group_stride = (size_t)e->cfg.layers * e->prefix_layer_elems;
+    for (int gi = 0; gi < e->G; ++gi) a.p1_tab[gi] = e->P1g[gi];
+  }
+  if (e->sessions) {  // every row its own prefix group, prefix length and newest slot - all device data; P1 = the capacity
+    a.P1 = e->cfg.max_prefix; a.step = nullptr; a.host_tgen = 0;
+    a.row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; a.row_p1 = e->sess + SESS_P1 * e->cfg.max_batch;
+    a.prefix_group_stride = (size_t)e->cfg.layers * e->prefix_layer_elems;
+  }
+  return a;
+}
+
+// What the two generation paths share of the sampler's argument block.  Filled in place from memset(0): the block's bytes (padding
+// included) are part of the kept step graph's key.  The utterance path adds its scalars, exp_noise, groups and typical_mass; the
+// session path rows, row_launch, sess and pre_logits.  The Philox keys and the row offset go through device memory (seed / group_seeds
+// / row_offset stay zero): neither the seed nor the candidate range of a call is part of the step graph.
+static void ar_sample_args(const tt_ar* e, int B, SampleArgs* sa) {
+  memset(sa, 0, sizeof(*sa));
+  sa->B = B; sa->V = e->V; sa->seen = e->seen;
+  sa->state = e->state; sa->unfinished = e->unfinished; sa->stop_token = e->cfg.stop_mel_token;
+  sa->codes = e->codes_own; sa->ldcodes = e->tmax; sa->next_tok = e->next_tok; sa->unfinished_count = e->unfinished_count;
+  sa->embed_x = e->x; sa->tok_emb = e->w.mel_emb; sa->pos_emb = e->w.mel_pos; sa->D = e->D; sa->pos_offset = e->cfg.mel_pos_offset;
+  sa->pos_len = e->cfg.mel_pos_len;
+  sa->guard = e->guard.dev;
+  sa->typical_out = e->typ_logits;
+  sa->keys_dev = e->par_dev->keys;
+  sa->row_offset_dev = &e->par_dev->row_offset;
+  sa->logits = e->logits; sa->ldl = e->Vp; sa->ldg = e->Vp;  // every row its own logits (ldg is unused then; set so that every step shares one key)
 }
 
 // GPT2Model.forward over full sequences (causal), in place on e->x [B*n][D].
@@ -171,8 +259,8 @@ static int gpt_trunk_full(tt_ar* e, int B, int n, bool to_prefix, hipStream_t s,
   const int n_pad = round_up(n, 32);
   for (int l = 0; l < e->cfg.layers; ++l) {
     const tt_gpt_layer& w = e->L[l];
-    TT_TRY(ar_rownorm(e, e->x, M, w.ln1_g, w.ln1_b, nullptr, nullptr, nullptr, 0, 0, s));
-    GemmArgs g = ar_gemm(e, e->h, D, w.w_qkv, D, M, 3 * D, D);
+    TT_TRY(ar_norm(e, e->x, M, LnW{w.ln1_g, w.ln1_b}, Pending(), 0, s));
+    GemmArgs g = gemm_args(e->h, D, w.w_qkv, D, M, 3 * D, D);
     g.bias = w.b_qkv; g.seq_len = n; g.dmodel = D; g.heads = H;
     g.q = e->q;
     const size_t pl = ((size_t)group * e->cfg.layers + l) * e->prefix_layer_elems;
@@ -185,14 +273,14 @@ static int gpt_trunk_full(tt_ar* e, int B, int n, bool to_prefix, hipStream_t s,
     f.q = e->q; f.k = g.k; f.vt = e->vt; f.out = e->attn; f.ldo = D;
     f.BH = B * H; f.heads = H; f.n = n; f.n_pad = n_pad; f.causal = 1;
     TT_TRY(flash_attention_launch(dt, f, s));
-    g = ar_gemm(e, e->attn, D, w.w_proj, D, M, D, D);
+    g = gemm_args(e->attn, D, w.w_proj, D, M, D, D);
     g.bias = w.b_proj; g.res = e->x; g.ldres = D; g.out_f32 = e->x; g.ldo32 = D;
     TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(ar_rownorm(e, e->x, M, w.ln2_g, w.ln2_b, nullptr, nullptr, nullptr, 0, 0, s));
-    g = ar_gemm(e, e->h, D, w.w_fc, D, M, 4 * D, D);
+    TT_TRY(ar_norm(e, e->x, M, LnW{w.ln2_g, w.ln2_b}, Pending(), 0, s));
+    g = gemm_args(e->h, D, w.w_fc, D, M, 4 * D, D);
     g.bias = w.b_fc; g.act = ACT_GELU_TANH; g.out_t = e->ff; g.ldot = 4 * D;
     TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    g = ar_gemm(e, e->ff, 4 * D, w.w_proj2, 4 * D, M, D, 4 * D);
+    g = gemm_args(e->ff, 4 * D, w.w_proj2, 4 * D, M, D, 4 * D);
     g.bias = w.b_proj2; g.res = e->x; g.ldres = D; g.out_f32 = e->x; g.ldo32 = D;
     TT_TRY(gemm_launch(dt, EPI_STD, g, s));
   }
@@ -202,8 +290,7 @@ static int gpt_trunk_full(tt_ar* e, int B, int n, bool to_prefix, hipStream_t s,
 // Split-K factor of the decode projections.  Deliberately independent of the batch size: the k-order
 // of every output element is then the same for any B, so a candidate's logits (and therefore its
 // sampled codes) do not depend on how the candidates are sharded across GPUs.
-static int pick_split(int B, int N, int K) {
-  (void)B;
+static int pick_split(int N, int K) {
   // decode GEMMs run 64x64 tiles with 256-deep k-stages: aim for ~256 blocks at the full candidate batch
   // (4 row tiles) and at least one whole stage per split.  (In-situ A/B, round 3: 8 slabs for proj2 +4.8 %, 2 slabs for proj +0.9 %.)
   const int tiles = 4 * cdiv(N, 64);
@@ -215,185 +302,206 @@ static int pick_split(int B, int N, int K) {
   return sk;
 }
 
-// lm_head = Sequential(final_norm, mel_head) applied to ln_f(x) (autoregressive.py:42, 174)
-// lat_index: >= 0 files the normalised row(s) as that latent (prefill: 0); -1: under the device-side step counter (decode step
-// feeding token i - 1 produces latent i); -2: no capture
-static int ar_head_norm(tt_ar* e, float* x, void* h_out, int M, const float* add_bias, const float* slabs, int nslab, int slab_rows,
-                        hipStream_t s, int lat_index = -2, int lat_row = 0) {
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.ldx = e->D; a.M = M; a.D = e->D;
-  a.add_bias = add_bias;
-  a.add_slabs = nslab ? slabs : nullptr;
-  a.nslab = nslab; a.slab_stride = (size_t)slab_rows * e->D; a.ldslab = e->D;
-  a.write_x = (add_bias || nslab) ? 1 : 0;
-  a.mode = NORM_LAYER;
-  a.g1 = e->w.lnf_g; a.b1 = e->w.lnf_b; a.eps1 = 1e-5f;
-  a.g2 = e->w.final_norm_g; a.b2 = e->w.final_norm_b; a.eps2 = 1e-5f;
-  a.out_t = h_out; a.ldot = e->D;
-  a.row_blocks = 1;
-  a.guard = e->guard.dev;
-  if (e->lat && lat_index != -2 && M <= e->lat_batch) {
-    a.out_f32 = e->lat; a.ldo32 = e->D;
-    a.f32_slot_stride = (size_t)e->lat_batch * e->D;
-    if (lat_index >= 0) a.out_f32 += (size_t)lat_index * a.f32_slot_stride + (size_t)lat_row * e->D;
-    else if (e->sessions) { a.f32_row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; a.f32_slot_base = 1; }  // every row its own index
-    else { a.f32_slot = e->state + 1; a.f32_slot_base = 1; }
-  }
-  return rownorm_launch(e->cfg.dtype, a, s);
-}
+// The logits of M rows of e->h: into the decode step's logits from row logits_row0 on, or (out: a session's admission) into a
+// row of their own outside them
 static int ar_head_gemm(tt_ar* e, int M, hipStream_t s, int logits_row0 = 0, float* out = nullptr) {
-  if (out) {  // (a session's admission: its own logits row, outside the decode step's rows)
-    GemvArgs v;
-    memset(&v, 0, sizeof(v));
-    v.A = e->h; v.lda = e->D; v.W = e->w_head_p; v.ldw = e->D; v.M = M; v.N = e->Vp; v.K = e->D; v.bias = e->b_head_p; v.epi = GEMV_F32;
-    v.out_f32 = out; v.ldo32 = e->Vp;
-    return gemv_launch(e->cfg.dtype, v, s);
-  }
-  if (e->gemv && M <= ar_gemv_rows(e)) {
-    GemvArgs v;
-    memset(&v, 0, sizeof(v));
-    v.A = e->h; v.lda = e->D; v.W = e->w_head_p; v.ldw = e->D; v.M = M; v.N = e->Vp; v.K = e->D; v.bias = e->b_head_p; v.epi = GEMV_F32;
-    v.out_f32 = e->logits + (size_t)logits_row0 * e->Vp; v.ldo32 = e->Vp;
-    if (logits_row0 == 0 && M == e->cfg.max_batch) v.row_live = ar_gemv_live(e);  // (the decode step's rows)
+  float* dst = out ? out : e->logits + (size_t)logits_row0 * e->Vp;
+  if (out || (e->gemv && M <= ar_gemv_rows(e))) {
+    GemvArgs v = ar_gemv_args(e, e->h, e->D, e->w_head_p, e->D, e->Vp, e->D, e->b_head_p, GEMV_F32);
+    v.M = M; v.out_f32 = dst; v.ldo32 = e->Vp;
+    if (out || logits_row0 != 0 || M != e->cfg.max_batch) v.row_live = nullptr;  // (only the decode step's rows have a slot plane)
     TT_TRY(gemv_launch(e->cfg.dtype, v, s));
-    e->logits_rows = logits_row0 + M;
-    return 0;
+  } else {
+    GemmArgs g = gemm_args(e->h, e->D, e->w_head_p, e->D, M, e->Vp, e->D);
+    g.bias = e->b_head_p; g.out_f32 = dst; g.ldo32 = e->Vp;
+    TT_TRY(gemm_launch(e->cfg.dtype, EPI_STD, g, s));
   }
-  GemmArgs g = ar_gemm(e, e->h, e->D, e->w_head_p, e->D, M, e->Vp, e->D);
-  g.bias = e->b_head_p; g.out_f32 = e->logits + (size_t)logits_row0 * e->Vp; g.ldo32 = e->Vp;
-  TT_TRY(gemm_launch(e->cfg.dtype, EPI_STD, g, s));
-  e->logits_rows = logits_row0 + M;
+  if (!out) e->logits_rows = logits_row0 + M;
   return 0;
 }
-static int ar_head(tt_ar* e, float* x, int M, const float* add_bias, int nslab, hipStream_t s, int lat_index = -2, int logits_row0 = 0) {
-  TT_TRY(ar_head_norm(e, x, e->h, M, add_bias, e->slabs, nslab, e->B, s, lat_index));
-  return ar_head_gemm(e, M, s, logits_row0);
+
+// ------------------------------------------------------------------------------ the decode layer, in its two forms
+// GEMV form (handles of <= 4 sequences, wide session handles: <= 16): no split-K - the projections update x in place and the norms
+// fold nothing.  Five launches with the layer norms inside the GEMVs (gemv == 2), seven with norms of their own.
+static int ar_layer_gemv(tt_ar* e, int l, hipStream_t s) {
+  const tt_gpt_layer& w = e->L[l];
+  const int D = e->D, dt = e->cfg.dtype, nb = e->B;
+  const bool ln_inside = e->gemv == 2;
+  if (!ln_inside) TT_TRY(ar_norm(e, e->x, nb, LnW{w.ln1_g, w.ln1_b}, Pending(), nb, s));
+  GemvArgs v = ar_gemv_args(e, e->h, D, w.w_qkv, D, 3 * D, D, w.b_qkv, GEMV_QKV);  // QKV: q scaled, K / V appended at the newest slot
+  v.step = e->state + 1; v.qbuf = e->q; v.kc = ar_kc(e, l); v.vc = ar_vc(e, l);
+  v.heads = e->H; v.tmax = e->tmax; v.dmodel = D; v.q_scale = 0.125f;
+  if (e->sessions) { v.step = nullptr; v.row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; }
+  if (ln_inside) ar_gemv_ln(e, &v, w.ln1_g, w.ln1_b);
+  TT_TRY(gemv_launch(dt, v, s));
+  TT_TRY(decode_attention_launch(dt, ar_attn_args(e, l), s));
+  v = ar_gemv_args(e, e->attn, D, w.w_proj, D, D, D, w.b_proj, GEMV_RES);  // attention projection
+  v.out_f32 = e->x; v.ldo32 = D;
+  TT_TRY(gemv_launch(dt, v, s));
+  if (!ln_inside) TT_TRY(ar_norm(e, e->x, nb, LnW{w.ln2_g, w.ln2_b}, Pending(), nb, s));
+  v = ar_gemv_args(e, e->h, D, w.w_fc, D, 4 * D, D, w.b_fc, GEMV_GELU_T);  // c_fc + gelu
+  v.out_t = e->ff; v.ldot = 4 * D;
+  if (ln_inside) ar_gemv_ln(e, &v, w.ln2_g, w.ln2_b);
+  TT_TRY(gemv_launch(dt, v, s));
+  v = ar_gemv_args(e, e->ff, 4 * D, w.w_proj2, 4 * D, D, 4 * D, w.b_proj2, GEMV_RES);  // MLP projection
+  v.out_f32 = e->x; v.ldo32 = D;
+  return gemv_launch(dt, v, s);
 }
 
-// The 30 layers of one KV-cached decode step for the e->B sequences + the input norm of lm_head, all on stream s.
-static int decode_layers_enqueue(tt_ar* e, hipStream_t s) {
-  const int D = e->D, H = e->H, dt = e->cfg.dtype, nb = e->B;
-  float* x = e->x;
-  float* slabs = e->slabs;
-  const float* pend_bias = nullptr;
-  int pend_slabs = 0;
-  const bool fused = ar_fused_qkv_attn(e);
-  for (int l = 0; l < e->cfg.layers; ++l) {
-    const tt_gpt_layer& w = e->L[l];
-    if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln1_g, w.ln1_b, pend_bias, slabs, pend_slabs, nb, s));
-    if (e->gemv) {  // <= 4 sequences (wide session handles: <= 16): GEMV-shaped launches, no split-K - the projections update x in place,
-      GemvArgs v;   // the norms fold nothing
-      memset(&v, 0, sizeof(v));
-      v.A = e->h; v.lda = D; v.W = w.w_qkv; v.ldw = D; v.M = nb; v.N = 3 * D; v.K = D; v.bias = w.b_qkv; v.epi = GEMV_QKV;
-      v.step = e->state + 1; v.qbuf = e->q; v.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es); v.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
-      v.heads = H; v.tmax = e->tmax; v.dmodel = D; v.q_scale = 0.125f;
-      if (e->sessions) { v.step = nullptr; v.row_slot = e->sess + SESS_SLOT * e->cfg.max_batch; }
-      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln1_g; v.ln_b = w.ln1_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
-      v.row_live = ar_gemv_live(e);
-      TT_TRY(gemv_launch(dt, v, s));
-      DecodeAttnArgs a;
-      memset(&a, 0, sizeof(a));
-      a.q = e->q;
-      a.kp = offset_t(e->kp, (size_t)l * e->prefix_layer_elems, e->es);
-      a.vp = offset_t(e->vp, (size_t)l * e->prefix_layer_elems, e->es);
-      a.P1 = e->P1; a.kc = v.kc; a.vc = v.vc; a.tmax = e->tmax; a.step = e->state + 1;
-      a.out = e->attn; a.B = nb; a.heads = H; a.host_tgen = e->host_slot + 1;
-      if (e->sessions) {  // every row its own prefix group, prefix length and newest slot - all device data; P1 = the capacity
-        a.P1 = e->cfg.max_prefix; a.step = nullptr; a.host_tgen = 0;
-        a.row_slot = v.row_slot; a.row_p1 = e->sess + SESS_P1 * e->cfg.max_batch;
-        a.prefix_group_stride = (size_t)e->cfg.layers * e->prefix_layer_elems;
-      }
-      TT_TRY(decode_attention_launch(dt, a, s));
-      memset(&v, 0, sizeof(v));
-      v.A = e->attn; v.lda = D; v.W = w.w_proj; v.ldw = D; v.M = nb; v.N = D; v.K = D; v.bias = w.b_proj; v.epi = GEMV_RES; v.out_f32 = x; v.ldo32 = D;
-      v.row_live = ar_gemv_live(e);
-      TT_TRY(gemv_launch(dt, v, s));
-      if (e->gemv < 2) TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln2_g, w.ln2_b, nullptr, slabs, 0, nb, s));
-      memset(&v, 0, sizeof(v));
-      if (e->gemv == 2) { v.ln_x = x; v.ldx = D; v.ln_g = w.ln2_g; v.ln_b = w.ln2_b; v.ln_eps = 1e-5f; v.guard = e->guard.dev; }
-      v.A = e->h; v.lda = D; v.W = w.w_fc; v.ldw = D; v.M = nb; v.N = 4 * D; v.K = D; v.bias = w.b_fc; v.epi = GEMV_GELU_T; v.out_t = e->ff; v.ldot = 4 * D;
-      v.row_live = ar_gemv_live(e);
-      TT_TRY(gemv_launch(dt, v, s));
-      memset(&v, 0, sizeof(v));
-      v.A = e->ff; v.lda = 4 * D; v.W = w.w_proj2; v.ldw = 4 * D; v.M = nb; v.N = D; v.K = 4 * D; v.bias = w.b_proj2; v.epi = GEMV_RES; v.out_f32 = x; v.ldo32 = D;
-      v.row_live = ar_gemv_live(e);
-      TT_TRY(gemv_launch(dt, v, s));
-      pend_bias = nullptr;
-      pend_slabs = 0;
-      continue;
-    }
-    GemmArgs g = ar_gemm(e, e->h, D, w.w_qkv, D, nb, 3 * D, D);
-    g.bias = w.b_qkv;
-    g.dmodel = D; g.heads = H; g.q_scale = 0.125f;
-    g.step = e->state + 1; g.qbuf = e->q;
-    g.kc = offset_t(e->kc, (size_t)l * e->gen_layer_elems, e->es);
-    g.vc = offset_t(e->vc, (size_t)l * e->gen_layer_elems, e->es);
-    g.tmax = e->tmax;
-    if (!fused) TT_TRY(gemm_launch(dt, EPI_QKV_DECODE, g, s));
-    DecodeAttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = e->q;
-    a.kp = offset_t(e->kp, (size_t)l * e->prefix_layer_elems, e->es);
-    a.vp = offset_t(e->vp, (size_t)l * e->prefix_layer_elems, e->es);
-    if (e->G > 1) {
-      a.ngroups = e->G; a.group_size = nb / e->G;
-      a.prefix_group_stride = (size_t)e->cfg.layers * e->prefix_layer_elems;
-      for (int gi = 0; gi < e->G; ++gi) a.p1_tab[gi] = e->P1g[gi];
-    }
-    a.P1 = e->P1; a.kc = g.kc; a.vc = g.vc; a.tmax = e->tmax; a.step = e->state + 1;
-    a.out = e->attn; a.B = nb; a.heads = H; a.host_tgen = e->host_slot + 1;
-    if (fused) {  // one launch: the workgroups of the attention project their own q / k / v rows (e->q is not written)
-      DecodeQkvAttnArgs f;
-      memset(&f, 0, sizeof(f));
-      f.d = a;
-      f.h = e->h; f.w_qkv = w.w_qkv; f.b_qkv = w.b_qkv; f.q_scale = 0.125f;
-      TT_TRY(decode_qkv_attention_launch(dt, f, s));
-    } else {
-      TT_TRY(decode_attention_launch(dt, a, s));
-    }
-    // >= 1024 sequences (several utterances per batch): one block per output tile fills the chip, so the split-K partial
-    // sums are folded inside the launch in slab order (gemm.h serial_k: the same bits as slabs + row norm, without the slab traffic)
-    const bool serial = nb >= 1024;
-    int sk = pick_split(nb, D, D);
-    g = ar_gemm(e, e->attn, D, w.w_proj, D, nb, D, D);
-    if (serial && sk > 1) {
-      g.serial_k = sk; g.bias = w.b_proj; g.res = x; g.ldres = D; g.out_f32 = x; g.ldo32 = D;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln2_g, w.ln2_b, nullptr, slabs, 0, nb, s));
-    } else {
-      g.splitk = sk; g.out_f32 = slabs; g.ldo32 = D;
-      if (sk == 1) { g.bias = nullptr; }
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      TT_TRY(ar_rownorm_rows(e, x, e->h, nb, w.ln2_g, w.ln2_b, w.b_proj, slabs, sk, nb, s));
-    }
-    g = ar_gemm(e, e->h, D, w.w_fc, D, nb, 4 * D, D);
-    g.bias = w.b_fc; g.act = ACT_GELU_TANH; g.out_t = e->ff; g.ldot = 4 * D;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    sk = pick_split(nb, D, 4 * D);
-    g = ar_gemm(e, e->ff, 4 * D, w.w_proj2, 4 * D, nb, D, 4 * D);
-    if (serial && sk > 1) {
-      g.serial_k = sk; g.bias = w.b_proj2; g.res = x; g.ldres = D; g.out_f32 = x; g.ldo32 = D;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      pend_bias = nullptr;
-      pend_slabs = 0;
-    } else {
-      g.splitk = sk; g.out_f32 = slabs; g.ldo32 = D;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      pend_bias = w.b_proj2;
-      pend_slabs = sk;
-    }
+// One residual projection of the MFMA layer: x += A [B][K] W[D][K]^T + bias, K split pick_split() ways.  Either the partial sums go
+// to e->slabs and *pend reports what the next row norm must add (bias + slabs), or - >= 1024 sequences (several utterances per batch):
+// one block per output tile fills the chip - they are folded inside the launch in slab order (gemm.h serial_k: the same bits as
+// slabs + row norm, without the slab traffic) and nothing is pending.
+static int ar_proj(tt_ar* e, const void* A, const void* W, const float* bias, int K, Pending* pend, hipStream_t s) {
+  const int D = e->D, nb = e->B;
+  const int sk = pick_split(D, K);
+  GemmArgs g = gemm_args(A, K, W, K, nb, D, K);
+  if (nb >= 1024 && sk > 1) {
+    g.serial_k = sk; g.bias = bias; g.res = e->x; g.ldres = D; g.out_f32 = e->x; g.ldo32 = D;
+    *pend = Pending();
+  } else {
+    g.splitk = sk; g.out_f32 = e->slabs; g.ldo32 = D;
+    *pend = Pending{bias, sk};
   }
-  return ar_head_norm(e, x, e->h, nb, pend_bias, slabs, pend_slabs, nb, s, -1);
+  return gemm_launch(e->cfg.dtype, EPI_STD, g, s);
 }
 
-// One KV-cached decode step for e->B sequences up to the logits; the fed tokens are in e->next_tok (or, `embedded`, the sampler
-// already wrote this step's input rows into e->x: tt_ar_generate).
+// MFMA form, seven launches: LayerNorm (folds what the layer before left pending), QKV GEMM (K / V appended by its epilogue), decode
+// attention, attention projection, LayerNorm (folds it), c_fc GEMM + gelu, MLP projection (left pending for the next layer's norm).
+// fused (ar_fused_qkv_attn): the QKV GEMM and the attention are one launch - six.
+static int ar_layer_mfma(tt_ar* e, int l, bool fused, Pending* pend, hipStream_t s) {
+  const tt_gpt_layer& w = e->L[l];
+  const int D = e->D, dt = e->cfg.dtype, nb = e->B;
+  TT_TRY(ar_norm(e, e->x, nb, LnW{w.ln1_g, w.ln1_b}, *pend, nb, s));
+  if (fused) {  // the workgroups of the attention project their own q / k / v rows (e->q is not written)
+    DecodeQkvAttnArgs f;
+    memset(&f, 0, sizeof(f));
+    f.d = ar_attn_args(e, l);
+    f.h = e->h; f.w_qkv = w.w_qkv; f.b_qkv = w.b_qkv; f.q_scale = 0.125f;
+    TT_TRY(decode_qkv_attention_launch(dt, f, s));
+  } else {
+    GemmArgs g = gemm_args(e->h, D, w.w_qkv, D, nb, 3 * D, D);
+    g.bias = w.b_qkv;
+    g.dmodel = D; g.heads = e->H; g.q_scale = 0.125f;
+    g.step = e->state + 1; g.qbuf = e->q;
+    g.kc = ar_kc(e, l); g.vc = ar_vc(e, l);
+    g.tmax = e->tmax;
+    TT_TRY(gemm_launch(dt, EPI_QKV_DECODE, g, s));
+    TT_TRY(decode_attention_launch(dt, ar_attn_args(e, l), s));
+  }
+  TT_TRY(ar_proj(e, e->attn, w.w_proj, w.b_proj, D, pend, s));
+  TT_TRY(ar_norm(e, e->x, nb, LnW{w.ln2_g, w.ln2_b}, *pend, nb, s));
+  GemmArgs g = gemm_args(e->h, D, w.w_fc, D, nb, 4 * D, D);
+  g.bias = w.b_fc; g.act = ACT_GELU_TANH; g.out_t = e->ff; g.ldot = 4 * D;
+  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  return ar_proj(e, e->ff, w.w_proj2, w.b_proj2, 4 * D, pend, s);
+}
+
+// One KV-cached decode step for the e->B sequences up to the logits, all on stream s: the layers in the handle's form, lm_head's
+// input norm (which folds what the last layer left pending and files the step's latent) and lm_head.  The fed tokens are in
+// e->next_tok (or, `embedded`, the sampler already wrote this step's input rows into e->x: the generation paths).
 static int decode_step_enqueue(tt_ar* e, hipStream_t s, bool embedded = false) {
   const int B = e->B;
   if (!embedded) TT_TRY(ar_embed_launch(e->next_tok, e->state, e->w.mel_emb, e->w.mel_pos, e->x, B, e->D, e->cfg.mel_pos_offset, s));
-  TT_TRY(decode_layers_enqueue(e, s));
+  const bool fused = ar_fused_qkv_attn(e);
+  Pending pend;
+  for (int l = 0; l < e->cfg.layers; ++l) TT_TRY(e->gemv ? ar_layer_gemv(e, l, s) : ar_layer_mfma(e, l, fused, &pend, s));
+  TT_TRY(ar_head_norm(e, e->x, B, pend, B, s, -1));
   return ar_head_gemm(e, B, s);
+}
+
+// ------------------------------------------------------------------------------ running steps: one pacing loop, one finish
+// The bytes of everything a captured step bakes in that a later call could change: the sampler's argument block + the geometry words
+// the launchers read from the handle.
+static std::vector<unsigned char> ar_step_key(const SampleArgs& sa, const int* geo, int n_geo) {
+  std::vector<unsigned char> key(sizeof(sa) + n_geo * sizeof(int));
+  memcpy(key.data(), &sa, sizeof(sa));
+  memcpy(key.data() + sizeof(sa), geo, n_geo * sizeof(int));
+  return key;
+}
+
+// Launches decode steps [first, last) on stream s: replays of `graph` (captured from step_enqueue(s, -1) unless the kept one has the
+// key of sa + geo), or with graph == null step_enqueue(s, step) itself.  The host stays at most e->lookahead steps ahead of the progress words the
+// last kernel of every step writes, and stops launching once they say that every row has stopped.  *launched = steps put on the stream.
+template <typename F>
+static int ar_run_steps(tt_ar* e, hipStream_t s, KeptGraph* graph, const SampleArgs& sa, const int* geo, int n_geo, F&& step_enqueue, int first,
+                        int last, const char* who, int* launched) {
+  *launched = 0;
+  if (graph) {
+    const auto key = ar_step_key(sa, geo, n_geo);
+    TT_TRY(graph->ensure(s, key.data(), key.size(), who, [&]() -> int { return step_enqueue(s, -1); }));
+  }
+  volatile int* prog = e->progress_host;
+  for (int step = first; step < last; ++step) {
+    const auto wait0 = std::chrono::steady_clock::now();
+    while (step - prog[0] >= e->lookahead && prog[1] < 0) {
+      // 200 ms of wall time without the expected progress (not a spin count: a slow first replay - code-object load, a profiler - must
+      // not look like lost progress words): fall back to a queue drain, always correct, only slower - and take the progress from the
+      // DEVICE state the words mirror, so a host that cannot see the mapped words still paces and ends the loop correctly
+      if (std::chrono::steady_clock::now() - wait0 > std::chrono::milliseconds(200)) {
+        int st3[3] = {0, 0, -1};
+        hipError_t ce = hipStreamSynchronize(s);
+        if (ce == hipSuccess) ce = hipMemcpy(st3, e->state, sizeof(st3), hipMemcpyDeviceToHost);
+        if (ce != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(ce)); return -2; }
+        prog[0] = st3[0];
+        if (st3[2] >= 0) prog[1] = st3[2];
+        e->drains += 1;
+        break;
+      }
+      usleep(50);
+    }
+    if (prog[1] >= 0) break;
+    TT_TRY(graph ? graph->launch(s, who) : step_enqueue(s, step));
+    *launched += 1;
+  }
+  return 0;
+}
+
+// The end of a generation call, after ar_run_steps returned rc: the first `cols` columns of `rows` rows of the handle's code buffer go
+// to the caller's [rows][ldcodes] buffer (the caller's pointer is not part of the kept graph), a session handle reads its state planes
+// back, the guard is snapshot, and the stream is synchronised: one host-visible completion point per call.  On any error the stream is
+// drained and `graph` dropped: a failed replay leaves nothing to trust.
+static int ar_finish(tt_ar* e, hipStream_t s, KeptGraph& graph, int rc, int* codes, int ldcodes, int cols, int rows, bool read_sessions, const char* who) {
+  if (!rc) {
+    hipError_t ce = hipMemcpy2DAsync(codes, (size_t)ldcodes * sizeof(int), e->codes_own, (size_t)e->tmax * sizeof(int), (size_t)cols * sizeof(int),
+                                     (size_t)rows, hipMemcpyDeviceToDevice, s);
+    if (ce == hipSuccess && read_sessions) ce = hipMemcpyAsync(e->sess_host, e->sess, (size_t)4 * rows * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (ce != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(ce)); rc = -2; }
+    if (!rc) rc = e->guard.snapshot(s);
+    if (!rc && (ce = hipStreamSynchronize(s)) != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(ce)); rc = -2; }
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    graph.drop();
+  }
+  return rc;
+}
+
+// ------------------------------------------------------------------------------ admission checks: they run before anything of a
+// running generation is touched (before sb.run), so a refused call leaves it resumable
+static inline bool typical_mass_ok(float m) { return m == 0.f || (m > 0.f && m < 1.f); }
+// The sampling scalars of one call (slot < 0) or of one slot's session.  positive: temperature, top_p and repetition_penalty must be
+// > 0 (the session paths; the utterance path leaves them to the sampler).
+static int ar_check_scalars(const char* who, int slot, const tt_sampling& q, bool positive) {
+  const bool pos_ok = !positive || (q.temperature > 0.f && q.top_p > 0.f && q.repetition_penalty > 0.f);
+  if (slot >= 0) {
+    TT_REQUIRE(pos_ok && typical_mass_ok(q.typical_mass), "%s: slot %d: bad sampling parameters (temperature %g, top_p %g, repetition_penalty %g, typical_mass %g)", who, slot,
+               (double)q.temperature, (double)q.top_p, (double)q.repetition_penalty, (double)q.typical_mass);
+    return 0;
+  }
+  TT_REQUIRE(typical_mass_ok(q.typical_mass), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)", (double)q.typical_mass);  // (one text on every path)
+  TT_REQUIRE(pos_ok, "%s: bad sampling parameters", who);
+  return 0;
+}
+// n_more further tokens after `done` fit the caller's code columns, the KV slots and the mel position table
+static int ar_check_chunk(const tt_ar* e, const char* who, int slot, int done, int n_more, int ldcodes) {
+  char pre[24] = "";
+  if (slot >= 0) snprintf(pre, sizeof(pre), "slot %d: ", slot);
+  const int target = done + n_more;
+  TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "%s: %s%d + %d tokens exceed capacity (%d code columns, %d KV slots)", who, pre, done, n_more, ldcodes,
+             e->tmax);
+  TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "%s: %s%d tokens exceed the mel position table", who, pre, target);
+  return 0;
 }
 
 extern "C" {
@@ -496,6 +604,15 @@ void tt_ar_destroy(tt_ar* e) {
   delete e;
 }
 
+// What every prefill shares: [prefix | start token] (P + 1 rows) through the trunk, their K / V into prefix-cache group `group` (per-layer
+// stride of the prefix cache = its capacity H * max_prefix * 64: group g, layer l at (g * layers + l) strides).  The start-token row's
+// hidden state is left in row P of e->x for the caller's head.
+static int ar_prefill_trunk(tt_ar* e, const float* prefix_emb, int P, int group, hipStream_t s) {
+  TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * e->D * sizeof(float), hipMemcpyDeviceToDevice, s));
+  TT_TRY(ar_start_row(e, P, s));
+  return gpt_trunk_full(e, 1, P + 1, true, s, group);
+}
+
 // Session handles: admit a session into slot `slot` of the S = max_batch rows.  The running rows are untouched: the prefix goes to
 // prefix-cache group `slot`, its logits to pre_logits[slot], its start-token latent to latent 0 of row `slot`.
 static int ar_admit(tt_ar* e, int slot, int S, const float* prefix_emb, int P, hipStream_t stream) {
@@ -503,17 +620,9 @@ static int ar_admit(tt_ar* e, int slot, int S, const float* prefix_emb, int P, h
   TT_REQUIRE(P >= 1 && P + 1 <= e->cfg.max_prefix, "tt_ar_prefill: prefix of %d rows exceeds capacity %d", P + 1, e->cfg.max_prefix);
   TT_REQUIRE(e->s_run[slot] == SESS_FREE, "tt_ar_prefill_group: slot %d holds a session (close it with TT_AR_OPT_SESSION_CLOSE first)", slot);
   return e->sb.run(stream, [&](hipStream_t s) -> int {
-    const int D = e->D, P1 = P + 1;
-    TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-    RowNormArgs a;  // start-token row, as tt_ar_prefill_group
-    memset(&a, 0, sizeof(a));
-    a.x = e->x + (size_t)P * D; a.ldx = D; a.M = 1; a.D = D;
-    a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * D; a.ldxin = D;
-    a.add_bias = e->w.mel_pos;
-    a.write_x = 1; a.mode = NORM_NONE;
-    TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
-    TT_TRY(gpt_trunk_full(e, 1, P1, true, s, slot));
-    TT_TRY(ar_head_norm(e, e->x + (size_t)P * D, e->h, 1, nullptr, e->slabs, 0, 1, s, 0, slot));
+    const int P1 = P + 1;
+    TT_TRY(ar_prefill_trunk(e, prefix_emb, P, slot, s));
+    TT_TRY(ar_head_norm(e, e->x + (size_t)P * e->D, 1, Pending(), 1, s, 0, slot));
     TT_TRY(ar_head_gemm(e, 1, s, 0, e->pre_logits + (size_t)slot * e->Vp));
     TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->codes_own + (size_t)slot * e->tmax), e->cfg.stop_mel_token, (size_t)e->tmax, s));
     TT_TRY(ar_sess_admit_launch(e->sess, S, slot, P1, e->seen, e->unfinished, e->V, e->cfg.start_mel_token, s));
@@ -532,35 +641,19 @@ int tt_ar_prefill_group(tt_ar* e, int group, int n_groups, const float* prefix_e
   TT_REQUIRE(n_groups >= 1 && n_groups <= e->cfg.max_groups && group >= 0 && group < n_groups, "tt_ar_prefill_group: group %d of %d (capacity %d groups)", group, n_groups, e->cfg.max_groups);
   TT_REQUIRE(P >= 1 && P + 1 <= e->cfg.max_prefix, "tt_ar_prefill: prefix of %d rows exceeds capacity %d", P + 1, e->cfg.max_prefix);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
-    const int D = e->D;
     if (n_groups != e->G || group == 0) {  // a new batch starts with its group 0
       e->G = n_groups;
       e->prefilled = 0;
     }
-    const int P1 = P + 1;
-    e->P1g[group] = P1;
+    e->P1g[group] = P + 1;
     e->prefilled |= 1u << group;
     e->P1 = 0;
     for (int gi = 0; gi < n_groups; ++gi)
       if ((e->prefilled >> gi) & 1u) e->P1 = std::max(e->P1, e->P1g[gi]);
-    // per-layer stride of the prefix cache = its capacity (H * max_prefix * 64): group g, layer l at (g * layers + l) strides
-    TT_CHECK_HIP(hipMemcpyAsync(e->x, prefix_emb, (size_t)P * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-    // start-token row: mel_embedding[start] + mel_pos_embedding[0]  (autoregressive.py:137-141)
-    {
-      RowNormArgs a;
-      memset(&a, 0, sizeof(a));
-      a.x = e->x + (size_t)P * D; a.ldx = D; a.M = 1; a.D = D;
-      a.x_in = e->w.mel_emb + (size_t)e->cfg.start_mel_token * D; a.ldxin = D;
-      a.add_bias = e->w.mel_pos;  // row 0
-      a.write_x = 1; a.mode = NORM_NONE;
-      TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
-    }
-    TT_TRY(gpt_trunk_full(e, 1, P1, true, s, group));
-    const int B_saved = e->B;
-    e->B = 1;
-    int rc = ar_head(e, e->x + (size_t)P * D, 1, nullptr, 0, s, group == 0 ? 0 : -2, group);  // logits row `group`
-    e->B = B_saved;
-    TT_TRY(rc);
+    TT_TRY(ar_prefill_trunk(e, prefix_emb, P, group, s));
+    // logits row `group`; group 0's start-token row is latent 0 of the batch
+    TT_TRY(ar_head_norm(e, e->x + (size_t)P * e->D, 1, Pending(), 1, s, group == 0 ? 0 : -2));
+    TT_TRY(ar_head_gemm(e, 1, s, group));
     e->logits_from_prefill = e->prefilled == (n_groups >= 32 ? ~0u : (1u << n_groups) - 1u);
     return 0;
   });
@@ -602,11 +695,9 @@ int tt_ar_decode_step(tt_ar* e, const int* tokens, void* stream) {
   });
 }
 
-// The checks of a generation that depend on the sampling arguments and the handle's state: they run before anything of a running
-// generation is touched, so a rejected call leaves it resumable.
+// The checks of a generation that depend on the sampling arguments and the handle's state
 static int ar_generate_check(const tt_ar* e, int B, bool fresh, const tt_sampling* sp) {
-  TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
-             (double)sp->typical_mass);
+  TT_TRY(ar_check_scalars("tt_ar_generate", -1, *sp, false));
   TT_REQUIRE(e->G <= 1 || (B % e->G == 0 && (B / e->G) % 4 == 0), "tt_ar_generate: %d sequences do not split into %d groups of a multiple of 4", B, e->G);
   TT_REQUIRE(!fresh || e->logits_from_prefill, "tt_ar_generate: the logits buffer does not hold the prefill logits of all %d group(s); call tt_ar_prefill / tt_ar_prefill_group first", e->G);
   return 0;
@@ -618,23 +709,11 @@ static int ar_generate_check(const tt_ar* e, int B, bool fresh, const tt_samplin
 static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes, const tt_sampling* sp, int* codes, int* n_steps_host,
                            int* finished_host, hipStream_t s) {
   SampleArgs sa;
-  memset(&sa, 0, sizeof(sa));
-  sa.B = B; sa.V = e->V; sa.seen = e->seen;
+  ar_sample_args(e, B, &sa);
   sa.rep_penalty = sp->repetition_penalty; sa.temperature = sp->temperature; sa.top_p = sp->top_p; sa.top_k = sp->top_k;
   sa.exp_noise = sp->exp_noise;
-  sa.state = e->state; sa.unfinished = e->unfinished; sa.stop_token = e->cfg.stop_mel_token;
-  sa.codes = e->codes_own; sa.ldcodes = e->tmax; sa.next_tok = e->next_tok; sa.unfinished_count = e->unfinished_count;
-  sa.embed_x = e->x; sa.tok_emb = e->w.mel_emb; sa.pos_emb = e->w.mel_pos; sa.D = e->D; sa.pos_offset = e->cfg.mel_pos_offset;
-  sa.pos_len = e->cfg.mel_pos_len;
-  sa.guard = e->guard.dev;
-  sa.typical_mass = sp->typical_mass; sa.typical_out = e->typ_logits;
+  sa.typical_mass = sp->typical_mass;
   e->typical = sp->typical_mass != 0.f;
-  // the Philox keys and the row offset go through device memory (sa.seed / sa.group_seeds / sa.row_offset stay zero): neither the
-  // seed nor the candidate range of a call is part of the step graph
-  sa.seed = 0;
-  sa.row_offset = 0;
-  sa.keys_dev = e->par_dev->keys;
-  sa.row_offset_dev = &e->par_dev->row_offset;
   for (int gi = 0; gi < 16; ++gi) e->par_host->keys[gi] = sp->seed;
   e->par_host->row_offset = sp->row_offset;
   if (e->G > 1) {
@@ -653,17 +732,15 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
     TT_TRY(ar_begin_launch(e->state, e->seen, e->unfinished, e->unfinished_count, B, e->V, e->tmax + 8, e->cfg.start_mel_token, s));
     TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)codes, e->cfg.stop_mel_token, (size_t)B * ldcodes, s));
     TT_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)e->codes_own, e->cfg.stop_mel_token, (size_t)B * e->tmax, s));
-    // token 0: every row samples from the shared prefill logits
-    sa.logits = e->logits; sa.ldl = 0; sa.ldg = e->Vp;
+    // token 0: every row samples from the shared prefill logits (ldl == 0: one row per group); every later one from its own row
+    sa.ldl = 0;
     e->logits_from_prefill = false;
     TT_TRY(sample_launch(sa, s));
+    sa.ldl = e->Vp;
     TT_TRY(ar_state_advance_launch(e->state, e->unfinished_count, e->progress_dev, s));
     e->gen_done = 1;
   } else {
     prog[0] = e->gen_done;
-  }
-  sa.logits = e->logits; sa.ldl = e->Vp; sa.ldg = e->Vp;  // (ldg is unused with per-row logits; set so that fresh and resumed runs share one step key)
-  if (!fresh) {
     // Resumed chunk (streaming): between two chunks the caller may have run tt_ar_latents / tt_ar_prefill, which use e->x as
     // their residual stream, so the input row the sampler fused into e->x for the next step is gone.  Rebuild it from the
     // device-side state (newest token, its index): mel_embedding[next_tok] + mel_pos_embedding[state[1] + offset].
@@ -671,73 +748,21 @@ static int ar_generate_run(tt_ar* e, int B, bool fresh, int target, int ldcodes,
   }
 
   const bool use_graph = graphs_enabled() && target - e->gen_done > 1;
-  int rc = 0;
-  auto tail_enqueue = [&](hipStream_t st) -> int {
+  // what the captured step bakes in besides device pointers owned by the handle: the sampler's argument block (scalars, the optional
+  // injected-noise pointer) and the batch geometry / range structure the launchers read from the handle
+  int geo[24] = {B, e->G, e->P1, g_prof_on ? 1 : 0};
+  for (int gi = 0; gi < 16; ++gi) geo[4 + gi] = gi < e->G ? e->P1g[gi] : 0;
+  geo[20] = ar_fused_qkv_attn(e) ? 1 : 0;
+  auto step_enqueue = [&](hipStream_t st, int step) -> int {
+    if (step >= 0) e->host_slot = step - 1;  // (eager launches: the profiler's byte estimates follow the step)
+    TT_TRY(decode_step_enqueue(e, st, true));
     TT_TRY(sample_launch(sa, st));
     return ar_state_advance_launch(e->state, e->unfinished_count, e->progress_dev, st);
   };
-  if (use_graph) {
-    // what the captured step bakes in besides device pointers owned by the handle: the sampler's argument block (scalars, the optional
-    // injected-noise pointer) and the batch geometry / range structure the launchers read from the handle
-    std::vector<unsigned char> key(sizeof(sa) + 24 * sizeof(int));
-    memcpy(key.data(), &sa, sizeof(sa));
-    int geo[24] = {B, e->G, e->P1, g_prof_on ? 1 : 0};
-    for (int gi = 0; gi < 16; ++gi) geo[4 + gi] = gi < e->G ? e->P1g[gi] : 0;
-    geo[20] = ar_fused_qkv_attn(e) ? 1 : 0;
-    memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
-    TT_TRY(e->step.ensure(s, key.data(), key.size(), "tt_ar_generate", [&]() -> int {
-      TT_TRY(decode_step_enqueue(e, s, true));
-      return tail_enqueue(s);
-    }));
-  }
-  const int first_step = e->gen_done;
-  int steps_done = e->gen_done;
-  bool stop_seen = false;
-  for (int step = first_step; step < target; ++step) {
-    // stay at most `lookahead` steps ahead of the device; the words are written by the last kernel of every step
-    const auto wait0 = std::chrono::steady_clock::now();
-    while (step - prog[0] >= e->lookahead && prog[1] < 0) {
-      // 200 ms of wall time without the expected progress (not a spin count: a slow first replay - code-object load, a profiler - must
-      // not look like lost progress words): fall back to a queue drain, always correct, only slower - and take the progress from the
-      // DEVICE state the words mirror, so a host that cannot see the mapped words still paces and ends the loop correctly
-      if (std::chrono::steady_clock::now() - wait0 > std::chrono::milliseconds(200)) {
-        int st3[3] = {0, 0, -1};
-        hipError_t ce = hipStreamSynchronize(s);
-        if (ce == hipSuccess) ce = hipMemcpy(st3, e->state, sizeof(st3), hipMemcpyDeviceToHost);
-        if (ce != hipSuccess) { set_error("tt_ar_generate: %s", hipGetErrorString(ce)); rc = -2; break; }
-        prog[0] = st3[0];
-        if (st3[2] >= 0) prog[1] = st3[2];
-        e->drains += 1;
-        break;
-      }
-      usleep(50);
-    }
-    if (rc) break;
-    if (prog[1] >= 0) { stop_seen = true; break; }
-    if (use_graph) {
-      rc = e->step.launch(s, "tt_ar_generate");
-    } else {
-      e->host_slot = step - 1;
-      rc = decode_step_enqueue(e, s, true);
-      if (!rc) rc = tail_enqueue(s);
-    }
-    if (rc) break;
-    steps_done = step + 1;
-  }
-  (void)stop_seen;
-  if (!rc) {
-    // the finished columns go to the caller's buffer; one host-visible completion point per call
-    hipError_t ce = hipMemcpy2DAsync(codes, (size_t)ldcodes * sizeof(int), e->codes_own, (size_t)e->tmax * sizeof(int),
-                                     (size_t)steps_done * sizeof(int), (size_t)B, hipMemcpyDeviceToDevice, s);
-    if (ce != hipSuccess) { set_error("tt_ar_generate: %s", hipGetErrorString(ce)); rc = -2; }
-    if (!rc) rc = e->guard.snapshot(s);
-    if (!rc && (ce = hipStreamSynchronize(s)) != hipSuccess) { set_error("tt_ar_generate: %s", hipGetErrorString(ce)); rc = -2; }
-  }
-  if (rc) {
-    (void)hipStreamSynchronize(s);
-    e->step.drop();  // a failed replay leaves nothing to trust
-  }
-  TT_TRY(rc);
+  int launched = 0;
+  const int rc = ar_run_steps(e, s, use_graph ? &e->step : nullptr, sa, geo, 24, step_enqueue, e->gen_done, target, "tt_ar_generate", &launched);
+  const int steps_done = e->gen_done + launched;
+  TT_TRY(ar_finish(e, s, e->step, rc, codes, ldcodes, steps_done, B, false, "tt_ar_generate"));
   const int first_zero = prog[1];
   const bool finished = first_zero >= 0;
   e->gen_done = finished ? (first_zero + 1 < steps_done ? first_zero + 1 : steps_done) : steps_done;
@@ -766,36 +791,27 @@ static bool same_scalars(const tt_sampling& a, const tt_sampling& b) {
          a.typical_mass == b.typical_mass;
 }
 
-static bool valid_scalars(const tt_sampling& q) {
-  return q.temperature > 0.f && q.top_p > 0.f && q.repetition_penalty > 0.f && (q.typical_mass == 0.f || (q.typical_mass > 0.f && q.typical_mass < 1.f));
-}
-
 // Session handles: every running row advances by up to n_more tokens through the kept step graph of the optional sampler launches its
 // rows need.  A row stops advancing at its stop token; the loop ends early once no row runs.  codes [S][ldcodes]; n_total_host /
 // finished_host [S].  sp: one tt_sampling for every row, or with TT_AR_OPT_SESSION_SAMPLING one per slot (sp[S]).
 static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_sampling* sp, int* codes, int* n_total_host, int* finished_host,
                              hipStream_t stream) {
+  const char* who = "tt_ar_generate_chunk";
   TT_REQUIRE(S == e->cfg.max_batch, "tt_ar_generate_chunk: a session handle advances all %d slots (got %d)", e->cfg.max_batch, S);
   if (!e->sess_sampling) {
     TT_REQUIRE(sp->exp_noise == nullptr, "tt_ar_generate_chunk: injected exp_noise is not available on a session handle");
-    TT_REQUIRE(sp->typical_mass == 0.f || (sp->typical_mass > 0.f && sp->typical_mass < 1.f), "tt_ar_generate: typical_mass %g outside (0, 1) (0 = off)",
-               (double)sp->typical_mass);
-    TT_REQUIRE(sp->temperature > 0.f && sp->top_p > 0.f && sp->repetition_penalty > 0.f, "tt_ar_generate_chunk: bad sampling parameters");
+    TT_TRY(ar_check_scalars(who, -1, *sp, true));
   }
   bool running = false, others = false;
   for (int r = 0; r < S; ++r) {
     if (e->s_run[r] != SESS_RUNNING) continue;
     running = true;
     others = others || !e->s_key_pending[r];
-    const int target = e->s_n[r] + n_more;
-    TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "tt_ar_generate_chunk: slot %d: %d + %d tokens exceed capacity (%d code columns, %d KV slots)", r,
-               e->s_n[r], n_more, ldcodes, e->tmax);
-    TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate_chunk: slot %d: %d tokens exceed the mel position table", r, target);
+    TT_TRY(ar_check_chunk(e, who, r, e->s_n[r], n_more, ldcodes));
     if (e->sess_sampling) {  // (entries of free and finished slots are not read)
       const tt_sampling& q = sp[r];
       TT_REQUIRE(q.exp_noise == nullptr && q.group_seeds == nullptr, "tt_ar_generate_chunk: slot %d: exp_noise and group_seeds are not available with per-session sampling (seed is the key)", r);
-      TT_REQUIRE(valid_scalars(q), "tt_ar_generate_chunk: slot %d: bad sampling parameters (temperature %g, top_p %g, repetition_penalty %g, typical_mass %g)", r,
-                 (double)q.temperature, (double)q.top_p, (double)q.repetition_penalty, (double)q.typical_mass);
+      TT_TRY(ar_check_scalars(who, r, q, true));
       TT_REQUIRE(e->s_key_pending[r] || (same_scalars(q, e->s_rows[r]) && q.seed == e->s_rows[r].seed),
                  "tt_ar_generate_chunk: slot %d: sampling settings differ from those its session started with", r);
     }
@@ -825,19 +841,9 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
       }
       e->par_host->row_offset = 0;
       SampleArgs sa;
-      memset(&sa, 0, sizeof(sa));
-      sa.B = S; sa.V = e->V; sa.seen = e->seen;
+      ar_sample_args(e, S, &sa);
       sa.rows = e->par_dev->rows; sa.row_launch = launch;  // (the five scalars of the argument block stay zero: every row reads its own)
-      sa.state = e->state; sa.unfinished = e->unfinished; sa.stop_token = e->cfg.stop_mel_token;
-      sa.codes = e->codes_own; sa.ldcodes = e->tmax; sa.next_tok = e->next_tok; sa.unfinished_count = e->unfinished_count;
-      sa.embed_x = e->x; sa.tok_emb = e->w.mel_emb; sa.pos_emb = e->w.mel_pos; sa.D = e->D; sa.pos_offset = e->cfg.mel_pos_offset;
-      sa.pos_len = e->cfg.mel_pos_len;
-      sa.guard = e->guard.dev;
-      sa.typical_out = e->typ_logits;
-      sa.keys_dev = e->par_dev->keys;
-      sa.row_offset_dev = &e->par_dev->row_offset;
       sa.sess = e->sess; sa.pre_logits = e->pre_logits;
-      sa.logits = e->logits; sa.ldl = e->Vp; sa.ldg = e->Vp;
       e->typical = (launch & SAMPLE_ROWS_TYPICAL) != 0;
       e->sess_launch = launch;
       TT_CHECK_HIP(hipMemcpyAsync(e->par_dev, e->par_host, sizeof(ArParams), hipMemcpyHostToDevice, s));
@@ -850,57 +856,18 @@ static int ar_sessions_chunk(tt_ar* e, int S, int n_more, int ldcodes, const tt_
       volatile int* prog = e->progress_host;
       prog[0] = 0;
       prog[1] = -1;
-      auto step_enqueue = [&](hipStream_t st) -> int {
-        TT_TRY(decode_layers_enqueue(e, st));
-        TT_TRY(ar_head_gemm(e, S, st));
+      auto step_enqueue = [&](hipStream_t st, int) -> int {
+        TT_TRY(decode_step_enqueue(e, st, true));
         TT_TRY(sample_launch(sa, st));
         return ar_sess_advance_launch(e->state, e->sess, S, e->unfinished, e->unfinished_count, e->progress_dev, st);
       };
       KeptGraph& graph = launch ? e->sess_steps[launch - 1] : e->step;
-      const bool use_graph = graphs_enabled();
-      if (use_graph) {
-        // baked in: the sampler's argument block (pointers and the combination of optional launches) and the profiler switch - no
-        // batch, prefix length, step or sampling scalar of any row
-        std::vector<unsigned char> key(sizeof(sa) + 4 * sizeof(int));
-        memcpy(key.data(), &sa, sizeof(sa));
-        int geo[4] = {S, -1, e->cfg.max_prefix, g_prof_on ? 1 : 0};
-        memcpy(key.data() + sizeof(sa), geo, sizeof(geo));
-        TT_TRY(graph.ensure(s, key.data(), key.size(), "tt_ar_generate_chunk", [&]() -> int { return step_enqueue(s); }));
-      }
-      int rc = 0;
-      for (int step = 0; step < n_more; ++step) {
-        const auto wait0 = std::chrono::steady_clock::now();
-        while (step - prog[0] >= e->lookahead && prog[1] < 0) {
-          if (std::chrono::steady_clock::now() - wait0 > std::chrono::milliseconds(200)) {  // (as ar_generate_run)
-            int st3[3] = {0, 0, -1};
-            hipError_t ce = hipStreamSynchronize(s);
-            if (ce == hipSuccess) ce = hipMemcpy(st3, e->state, sizeof(st3), hipMemcpyDeviceToHost);
-            if (ce != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; break; }
-            prog[0] = st3[0];
-            if (st3[2] >= 0) prog[1] = st3[2];
-            e->drains += 1;
-            break;
-          }
-          usleep(50);
-        }
-        if (rc || prog[1] >= 0) break;
-        rc = use_graph ? graph.launch(s, "tt_ar_generate_chunk") : step_enqueue(s);
-        if (rc) break;
-      }
-      if (!rc) {
-        const int cols = std::min(ldcodes, e->tmax);
-        hipError_t ce = hipMemcpy2DAsync(codes, (size_t)ldcodes * sizeof(int), e->codes_own, (size_t)e->tmax * sizeof(int), (size_t)cols * sizeof(int),
-                                         (size_t)S, hipMemcpyDeviceToDevice, s);
-        if (ce == hipSuccess) ce = hipMemcpyAsync(e->sess_host, e->sess, (size_t)4 * S * sizeof(int), hipMemcpyDeviceToHost, s);
-        if (ce != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; }
-        if (!rc) rc = e->guard.snapshot(s);
-        if (!rc && (ce = hipStreamSynchronize(s)) != hipSuccess) { set_error("tt_ar_generate_chunk: %s", hipGetErrorString(ce)); rc = -2; }
-      }
-      if (rc) {
-        (void)hipStreamSynchronize(s);
-        graph.drop();
-        return rc;
-      }
+      // baked in: the sampler's argument block (pointers and the combination of optional launches) and the profiler switch - no
+      // batch, prefix length, step or sampling scalar of any row
+      const int geo[4] = {S, -1, e->cfg.max_prefix, g_prof_on ? 1 : 0};
+      int launched = 0;
+      const int rc = ar_run_steps(e, s, graphs_enabled() ? &graph : nullptr, sa, geo, 4, step_enqueue, 0, n_more, who, &launched);
+      TT_TRY(ar_finish(e, s, graph, rc, codes, ldcodes, std::min(ldcodes, e->tmax), S, true, who));
       for (int r = 0; r < S; ++r) {
         if (e->s_run[r] == SESS_RUNNING) e->s_key_pending[r] = false;
         e->s_n[r] = e->sess_host[SESS_N * S + r];
@@ -923,9 +890,7 @@ int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, co
   TT_REQUIRE(e->P1 > 0, "tt_ar_generate_chunk: call tt_ar_prefill first");
   TT_REQUIRE(first || (e->gen_done >= 1 && e->B == B), "tt_ar_generate_chunk: no generation of %d rows to resume", B);
   const int done = first ? 0 : e->gen_done;
-  const int target = done + n_more;
-  TT_REQUIRE(n_more >= 1 && target <= ldcodes && target <= e->tmax, "tt_ar_generate_chunk: %d + %d tokens exceed capacity (%d code columns, %d KV slots)", done, n_more, ldcodes, e->tmax);
-  TT_REQUIRE(target - 2 + e->cfg.mel_pos_offset < e->cfg.mel_pos_len, "tt_ar_generate_chunk: %d tokens exceed the mel position table", target);
+  TT_TRY(ar_check_chunk(e, "tt_ar_generate_chunk", -1, done, n_more, ldcodes));
   const bool stopped = !first && e->gen_finished;  // every row already stopped
   if (!stopped) TT_TRY(ar_generate_check(e, B, first != 0, sp));
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
@@ -934,7 +899,7 @@ int tt_ar_generate_chunk(tt_ar* e, int B, int first, int n_more, int ldcodes, co
       *finished_host = 1;
       return 0;
     }
-    return ar_generate_run(e, B, first != 0, target, ldcodes, sp, codes, n_total_host, finished_host, s);
+    return ar_generate_run(e, B, first != 0, done + n_more, ldcodes, sp, codes, n_total_host, finished_host, s);
   });
 }
 
@@ -975,13 +940,9 @@ int tt_ar_latents(tt_ar* e, const float* emb, int k, int n, float* out, void* st
     const int D = e->D, M = k * n;
     TT_CHECK_HIP(hipMemcpyAsync(e->x, emb, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     TT_TRY(gpt_trunk_full(e, k, n, false, s));
-    RowNormArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER;
-    a.g1 = e->w.lnf_g; a.b1 = e->w.lnf_b; a.eps1 = 1e-5f;
-    a.g2 = e->w.final_norm_g; a.b2 = e->w.final_norm_b; a.eps2 = 1e-5f;
+    RowNormArgs a = ar_norm_args(e, e->x, nullptr, M, ar_head_ln(e));  // the latents are the f32 rows alone
     a.out_f32 = out; a.ldo32 = D;
-    a.guard = e->guard.dev;
+    a.row_blocks = 0;  // (a teacher-forced pass of >= 1024 rows takes the wave-per-row kernel)
     TT_TRY(rownorm_launch(e->cfg.dtype, a, s));
     return e->guard.snapshot(s);
   });
