@@ -254,6 +254,17 @@ int tt_op_f0_track(void* h, int n_clips, const float* audio, const int* in_off, 
                    float* f0, float* aper, int* n_voiced, int* status, double* dprime, void* stream);
 int tt_op_f0_group(void);
 
+/* Viterbi F0 path staged (csrc/f0_viterbi.hip, include/tortoise_mi355x_f0v.h; `h` is a tt_f0v handle).  The candidate tables of a batch are
+ * c_lag i32, c_dp f64 and c_f0 f32 [frm_off[n_clips]][8], sliced by frm_off like lag: slots 0 .. 6 the candidates by ascending lag (lag 0 =
+ * absent), slot 7 tt_f0_track's own pick.  tt_op_f0v_candidates runs the first launch alone and gives the tables back (no costs: a clip's
+ * status is tt_f0_track's).  tt_op_f0v_path runs the second launch alone on tables the caller gives: frames i32 [n_clips] is F of every
+ * clip (0: EMPTY; more than the handle's, a short frame slice, bad lags or costs: REFUSED), par's lag_lo prices the octave cost. */
+int tt_op_f0v_candidates(void* h, int n_clips, const float* audio, const int* in_off, const int* par, const double* thr, const int* frm_off,
+                         int* c_lag, double* c_dp, float* c_f0, int* status, void* stream);
+int tt_op_f0v_path(void* h, int n_clips, const int* frames, const int* par, const double* cost, const int* frm_off, const int* c_lag,
+                   const double* c_dp, const float* c_f0, int* lag, float* f0, float* aper, int* state, int* n_voiced, double* path_cost,
+                   int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

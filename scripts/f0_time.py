@@ -1,9 +1,11 @@
-"""What the F0 tracker (csrc/f0.hip) costs on a rendered clip, and how far it is from its floors.  A record, not a gate.
+"""What the F0 tracker (csrc/f0.hip) and its Viterbi path (csrc/f0_viterbi.hip) cost on a rendered clip, and how far tt_f0_track is from
+its floors.  A record, not a gate.
 
     python scripts/f0_time.py [--out profiles/rNN_f0.txt]      (default: the next free round prefix)
 
-ONE process: tt_f0_track on 1 and 16 clips of 9.28 s (222,720 samples at 24 kHz, the time-stretch family's speech-like audio with its own
-pitch contours) and, for scale, tt_sil_find and tt_tsm_stretch (rate 0.75) of the same samples.  The six calls are INTERLEAVED: every
+ONE process: tt_f0_track, tt_f0v_track (the Viterbi path: both launches) and each of its launches alone (tt_op_f0v_candidates,
+tt_op_f0v_path) on 1 and 16 clips of 9.28 s (222,720 samples at 24 kHz, the time-stretch family's speech-like audio with its own
+pitch contours) and, for scale, tt_sil_find and tt_tsm_stretch (rate 0.75) of the same samples.  The calls are INTERLEAVED: every
 repeat runs each of them once, in turn, with device events around the call alone, inputs resident on the device and a FRESH input buffer
 for every repeat; median and spread of 25 repeats after 3 warm-up rounds on buffers of their own.
 
@@ -57,6 +59,45 @@ def f0_call(st, n, base):
     return call, status, nv
 
 
+def f0v_call(which):
+    """The Viterbi path's rows (csrc/f0_viterbi.hip) on the same samples and parameters: "track" the whole call tt_f0v_track, "candidates" the
+    first launch alone (tt_op_f0v_candidates: f0_track_kernel's geometry and steps, beside tt_f0_track's launch), "path" the second launch
+    alone (tt_op_f0v_path on the tables the first launch made of these samples: a chain of F frames, one wave a clip)."""
+    def make(st, n, base):
+        import numpy as np
+        import torch
+        from tortoise_tts_amd import engine as E
+        from tortoise_tts_amd import pitch
+        F = pitch.frames(SAMPLES)
+        p, k = pitch.params(), pitch.smooth_params(True)
+        audio = torch.from_numpy(np.concatenate([np.roll(base, 997 * i) for i in range(n)])).cuda()
+        io, fo = (torch.arange(n + 1, dtype=torch.int32).cuda() * v for v in (SAMPLES, F))
+        par = torch.tensor([[p.lag_lo, p.lag_hi]] * n, dtype=torch.int32).cuda()
+        thr = torch.tensor([[p.thr, p.floor_e]] * n, dtype=torch.float64).cuda()
+        cost = torch.tensor([list(k)] * n, dtype=torch.float64).cuda()
+        frames = torch.full((n,), F, dtype=torch.int32).cuda()
+        lag, f0, aper, state = torch.zeros(n * F, dtype=torch.int32).cuda(), torch.zeros(n * F).cuda(), torch.zeros(n * F).cuda(), torch.zeros(n * F, dtype=torch.int32).cuda()
+        c_lag, c_dp, c_f0 = torch.zeros(8 * n * F, dtype=torch.int32).cuda(), torch.zeros(8 * n * F, dtype=torch.float64).cuda(), torch.zeros(8 * n * F).cuda()
+        nv, pc, status = torch.zeros(n, dtype=torch.int32).cuda(), torch.zeros(n, dtype=torch.float64).cuda(), torch.full((n,), -1, dtype=torch.int32).cuda()
+        keep = (audio, io, fo, par, thr, cost, frames, lag, f0, aper, state, c_lag, c_dp, c_f0, nv, pc)  # (alive as long as the call is)
+
+        def candidates():
+            E.check(st.lib.tt_op_f0v_candidates(st.h, n, E.ptr(audio), E.ptr(io), E.ptr(par), E.ptr(thr), E.ptr(fo), E.ptr(c_lag), E.ptr(c_dp), E.ptr(c_f0),
+                                                E.ptr(status), E.stream_ptr()))
+
+        def path(keep=keep):
+            E.check(st.lib.tt_op_f0v_path(st.h, n, E.ptr(frames), E.ptr(par), E.ptr(cost), E.ptr(fo), E.ptr(c_lag), E.ptr(c_dp), E.ptr(c_f0), E.ptr(lag),
+                                          E.ptr(f0), E.ptr(aper), E.ptr(state), E.ptr(nv), E.ptr(pc), E.ptr(status), E.stream_ptr()))
+
+        def track(keep=keep):
+            E.check(st.lib.tt_f0v_track(st.h, n, E.ptr(audio), E.ptr(io), E.ptr(par), E.ptr(thr), E.ptr(cost), E.ptr(fo), E.ptr(lag), E.ptr(f0), E.ptr(aper),
+                                        E.ptr(state), E.ptr(nv), E.ptr(pc), E.ptr(status), E.stream_ptr()))
+        if which == "path":
+            candidates()  # (the tables the path launch reads, made before the events)
+        return {"track": track, "candidates": candidates, "path": path}[which], status, None
+    return make
+
+
 def sil_call(st, n, base):
     import numpy as np
     import torch
@@ -102,6 +143,9 @@ def child():
     from tortoise_tts_amd import stages
     makers = (("tt_f0_track", stages.F0Stage(SAMPLES, max_clips=16), f0_call), ("tt_sil_find", stages.SilenceStage(SAMPLES, max_clips=16), sil_call),
               ("tt_tsm_stretch_0.75", stages.TimeStretchStage(SAMPLES, max_clips=16), tsm_call))
+    if hasattr(makers[0][1].lib, "tt_f0v_track"):  # (a library from before the Viterbi path - the parent's, for tt_f0_track's own figure - has none)
+        makers += tuple((name, stages.F0ViterbiStage(SAMPLES, max_clips=16), f0v_call(which)) for name, which in (
+            ("tt_f0v_track", "track"), ("tt_op_f0v_candidates", "candidates"), ("tt_op_f0v_path", "path")))
     bases = [long_clip(s) for s in range(4)]
     ms = {(name, n): [] for name, _, _ in makers for n in CLIPS}
     voiced = None
@@ -134,6 +178,12 @@ def child():
         res["floors_tt_f0_track_x%d" % n] = ("%d frames in %d workgroups of %d a clip, %.3e terms (%.3f x the F + 3 slots a clip needs; frame by frame is 4 F); f32 VALU floor %.4f ms, "
                                              "LDS floor %.4f ms; the call is %.1f x its VALU floor, %.1f x its LDS floor" % (
                                                  F, groups, GROUP, terms, slots / (F + 3.0), valu, lds, med / valu, med / lds))
+    for n in CLIPS:
+        if ("tt_f0v_track", n) in ms:  # the path launch is a chain of F frames, one wave a clip: what the call adds over tt_f0_track, a frame
+            extra = statistics.median(ms[("tt_f0v_track", n)]) - statistics.median(ms[("tt_f0_track", n)])
+            res["chain_tt_f0v_track_x%d" % n] = "%d frames a clip: the call is %.4f ms over tt_f0_track's, %.3f us a frame of the chain" % (F, extra, 1e3 * extra / F)
+            med = statistics.median(ms[("tt_op_f0v_path", n)])
+            res["chain_tt_op_f0v_path_x%d" % n] = "the path launch alone: %.3f us a frame, %.2f frames a us" % (1e3 * med / F, F / (1e3 * med))
     res["clip"] = "%d of %d frames voiced in the first clip of the last repeat (defaults: 60 .. 500 Hz, threshold 0.15, floor -50 dB)" % (voiced, F)
     for _, st, _ in makers:
         st.close()
@@ -163,7 +213,7 @@ def main():
     log("# F0 tracker (tt_f0_track) on clips of %d samples (%.2f s at 24 kHz): workgroups of 256 threads, 4 lags a thread; with "
         "tt_sil_find and tt_tsm_stretch of the same samples for scale%s" % (
             SAMPLES, SAMPLES / 24000, "; library " + os.path.basename(os.environ["TORTOISE_MI355X_LIB"]) if os.environ.get("TORTOISE_MI355X_LIB") else ""))
-    log("## one process, the six calls interleaved, device events around each call, a fresh input buffer per repeat: <call>_x<clips per call>")
+    log("## one process, the calls interleaved, device events around each call, a fresh input buffer per repeat: <call>_x<clips per call>")
     cmd = ["timeout", "-k", "10", str(LIMIT), sys.executable, os.path.abspath(__file__), "--child"]
     log("$ timeout -k 10 %d python scripts/f0_time.py --child" % LIMIT)
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)

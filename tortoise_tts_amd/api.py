@@ -476,6 +476,8 @@ class _Common:
         word_rates, word_pitches = tsm.word_rates(tts_kwargs), rs.word_pitches(tts_kwargs)
         if tts_kwargs.get("pitch_hz") is not None:  # (refused before anything renders; the inner tts() call measures and shifts)
             f0m.options(dict(pitch_hz=tts_kwargs["pitch_hz"], word_pitches=word_pitches), tts_kwargs.get("pitch") or None, "tts_with_timings")
+        if "f0_smooth" in tts_kwargs:  # (validated, and refused without pitch_hz, before anything renders)
+            f0m.smooth_option(dict(f0_smooth=tts_kwargs["f0_smooth"]), tts_kwargs.get("pitch_hz"), "tts_with_timings")
         if word_pitches is not None:
             res = self._tts_at_word_pitches(text, word_rates, word_pitches, tts_kwargs)
         else:
@@ -870,7 +872,7 @@ class _Common:
 
     @torch.no_grad()
     def shift_pitch_many(self, audios, semitones=None, return_info=False, formants=None, formant_lifter_ms=None, formant_max_gain_db=None,
-                         pitch_maps=None, return_map=False, to_hz=None):
+                         pitch_maps=None, return_map=False, to_hz=None, f0_smooth=None):
         """The same speech at another pitch and the same duration: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device), semitones
         (+: up; one value or one per clip, each within +-12) -> the shifted clips.  Two batched device calls: a time-stretch at rate
         65536^2 / pq (rounded; pq = round(2^(s/12) 65536)), then a resampling by (pq, 65536), which undoes the stretch's change of duration
@@ -891,15 +893,18 @@ class _Common:
         f0_many call measures the clips (csrc/f0.hip), and every clip is shifted by 12 log2(H / its median F0) through the calls above, a
         ratio per clip; formants='keep' stays allowed.  A shift beyond +-12 semitones is clamped and a clip with fewer than 10 voiced
         frames is returned bit for bit, each with a warning.  return_info=True then gives, per clip, a dict measured_hz (None: no
-        median), semitones, clamped and peak; the readings are also left in self.pitch_info."""
+        median), semitones, clamped and peak; the readings are also left in self.pitch_info.
+        f0_smooth= (True, or a dict of costs: pitch.smooth_params) with to_hz: that one f0_many call runs smoothed (f0_many's smooth=), so
+        a run of frames read an octave off does not move the median; without to_hz it is refused."""
         audios = self._clips(audios, "shift_pitch")
         if (semitones is None) + (pitch_maps is None) + (to_hz is None) != 2:
             raise ValueError("shift_pitch: give exactly one of semitones and pitch_map, or to_hz")
+        smooth = f0m.smooth_option(dict(f0_smooth=f0_smooth), to_hz, "shift_pitch")
         if to_hz is not None:
             if return_map:
                 raise ValueError("shift_pitch: return_map=True goes with pitch_map")
             fmt.mode(formants)
-            semis, info = self._shifts_to(audios, to_hz, "shift_pitch")
+            semis, info = self._shifts_to(audios, to_hz, "shift_pitch", smooth)
             out, peaks = self.shift_pitch_many(audios, semis, True, formants, formant_lifter_ms, formant_max_gain_db) if audios else ([], [])
             for d, pk in zip(info, peaks):
                 d["peak"] = pk
@@ -1007,36 +1012,63 @@ class _Common:
         """The F0 stage (stages.F0Stage), built on first use for clips of 30 s and rebuilt for a longer one."""
         return self._clip_stage("f0_stage", "F0Stage", max_samples, E.F0_MAX_SAMPLES, "F0 tracker", ORIG_ALIGNER_SECONDS * f0m.SAMPLE_RATE)
 
+    f0_path_stage = None
+
+    def load_f0_path(self, max_samples=0):
+        """The Viterbi F0 stage (stages.F0ViterbiStage), built on first use for clips of 30 s and rebuilt for a longer one."""
+        return self._clip_stage("f0_path_stage", "F0ViterbiStage", max_samples, E.F0_MAX_SAMPLES, "F0 tracker", ORIG_ALIGNER_SECONDS * f0m.SAMPLE_RATE)
+
     @torch.no_grad()
     def f0_many(self, audios, fmin=f0m.DEFAULTS["fmin"], fmax=f0m.DEFAULTS["fmax"], threshold=f0m.DEFAULTS["threshold"],
-                floor_db=f0m.DEFAULTS["floor_db"]):
+                floor_db=f0m.DEFAULTS["floor_db"], smooth=None):
         """The fundamental frequency of every clip: audios f32 [n] / [1, n] / [1, 1, n] at 24 kHz (any device) -> [pitch.F0Track], a frame
         every 10 ms (hz 0 where unvoiced, aperiodicity, voiced, times(), median_hz(), semitones(ref), range_semitones(), at(seconds),
         for_words(alignment)).  YIN (de Cheveigne & Kawahara 2002) over a 40 ms window: the first dip of the normalised difference
         below `threshold` among the periods of fmin .. fmax Hz (within 50 .. 1000), refined by a parabola; a frame without such a dip, or
         with its power below floor_db dBFS, is unvoiced.  No smoothing over frames: an octave jump in one frame stays in the track (the
         median does not see it).  All clips go through ONE device call per 16 (csrc/f0.hip).  The defaults were chosen from the paper
-        and the code: nobody has tuned them on a trained checkpoint's audio."""
+        and the code: nobody has tuned them on a trained checkpoint's audio.
+        smooth= (one value or one per clip; None / False: off, the call and the bits above): True or a dict of costs (octave_cost,
+        jump_cost, voicing_cost, unvoiced_cost; pitch.smooth_params) keeps up to seven dips of every frame as candidates and chooses among
+        them, and "unvoiced", with a Viterbi path over the whole clip (csrc/f0_viterbi.hip), so a run of frames read an octave high or low
+        is pulled back by its neighbours.  The tracks are then `.smoothed`, with `.state` and `.path_cost`; `.octave_jumps()` counts what
+        is left on either kind of track.  Clips with smooth off and clips with it on take one call each.  The default costs were chosen
+        from the arithmetic: nobody has tuned them on a trained checkpoint's audio either."""
         audios = self._clips(audios, "f0")
         p = f0m.params(fmin, fmax, threshold, floor_db)
+        costs = [smooth] * len(audios) if isinstance(smooth, f0m.Costs) else self._per_clip(smooth, len(audios))  # (a Costs is a tuple, and ONE setting)
+        if len(costs) != len(audios):
+            raise ValueError(f"f0: {len(audios)} clips with {len(costs)} smooth settings")
+        costs = [f0m.smooth_params(c) for c in costs]
         if not audios:
             return []
-        res = self.load_f0(max(a.shape[-1] for a in audios)).track_many([a.reshape(-1) for a in audios], [p] * len(audios))
+        seq = [a.reshape(-1) for a in audios]
+        plain, path = [i for i, c in enumerate(costs) if c is None], [i for i, c in enumerate(costs) if c is not None]
+        res = [None] * len(seq)
+        if plain:
+            sub = [seq[i] for i in plain]
+            for i, r in zip(plain, self.load_f0(max(x.shape[0] for x in sub)).track_many(sub, [p] * len(sub))):
+                res[i] = r
+        if path:
+            sub = [seq[i] for i in path]
+            for i, r in zip(path, self.load_f0_path(max(x.shape[0] for x in sub)).track_many(sub, [p] * len(sub), [costs[i] for i in path])):
+                res[i] = r
         return [f0m.track_of(r, a.shape[-1]) for r, a in zip(res, audios)]
 
     def f0(self, audio, **options):
         """f0_many of one clip -> pitch.F0Track."""
         return self.f0_many([audio], **options)[0]
 
-    def _shifts_to(self, audios, to_hz, who):
+    def _shifts_to(self, audios, to_hz, who, smooth=None):
         """audios (validated) and the pitch to land on (Hz: one value or one per clip) -> (semitones per clip, [dict(measured_hz, semitones,
-        clamped)]): ONE f0_many call, then pitch.shift_to per clip.  The readings are left in self.pitch_info."""
+        clamped)]): ONE f0_many call (smoothed with `smooth`, a pitch.Costs), then pitch.shift_to per clip.  The readings are left in
+        self.pitch_info."""
         hzs = self._per_clip(to_hz, len(audios))
         if len(hzs) != len(audios):
             raise ValueError(f"{who}: {len(audios)} clips with {len(hzs)} target pitches")
         hzs = [f0m.target_hz("to_hz" if who == "shift_pitch" else "pitch_hz", h) for h in hzs]
         t0 = time.perf_counter()
-        tracks = self.f0_many(audios)
+        tracks = self.f0_many(audios, smooth=smooth)
         semis, info = [], []
         for i, (tr, h) in enumerate(zip(tracks, hzs)):
             med = tr.median_hz()
@@ -1047,11 +1079,11 @@ class _Common:
         self._f0_s = time.perf_counter() - t0
         return semis, info
 
-    def _pitch_hz_plan(self, clips, hz, formant_kw, who="tts"):
+    def _pitch_hz_plan(self, clips, hz, formant_kw, who="tts", smooth=None):
         """pitch_hz= of a tts call: the clips it is about to return ({winner: clip} or a list), measured in ONE device call -> (semitones
         per clip in the clips' order, formant.Params or None per clip: formants='keep' takes every clip's own shift back)."""
         seq = [clips[i] for i in sorted(clips)] if isinstance(clips, dict) else clips
-        semis, _ = self._shifts_to(self._clips(seq, who), hz, who)
+        semis, _ = self._shifts_to(self._clips(seq, who), hz, who, smooth)
         self._note(f0_s=self._f0_s)
         kw = dict(formant_kw or {})
         keep = fmt.mode(kw.get("formants"))
@@ -1570,7 +1602,7 @@ class TextToSpeech(_Common):
         # (every rank works on the clips it holds) the chain: redaction -> speaking rate and pitch -> formants -> pauses -> level -> output sample rate
         pitch, formants = o.pitch, o.formants
         if o.pitch_hz is not None:  # measured after redaction, ONE device call for all clips: a shift per clip
-            pitch, formants = self._pitch_hz_plan(wavs, o.pitch_hz, o.formant_kw)
+            pitch, formants = self._pitch_hz_plan(wavs, o.pitch_hz, o.formant_kw, smooth=o.f0_smooth)
         wavs = self._voiced(wavs, o.speaking_rate, pitch, o.level, o.sample_rate, o.pauses, formants)
         # Rendered winners go to rank 0 only (the reference returns the audio to ONE caller); other ranks get None entries.
         if self.world > 1:
@@ -1596,11 +1628,12 @@ class TextToSpeech(_Common):
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
         pitch_hz, formant_kw = f0m.options(kwargs, pitch, "tts_many"), f0m.formant_keywords(kwargs)
+        f0_smooth = f0m.smooth_option(kwargs, pitch_hz, "tts_many")
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples=voice_samples, conditioning_latents=conditioning_latents,
                              use_deterministic_seed=use_deterministic_seed, verbose=verbose, **kwargs)
         if pitch_hz is not None:  # pitch_hz= (Hz): every clip's median F0 measured in ONE call, then a shift per clip through the same chain
-            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many")
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many", f0_smooth)
         return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()
@@ -1691,6 +1724,7 @@ class TextToSpeech(_Common):
         speaking_rate, level = tsm.speaking_rate(hf), loud.level_options(hf)
         pitch, sample_rate = rs.options(hf, speaking_rate)
         pitch_hz, formant_kw = f0m.options(hf, pitch), f0m.formant_keywords(hf)
+        f0_smooth = f0m.smooth_option(hf, pitch_hz)
         pauses, formants = sil.options(hf), fmt.options(hf, pitch)
         plan = fastsolver.sampler_options(hf, args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"])
         top_k, typical_mass = sampler_kwargs(hf)
@@ -1703,7 +1737,7 @@ class TextToSpeech(_Common):
             sched=Schedule(args["diffusion_iterations"], self.diff_cfg.trained_steps, args["cond_free"], args["cond_free_k"]),
             solver=plan,  # None: the reference's p sampler over `sched`; a solver.SolverPlan: that solver instead (no step noise)
             diffusion_temperature=args["diffusion_temperature"], speaking_rate=speaking_rate, level=level, pitch=pitch, sample_rate=sample_rate, pauses=pauses, formants=formants,
-            pitch_hz=pitch_hz, formant_kw=formant_kw)
+            pitch_hz=pitch_hz, formant_kw=formant_kw, f0_smooth=f0_smooth)
 
     def _voice(self, voice_samples, conditioning_latents, mels=False):
         """api.py:393-399 -> (auto_latent, diffusion_latent) f32 on the device, and for mels=True the voice clips' mels (what CVVP compares

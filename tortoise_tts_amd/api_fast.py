@@ -200,6 +200,7 @@ class TextToSpeech(_Common):
         speaking_rate, level = tsm.speaking_rate(hf_generate_kwargs), loud.level_options(hf_generate_kwargs)
         pitch, sample_rate = rs.options(hf_generate_kwargs, speaking_rate)
         pitch_hz, formant_kw = f0m.options(hf_generate_kwargs, pitch), f0m.formant_keywords(hf_generate_kwargs)
+        f0_smooth = f0m.smooth_option(hf_generate_kwargs, pitch_hz)
         pauses, formants = sil.options(hf_generate_kwargs), fmt.options(hf_generate_kwargs, pitch)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
@@ -212,7 +213,7 @@ class TextToSpeech(_Common):
         wav = self.hifi_decoder.inference(latents, cond)             # api_fast.py:517
         out = [wav.cpu()]
         if pitch_hz is not None:  # pitch_hz= (Hz): the clip's median F0 measured, then the shift that lands on it
-            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw)
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, smooth=f0_smooth)
         return self._voiced(out, speaking_rate, pitch, level, sample_rate, pauses, formants)[0]  # (rate and pitch -> formants -> pauses -> level -> sample rate)
 
     def tts_many(self, texts, voice_samples=None, conditioning_latents=None, use_deterministic_seed=None, **kwargs):
@@ -231,10 +232,11 @@ class TextToSpeech(_Common):
         rate, level = tsm.speaking_rate(kwargs), loud.level_options(kwargs)
         pitch, sample_rate = rs.options(kwargs, rate)
         pitch_hz, formant_kw = f0m.options(kwargs, pitch, "tts_many"), f0m.formant_keywords(kwargs)
+        f0_smooth = f0m.smooth_option(kwargs, pitch_hz, "tts_many")
         pauses, formants = sil.options(kwargs), fmt.options(kwargs, pitch)
         out = self._tts_many(texts, voice_samples, conditioning_latents, use_deterministic_seed, **kwargs)
         if pitch_hz is not None:  # pitch_hz= (Hz): every clip's median F0 measured in ONE call, then a shift per clip
-            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many")
+            pitch, formants = self._pitch_hz_plan(out, pitch_hz, formant_kw, "tts_many", f0_smooth)
         return self._voiced(out, rate, pitch, level, sample_rate, pauses, formants)
 
     @torch.no_grad()

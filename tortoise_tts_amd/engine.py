@@ -527,6 +527,15 @@ F0_HOP, F0_WINDOW, F0_LEAD, F0_LAG_MIN, F0_LAG_MAX = 240, 960, 720, 24, 480  # T
 F0_SAMPLE_RATE = 24000
 F0_MAX_SAMPLES, F0_MAX_CLIPS = 8388608, 64
 F0_OK, F0_EMPTY, F0_REFUSED = 0, 1, 2
+# include/tortoise_mi355x_f0v.h: the Viterbi path over YIN candidates (its own header and version, same library)
+_F0V_PROTOS = {
+    "tt_f0v_abi_version": (_i, []),
+    "tt_f0v_create": (_i, [_i, _i, C.POINTER(C.c_double), C.POINTER(vp)]),
+    "tt_f0v_destroy": (None, [vp]),
+    "tt_f0v_track": (_i, [vp, _i] + [vp] * 14),
+}
+F0V_ABI_VERSION = 1
+F0V_STATES, F0V_UNVOICED, F0V_TABLE = 8, 7, 481  # TT_F0V_STATES, TT_F0V_UNVOICED, TT_F0V_TABLE
 # include/tortoise_mi355x_fmt.h: formant-preserving pitch, the cepstral envelope correction (its own header and version, same library)
 _FMT_PROTOS = {
     "tt_fmt_abi_version": (_i, []),
@@ -604,6 +613,8 @@ _TEST_PROTOS = {
     "tt_op_fmt_synth": (_i, [vp, vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
     "tt_op_f0_track": (_i, [vp, _i] + [vp] * 12),
     "tt_op_f0_group": (_i, []),
+    "tt_op_f0v_candidates": (_i, [vp, _i] + [vp] * 10),
+    "tt_op_f0v_path": (_i, [vp, _i] + [vp] * 15),
 }
 
 _lib = None
@@ -623,7 +634,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_F0V_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -677,6 +688,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_sil.h is version %d in the library, %d in Python" % (lib.tt_sil_abi_version(), SIL_ABI_VERSION))
     if lib.tt_f0_abi_version() != F0_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_f0.h is version %d in the library, %d in Python" % (lib.tt_f0_abi_version(), F0_ABI_VERSION))
+    if lib.tt_f0v_abi_version() != F0V_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_f0v.h is version %d in the library, %d in Python" % (lib.tt_f0v_abi_version(), F0V_ABI_VERSION))
     if lib.tt_solver_abi_version() != SOLVER_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_solver.h is version %d in the library, %d in Python" % (lib.tt_solver_abi_version(), SOLVER_ABI_VERSION))
     for st, want in ((GemmDesc, lib.tt_op_gemm_desc_size()), (RowNormDesc, lib.tt_op_rownorm_desc_size()), (GroupNormDesc, lib.tt_op_groupnorm_desc_size())):

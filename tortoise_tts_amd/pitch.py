@@ -1,5 +1,7 @@
-"""Host side of the F0 tracker (include/tortoise_mi355x_f0.h, csrc/f0.hip, stages.F0Stage): the options of f0() / shift_pitch(to_hz=) /
-tts(pitch_hz=), their integers, the track a measurement returns (F0Track), and the shift that carries a measured median to a target."""
+"""Host side of the F0 tracker (include/tortoise_mi355x_f0.h, csrc/f0.hip, stages.F0Stage) and of its Viterbi path
+(include/tortoise_mi355x_f0v.h, csrc/f0_viterbi.hip, stages.F0ViterbiStage): the options of f0() / shift_pitch(to_hz=) / tts(pitch_hz=),
+their integers, the costs of smooth= / f0_smooth=, the track a measurement returns (F0Track), and the shift that carries a measured median
+to a target."""
 import math
 import warnings
 from collections import namedtuple
@@ -21,6 +23,15 @@ DEFAULTS = dict(fmin=60.0, fmax=500.0, threshold=0.15, floor_db=-50.0)
 
 # what the device takes per clip: par = (lag_lo, lag_hi) i32, thr = (thr, floor_e) f64
 Params = namedtuple("Params", "lag_lo lag_hi thr floor_e")
+# smooth=: the costs of the Viterbi path, cost = (oct, jump, vuv, uv) f64 per clip.  Praat's shape of costs (octave cost, octave-jump cost,
+# voiced / unvoiced cost, and a price for staying unvoiced) on the scale of YIN's aperiodicity d', chosen from the arithmetic: a clean dip
+# reads d' below 0.1, a frame of noise above 0.5, and an octave is 1.0 in log2 of the lag.  Nobody has tuned them on a trained checkpoint.
+Costs = namedtuple("Costs", "oct jump vuv uv")
+SMOOTH_DEFAULTS = dict(octave_cost=0.01, jump_cost=0.35, voicing_cost=0.14, unvoiced_cost=0.30)
+# L2[tau] = log2(tau) for tau = 1 .. 480 (entry 0 unused): computed here, once, and handed to tt_f0v_create - the device evaluates no
+# transcendental, and a reference that reads this list prices every step with the same 480 doubles
+LOG2_TABLE = [0.0] + [math.log2(tau) for tau in range(1, E.F0_LAG_MAX + 1)]
+JUMP_SEMITONES = 7.0                                                                  # octave_jumps(): further apart than a fifth
 
 
 def _number(name, v):
@@ -55,6 +66,40 @@ def params(fmin=DEFAULTS["fmin"], fmax=DEFAULTS["fmax"], threshold=DEFAULTS["thr
 
 def frames(n):
     return -(-int(n) // E.F0_HOP)
+
+
+def smooth_params(smooth):
+    """smooth= of f0() / f0_smooth= of shift_pitch(to_hz=) and tts(pitch_hz=), validated -> Costs, or None for off (None / False).  True: the
+    defaults; a dict with any of octave_cost, jump_cost, voicing_cost, unvoiced_cost sets those (the others keep their defaults).  An
+    unknown key, or a value that is negative or not a finite number, is a ValueError that names it."""
+    if smooth is None or smooth is False:
+        return None
+    if isinstance(smooth, Costs):
+        smooth = dict(zip(SMOOTH_DEFAULTS, smooth))
+    elif smooth is True:
+        smooth = {}
+    elif not isinstance(smooth, dict):
+        raise ValueError(f"smooth={smooth!r}: None / False (off), True (the default costs) or a dict with any of {sorted(SMOOTH_DEFAULTS)}")
+    unknown = sorted(set(smooth) - set(SMOOTH_DEFAULTS))
+    if unknown:
+        raise ValueError(f"smooth: unknown key {unknown[0]!r} (the costs are {sorted(SMOOTH_DEFAULTS)})")
+    v = {k: _number(k, smooth.get(k, d)) for k, d in SMOOTH_DEFAULTS.items()}
+    for k, x in v.items():
+        if x < 0:
+            raise ValueError(f"{k}={x}: a cost is not negative")
+    return Costs(v["octave_cost"], v["jump_cost"], v["voicing_cost"], v["unvoiced_cost"])
+
+
+def smooth_option(kwargs, pitch_hz, who="tts"):
+    """Takes `f0_smooth` out of a call's **kwargs -> Costs, or None (absent, None or False: the plain tracker measures).  It belongs to the
+    one f0_many call of pitch_hz= / to_hz=: without that target it is a ValueError."""
+    if "f0_smooth" not in kwargs:
+        return None
+    costs = smooth_params(kwargs.pop("f0_smooth"))
+    if costs is not None and pitch_hz is None:
+        raise ValueError(f"{who}: f0_smooth= smooths the measurement of {'to_hz' if who.startswith('shift_pitch') else 'pitch_hz'}= and does "
+                         "nothing without it: give the target too, or call f0(audio, smooth=...) for the track")
+    return costs
 
 
 def target_hz(name, v):
@@ -104,8 +149,9 @@ def formant_keywords(kwargs):
 
 
 def refuse(kwargs, who, why, instead):
-    if "pitch_hz" in kwargs:
-        raise ValueError(f"{who}: pitch_hz is not available {why}; {instead}")
+    for key in ("pitch_hz", "f0_smooth"):
+        if key in kwargs:
+            raise ValueError(f"{who}: {key} is not available {why}; {instead}")
 
 
 def refuse_streaming(kwargs, who):
@@ -125,17 +171,38 @@ def refuse_sharded(kwargs, who):
 
 class F0Track:
     """The F0 of one clip, a frame every 10 ms (frame f stands at f * hop_seconds): hz f32 [F] (0 where unvoiced), aperiodicity f32 [F]
-    (YIN's d' at the chosen lag: 0 periodic .. 1 and above noise), lag i32 [F] (the chosen period in samples before refinement)."""
+    (YIN's d' at the chosen lag: 0 periodic .. 1 and above noise), lag i32 [F] (the chosen period in samples before refinement).  A track
+    measured with smooth= is `smoothed`: state i32 [F] is the candidate the Viterbi path chose in every frame (0 .. 6 by ascending lag, 7
+    unvoiced) and path_cost the path's total cost; both are None on a plain track."""
 
     hop_seconds = HOP_SECONDS
 
-    def __init__(self, hz, aperiodicity, lag, samples=None):
+    def __init__(self, hz, aperiodicity, lag, samples=None, state=None, path_cost=None):
         self.hz = np.asarray(hz, dtype=np.float32)
         self.aperiodicity = np.asarray(aperiodicity, dtype=np.float32)
         self.lag = np.asarray(lag, dtype=np.int32)
         self.samples = None if samples is None else int(samples)
         if not (self.hz.ndim == 1 and self.hz.shape == self.aperiodicity.shape == self.lag.shape):
             raise ValueError(f"F0Track: hz {self.hz.shape}, aperiodicity {self.aperiodicity.shape} and lag {self.lag.shape} must be one [F]")
+        self.state = None if state is None else np.asarray(state, dtype=np.int32)
+        self.path_cost = None if state is None or path_cost is None else float(path_cost)
+        if self.state is not None and self.state.shape != self.hz.shape:
+            raise ValueError(f"F0Track: state {self.state.shape} must be hz's {self.hz.shape}")
+
+    @property
+    def smoothed(self):
+        return self.state is not None
+
+    def octave_jumps(self, min_semitones=JUMP_SEMITONES):
+        """The adjacent pairs of voiced frames whose F0 lies further apart than min_semitones: what an octave slip of the tracker leaves
+        in a track (a voice does not move a fifth in 10 ms)."""
+        m = _number("min_semitones", min_semitones)
+        if m <= 0:
+            raise ValueError(f"min_semitones={m}: a positive interval")
+        hz = self.hz.astype(np.float64)
+        both = (hz[:-1] > 0) & (hz[1:] > 0)
+        st = 12.0 * np.abs(np.log2(hz[1:][both] / hz[:-1][both]))
+        return int(np.count_nonzero(st > m))
 
     def __len__(self):
         return int(self.hz.shape[0])
@@ -196,5 +263,5 @@ class F0Track:
 
 
 def track_of(result, samples=None):
-    """One dict of stages.F0Stage.track_many -> F0Track."""
-    return F0Track(result["f0"], result["aper"], result["lag"], samples)
+    """One dict of stages.F0Stage.track_many (or stages.F0ViterbiStage.track_many: a smoothed track) -> F0Track."""
+    return F0Track(result["f0"], result["aper"], result["lag"], samples, result.get("state"), result.get("path_cost"))

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 from . import engine as E
 from . import formant as fmt
 from . import pack
+from . import pitch as f0m
 from . import resample as rs
 from . import stretch as tsm
 from .config import ARConfig, CLVPConfig, CVVPConfig, DiffusionConfig, VocoderConfig
@@ -1014,6 +1015,43 @@ class F0Stage(_ClipStage):
                 d["dprime"] = dpr[a:b].copy()
             out.append(d)
         return out
+
+
+class F0ViterbiStage(_ClipStage):
+    """The Viterbi path over YIN candidates (csrc/f0_viterbi.hip, include/tortoise_mi355x_f0v.h): ragged batches, each clip with its own
+    parameters (pitch.Params) and costs (pitch.Costs), one tt_f0v_track call per max_clips clips, every clip's result bit-identical to
+    running it alone.  The handle gets pitch.LOG2_TABLE at create: the device evaluates no logarithm."""
+
+    api, noun, what = "tt_f0v", "F0 path stage's", "f0 path"
+
+    def __init__(self, max_samples, max_clips=16, device="cuda"):
+        super().__init__(max_samples, max_clips, device, ((C.c_double * E.F0V_TABLE)(*f0m.LOG2_TABLE),))
+
+    def track_many(self, clips, params, costs):
+        """clips f32 [n_i] (device or host), a pitch.Params and a pitch.Costs each -> one dict per clip: lag (i32 [F]), f0 (f32 [F], 0 where
+        the path is unvoiced), aper (f32 [F]), state (i32 [F], 0 .. 7) on the host, n_voiced and path_cost."""
+        if not len(clips) == len(params) == len(costs):
+            raise ValueError(f"{len(clips)} clips with {len(params)} parameter sets and {len(costs)} sets of costs")
+        for i, x in enumerate(clips):
+            self._check_clip(i, x)
+        return self._run(clips, params, costs)
+
+    def _group(self, clips, params, costs):
+        n, dev = len(clips), self.device
+        lens = [x.shape[0] for x in clips]
+        fo = self._offsets(self.lib.tt_f0_frames(m) for m in lens)
+        Fs = fo[-1]
+        audio = self._audio(clips)
+        t = _Tables(dev, io=self._offsets(lens), fo=fo, par=[v for p in params for v in (p.lag_lo, p.lag_hi)])
+        d = _Tables(dev, torch.float64, thr=[v for p in params for v in (p.thr, p.floor_e)], cost=[float(v) for k in costs for v in k])
+        r = _Results(dev, int32=dict(n_voiced=n, status=n, lag=Fs, state=Fs), float32=dict(f0=Fs, aper=Fs), float64=dict(path_cost=n))
+        E.check(self.lib.tt_f0v_track(self.h, n, audio.data_ptr(), t.p("io"), t.p("par"), d.p("thr"), d.p("cost"), t.p("fo"), r.p("lag"), r.p("f0"),
+                                      r.p("aper"), r.p("state"), r.p("n_voiced"), r.p("path_cost"), r.p("status"), E.stream_ptr()))
+        r.cpu()
+        self._accepted(r["status"], (E.F0_OK,))
+        lag, f0, aper, state, voiced, cost = r["lag"], r["f0"], r["aper"], r["state"], r["n_voiced"].tolist(), r["path_cost"].tolist()
+        return [dict(lag=lag[a:b].copy(), f0=f0[a:b].copy(), aper=aper[a:b].copy(), state=state[a:b].copy(), n_voiced=voiced[i], path_cost=cost[i])
+                for i, (a, b) in enumerate(zip(fo, fo[1:]))]
 
 
 class FormantStage(_ClipStage):
