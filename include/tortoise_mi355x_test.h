@@ -163,6 +163,11 @@ size_t tt_op_groupnorm_workspace(int B, int S);
 int tt_op_gn_gemm(int dtype, const float* x, int B, int S, const float* gamma, const float* beta, int act, const void* W,
                   const float* bias, int N, float* out_f32, float* workspace, void* stream);
 size_t tt_op_gn_gemm_workspace(int B, int S);
+/* flash attention (csrc/ops.h FlashArgs): q T [B * heads][n][64] pre-scaled, k T [B * heads][n][64], vt T [B * heads][64][n_pad] (V transposed;
+ * n_pad a multiple of 32 covering n), relpos f32 [heads][129] or NULL, out T [B][n][heads * 64].  Columns n .. n_pad of vt must hold FINITE
+ * values: the kernels load them (clamped to n_pad - 8) and multiply them by numerators that are exact zeros, so any finite value leaves the
+ * output untouched and a NaN or an infinity would reach it.  The engine's V^T buffers are zeroed when they are made and afterwards hold nothing
+ * but V values of the QKV epilogue (an earlier pass's where another n_pad moved the layout), so there the columns are finite as long as V is. */
 int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
                           int causal, const float* relpos, void* stream);
 /* the same with padded batch rows and the kernel choice exposed: batch row b attends to (and computes) its first nv[b % nv_period] rows only
@@ -170,6 +175,10 @@ int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* v
  * variant 0 = chosen from the shape, 1 = never the key-split form, 2 = never the 32-query-wave kernel. */
 int tt_op_flash_attention_rows(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int heads, int n, int n_pad,
                                int causal, const float* relpos, const int* nv, int nv_period, int variant, void* stream);
+/* what the last flash-attention launch of the calling thread started, recorded on the host by the launch path: ran = {kernel (0 flash_kernel,
+ * 1 flash_lds_kernel, 2 flash32_kernel, 3 the fp32 verification kernel; -1 before the first launch), NQ (16-query blocks per wave: the template
+ * argument, 2 for flash32_kernel, 0 for the fp32 kernel), KS (key halves per staged tile: the template argument, 0 where there is none)} */
+int tt_op_flash_ran(int ran[3]);
 /* the decode step's attention (HF GPT2Attention under tortoise/models/autoregressive.py:150-163, one query per (sequence, head)):
  * q T [B][heads * 64] pre-scaled by 1/8; shared prefix kp, vp T [heads][P1][64]; per-sequence caches kc T [B][heads][8][tmax][8]
  * (key-major 16-byte chunks), vc T [B][heads][tmax][64] with own keys 0 .. tgen - 1 valid; out T [B][heads * 64].

@@ -758,14 +758,17 @@ static int flash_with_type(int dtype, F&& f) { return dtype == DT_BF16 ? f(bf16(
 template <int NQ, int KS>
 static int launch_flash_lds(int dtype, const ProfScope& ps, const FlashArgs& a, hipStream_t stream) {
   typedef FlashStaged<64 * NQ, KS, 132> R;
+  g_flash_ran = FlashRan{FLASH_RAN_LDS, NQ, KS};
   return flash_with_type(dtype, [&](auto t) { return launch_flash_staged<R, flash_lds_kernel<decltype(t), NQ, KS>>(ps, a, stream); });
 }
 template <int KS>
 static int launch_flash32(int dtype, const ProfScope& ps, const FlashArgs& a, hipStream_t stream) {
   typedef FlashStaged<128, KS, 260> R;
+  g_flash_ran = FlashRan{FLASH_RAN_32, 2, KS};
   return flash_with_type(dtype, [&](auto t) { return launch_flash_staged<R, flash32_kernel<decltype(t), KS>>(ps, a, stream); });
 }
 
+thread_local FlashRan g_flash_ran = {-1, 0, 0};
 bool g_flash32 = true;  // tt_flash_variant: 0 = the 16-query-wave kernels everywhere (A/B runs)
 
 int flash_attention_launch(int dtype, const FlashArgs& a, hipStream_t stream) {
@@ -796,6 +799,7 @@ int flash_attention_launch(int dtype, const FlashArgs& a, hipStream_t stream) {
   // short sequences (prefill of a few dozen rows, reduced test configurations): the register-prefetch kernel, the 4 waves of a
   // block share one 16-query block and split the keys
   dim3 grid(cdiv(a.n, 16), a.BH);
+  g_flash_ran = FlashRan{FLASH_RAN_REG, 1, 0};
   return flash_with_type(dtype, [&](auto t) {
     launch_timed(ps, flash_kernel<decltype(t), 1, true>, grid, dim3(256), 0, stream, a);
     TT_CHECK_HIP(hipGetLastError());

@@ -56,6 +56,7 @@ __global__ __launch_bounds__(256) void flash_f32_kernel(FlashArgs a) {
 }
 
 int flash_f32_launch(const FlashArgs& a, hipStream_t stream) {
+  g_flash_ran = FlashRan{FLASH_RAN_F32, 0, 0};
   ProfScope ps(PROF_FLASH, stream, 4.0 * a.BH * (double)a.n * a.n * 64.0, (double)a.BH * a.n * 64 * 4.0 * 4.0, true);
   launch_timed(ps, flash_f32_kernel, dim3(cdiv(a.n, 4), a.BH), dim3(256), 0, stream, a);
   TT_CHECK_HIP(hipGetLastError());

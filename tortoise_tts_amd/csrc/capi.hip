@@ -247,6 +247,12 @@ int tt_op_flash_attention(int dtype, const void* q, const void* k, const void* v
                           int causal, const float* relpos, void* stream) {
   return tt_op_flash_attention_rows(dtype, q, k, vt, out, B, heads, n, n_pad, causal, relpos, nullptr, 0, 0, stream);
 }
+// what the last flash launch of this thread started (ops.h FlashRan)
+int tt_op_flash_ran(int ran[3]) {
+  TT_REQUIRE(ran != nullptr, "tt_op_flash_ran: null record");
+  ran[0] = g_flash_ran.kernel; ran[1] = g_flash_ran.nq; ran[2] = g_flash_ran.ks;
+  return 0;
+}
 
 // GEMV-shaped decode GEMM (gemv.hip; handles of <= 4 sequences, wide session handles of <= 16): epi 0 = out_f32 = A W^T + bias, 1 = x (out_f32) += A W^T + bias, 2 = out_t = gelu_tanh(A W^T + bias)
 int tt_op_gemv(int dtype, const void* A, const void* W, int M, int N, int K, const float* bias, int epi, float* out_f32, void* out_t, void* stream) {

@@ -105,6 +105,13 @@ struct FlashArgs {
 };
 int flash_attention_launch(int dtype, const FlashArgs& a, hipStream_t stream);
 int flash_f32_launch(const FlashArgs& a, hipStream_t stream);  // fp32 verification mode (attention_f32.hip)
+// What the last flash_attention_launch of this thread started, recorded on the host (as g_gemm_ran; the operator-level tests assert it):
+// kernel 0 flash_kernel, 1 flash_lds_kernel, 2 flash32_kernel, 3 flash_f32_kernel (the fp32 verification form); nq = 16-query blocks per wave
+// (the NQ template argument; 2 for the 32-query waves of flash32_kernel, 0 for the fp32 form's wave per query); ks = the KS template argument
+// (key halves of a staged tile), 0 for the two kernels that have none
+enum FlashKernelId { FLASH_RAN_REG = 0, FLASH_RAN_LDS = 1, FLASH_RAN_32 = 2, FLASH_RAN_F32 = 3 };
+struct FlashRan { int kernel, nq, ks; };
+extern thread_local FlashRan g_flash_ran;  // attention.hip
 
 struct DecodeAttnArgs {
   const void* q;    // [B][heads*64], pre-scaled

@@ -270,6 +270,9 @@ GEMM_TILES = {0: "64x64", 1: "128x64", 2: "128x128", 3: "256x256", 4: "32x16", 5
 GEMM_VARIANTS = {-1: "-", 0: "V_GEN", 1: "V_NONE", 2: "V_SLAB", 3: "V_GELU_T", 4: "V_ST_F32", 5: "V_ST_RES", 6: "V_ST_A2", 7: "V_BIAS_T", 8: "V_SERIAL"}
 EPI_STD, EPI_QKV_HEADS, EPI_QKV_DECODE, EPI_GEGLU = 0, 1, 2, 3
 
+# tt_op_flash_ran record {kernel, NQ, KS} (csrc/ops.h FlashRan)
+FLASH_KERNELS = {-1: "-", 0: "flash_kernel", 1: "flash_lds_kernel", 2: "flash32_kernel", 3: "flash_f32_kernel"}
+
 # include/tortoise_mi355x_hifi.h, order == tt_hifi_batch_struct_size(which)
 HIFI_BATCH_STRUCTS = [HifiConfig, HifiWeights, HifiResBlock]
 HIFI_MAX_BATCH = 64  # TT_HIFI_MAX_BATCH
@@ -588,6 +591,7 @@ _TEST_PROTOS = {
     "tt_op_gn_gemm_workspace": (_sz, [_i, _i]),
     "tt_op_flash_attention": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp]),
     "tt_op_flash_attention_rows": (_i, [_i, vp, vp, vp, vp, _i, _i, _i, _i, _i, vp, vp, _i, _i, vp]),
+    "tt_op_flash_ran": (_i, [C.POINTER(_i)]),
     "tt_op_decode_attention": (_i, [_i, vp, vp, vp, _i, vp, vp, _i, _i, vp, _i, _i, _i, vp]),
     "tt_op_decode_qkv_attention": (_i, [_i, vp, vp, vp, C.c_float, vp, vp, _i, vp, vp, _i, _i, vp, vp, _i, _i, vp]),
     "tt_op_decode_attention_rows": (_i, [_i, vp, vp, vp, C.c_longlong, vp, _i, vp, vp, _i, vp, vp, _i, _i, vp]),
