@@ -5,7 +5,7 @@
 // launches in the token-major layout: the strided 512 -> 512 convolutions are plain GEMMs whose A rows overlap (lda = stride * 512 < K =
 // k * 512: output row t reads input rows stride * t .. stride * t + k - 1, which are contiguous), each followed by LayerNorm + GELU in one
 // row-norm launch; the grouped positional convolution is one tap GEMM per group; the encoder layers are pre-LN transformer layers.
-#include "runtime.h"
+#include "stage_blocks.h"
 #include "../../include/tortoise_mi355x_align.h"
 #include "../../include/tortoise_mi355x_test.h"
 
@@ -212,14 +212,9 @@ static int w2v_conv_frames(const tt_w2v_config& c, int n, int upto) {
   return n;
 }
 
-static int w2v_rownorm(tt_w2v* e, float* x, int ldx, int M, int D, const float* g, const float* b, float eps, int act, void* out_t, int ldot,
-                       float* out_f32, hipStream_t s) {
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.ldx = ldx; a.M = M; a.D = D; a.mode = NORM_LAYER; a.g1 = g; a.b1 = b; a.eps1 = eps; a.act = act;
-  a.out_t = out_t; a.ldot = ldot; a.out_f32 = out_f32; a.ldo32 = ldx;
-  a.guard = e->guard.dev;
-  return rownorm_launch(e->cfg.dtype, a, s);
+static int w2v_rownorm(tt_w2v* e, float* x, int M, int D, const float* g, const float* b, float eps, int act, void* out_t, float* out_f32,
+                       hipStream_t s) {
+  return rownorm_launch(e->cfg.dtype, layernorm_args(x, M, D, g, b, eps, act, out_t, out_f32, e->guard.dev), s);
 }
 
 static int w2v_forward(tt_w2v* e, const float* audio, int S, int* ids, float* logits_out, hipStream_t s) {
@@ -235,62 +230,48 @@ static int w2v_forward(tt_w2v* e, const float* audio, int S, int* ids, float* lo
     const int k = c.conv_kernel[i], st = c.conv_stride[i];
     const int Fo = (F - k) / st + 1;
     // overlapping A rows: output row t reads rows st t .. st t + k - 1 of the previous layer = K = k * CD contiguous elements at st t * CD
-    GemmArgs g = gemm_args(cur, st * CD, e->w.w_conv[i], k * CD, Fo, CD, k * CD);
-    g.bias = e->w.b_conv[i]; g.out_f32 = e->cf; g.ldo32 = CD;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(cur, st * CD, e->w.w_conv[i], k * CD, Fo, CD, k * CD, e->w.b_conv[i], e->cf), s));
     void* nxt = cur == e->ca ? e->cb : e->ca;
     const bool last = i == TT_W2V_CONV_LAYERS - 1;
     // LayerNorm + GELU; the last layer's rows stay f32 (in place) for the feature projection's LayerNorm
-    TT_TRY(w2v_rownorm(e, e->cf, CD, Fo, CD, e->w.ln_conv_g[i], e->w.ln_conv_b[i], 1e-5f, ACT_GELU_ERF, last ? nullptr : nxt, CD,
-                       last ? e->cf : nullptr, s));
+    TT_TRY(w2v_rownorm(e, e->cf, Fo, CD, e->w.ln_conv_g[i], e->w.ln_conv_b[i], 1e-5f, ACT_GELU_ERF, last ? nullptr : nxt, last ? e->cf : nullptr, s));
     cur = nxt;
     F = Fo;
   }
-  const int T = F, n_pad = round_up(T, 32);
+  const int T = F;
   // feature projection: LayerNorm(conv_dim) -> Linear(conv_dim, dim)
-  TT_TRY(w2v_rownorm(e, e->cf, CD, T, CD, e->w.fp_ln_g, e->w.fp_ln_b, c.eps, ACT_NONE, cur, CD, nullptr, s));
-  GemmArgs g = gemm_args(cur, CD, e->w.w_fp, CD, T, D, CD);
-  g.bias = e->w.b_fp; g.out_f32 = e->x; g.ldo32 = D;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(w2v_rownorm(e, e->cf, T, CD, e->w.fp_ln_g, e->w.fp_ln_b, c.eps, ACT_NONE, cur, nullptr, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(cur, CD, e->w.w_fp, CD, T, D, CD, e->w.b_fp, e->x), s));
   // positional convolution: h += GELU(conv_g(h) + b) per group g of cg channels, taps centred at pos_kernel / 2 = the reference's padding
   // pos_kernel / 2 with the last output frame dropped (Wav2Vec2SamePadLayer)
   TT_TRY(cast_pad_launch(dt, e->x, D, e->xt, D, T, D, D, s));
   const int cg = D / c.pos_groups, KP = c.pos_kernel * cg;
   for (int gi = 0; gi < c.pos_groups; ++gi) {
-    g = gemm_args(offset_t(e->xt, (size_t)gi * cg, e->es), D, offset_t(e->w.w_pos, (size_t)gi * cg * KP, e->es), KP, T, cg, KP);
+    GemmArgs g = gemm_args(offset_t(e->xt, (size_t)gi * cg, e->es), D, offset_t(e->w.w_pos, (size_t)gi * cg * KP, e->es), KP, T, cg, KP);
     g.taps = c.pos_kernel; g.seq_len = T;
     g.bias = e->w.b_pos + gi * cg; g.act = ACT_GELU_ERF; g.res = e->x + gi * cg; g.ldres = D; g.out_f32 = e->x + gi * cg; g.ldo32 = D;
     TT_TRY(gemm_launch(dt, EPI_STD, g, s));
   }
-  // pre-LN encoder layers (Wav2Vec2EncoderLayerStableLayerNorm): h += out_proj(attn(LN1 h)); h += fc2(gelu(fc1(LN2 h))).  The same
-  // launch sequence as gpt2.hip gpt_trunk_full, which is not shared: that loop is causal, uses tanh-GELU, writes K / V into the handle's
-  // per-layer prefix cache and takes its buffers from tt_ar - a common loop would have to parameterise all four on the decode hot path.
+  // pre-LN encoder layers (Wav2Vec2EncoderLayerStableLayerNorm): h += out_proj(attn(LN1 h)); h += fc2(gelu(fc1(LN2 h))).  The steps -
+  // the LayerNorm block, the head-split attention pair, the residual GEMM - are the ones of stage_blocks.h that xenc.h and the
+  // AttentionBlocks use.  The loop itself is deliberately not shared with gpt2.hip gpt_trunk_full, which issues the same sequence: that
+  // loop is causal, uses tanh-GELU, writes K / V into the handle's per-layer prefix cache, takes its buffers from tt_ar and builds its
+  // argument blocks with gpt2.hip's own builders (their bytes are graph-key material) - a common loop would have to parameterise all of
+  // that on the decode hot path.
   for (int l = 0; l < c.layers; ++l) {
     const tt_gpt_layer& w = e->L[l];
-    TT_TRY(w2v_rownorm(e, e->x, D, T, D, w.ln1_g, w.ln1_b, c.eps, ACT_NONE, e->h, D, nullptr, s));
-    g = gemm_args(e->h, D, w.w_qkv, D, T, 3 * D, D);
-    g.bias = w.b_qkv; g.seq_len = T; g.dmodel = D; g.heads = H; g.q = e->q; g.k = e->k; g.vt = e->vt; g.seq_pad = n_pad; g.q_scale = 0.125f;
-    TT_TRY(gemm_launch(dt, EPI_QKV_HEADS, g, s));
-    FlashArgs f;
-    memset(&f, 0, sizeof(f));
-    f.q = e->q; f.k = e->k; f.vt = e->vt; f.out = e->attn; f.ldo = D; f.BH = H; f.heads = H; f.n = T; f.n_pad = n_pad;
-    TT_TRY(flash_attention_launch(dt, f, s));
-    g = gemm_args(e->attn, D, w.w_proj, D, T, D, D);
-    g.bias = w.b_proj; g.res = e->x; g.ldres = D; g.out_f32 = e->x; g.ldo32 = D;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(w2v_rownorm(e, e->x, D, T, D, w.ln2_g, w.ln2_b, c.eps, ACT_NONE, e->h, D, nullptr, s));
-    g = gemm_args(e->h, D, w.w_fc, D, T, c.ff_dim, D);
+    TT_TRY(w2v_rownorm(e, e->x, T, D, w.ln1_g, w.ln1_b, c.eps, ACT_NONE, e->h, nullptr, s));
+    TT_TRY(heads_attention(dt, e->h, w.w_qkv, w.b_qkv, e->q, e->k, e->vt, e->attn, 1, T, D, H, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_residual_args(e->attn, D, w.w_proj, D, T, D, D, w.b_proj, e->x, e->x), s));
+    TT_TRY(w2v_rownorm(e, e->x, T, D, w.ln2_g, w.ln2_b, c.eps, ACT_NONE, e->h, nullptr, s));
+    GemmArgs g = gemm_args(e->h, D, w.w_fc, D, T, c.ff_dim, D);
     g.bias = w.b_fc; g.act = ACT_GELU_ERF; g.out_t = e->ff; g.ldot = c.ff_dim;
     TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    g = gemm_args(e->ff, c.ff_dim, w.w_proj2, c.ff_dim, T, D, c.ff_dim);
-    g.bias = w.b_proj2; g.res = e->x; g.ldres = D; g.out_f32 = e->x; g.ldo32 = D;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_residual_args(e->ff, c.ff_dim, w.w_proj2, c.ff_dim, T, D, c.ff_dim, w.b_proj2, e->x, e->x), s));
   }
   // head: encoder.layer_norm -> lm_head -> argmax per frame
-  TT_TRY(w2v_rownorm(e, e->x, D, T, D, e->w.lnf_g, e->w.lnf_b, c.eps, ACT_NONE, e->h, D, nullptr, s));
-  g = gemm_args(e->h, D, e->w.w_head, D, T, c.vocab_pad, D);
-  g.bias = e->w.b_head; g.out_f32 = e->logits; g.ldo32 = c.vocab_pad;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(w2v_rownorm(e, e->x, T, D, e->w.lnf_g, e->w.lnf_b, c.eps, ACT_NONE, e->h, nullptr, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->h, D, e->w.w_head, D, T, c.vocab_pad, D, e->w.b_head, e->logits), s));
   return w2v_argmax_launch(e->logits, c.vocab_pad, T, c.vocab, ids, logits_out, s);
 }
 
@@ -376,8 +357,7 @@ int tt_w2v_run(tt_w2v* e, const float* audio, int samples, int* frame_ids, float
 
 int tt_w2v_guard(tt_w2v* e, int reset) {
   if (!e) { set_error("tt_w2v_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_w2v_guard", "aligner stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
+  return e->read_guard(reset, "tt_w2v_guard", "aligner", e->cfg.dtype);
 }
 
 // ------------------------------------------------------------------------------ operator-level test entries (tortoise_mi355x_test.h)

@@ -6,7 +6,7 @@
 // encoder tail are the engine's GroupNorm and GEMM launches: the ResBlock convs are tap GEMMs (taps = 5), the Downsample a GEMM whose A
 // rows overlap (lda = 4 C < K = 5 C) over an operand copy that starts 2 zero rows early (padding 2).
 #include <limits.h>
-#include "runtime.h"
+#include "stage_blocks.h"
 #include "../../include/tortoise_mi355x_classify.h"
 #include "../../include/tortoise_mi355x_test.h"
 
@@ -379,11 +379,7 @@ struct tt_cls : EngineHandle {  // guard: narrow and wide GroupNorm statistics a
 };
 
 static int cls_gn(tt_cls* e, const float* x, int L, int C, const float* g, const float* b, int act, void* out_t, hipStream_t s) {
-  GroupNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.B = 1; a.S = L; a.C = C; a.gamma = g; a.beta = b; a.eps = kClsEps; a.act = act;
-  a.out_t = out_t; a.ldot = C; a.partial = e->gnpart; a.guard = e->guard.dev;
-  return groupnorm_launch(e->cfg.dtype, a, s);
+  return groupnorm_launch(e->cfg.dtype, groupnorm_args(x, 1, L, C, g, b, kClsEps, act, out_t, nullptr, e->gnpart, e->guard.dev), s);
 }
 
 static int cls_forward(tt_cls* e, const float* clip, int n, float* logits, float* emb, hipStream_t s) {
@@ -421,12 +417,12 @@ static int cls_forward(tt_cls* e, const float* clip, int n, float* logits, float
       for (int r = 0; r < TT_CLS_RES_BLOCKS; ++r) {
         const tt_cls_resblock& rb = W.res[lv][r];
         TT_TRY(cls_gn(e, x, L, C, rb.gn1_g, rb.gn1_b, ACT_SILU, e->ht, s));
-        GemmArgs g = gemm_args(e->ht, C, rb.w1, 5 * C, L, C, 5 * C);
-        g.taps = 5; g.seq_len = L; g.bias = rb.b1; g.out_f32 = e->hf; g.ldo32 = C;
+        GemmArgs g = gemm_conv_args(e->ht, C, rb.w1, 5, L, L, C, rb.b1);
+        g.out_f32 = e->hf; g.ldo32 = C;
         TT_TRY(gemm_launch(dt, EPI_STD, g, s));
         TT_TRY(cls_gn(e, e->hf, L, C, rb.gn2_g, rb.gn2_b, ACT_SILU, e->ht, s));
-        g = gemm_args(e->ht, C, rb.w2, 5 * C, L, C, 5 * C);
-        g.taps = 5; g.seq_len = L; g.bias = rb.b2; g.res = x; g.ldres = C; g.out_f32 = x; g.ldo32 = C;
+        g = gemm_conv_args(e->ht, C, rb.w2, 5, L, L, C, rb.b2);
+        g.res = x; g.ldres = C; g.out_f32 = x; g.ldo32 = C;
         if (r == TT_CLS_RES_BLOCKS - 1) { g.out_t = offset_t(e->xt, 2 * (size_t)C, es); g.ldot = C; }
         TT_TRY(gemm_launch(dt, EPI_STD, g, s));
       }
@@ -435,9 +431,7 @@ static int cls_forward(tt_cls* e, const float* clip, int n, float* logits, float
       TT_CHECK_HIP(hipMemsetAsync(e->xt, 0, (size_t)2 * C * es, s));
       TT_CHECK_HIP(hipMemsetAsync(offset_t(e->xt, (size_t)(L + 2) * C, es), 0, (size_t)4 * C * es, s));
       // Downsample: output row t reads operand rows 4 t - 2 .. 4 t + 2 = 5 C contiguous elements 4 t C into the guarded copy
-      GemmArgs g = gemm_args(e->xt, 4 * C, W.w_down[lv], 5 * C, cls_down(L), 2 * C, 5 * C);
-      g.bias = W.b_down[lv]; g.out_f32 = y; g.ldo32 = 2 * C;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+      TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->xt, 4 * C, W.w_down[lv], 5 * C, cls_down(L), 2 * C, 5 * C, W.b_down[lv], y), s));
     }
     std::swap(x, y);
     L = cls_down(L);
@@ -445,21 +439,15 @@ static int cls_forward(tt_cls* e, const float* clip, int n, float* logits, float
   }
   // final: GroupNorm(1024) -> SiLU -> Conv1d(1024, 512, 1) into y
   TT_TRY(cls_gn(e, x, L, C, W.final_g, W.final_b, ACT_SILU, e->ht, s));
-  GemmArgs g = gemm_args(e->ht, C, W.w_final, C, L, kClsDim, C);
-  g.bias = W.b_final; g.out_f32 = y; g.ldo32 = kClsDim;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->ht, C, W.w_final, C, L, kClsDim, C, W.b_final, y), s));
   x = y;
   for (int b = 0; b < TT_CLS_ATTN_BLOCKS; ++b) {
     const tt_cls_attn& A = W.attn[b];
     const int nq = b == TT_CLS_ATTN_BLOCKS - 1 ? 1 : L;  // only frame 0 of the last block reaches the head
     TT_TRY(cls_gn(e, x, L, kClsDim, A.norm_g, A.norm_b, ACT_NONE, e->ht, s));
-    g = gemm_args(e->ht, kClsDim, A.w_qkv, kClsDim, L, 3 * kClsDim, kClsDim);
-    g.bias = A.b_qkv; g.out_f32 = e->qkv; g.ldo32 = 3 * kClsDim;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->ht, kClsDim, A.w_qkv, kClsDim, L, 3 * kClsDim, kClsDim, A.b_qkv, e->qkv), s));
     TT_TRY(cls_attention_launch(dt, e->qkv, L, nq, e->att, s));
-    g = gemm_args(e->att, kClsDim, A.w_proj, kClsDim, nq, kClsDim, kClsDim);
-    g.bias = A.b_proj; g.res = x; g.ldres = kClsDim; g.out_f32 = x; g.ldo32 = kClsDim;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_residual_args(e->att, kClsDim, A.w_proj, kClsDim, nq, kClsDim, kClsDim, A.b_proj, x, x), s));
   }
   return cls_head_launch(x, W.w_head, W.b_head, logits, emb, guard, s);
 }
@@ -546,8 +534,7 @@ int tt_cls_run(tt_cls* e, const float* clip, int n, float* logits, float* embedd
 
 int tt_cls_guard(tt_cls* e, int reset) {
   if (!e) { set_error("tt_cls_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_cls_guard", "classifier stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
+  return e->read_guard(reset, "tt_cls_guard", "classifier", e->cfg.dtype);
 }
 
 // ------------------------------------------------------------------------------ operator-level test entries (tortoise_mi355x_test.h)

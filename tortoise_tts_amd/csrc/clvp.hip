@@ -29,17 +29,8 @@ static int clvp_tower_run(tt_clvp* e, const ClvpTower& t, const int* tokens, int
   TT_TRY(gather_rows_launch(t.w.emb, tokens, e->x, M, D, s));
   XencBufs xb{e->x, e->h, e->gg, e->attn, e->q, e->k, e->vt, e->guard.dev};
   TT_TRY(xenc_layers_run(dt, xb, t.L.data(), e->cfg.depth, t.w.inv_freq, D, H, inner, e->cfg.rot_dim, B, n, s));
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER; a.g1 = t.w.norm_g; a.b1 = t.w.norm_b; a.eps1 = 1e-5f;
-  a.out_f32 = e->enc; a.ldo32 = D;
-  a.guard = e->guard.dev;
-  TT_TRY(rownorm_launch(dt, a, s));
-  TT_TRY(mean_rows_launch(e->enc, e->pooled, B, n, D, s));
-  TT_TRY(cast_pad_launch(dt, e->pooled, D, e->pooled_t, D, B, D, D, s));
-  GemmArgs g = gemm_args(e->pooled_t, D, t.w.w_latent, D, B, e->cfg.latent_dim, D);
-  g.out_f32 = latent_out; g.ldo32 = e->cfg.latent_dim;
-  return gemm_launch(dt, EPI_STD, g, s);
+  TT_TRY(rownorm_launch(dt, layernorm_args(e->x, M, D, t.w.norm_g, t.w.norm_b, 1e-5f, ACT_NONE, nullptr, e->enc, e->guard.dev), s));
+  return pooled_latent(dt, e->enc, B, n, D, t.w.w_latent, e->cfg.latent_dim, e->pooled, e->pooled_t, latent_out, s);
 }
 
 extern "C" {
@@ -122,8 +113,7 @@ int tt_clvp_score_groups(tt_clvp* e, const int* texts, const int* T_host, int G,
 // Operand-overflow guard of this stage (see tt_ar_guard), as of the last finished tt_clvp_score (after the caller synchronised).
 int tt_clvp_guard(tt_clvp* e, int reset) {
   if (!e) { set_error("tt_clvp_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_clvp_guard", "CLVP stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
+  return e->read_guard(reset, "tt_clvp_guard", "CLVP", e->cfg.dtype);
 }
 
 }  // extern "C"

@@ -7,12 +7,12 @@
 //       positions); the clips are concatenated along time and averaged.
 // Both run once per voice (the reference caches the result per voice as a .pth file, utils/audio.py:104-124), so nothing
 // here is tuned: the stages reuse the engine's GEMM / GroupNorm / flash kernels through the same token-major layout as
-// the denoiser, a stride-2 convolution is the stride-1 tap GEMM followed by an even-row gather, and the 128-wide heads of
+// the denoiser: the mel operand, the stride-2 convolutions (stride-1 tap GEMM, then an even-row gather) and the 64-wide-head
+// AttentionBlock are stage_blocks.h mel_operand / conv_stride2 / attention_block, shared with cvvp.hip; the 128-wide heads of
 // the embedder (the flash kernels are built for 64) use a small wave-per-query kernel.  One clip per call: the host
 // averages the per-clip results exactly as the reference does (mean of the clip vectors / sum over frames of all clips
 // divided by the total frame count).
-#include "runtime.h"
-#include "../../include/tortoise_mi355x.h"
+#include "stage_blocks.h"
 
 using namespace tt;
 
@@ -70,11 +70,6 @@ __global__ void colsum_kernel(const float* __restrict__ x, float* __restrict__ o
   out[c] = s;
 }
 
-__global__ void even_rows_index_kernel(int* idx, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) idx[i] = 2 * i;
-}
-
 }  // namespace
 
 struct tt_cond : EngineHandle {
@@ -95,43 +90,23 @@ struct tt_cond : EngineHandle {
   int* even_idx = nullptr;  // [rows] = 2 i
 };
 
-static int cond_gn(tt_cond* e, const float* x, int S, int C, const float* g, const float* b, void* out_t, hipStream_t s) {
-  GroupNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.B = 1; a.S = S; a.C = C; a.gamma = g; a.beta = b; a.eps = 1e-5f; a.act = ACT_NONE;
-  a.out_t = out_t; a.ldot = C; a.partial = e->gn_partial;
-  return groupnorm_launch(e->cfg.dtype, a, s);
-}
-
 // AttentionBlock (arch_util.py:80-123): out = in + proj(attn(qkv(GN(in)))), token-major [S][C]
 static int cond_attn_block(tt_cond* e, const tt_attn_block& w, const float* in, int S, int C, int heads, float* out, hipStream_t s) {
   const int dt = e->cfg.dtype, ch = C / heads;
-  TT_TRY(cond_gn(e, in, S, C, w.norm_g, w.norm_b, e->act, s));
-  if (ch == 64) {  // the engine's flash path: QKV rows packed [q|k|v][head][64], epilogue scatters into the attention layouts
-    const int n_pad = round_up(S, 32);
-    GemmArgs g = gemm_args(e->act, C, w.w_qkv, C, S, 3 * C, C);
-    g.bias = w.b_qkv; g.seq_len = S; g.dmodel = C; g.heads = heads; g.q = e->q; g.k = e->k; g.vt = e->vt; g.seq_pad = n_pad;
-    g.q_scale = 0.125f;  // (q * 64^-1/4) . (k * 64^-1/4)
-    TT_TRY(gemm_launch(dt, EPI_QKV_HEADS, g, s));
-    FlashArgs f;
-    memset(&f, 0, sizeof(f));
-    f.q = e->q; f.k = e->k; f.vt = e->vt; f.out = e->att; f.ldo = C; f.BH = heads; f.heads = heads; f.n = S; f.n_pad = n_pad;
-    f.relpos = w.relpos;
-    TT_TRY(flash_attention_launch(dt, f, s));
-  } else {  // any other head width: QKV in the reference's own channel order, wave-per-query attention
-    GemmArgs g = gemm_args(e->act, C, w.w_qkv, C, S, 3 * C, C);
-    g.bias = w.b_qkv; g.out_t = e->qkv; g.ldot = 3 * C;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    const size_t smem = ((size_t)S + ch) * sizeof(float);
-    TT_REQUIRE(smem <= 60 * 1024, "conditioning: %d frames x %d-wide heads exceed the attention score buffer", S, ch);
-    const float scale = 1.0f / sqrtf((float)ch);
-    if (dt == DT_BF16) attn_small_kernel<bf16><<<dim3(S, heads), 64, smem, s>>>((const bf16*)e->qkv, 3 * C, (bf16*)e->att, C, S, ch, w.relpos, scale);
-    else attn_small_kernel<f16><<<dim3(S, heads), 64, smem, s>>>((const f16*)e->qkv, 3 * C, (f16*)e->att, C, S, ch, w.relpos, scale);
-    TT_CHECK_HIP(hipGetLastError());
-  }
-  GemmArgs g = gemm_args(e->att, C, w.w_proj, C, S, C, C);
-  g.bias = w.b_proj; g.res = in; g.ldres = C; g.out_f32 = out; g.ldo32 = C;
-  return gemm_launch(dt, EPI_STD, g, s);
+  // 64-wide heads: the engine's flash path (QKV rows packed [q|k|v][head][64])
+  if (ch == 64) return attention_block(dt, w, in, out, 1, S, C, heads, AttnBlockBufs{e->act, e->q, e->k, e->vt, e->att, e->gn_partial, nullptr}, s);
+  // any other head width: QKV in the reference's own channel order, wave-per-query attention
+  TT_TRY(groupnorm_launch(dt, groupnorm_args(in, 1, S, C, w.norm_g, w.norm_b, 1e-5f, ACT_NONE, e->act, nullptr, e->gn_partial, nullptr), s));
+  GemmArgs g = gemm_args(e->act, C, w.w_qkv, C, S, 3 * C, C);
+  g.bias = w.b_qkv; g.out_t = e->qkv; g.ldot = 3 * C;
+  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  const size_t smem = ((size_t)S + ch) * sizeof(float);
+  TT_REQUIRE(smem <= 60 * 1024, "conditioning: %d frames x %d-wide heads exceed the attention score buffer", S, ch);
+  const float scale = 1.0f / sqrtf((float)ch);
+  if (dt == DT_BF16) attn_small_kernel<bf16><<<dim3(S, heads), 64, smem, s>>>((const bf16*)e->qkv, 3 * C, (bf16*)e->att, C, S, ch, w.relpos, scale);
+  else attn_small_kernel<f16><<<dim3(S, heads), 64, smem, s>>>((const f16*)e->qkv, 3 * C, (f16*)e->att, C, S, ch, w.relpos, scale);
+  TT_CHECK_HIP(hipGetLastError());
+  return gemm_launch(dt, EPI_STD, gemm_residual_args(e->att, C, w.w_proj, C, S, C, C, w.b_proj, in, out), s);
 }
 
 extern "C" {
@@ -164,13 +139,8 @@ int tt_cond_create(const tt_cond_config* cfg, const tt_cond_weights* w, tt_cond*
   if (!rc) rc = e->arena.alloc(&e->att, rows * cm * 2);
   if (!rc) rc = e->arena.alloc_t(&e->gn_partial, groupnorm_partial_floats(1, (int)rows) + 64);
   if (!rc) rc = e->arena.alloc_t(&e->even_idx, rows);
-  if (!rc) {
-    even_rows_index_kernel<<<cdiv((int)rows, 256), 256>>>(e->even_idx, (int)rows);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-      set_error("tt_cond_create: index fill failed");
-      rc = -2;
-    }
-  }
+  if (!rc) rc = even_rows_index_launch(e->even_idx, (int)rows, nullptr);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) { set_error("tt_cond_create: index fill failed"); rc = -2; }
   if (rc) {
     tt_cond_destroy(e);
     return rc;
@@ -190,11 +160,8 @@ int tt_cond_ar_clip(tt_cond* e, const float* mel, int T, float* out, void* strea
   TT_REQUIRE(T >= 1 && T <= e->cfg.max_frames, "tt_cond_ar_clip: %d frames exceed capacity %d", T, e->cfg.max_frames);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
     const int D = e->cfg.ar_dim, MC = e->cfg.ar_mel, MP = e->cfg.ar_mel_pad, dt = e->cfg.dtype;
-    TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));                       // [mel][T] -> [T][mel]
-    TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-    GemmArgs g = gemm_args(e->mel_op, MP, e->w.ar_w_init, MP, T, D, MP);     // conditioning_encoder.init (1x1)
-    g.bias = e->w.ar_b_init; g.out_f32 = e->ha; g.ldo32 = D;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+    TT_TRY(mel_operand(dt, mel, MC, MP, T, e->mel_t, e->mel_op, s));
+    TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->mel_op, MP, e->w.ar_w_init, MP, T, D, MP, e->w.ar_b_init, e->ha), s));  // conditioning_encoder.init (1x1)
     float* cur = e->ha;
     float* oth = e->hb;
     for (int i = 0; i < e->cfg.ar_blocks; ++i) {
@@ -213,17 +180,9 @@ int tt_cond_diff_clip(tt_cond* e, const float* mel, int T, float* out_sum, int* 
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
     const int C = e->cfg.diff_channels, C2 = 2 * C, MC = e->cfg.diff_mel, MP = e->cfg.diff_mel_pad, dt = e->cfg.dtype;
     const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(k = 3, stride = 2, padding = 1): ceil(n / 2) outputs
-    TT_TRY(transpose_launch(mel, e->mel_t, MC, T, s));
-    TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-    // stride-2 convolution = stride-1 tap GEMM at every position, then the even rows
-    GemmArgs g = gemm_args(e->mel_op, MP, e->w.diff_w_c0, 3 * MP, T, C, 3 * MP);
-    g.taps = 3; g.seq_len = T; g.bias = e->w.diff_b_c0; g.out_t = e->act; g.ldot = C;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(gather_rows_launch((const float*)e->act, e->even_idx, (float*)e->act2, T2, C / 2, s));  // T rows of C elements == C / 2 words
-    g = gemm_args(e->act2, C, e->w.diff_w_c1, 3 * C, T2, C2, 3 * C);
-    g.taps = 3; g.seq_len = T2; g.bias = e->w.diff_b_c1; g.out_f32 = e->ha; g.ldo32 = C2;
-    TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-    TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->hb, T3, C2, s));
+    TT_TRY(mel_operand(dt, mel, MC, MP, T, e->mel_t, e->mel_op, s));
+    TT_TRY(conv_stride2(dt, e->mel_op, MP, e->w.diff_w_c0, 3, T, C, e->w.diff_b_c0, e->act, e->act2, false, e->even_idx, s));
+    TT_TRY(conv_stride2(dt, e->act2, C, e->w.diff_w_c1, 3, T2, C2, e->w.diff_b_c1, e->ha, e->hb, true, e->even_idx, s));
     float* cur = e->hb;
     float* oth = e->ha;
     for (int i = 0; i < e->cfg.diff_blocks; ++i) {

@@ -7,17 +7,11 @@
 // score[b] = mean over clips of <normalize(cond latent), normalize(speech latent b)> * exp(temperature).  The conditioning latent of a clip
 // does not depend on the candidate, so it is evaluated once per clip (the reference repeats the clip B times).  Nothing here is a new kernel:
 // the stage is composed of the engine's GEMM / norm / flash / rotary launches in the token-major layout of the other stages; a stride-2
-// convolution is the stride-1 tap GEMM followed by an even-row gather, as in cond.hip.
+// convolution is the stride-1 tap GEMM followed by an even-row gather (stage_blocks.h conv_stride2, shared with cond.hip), and the
+// AttentionBlock and the pooled-latent tail are stage_blocks.h attention_block / pooled_latent.
 #include "xenc.h"
 
 using namespace tt;
-
-namespace {
-__global__ void cvvp_even_rows_kernel(int* idx, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) idx[i] = 2 * i;
-}
-}  // namespace
 
 struct CvvpTower {
   tt_cvvp_tower w;
@@ -46,46 +40,20 @@ struct tt_cvvp : EngineHandle {  // guard: bumped by the row norms / GroupNorm s
 // e->x holds the embedded rows [B * n][dim]; leaves the tower's latent rows in latent_out [B][dim]
 static int cvvp_tower_run(tt_cvvp* e, const CvvpTower& t, int B, int n, float* latent_out, hipStream_t s) {
   const int D = e->cfg.dim, H = e->cfg.heads, dt = e->cfg.dtype;
-  const int M = B * n, n_pad = round_up(n, 32);
+  const int M = B * n;
   XencBufs xb{e->x, e->h, e->gg, e->attn, e->q, e->k, e->vt, e->guard.dev};
   TT_TRY(xenc_layers_run(dt, xb, t.L.data(), e->cfg.depth, t.w.inv_freq, D, H, D, e->cfg.rot_dim, B, n, s));
-  RowNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = e->x; a.ldx = D; a.M = M; a.D = D; a.mode = NORM_LAYER; a.g1 = t.w.norm_g; a.b1 = t.w.norm_b; a.eps1 = 1e-5f;
-  a.out_t = e->h; a.ldot = D;
-  a.guard = e->guard.dev;
-  TT_TRY(rownorm_launch(dt, a, s));
+  TT_TRY(rownorm_launch(dt, layernorm_args(e->x, M, D, t.w.norm_g, t.w.norm_b, 1e-5f, ACT_NONE, e->h, nullptr, e->guard.dev), s));
   // pre_combiner.0
-  GemmArgs g = gemm_args(e->h, D, t.w.w_pre0, D, M, D, D);
-  g.bias = t.w.b_pre0; g.out_f32 = e->ha; g.ldo32 = D;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  // pre_combiner.1: AttentionBlock (arch_util.py:80-123), one GroupNorm sample per sequence
-  GroupNormArgs gn;
-  memset(&gn, 0, sizeof(gn));
-  gn.x = e->ha; gn.B = B; gn.S = n; gn.C = D; gn.gamma = t.w.attn.norm_g; gn.beta = t.w.attn.norm_b; gn.eps = 1e-5f; gn.act = ACT_NONE;
-  gn.out_t = e->act; gn.ldot = D; gn.partial = e->gn_partial; gn.guard = e->guard.dev;
-  TT_TRY(groupnorm_launch(dt, gn, s));
-  g = gemm_args(e->act, D, t.w.attn.w_qkv, D, M, 3 * D, D);
-  g.bias = t.w.attn.b_qkv; g.seq_len = n; g.dmodel = D; g.heads = H; g.q = e->q; g.k = e->k; g.vt = e->vt; g.seq_pad = n_pad;
-  g.q_scale = 0.125f;  // (q * 64^-1/4) . (k * 64^-1/4)
-  TT_TRY(gemm_launch(dt, EPI_QKV_HEADS, g, s));
-  FlashArgs f;
-  memset(&f, 0, sizeof(f));
-  f.q = e->q; f.k = e->k; f.vt = e->vt; f.out = e->attn; f.ldo = D; f.BH = B * H; f.heads = H; f.n = n; f.n_pad = n_pad;
-  TT_TRY(flash_attention_launch(dt, f, s));
-  g = gemm_args(e->attn, D, t.w.attn.w_proj, D, M, D, D);
-  g.bias = t.w.attn.b_proj; g.res = e->ha; g.ldres = D; g.out_f32 = e->hb; g.ldo32 = D;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->h, D, t.w.w_pre0, D, M, D, D, t.w.b_pre0, e->ha), s));
+  // pre_combiner.1: AttentionBlock, one GroupNorm sample per sequence.  (attention_block applies the block's relpos table when the weights
+  // carry one; the reference's CVVP block has none - tt_cvvp_tower documents relpos = NULL - so the flash launch gets the null it always got.)
+  const AttnBlockBufs ab{e->act, e->q, e->k, e->vt, e->attn, e->gn_partial, e->guard.dev};
+  TT_TRY(attention_block(dt, t.w.attn, e->ha, e->hb, B, n, D, H, ab, s));
   // pre_combiner.2, then masked_mean with the all-ones eval mask (cvvp.py:46-51)
   TT_TRY(cast_pad_launch(dt, e->hb, D, e->act, D, M, D, D, s));
-  g = gemm_args(e->act, D, t.w.w_pre2, D, M, D, D);
-  g.bias = t.w.b_pre2; g.out_f32 = e->ha; g.ldo32 = D;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  TT_TRY(mean_rows_launch(e->ha, e->pooled, B, n, D, s));
-  TT_TRY(cast_pad_launch(dt, e->pooled, D, e->pooled_t, D, B, D, D, s));
-  g = gemm_args(e->pooled_t, D, t.w.w_latent, D, B, D, D);
-  g.out_f32 = latent_out; g.ldo32 = D;
-  return gemm_launch(dt, EPI_STD, g, s);
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->act, D, t.w.w_pre2, D, M, D, D, t.w.b_pre2, e->ha), s));
+  return pooled_latent(dt, e->ha, B, n, D, t.w.w_latent, D, e->pooled, e->pooled_t, latent_out, s);
 }
 
 extern "C" {
@@ -117,7 +85,7 @@ int tt_cvvp_create(const tt_cvvp_config* cfg, const tt_cvvp_weights* w, tt_cvvp*
   if (!rc) rc = e->arena.alloc_t(&e->ha, rows * D);
   if (!rc) rc = e->arena.alloc_t(&e->hb, rows * D);
   if (!rc) rc = e->arena.alloc(&e->act, rows * D * es);
-  if (!rc) rc = e->arena.alloc_t(&e->gn_partial, (rows / 16 + rows + 64) * 64);  // [samples][row chunks >= 16 rows][32][2], worst case as in diffusion.hip
+  if (!rc) rc = e->arena.alloc_t(&e->gn_partial, groupnorm_partial_floats_rows(rows));  // any number of sequences in `rows` rows
   if (!rc) rc = e->arena.alloc_t(&e->pooled, (size_t)e->max_seqs * D);
   if (!rc) rc = e->arena.alloc(&e->pooled_t, (size_t)e->max_seqs * D * es);
   if (!rc) rc = e->arena.alloc_t(&e->cond_latent, (size_t)16 * D);
@@ -129,10 +97,8 @@ int tt_cvvp_create(const tt_cvvp_config* cfg, const tt_cvvp_weights* w, tt_cvvp*
   if (!rc) rc = e->arena.alloc(&e->c0, cf * (D / 2) * es);
   if (!rc) rc = e->arena.alloc(&e->c0e, cf * (D / 2) * es);
   if (!rc) rc = e->arena.alloc_t(&e->even_idx, cf);
-  if (!rc) {
-    cvvp_even_rows_kernel<<<cdiv((int)cf, 256), 256>>>(e->even_idx, (int)cf);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { set_error("tt_cvvp_create: index fill failed"); rc = -2; }
-  }
+  if (!rc) rc = even_rows_index_launch(e->even_idx, (int)cf, nullptr);
+  if (!rc && hipDeviceSynchronize() != hipSuccess) { set_error("tt_cvvp_create: index fill failed"); rc = -2; }
   if (rc) {
     tt_cvvp_destroy(e);
     return rc;
@@ -153,19 +119,11 @@ int tt_cvvp_score(tt_cvvp* e, const float* mels, int n_clips, int T, const int* 
   TT_REQUIRE(B >= 1 && n >= 8 && (size_t)B * n <= (size_t)e->cfg.max_rows && B <= e->max_seqs, "tt_cvvp_score: B=%d n=%d exceed capacity %d rows (n must be >= 8)", B, n, e->cfg.max_rows);
   return e->sb.run((hipStream_t)stream, [&](hipStream_t s) -> int {
     const int D = e->cfg.dim, D2 = D / 2, MC = e->cfg.mel_channels, MP = e->cfg.mel_pad, dt = e->cfg.dtype;
-    const int es = dtype_bytes(dt);
     const int T2 = (T + 1) / 2, T3 = (T2 + 1) / 2;  // Conv1d(stride 2) with "same" padding: ceil(n / 2) outputs, output j = the stride-1 result at 2 j
     for (int c = 0; c < n_clips; ++c) {
-      TT_TRY(transpose_launch(mels + (size_t)c * MC * T, e->mel_t, MC, T, s));          // [mel][T] -> [T][mel]
-      TT_TRY(cast_pad_launch(dt, e->mel_t, MC, e->mel_op, MP, T, MC, MP, s));
-      GemmArgs g = gemm_args(e->mel_op, MP, e->w.w_cond0, 5 * MP, T, D2, 5 * MP);
-      g.taps = 5; g.seq_len = T; g.bias = e->w.b_cond0; g.out_t = e->c0; g.ldot = D2;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      TT_TRY(gather_rows_launch((const float*)e->c0, e->even_idx, (float*)e->c0e, T2, D2 * es / 4, s));  // rows of D2 elements as 4-byte words
-      g = gemm_args(e->c0e, D2, e->w.w_cond1, 3 * D2, T2, D, 3 * D2);
-      g.taps = 3; g.seq_len = T2; g.bias = e->w.b_cond1; g.out_f32 = e->ha; g.ldo32 = D;
-      TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-      TT_TRY(gather_rows_launch(e->ha, e->even_idx, e->x, T3, D, s));
+      TT_TRY(mel_operand(dt, mels + (size_t)c * MC * T, MC, MP, T, e->mel_t, e->mel_op, s));
+      TT_TRY(conv_stride2(dt, e->mel_op, MP, e->w.w_cond0, 5, T, D2, e->w.b_cond0, e->c0, e->c0e, false, e->even_idx, s));
+      TT_TRY(conv_stride2(dt, e->c0e, D2, e->w.w_cond1, 3, T2, D, e->w.b_cond1, e->ha, e->x, true, e->even_idx, s));
       TT_TRY(cvvp_tower_run(e, e->cond, 1, T3, e->cond_latent + (size_t)c * D, s));
     }
     TT_TRY(gather_rows_launch(e->w.speech_emb, codes, e->x, B * n, D, s));
@@ -179,8 +137,7 @@ int tt_cvvp_score(tt_cvvp* e, const float* mels, int n_clips, int T, const int* 
 
 int tt_cvvp_guard(tt_cvvp* e, int reset) {
   if (!e) { set_error("tt_cvvp_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_cvvp_guard", "CVVP stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
+  return e->read_guard(reset, "tt_cvvp_guard", "CVVP", e->cfg.dtype);
 }
 
 }  // extern "C"

@@ -16,8 +16,7 @@
 // are all indexed by a device-side step counter, so one captured hipGraph replays every step.
 // The deterministic solvers of include/tortoise_mi355x_solver.h (DDIM, DPM-Solver++(2M)) run the same loop with another epilogue
 // kernel and their own kept graph (DiffUpdate, diff_sample_run).
-#include "runtime.h"
-#include "../../include/tortoise_mi355x.h"
+#include "stage_blocks.h"
 #include "../../include/tortoise_mi355x_solver.h"
 
 using namespace tt;
@@ -103,15 +102,10 @@ struct tt_diff : EngineHandle {
 
 // ss: scale / shift rows [2C]; batch row b reads ss + (b / ss_div) * ss_stride (ss_stride 0: one row for the whole batch)
 static int run_gn(tt_diff* e, DiffWork& w_, const float* x, int B, int S, const float* g, const float* b, const float* ss, size_t ss_stride, int ss_div,
-                  int act, void* out_t, int ldot, float* out_f32, hipStream_t s) {
-  GroupNormArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.B = B; a.S = S; a.C = e->C; a.gamma = g; a.beta = b; a.eps = 1e-5f;
-  a.scale_shift = ss; a.ss_batch_stride = ss_stride; a.ss_batch_div = ss_div; a.act = act;
+                  int act, void* out_t, float* out_f32, hipStream_t s) {
+  GroupNormArgs a = groupnorm_args(x, B, S, e->C, g, b, 1e-5f, act, out_t, out_f32, w_.gn_partial, e->guard.dev);
   // per-step scale / shift rows are staged at a fixed address (e->ss_cur): no step-dependent addressing in the kernel
-  a.out_t = out_t; a.ldot = ldot; a.out_f32 = out_f32; a.ldo32 = e->C;
-  a.partial = w_.gn_partial;
-  a.guard = e->guard.dev;
+  a.scale_shift = ss; a.ss_batch_stride = ss_stride; a.ss_batch_div = ss_div;
   if (e->masked) {
     a.vperiod = e->U;
     for (int u = 0; u < e->U; ++u) a.vlen[u] = e->Su[u];
@@ -150,23 +144,14 @@ static int gemm_with_stats(tt_diff* e, DiffWork& w_, GemmArgs& g, int S, hipStre
 // AttentionBlock (arch_util.py:80-123): out = in + proj(attn(qkv(GN(in))))
 static int run_attn_block(tt_diff* e, DiffWork& w_, const tt_attn_block& w, const float* in, int B, int S, float* out_f32, void* out_t, int ldot,
                           hipStream_t s) {
-  const int C = e->C, H = e->H, dt = e->cfg.dtype, M = B * S, n_pad = round_up(S, 32);
-  GemmArgs g = gemm_args(w_.act, C, w.w_qkv, C, M, 3 * C, C);
-  g.bias = w.b_qkv; g.seq_len = S; g.dmodel = C; g.heads = H; g.q = w_.q; g.k = w_.k; g.vt = w_.vt; g.seq_pad = n_pad;
-  g.q_scale = 0.125f;  // (q * 64^-1/4) . (k * 64^-1/4)  ==  (q/8) . k   (arch_util.py:64-67)
-  TT_TRY(run_gn(e, w_, in, B, S, w.norm_g, w.norm_b, nullptr, 0, 1, ACT_NONE, w_.act, C, nullptr, s));
-  TT_TRY(gemm_launch(dt, EPI_QKV_HEADS, g, s));
-  FlashArgs f;
-  memset(&f, 0, sizeof(f));
-  f.q = w_.q; f.k = w_.k; f.vt = w_.vt; f.out = w_.att; f.ldo = C; f.BH = B * H; f.heads = H; f.n = S; f.n_pad = n_pad;
-  f.relpos = w.relpos;
-  if (e->masked) {
-    f.nv_period = e->U;
-    for (int u = 0; u < e->U; ++u) f.nv[u] = e->Su[u];
-  }
-  TT_TRY(flash_attention_launch(dt, f, s));
-  g = gemm_args(w_.att, C, w.w_proj, C, M, C, C);
-  g.bias = w.b_proj; g.res = in; g.ldres = C; g.out_f32 = out_f32; g.ldo32 = C; g.out_t = out_t; g.ldot = ldot;
+  const int C = e->C;
+  TT_TRY(run_gn(e, w_, in, B, S, w.norm_g, w.norm_b, nullptr, 0, 1, ACT_NONE, w_.act, nullptr, s));
+  HeadsAttnOpts o;
+  o.relpos = w.relpos;
+  if (e->masked) { o.nv_period = e->U; o.nv = e->Su; }
+  TT_TRY(heads_attention(e->cfg.dtype, w_.act, w.w_qkv, w.b_qkv, w_.q, w_.k, w_.vt, w_.att, B, S, C, e->H, s, o));
+  GemmArgs g = gemm_residual_args(w_.att, C, w.w_proj, C, B * S, C, C, w.b_proj, in, out_f32);
+  g.out_t = out_t; g.ldot = ldot;
   return gemm_with_stats(e, w_, g, S, s);
 }
 
@@ -174,8 +159,7 @@ static int run_attn_block(tt_diff* e, DiffWork& w_, const tt_attn_block& w, cons
 static int run_res_block(tt_diff* e, DiffWork& w_, const tt_res_block& w, const float* ss, size_t ss_stride, int ss_div, const float* in, int B, int S,
                          float* out_f32, hipStream_t s) {
   const int C = e->C, dt = e->cfg.dtype, M = B * S;
-  GemmArgs g = gemm_args(w_.act, C, w.w_in, C, M, C, C);
-  g.bias = w.b_in; g.out_f32 = w_.tmp_c; g.ldo32 = C;
+  GemmArgs g = gemm_f32_args(w_.act, C, w.w_in, C, M, C, C, w.b_in, w_.tmp_c);
   bool fused_gn = false;
   if (e->fuse_gn && !e->masked && in == w_.stats_ptr && w_.stats_seq == S && S >= w_.stats_rows) {
     // in_layers as ONE launch: GroupNorm32 + SiLU applied on the 1x1 conv's A path (gemm_gna.h), statistics for out_layers' norm in its epilogue
@@ -194,12 +178,12 @@ static int run_res_block(tt_diff* e, DiffWork& w_, const tt_res_block& w, const 
     }
   }
   if (!fused_gn) {
-    TT_TRY(run_gn(e, w_, in, B, S, w.gn1_g, w.gn1_b, nullptr, 0, 1, ACT_SILU, w_.act, C, nullptr, s));
+    TT_TRY(run_gn(e, w_, in, B, S, w.gn1_g, w.gn1_b, nullptr, 0, 1, ACT_SILU, w_.act, nullptr, s));
     TT_TRY(gemm_with_stats(e, w_, g, S, s));
   }
-  TT_TRY(run_gn(e, w_, w_.tmp_c, B, S, w.gn2_g, w.gn2_b, ss, ss_stride, ss_div, ACT_SILU, w_.act, C, nullptr, s));
-  g = gemm_args(w_.act, C, w.w_out, 3 * C, M, C, 3 * C);
-  g.taps = 3; g.seq_len = S; g.bias = w.b_out; g.res = in; g.ldres = C; g.out_f32 = out_f32; g.ldo32 = C;
+  TT_TRY(run_gn(e, w_, w_.tmp_c, B, S, w.gn2_g, w.gn2_b, ss, ss_stride, ss_div, ACT_SILU, w_.act, nullptr, s));
+  g = gemm_conv_args(w_.act, C, w.w_out, 3, M, S, C, w.b_out);
+  g.res = in; g.ldres = C; g.out_f32 = out_f32; g.ldo32 = C;
   return gemm_with_stats(e, w_, g, S, s);
 }
 
@@ -247,13 +231,12 @@ static int diff_forward(tt_diff* e, int B, hipStream_t s) {
   DiffWork& w_ = e->wk[0];
   w_.stats_ptr = nullptr;       // no epilogue statistics are valid at the start of a pass
   // inp_block (k3, in_pad -> C): left half of the integrating conv's K
-  GemmArgs g = gemm_args(e->x_t, e->cfg.in_pad, e->w.w_inp, 3 * e->cfg.in_pad, M, C, 3 * e->cfg.in_pad);
-  g.taps = 3; g.seq_len = S; g.bias = e->w.b_inp; g.out_t = e->cat; g.ldot = C;
+  GemmArgs g = gemm_conv_args(e->x_t, e->cfg.in_pad, e->w.w_inp, 3, M, S, C, e->w.b_inp);
+  g.out_t = e->cat; g.ldot = C;
   TT_TRY(gemm_launch(dt, EPI_STD, g, s));
   // integrating_conv over [inp_block(x) | integrator(code_emb, t)]: the right half comes straight from this slot's slice
-  g = gemm_args(e->cat, C, e->w.w_integ, 2 * C, M, C, 2 * C);
+  g = gemm_f32_args(e->cat, C, e->w.w_integ, 2 * C, M, C, 2 * C, e->w.b_integ, w_.tmp_a);
   g.A2 = e->integ_all; g.lda2 = C; g.k_split = C; g.a2_slot = e->slot; g.a2_slot_stride = (size_t)B * S * C;
-  g.bias = e->w.b_integ; g.out_f32 = w_.tmp_a; g.ldo32 = C;
   TT_TRY(gemm_with_stats(e, w_, g, S, s));
   float* hcur = w_.tmp_a;
   float* hoth = w_.tmp_b;
@@ -265,9 +248,9 @@ static int diff_forward(tt_diff* e, int B, hipStream_t s) {
     TT_TRY(run_res_block(e, w_, e->res[3 + L + i], ss + (size_t)(3 + L + i) * 2 * C, 0, 1, hcur, B, S, hoth, s));
     float* t = hcur; hcur = hoth; hoth = t;
   }
-  TT_TRY(run_gn(e, w_, hcur, B, S, e->w.out_gn_g, e->w.out_gn_b, nullptr, 0, 1, ACT_SILU, w_.act, C, nullptr, s));
-  g = gemm_args(w_.act, C, e->w.w_final, 3 * C, M, e->cfg.out_channels, 3 * C);
-  g.taps = 3; g.seq_len = S; g.bias = e->w.b_final; g.out_f32 = e->out; g.ldo32 = e->cfg.out_channels;
+  TT_TRY(run_gn(e, w_, hcur, B, S, e->w.out_gn_g, e->w.out_gn_b, nullptr, 0, 1, ACT_SILU, w_.act, nullptr, s));
+  g = gemm_conv_args(w_.act, C, e->w.w_final, 3, M, S, e->cfg.out_channels, e->w.b_final);
+  g.out_f32 = e->out; g.ldo32 = e->cfg.out_channels;
   return gemm_launch(dt, EPI_STD, g, s);
 }
 
@@ -292,14 +275,10 @@ static int diff_prepare_timesteps(tt_diff* e, int n, hipStream_t s) {
   GemmArgs g = gemm_args(e->temb_t, C, e->w.w_time1, C, n, C, C);
   g.bias = e->w.b_time1; g.act = ACT_SILU; g.out_t = e->temb_t2; g.ldot = C;
   TT_TRY(gemm_launch(dt, EPI_STD, g, s));
-  g = gemm_args(e->temb_t2, C, e->w.w_time2, C, n, C, C);
-  g.bias = e->w.b_time2; g.out_f32 = e->temb_mid; g.ldo32 = C;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->temb_t2, C, e->w.w_time2, C, n, C, C, e->w.b_time2, e->temb_mid), s));
   TT_TRY(silu_cast_launch(dt, e->temb_mid, e->temb_t, n * C, s));
   const int N = e->NR * 2 * C;
-  g = gemm_args(e->temb_t, C, e->w.w_emb_all, C, n, N, C);
-  g.bias = e->w.b_emb_all; g.out_f32 = e->ss_all; g.ldo32 = N;
-  TT_TRY(gemm_launch(dt, EPI_STD, g, s));
+  TT_TRY(gemm_launch(dt, EPI_STD, gemm_f32_args(e->temb_t, C, e->w.w_emb_all, C, n, N, C, e->w.b_emb_all, e->ss_all), s));
   e->n_steps_cur = n;
   TT_CHECK_HIP(hipMemcpyAsync(e->ss_cur, e->ss_all, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));  // step 0
   return 0;
@@ -378,7 +357,7 @@ int tt_diff_create(const tt_diff_config* cfg, const tt_diff_weights* w, tt_diff*
     if (!rc) rc = e->arena.alloc(&w_.k, r * C * es);
     if (!rc) rc = e->arena.alloc(&w_.vt, (size_t)C * (2 * r + 64) * es);  // per sample C x round_up(S, 32) keys: <= 2x the rows for short sequences
     if (!rc) rc = e->arena.alloc(&w_.att, r * C * es);
-    if (!rc) rc = e->arena.alloc_t(&w_.gn_partial, (r / 16 + r + 64) * 64);  // [samples][row chunks >= 16 rows][32][2], worst case one-row samples
+    if (!rc) rc = e->arena.alloc_t(&w_.gn_partial, groupnorm_partial_floats_rows(r));  // any split of r rows into samples, down to one-row samples
     if (!rc) rc = e->arena.alloc_t(&w_.gn_gemm_part, (r / 32 + 2) * 2 * (C / 16) * 2 + 64);
     if (!rc) rc = e->arena.alloc_t(&w_.gn_gemm_part2, (r / 32 + 2) * 2 * (C / 16) * 2 + 64);
   }
@@ -433,8 +412,8 @@ static int diff_condition_into(tt_diff* e, const float* latents, int M, const fl
   e->masked = false;
   w_.stats_ptr = nullptr;
   TT_TRY(cast_pad_launch(dt, latents, LC, e->lat_t, LC, M, LC, LC, s));
-  GemmArgs g = gemm_args(e->lat_t, LC, e->w.w_latent_conv, 3 * LC, M, C, 3 * LC);
-  g.taps = 3; g.seq_len = M; g.bias = e->w.b_latent_conv; g.out_f32 = w_.tmp_a; g.ldo32 = C;
+  GemmArgs g = gemm_conv_args(e->lat_t, LC, e->w.w_latent_conv, 3, M, M, C, e->w.b_latent_conv);
+  g.out_f32 = w_.tmp_a; g.ldo32 = C;
   TT_TRY(gemm_with_stats(e, w_, g, M, s));
   float* cur = w_.tmp_a;
   float* oth = w_.tmp_b;
@@ -443,7 +422,7 @@ static int diff_condition_into(tt_diff* e, const float* latents, int M, const fl
     float* t = cur; cur = oth; oth = t;
   }
   // code_norm(h) * (1 + cond_scale) + cond_shift   (diffusion_decoder.py:249-250)
-  TT_TRY(run_gn(e, w_, cur, 1, M, e->w.code_norm_g, e->w.code_norm_b, cond, 0, 1, ACT_NONE, nullptr, 0, oth, s));
+  TT_TRY(run_gn(e, w_, cur, 1, M, e->w.code_norm_g, e->w.code_norm_b, cond, 0, 1, ACT_NONE, nullptr, oth, s));
   TT_TRY(gather_rows_launch(oth, interp_idx, dst_cond, S, C, s));        // F.interpolate(nearest)
   TT_TRY(broadcast_rows_launch(e->w.uncond_emb, dst_uncond, S, C, s));   // unconditioned_embedding.repeat
   w_.stats_ptr = nullptr;
@@ -793,8 +772,7 @@ int tt_diff_set_option(tt_diff* e, int option, int value) {
 // the last reset, as of the end of the last finished tt_diff_sample / tt_diff_sample_batch / tt_diff_split_end.  reset != 0 clears it.
 int tt_diff_guard(tt_diff* e, int reset) {
   if (!e) { set_error("tt_diff_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_diff_guard", "diffusion stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: re-run this stage with bf16 operands" : "bf16");
+  return e->read_guard(reset, "tt_diff_guard", "diffusion", e->cfg.dtype, "kernel(s) met non-finite values", "fp16: re-run this stage with bf16 operands");
 }
 
 }  // extern "C"

@@ -953,8 +953,7 @@ int tt_ar_latents(tt_ar* e, const float* emb, int k, int n, float* out, void* st
 // synchronised its stream).  reset != 0 clears the counter.  Returns the count (>= 0) or a negative error.
 int tt_ar_guard(tt_ar* e, int reset) {
   if (!e) { set_error("tt_ar_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_ar_guard", "autoregressive stage: %d kernel(s) met non-finite values (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: use bf16 operands for this stage" : "bf16");
+  return e->read_guard(reset, "tt_ar_guard", "autoregressive", e->cfg.dtype);
 }
 
 // Counters for tests / diagnostics: 0 = decode-step graph captures so far, 1 = queue drains of the launch loop (expected 0),

@@ -74,6 +74,16 @@ int gather_rows_launch(const float* src, const int* idx, float* dst, int rows, i
   return 0;
 }
 
+__global__ void even_rows_index_kernel(int* idx, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) idx[i] = 2 * i;
+}
+int even_rows_index_launch(int* idx, int n, hipStream_t stream) {
+  even_rows_index_kernel<<<cdiv(n, 256), 256, 0, stream>>>(idx, n);
+  TT_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 __global__ void mean_rows_kernel(const float* src, float* dst, int n, int C) {
   const int b = blockIdx.y;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;

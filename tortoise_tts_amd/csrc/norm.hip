@@ -398,5 +398,9 @@ int groupnorm_launch(int dtype, const GroupNormArgs& a0, hipStream_t stream) {
 }
 
 size_t groupnorm_partial_floats(int B, int S) { return (size_t)B * cdiv(S, gn_rows_per_chunk(S)) * 32 * 2; }
+// The workspace of any batch whose samples total at most `rows` rows, whatever its split into samples: a sample of S rows has
+// cdiv(S, max(GN_ROWS, ..)) <= S / GN_ROWS + 1 chunks; summed over the samples that is <= rows / GN_ROWS + one per sample, and there are at most
+// `rows` samples (one-row samples): <= rows / GN_ROWS + rows chunks of [32 groups][sum, sumsq].  64 chunks of slack on top.
+size_t groupnorm_partial_floats_rows(size_t rows) { return (rows / GN_ROWS + rows + 64) * 32 * 2; }
 
 }  // namespace tt

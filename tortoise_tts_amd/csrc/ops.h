@@ -86,6 +86,7 @@ int groupnorm_launch(int dtype, const GroupNormArgs& a, hipStream_t stream);
 struct GroupNormRan { int stats, apply, rows, fused; };
 extern thread_local GroupNormRan g_groupnorm_ran;  // norm.hip
 size_t groupnorm_partial_floats(int B, int S);
+size_t groupnorm_partial_floats_rows(size_t rows);  // enough for ANY batch whose samples total at most `rows` rows
 
 // ------------------------------------------------------------------------------ attention
 struct FlashArgs {
@@ -289,6 +290,8 @@ int rotary_launch(int dtype, void* q, void* k, void* vt, const float* inv_freq, 
                   hipStream_t stream);
 // dst[r][:] = src[idx[r]][:]   (f32 rows of C floats)
 int gather_rows_launch(const float* src, const int* idx, float* dst, int rows, int C, hipStream_t stream);
+// idx[i] = 2 i for i < n: the gather index of a stride-2 convolution's outputs (stage_blocks.h conv_stride2)
+int even_rows_index_launch(int* idx, int n, hipStream_t stream);
 // dst[b][:] = mean over n rows of src[b][n][:]
 int mean_rows_launch(const float* src, float* dst, int B, int n, int C, hipStream_t stream);
 // CLVP tail: out[b] = <normalize(t[b or 0]), normalize(s[b])> * exp(temperature)

@@ -95,11 +95,11 @@ struct OverflowGuard {
     TT_CHECK_HIP(hipMemcpyAsync(host, dev, sizeof(int), hipMemcpyDeviceToHost, s));
     return 0;
   }
-  // The count as of the last snapshot (>= 0), or a negative error.  A non-zero count becomes the error message: fmt takes the count
-  // (%d) and `detail` (%s).  reset != 0 clears it on stream s.
-  int read(int reset, hipStream_t s, const char* who, const char* fmt, const char* detail) {
+  // The count as of the last snapshot (>= 0), or a negative error.  A non-zero count becomes the error message "<stage> stage: <count>
+  // <met> (operand overflow in <detail>)".  reset != 0 clears it on stream s.
+  int read(int reset, hipStream_t s, const char* who, const char* stage, const char* met, const char* detail) {
     const int n = host[0];
-    if (n > 0) set_error(fmt, n, detail);
+    if (n > 0) set_error("%s stage: %d %s (operand overflow in %s)", stage, n, met, detail);
     if (reset && n > 0) {  // (a clean counter needs no device work: this sits at the end of every utterance)
       if (hipMemsetAsync(dev, 0, 4 * sizeof(int), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         set_error("%s: reset failed", who);
@@ -179,6 +179,12 @@ struct EngineHandle {
   int open(const char* who, bool with_guard) {
     TT_TRY(sb.init());
     return with_guard ? guard.init(arena, who) : 0;
+  }
+  // The body of every tt_*_guard entry point `who`: the guard of the `stage` stage as of its last finished run; the fp16 case of the
+  // message ends in the stage's advice.
+  int read_guard(int reset, const char* who, const char* stage, int dtype, const char* met = "kernel(s) met non-finite values",
+                 const char* f16_advice = "fp16: use bf16 operands for this stage") {
+    return guard.read(reset, sb.own, who, stage, met, dtype == DT_F16 ? f16_advice : "bf16");
   }
   void close() {
     (void)hipDeviceSynchronize();

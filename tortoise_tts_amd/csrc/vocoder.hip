@@ -133,8 +133,7 @@ void tt_voc_destroy(tt_voc* e) {
 // last tt_voc_run after the caller synchronised its stream.  reset != 0 clears it.
 int tt_voc_guard(tt_voc* e, int reset) {
   if (!e) { set_error("tt_voc_guard: null handle"); return -1; }
-  return e->guard.read(reset, e->sb.own, "tt_voc_guard", "vocoder stage: %d workgroup(s) met non-finite predicted kernels (operand overflow in %s)",
-                       e->cfg.dtype == DT_F16 ? "fp16: re-run this stage with bf16 operands" : "bf16");
+  return e->read_guard(reset, "tt_voc_guard", "vocoder", e->cfg.dtype, "workgroup(s) met non-finite predicted kernels", "fp16: re-run this stage with bf16 operands");
 }
 
 int tt_voc_batch_abi_version(void) { return 1; }  // ABI changes
