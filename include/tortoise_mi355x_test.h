@@ -216,6 +216,59 @@ int tt_op_convt1d(const float* x, const float* w, const float* bias, float* y, i
 /* location-variable convolution + gate (vocoder.py:182-216, 178-179); kernels [L][ldk] in the operand type `dtype` (TT_F32: float) */
 int tt_op_lvc(int dtype, const float* x_in, const void* kernels, int ldk, int koff, const float* bias, int ldb, int boff, float* x, int L,
               int hop, void* stream);
+/* The three audio-rate UnivNet launches with every argument: the caller-set fields of csrc/ops.h Conv1dArgs, ConvT1dArgs and LvcArgs with the
+ * same meanings; the problem goes to conv1d_direct_launch / convt1d_launch / lvc_launch unchanged.  seq_n, seq_mul, seq_frames are the ragged
+ * batch (VocSeqs; include/tortoise_mi355x_univnet.h): seq_n = 0 is one sequence that fills the tensor; seq_n = 1 .. 32 sequences own slot b of
+ * every tensor ([C][P], P = T / Tin / L * hop columns; Tin * stride for the transposed convolution's output) and their first
+ * seq_frames[b] * seq_mul columns are valid (the LVC: seq_frames[b] frames of hop columns, seq_mul unused; its kernel and bias rows are
+ * b * L + l).  in_slope >= 0 applies LeakyReLU to the input, negative none; out_act 0 none, 4 LeakyReLU(out_slope), 5 tanh.  With reflect set
+ * every sequence must be longer than (k / 2) * dilation columns: the launcher refuses anything shorter.  ran (optional, int[4]) receives what
+ * launched, recorded on the host by the launch path ({-1, 0, 0, 0} when the launcher refused the problem):
+ *   conv1d   {kernel (0 conv1d_direct_kernel<32>, 1 conv1d_direct_kernel<1>, 2 conv1d_mfma_kernel), grid.x, grid.y, 0}
+ *   convt1d  {0, grid.x, grid.y, grid.z}
+ *   lvc      {kernel (0 lvc_kernel, 1 lvc_mfma_kernel), HOP template argument, kernel element type (0 f32, 1 bf16, 2 f16), 0} */
+typedef struct tt_op_conv1d_desc {
+  const float* x;        /* [Cin][T] */
+  const float* w;        /* [Cout][Cin][k] */
+  const float* bias;     /* [Cout] or NULL */
+  float* y;              /* [Cout][T] */
+  int Cin, Cout, T, k, dilation;
+  int seq_n, seq_mul;
+  int seq_frames[32];
+  int reflect;
+  float in_slope;
+  int out_act;
+  float out_slope;
+} tt_op_conv1d_desc;
+size_t tt_op_conv1d_desc_size(void);
+int tt_op_conv1d_ex(const tt_op_conv1d_desc* d, int* ran, void* stream);
+typedef struct tt_op_convt1d_desc {
+  const float* x;        /* [C][Tin] */
+  const float* w;        /* [C][C][2 * stride] */
+  const float* bias;     /* [C] */
+  float* y;              /* [C][Tin * stride] */
+  int C, Tin, stride;
+  float in_slope;
+  int seq_n, seq_mul;
+  int seq_frames[32];
+} tt_op_convt1d_desc;
+size_t tt_op_convt1d_desc_size(void);
+int tt_op_convt1d_ex(const tt_op_convt1d_desc* d, int* ran, void* stream);
+typedef struct tt_op_lvc_desc {
+  const float* x_in;     /* [32][L * hop] */
+  const void* kernels;   /* [L][ldk] in the type dtype (TT_BF16 / TT_F16 / TT_F32), the [32][64][3] block at column koff */
+  int ldk, koff, dtype;
+  const float* bias;     /* [L][ldb], the [64] block at column boff */
+  int ldb, boff;
+  float* x;              /* [32][L * hop], updated in place */
+  int L, hop;
+  int seq_n, seq_mul;
+  int seq_frames[32];
+  float in_slope;
+  int* guard;            /* DEVICE counter of waves that staged a non-finite kernel value, or NULL */
+} tt_op_lvc_desc;
+size_t tt_op_lvc_desc_size(void);
+int tt_op_lvc_ex(const tt_op_lvc_desc* d, int* ran, void* stream);
 
 /* wav2vec2 aligner front (csrc/align.hip, include/tortoise_mi355x_align.h).  Resampler: y f32 [ceil(2 S / 3)] = torchaudio's 24 -> 16 kHz
  * resample of x f32 [S] with taps f32 [2][23]; stats f32 [2] = {mean, 1 / sqrt(unbiased var + 1e-7)} of y; workspace of

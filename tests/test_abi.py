@@ -44,11 +44,13 @@ def test_struct_mirrors_match(lib):
     for i, st in enumerate(E.BOUNDARY_STRUCTS):
         assert C.sizeof(st) == lib.tt_struct_size(i), st.__name__
     assert lib.tt_abi_version() == 6
-    # the operator-level descriptors of the test header (tt_op_gemm_ex, tt_op_rownorm_ex, tt_op_groupnorm_ex), field by field: a reordered
-    # field keeps the size
+    # the operator-level descriptors of the test header (tt_op_gemm_ex, tt_op_rownorm_ex, tt_op_groupnorm_ex, tt_op_conv1d_ex, tt_op_convt1d_ex,
+    # tt_op_lvc_ex), field by field: a reordered field keeps the size
     src = open(os.path.join(ROOT, "include", "tortoise_mi355x_test.h")).read()
     for cname, mirror, size in (("tt_op_gemm_desc", E.GemmDesc, lib.tt_op_gemm_desc_size()), ("tt_op_rownorm_desc", E.RowNormDesc, lib.tt_op_rownorm_desc_size()),
-                                ("tt_op_groupnorm_desc", E.GroupNormDesc, lib.tt_op_groupnorm_desc_size())):
+                                ("tt_op_groupnorm_desc", E.GroupNormDesc, lib.tt_op_groupnorm_desc_size()),
+                                ("tt_op_conv1d_desc", E.Conv1dDesc, lib.tt_op_conv1d_desc_size()), ("tt_op_convt1d_desc", E.ConvT1dDesc, lib.tt_op_convt1d_desc_size()),
+                                ("tt_op_lvc_desc", E.LvcDesc, lib.tt_op_lvc_desc_size())):
         assert C.sizeof(mirror) == size, cname
         names = [f[0] for f in mirror._fields_]
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
@@ -58,6 +60,19 @@ def test_struct_mirrors_match(lib):
             rest = re.match(r"^(?:const\s+)?\w+\s*\**\s*(.*)$", decl, flags=re.S).group(1)
             declared += [re.sub(r"\[\d+\]", "", n).strip(" *") for n in rest.split(",")]
         assert declared == names, (cname, declared, names)
+
+
+def test_reflect_padding_the_kernel_cannot_index_is_refused_on_the_host(lib):
+    """conv1d_direct_kernel reflects an index once: conv1d_direct_launch refuses a sequence of no more than (k / 2) * dilation columns before
+    anything is launched (no device is touched: the pointers are never read), for the n = 0 form and for one short sequence of a batch"""
+    for T, n, mul, frames, k, d in ((3, 0, 0, (), 7, 1), (64, 2, 1, (64, 3), 7, 1), (64, 2, 3, (21, 1), 7, 1), (18, 0, 0, (), 7, 6), (1, 0, 0, (), 3, 1)):
+        desc = E.Conv1dDesc(Cin=32, Cout=32, T=T, k=k, dilation=d, reflect=1, in_slope=-1.0, seq_n=n, seq_mul=mul)
+        for i, f in enumerate(frames):
+            desc.seq_frames[i] = f
+        ran = (C.c_int * 4)(-2, -2, -2, -2)
+        rc = lib.tt_op_conv1d_ex(C.byref(desc), ran, None)
+        assert rc < 0 and b"reflect" in lib.tt_last_error(), (rc, lib.tt_last_error())
+        assert tuple(ran) == (-1, 0, 0, 0)
 
 
 def test_fails_loudly_without_gpu(lib):

@@ -405,6 +405,59 @@ int tt_op_lvc(int dtype, const float* x_in, const void* kernels, int ldk, int ko
   return lvc_launch(a, (hipStream_t)stream);
 }
 
+// the descriptor forms: every caller-set field of Conv1dArgs / ConvT1dArgs / LvcArgs, the ragged batch included
+static VocSeqs voc_desc_seqs(int n, int mul, const int* frames) {
+  VocSeqs q;
+  memset(&q, 0, sizeof(q));
+  q.n = n; q.mul = mul;
+  for (int i = 0; i < kVocSeqs; ++i) q.frames[i] = frames[i];
+  return q;
+}
+static void voc_ran(int* ran) {
+  if (ran) {
+    ran[0] = g_voc_ran.kernel; ran[1] = g_voc_ran.a; ran[2] = g_voc_ran.b; ran[3] = g_voc_ran.c;
+  }
+}
+
+size_t tt_op_conv1d_desc_size(void) { return sizeof(tt_op_conv1d_desc); }
+int tt_op_conv1d_ex(const tt_op_conv1d_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr, "tt_op_conv1d_ex: null descriptor");
+  Conv1dArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = d->x; a.w = d->w; a.bias = d->bias; a.y = d->y; a.Cin = d->Cin; a.Cout = d->Cout; a.T = d->T; a.k = d->k; a.dilation = d->dilation;
+  a.seq = voc_desc_seqs(d->seq_n, d->seq_mul, d->seq_frames);
+  a.reflect = d->reflect; a.in_slope = d->in_slope; a.out_act = d->out_act; a.out_slope = d->out_slope;
+  const int rc = conv1d_direct_launch(a, (hipStream_t)stream);
+  voc_ran(ran);
+  return rc;
+}
+
+size_t tt_op_convt1d_desc_size(void) { return sizeof(tt_op_convt1d_desc); }
+int tt_op_convt1d_ex(const tt_op_convt1d_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr, "tt_op_convt1d_ex: null descriptor");
+  ConvT1dArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = d->x; a.w = d->w; a.bias = d->bias; a.y = d->y; a.C = d->C; a.Tin = d->Tin; a.stride = d->stride; a.in_slope = d->in_slope;
+  a.seq = voc_desc_seqs(d->seq_n, d->seq_mul, d->seq_frames);
+  const int rc = convt1d_launch(a, (hipStream_t)stream);
+  voc_ran(ran);
+  return rc;
+}
+
+size_t tt_op_lvc_desc_size(void) { return sizeof(tt_op_lvc_desc); }
+int tt_op_lvc_ex(const tt_op_lvc_desc* d, int* ran, void* stream) {
+  TT_REQUIRE(d != nullptr, "tt_op_lvc_ex: null descriptor");
+  LvcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x_in = d->x_in; a.kernels = d->kernels; a.ldk = d->ldk; a.koff = d->koff; a.dtype = d->dtype; a.bias = d->bias; a.ldb = d->ldb; a.boff = d->boff;
+  a.x = d->x; a.L = d->L; a.hop = d->hop;
+  a.seq = voc_desc_seqs(d->seq_n, d->seq_mul, d->seq_frames);
+  a.in_slope = d->in_slope; a.guard = d->guard;
+  const int rc = lvc_launch(a, (hipStream_t)stream);
+  voc_ran(ran);
+  return rc;
+}
+
 }  // extern "C"
 
 // sizeof() of every struct that crosses the boundary, so host bindings can verify their mirrors

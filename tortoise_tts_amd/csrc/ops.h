@@ -374,7 +374,7 @@ struct Conv1dArgs {
   float* y;        // [Cout][T]
   int Cin, Cout, T, k, dilation;
   VocSeqs seq;     // ragged batch: x [n][Cin][T], y [n][Cout][T]
-  int reflect;     // reflect padding (k/2 * dilation each side) instead of zeros
+  int reflect;     // reflect padding (k/2 * dilation each side) instead of zeros; every sequence must be longer than k/2 * dilation columns
   float in_slope;  // LeakyReLU applied to the input when >= 0 (negative: none)
   int out_act;     // ACT_NONE / ACT_LRELU / 5 = tanh
   float out_slope;
@@ -401,8 +401,15 @@ struct LvcArgs {
   int L, hop;
   VocSeqs seq;          // ragged batch: x_in, x [n][32][L * hop], kernels / bias rows b * L + l; sequence b has frames[b] frames (mul unused)
   float in_slope;
-  int* guard;           // optional device counter: += 1 per workgroup that staged a non-finite predicted kernel value (operand-overflow guard)
+  int* guard;           // optional device counter: += 1 per wave that staged a non-finite predicted kernel value (operand-overflow guard; 1 .. 4 per frame)
 };
 int lvc_launch(const LvcArgs& a, hipStream_t stream);
+// What the last conv1d_direct_launch / convt1d_launch / lvc_launch of this host thread started (tt_op_conv1d_ex, tt_op_convt1d_ex, tt_op_lvc_ex;
+// include/tortoise_mi355x_test.h).  kernel = -1: the launcher refused the problem and started nothing.
+//   conv1d   {kernel (0 conv1d_direct_kernel<32>, 1 conv1d_direct_kernel<1>, 2 conv1d_mfma_kernel), grid.x, grid.y, 0}
+//   convt1d  {0, grid.x, grid.y, grid.z}
+//   lvc      {kernel (0 lvc_kernel, 1 lvc_mfma_kernel), HOP, kernel element type (0 f32, 1 bf16, 2 f16), 0}
+struct VocRan { int kernel, a, b, c; };
+extern thread_local VocRan g_voc_ran;  // univnet.hip
 
 }  // namespace tt

@@ -127,16 +127,27 @@ __global__ __launch_bounds__(256) void conv1d_mfma_kernel(Conv1dArgs a) {
 }
 
 bool g_voc_mfma = true;  // tt_voc_variant: 0 = the thread-per-sample VALU kernels (A/B runs)
+thread_local VocRan g_voc_ran = {-1, 0, 0, 0};
 
 int conv1d_direct_launch(const Conv1dArgs& a0, hipStream_t stream) {
+  g_voc_ran = VocRan{-1, 0, 0, 0};
   Conv1dArgs a = a0;
   a.seq = voc_seqs(a0.seq, a0.T);
   const int n = a.seq.n;
   TT_REQUIRE(n >= 1 && n <= kVocSeqs, "conv1d_direct: %d sequences (1 .. %d)", n, kVocSeqs);
   TT_REQUIRE(a.Cout == 32 || a.Cout == 1, "conv1d_direct: Cout=%d unsupported (32 or 1)", a.Cout);
+  if (a.reflect) {
+    // the kernel reflects an index once: a sequence of no more than (k / 2) * dilation columns would be indexed before its row
+    for (int b = 0; b < n; ++b)
+      TT_REQUIRE((long long)a.seq.frames[b] * a.seq.mul > (long long)(a.k / 2) * a.dilation,
+                 "conv1d_direct: reflect padding of %d needs longer sequences than %d columns (sequence %d)", (a.k / 2) * a.dilation,
+                 a.seq.frames[b] * a.seq.mul, b);
+  }
   if (g_voc_mfma && a.Cin == 32 && a.Cout == 32 && a.k == 3 && !a.reflect && a.dilation >= 1 && a.dilation <= CVM_MAXD) {
     ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T * n, 4.0 * (a.Cin + a.Cout) * (double)a.T * n);
-    conv1d_mfma_kernel<<<dim3(cdiv(a.T, CVM_TS), n), 256, 0, stream>>>(a);
+    const dim3 grid(cdiv(a.T, CVM_TS), n);
+    conv1d_mfma_kernel<<<grid, 256, 0, stream>>>(a);
+    g_voc_ran = VocRan{2, (int)grid.x, (int)grid.y, 0};
     TT_CHECK_HIP(hipGetLastError());
     return 0;
   }
@@ -146,6 +157,7 @@ int conv1d_direct_launch(const Conv1dArgs& a0, hipStream_t stream) {
   ProfScope ps(PROF_CONV1D, stream, 2.0 * a.Cin * a.Cout * a.k * (double)a.T * n, 4.0 * (a.Cin + a.Cout) * (double)a.T * n);
   if (a.Cout == 32) conv1d_direct_kernel<32><<<blocks, 256, smem, stream>>>(a);
   else conv1d_direct_kernel<1><<<blocks, 256, smem, stream>>>(a);
+  g_voc_ran = VocRan{a.Cout == 32 ? 0 : 1, (int)blocks.x, (int)blocks.y, 0};
   TT_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -188,6 +200,7 @@ __global__ __launch_bounds__(256) void convt1d_kernel(ConvT1dArgs a) {
   for (int co = 0; co < C; ++co) y[(size_t)co * ldo + t] = acc[co];
 }
 int convt1d_launch(const ConvT1dArgs& a0, hipStream_t stream) {
+  g_voc_ran = VocRan{-1, 0, 0, 0};
   ConvT1dArgs a = a0;
   a.seq = voc_seqs(a0.seq, a0.Tin);
   const int n = a.seq.n;
@@ -196,6 +209,7 @@ int convt1d_launch(const ConvT1dArgs& a0, hipStream_t stream) {
   dim3 grid(cdiv(a.Tin + 1, 256), a.stride, n);
   ProfScope ps(PROF_CONVT, stream, 2.0 * a.C * a.C * 2.0 * a.Tin * a.stride * n, 4.0 * a.C * (double)a.Tin * (1 + a.stride) * n);
   convt1d_kernel<<<grid, 256, 0, stream>>>(a);
+  g_voc_ran = VocRan{0, (int)grid.x, (int)grid.y, (int)grid.z};
   TT_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -348,6 +362,7 @@ __global__ __launch_bounds__(256) void lvc_mfma_kernel(LvcArgs a) {
 }
 
 int lvc_launch(const LvcArgs& a0, hipStream_t stream) {
+  g_voc_ran = VocRan{-1, 0, 0, 0};
   LvcArgs a = a0;
   a.seq = voc_seqs(a0.seq, a0.L);
   const int n = a.seq.n;
@@ -374,6 +389,7 @@ int lvc_launch(const LvcArgs& a0, hipStream_t stream) {
   else if (a.dtype == DT_BF16) TT_LVC(bf16);
   else TT_LVC(f16);
 #undef TT_LVC
+  g_voc_ran = VocRan{mfma ? 1 : 0, a.hop, a.dtype == DT_F32 ? 0 : a.dtype == DT_BF16 ? 1 : 2, 0};
   TT_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -260,6 +260,30 @@ class GroupNormDesc(C.Structure):
                 ("guard", vp)]
 
 
+class Conv1dDesc(C.Structure):
+    """tt_op_conv1d_desc (include/tortoise_mi355x_test.h): every argument of the audio-rate conv1d launch, the ragged batch included."""
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("y", vp)] + [(n, C.c_int) for n in ("Cin", "Cout", "T", "k", "dilation", "seq_n", "seq_mul")] + [
+        ("seq_frames", C.c_int * 32), ("reflect", C.c_int), ("in_slope", C.c_float), ("out_act", C.c_int), ("out_slope", C.c_float)]
+
+
+class ConvT1dDesc(C.Structure):
+    """tt_op_convt1d_desc (include/tortoise_mi355x_test.h)"""
+    _fields_ = [("x", vp), ("w", vp), ("bias", vp), ("y", vp), ("C", C.c_int), ("Tin", C.c_int), ("stride", C.c_int), ("in_slope", C.c_float),
+                ("seq_n", C.c_int), ("seq_mul", C.c_int), ("seq_frames", C.c_int * 32)]
+
+
+class LvcDesc(C.Structure):
+    """tt_op_lvc_desc (include/tortoise_mi355x_test.h)"""
+    _fields_ = [("x_in", vp), ("kernels", vp), ("ldk", C.c_int), ("koff", C.c_int), ("dtype", C.c_int), ("bias", vp), ("ldb", C.c_int),
+                ("boff", C.c_int), ("x", vp), ("L", C.c_int), ("hop", C.c_int), ("seq_n", C.c_int), ("seq_mul", C.c_int),
+                ("seq_frames", C.c_int * 32), ("in_slope", C.c_float), ("guard", vp)]
+
+
+# tt_op_conv1d_ex / tt_op_lvc_ex `ran` records (csrc/ops.h VocRan)
+CONV1D_KERNELS = {-1: "-", 0: "conv1d_direct_kernel<32>", 1: "conv1d_direct_kernel<1>", 2: "conv1d_mfma_kernel"}
+LVC_KERNELS = {-1: "-", 0: "lvc_kernel", 1: "lvc_mfma_kernel"}
+LVC_ELEM = {"f32": 0, "bf16": 1, "f16": 2}
+
 # tt_op_rownorm_ex / tt_op_groupnorm_ex `ran` records (csrc/ops.h RowNormRan, GroupNormRan)
 NORM_NONE, NORM_LAYER, NORM_RMS = 0, 1, 2
 ROWNORM_KERNELS = {0: "generic", 1: "narrow", 2: "wave"}
@@ -602,6 +626,12 @@ _TEST_PROTOS = {
     "tt_op_conv1d": (_i, [vp, vp, vp, vp, _i, _i, _i, _i, _i, _i, _f, _i, _f, vp]),
     "tt_op_convt1d": (_i, [vp, vp, vp, vp, _i, _i, _i, _f, vp]),
     "tt_op_lvc": (_i, [_i, vp, vp, _i, _i, vp, _i, _i, vp, _i, _i, vp]),
+    "tt_op_conv1d_desc_size": (_sz, []),
+    "tt_op_conv1d_ex": (_i, [C.POINTER(Conv1dDesc), C.POINTER(_i), vp]),
+    "tt_op_convt1d_desc_size": (_sz, []),
+    "tt_op_convt1d_ex": (_i, [C.POINTER(ConvT1dDesc), C.POINTER(_i), vp]),
+    "tt_op_lvc_desc_size": (_sz, []),
+    "tt_op_lvc_ex": (_i, [C.POINTER(LvcDesc), C.POINTER(_i), vp]),
     "tt_op_w2v_resample_workspace": (_sz, [_i]),
     "tt_op_w2v_resample": (_i, [vp, _i, vp, vp, vp, vp, vp]),
     "tt_op_w2v_conv0": (_i, [_i, vp, vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
