@@ -256,6 +256,66 @@ class StreamResampler:
         self.close()
 
 
+class StreamLeveler:
+    """One stream brought to a level (_Common.open_leveler): f32 chunks at 24 kHz in, f32 tensors on the device out (possibly empty) - a
+    slot of a stages.StreamLevelStage.  Under the look-ahead limiter an output appears once the 248 input samples behind it are in
+    (latency_seconds, 10.3 ms); finish() ends the stream and frees the slot.  reading() is the stream's loudness.StreamLevel so far.  A
+    context manager: leaving it closes the stream."""
+
+    def __init__(self, stage, settings):
+        self.stage, self.settings = stage, settings
+        self.closed = False
+        self.slot = stage.open(settings)
+        self.n_in = self.n_out = 0
+        self._last = None
+        self.latency_seconds = (E.LVS_DELAY if settings.limit == E.LVS_LOOKAHEAD else 0) / float(E.LOUD_SAMPLE_RATE)
+
+    def _push(self, chunk, flush):
+        if self.closed:
+            raise ValueError("this leveling stream is closed")
+        x = torch.as_tensor(chunk, dtype=torch.float32).reshape(-1)
+        y = self.stage.push_many([(self.slot, x, flush)])[0]
+        self.n_in += x.shape[0]
+        self.n_out += y.shape[0]
+        return y
+
+    def push(self, chunk):
+        return self._push(chunk, False)
+
+    def finish(self, chunk=None):
+        """The outputs still due (after an optional last chunk); the stream is over and its slot free (reading() keeps the last one)."""
+        y = self._push(torch.zeros(0) if chunk is None else chunk, True)
+        self._last = self.reading()
+        self.close()
+        return y
+
+    def reading(self):
+        """loudness.StreamLevel of the stream so far.  Synchronises."""
+        if self.slot is None:
+            if self._last is None:
+                raise ValueError("this leveling stream is closed")
+            return self._last
+        return loud.stream_reading(self.stage.read(self.slot))
+
+    def trace(self):
+        """The per-hop history (stages.StreamLevelStage.trace): q, lufs, gain_db, status, blocks_abs, blocks_rel.  Synchronises."""
+        if self.slot is None:
+            raise ValueError("this leveling stream is closed")
+        return self.stage.trace(self.slot)
+
+    def close(self):
+        self.closed = True
+        if self.slot is not None:
+            self.stage.close(self.slot)
+            self.slot = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class StreamStretcher:
     """One stream at another speaking rate and / or pitch (_Common.open_stretcher): f32 chunks at 24 kHz in, f32 tensors on the device out
     (possibly empty) - a slot of a stages.StreamStretchStage at rq_eff, then, for a pitch, a slot of a stages.StreamResampleStage at
@@ -817,6 +877,51 @@ class _Common:
         out = self._winners(clips, step)
         self._note(level_s=self._level_s)
         return out
+
+    # ------------------------------------------------------------------ level a stream: causal loudness, slew-limited gain, limiter
+    stream_leveller = None
+
+    def load_stream_level(self, max_streams=16):
+        """The streaming leveler of open_leveler / level (stages.StreamLevelStage), built on first use."""
+        return self._streaming_stage("stream_leveller", "StreamLevelStage", max_streams)
+
+    def open_leveler(self, loudness=None, gain=None, true_peak=None, limit=None, **options):
+        """A StreamLeveler for 24 kHz audio that arrives in chunks: push(chunk) returns the samples that became ready, finish() the rest;
+        their concatenation is level(whole clip, ...) to the bit, whatever the chunking.  loudness (LUFS: the gain follows the loudness
+        heard so far towards it) or gain (dB, fixed) - exactly one; true_peak (dBTP) and limit ('lookahead' | 'none') as
+        stream_true_peak= / stream_limit= of tts_stream; options: assume, boost, cut, rise, fall (loudness.STREAM_LEVEL_DEFAULTS).  Up to 16
+        may be open."""
+        settings = loud.stream_settings(loudness, gain, true_peak, limit, options or None)  # (validated before a slot is taken)
+        return StreamLeveler(self.load_stream_level(), settings)
+
+    @torch.no_grad()
+    def level_many(self, audios, loudness=None, gain=None, true_peak=None, limit=None, return_info=False, **options):
+        """The CAUSAL leveler applied to finished clips: every clip through one flushed push of a slot of the streaming leveler, each in
+        the shape and on the device it came in - what a stream with these settings would have emitted for it.  When the whole clip
+        exists, normalize() is the one to use: it measures the clip's integrated loudness first and reaches the target exactly.
+        return_info=True: also [loudness.StreamLevel]."""
+        audios = self._clips(audios, "level")
+        settings = loud.stream_settings(loudness, gain, true_peak, limit, options or None)
+        stage = self.load_stream_level()
+        out, info = [], []
+        for k in range(0, len(audios), stage.max_streams):
+            part = audios[k:k + stage.max_streams]
+            slots = []
+            try:
+                for _ in part:
+                    slots.append(stage.open(settings))
+                ys = stage.push_many([(s, a.reshape(-1), True) for s, a in zip(slots, part)])
+                out += [self._like(a, y) for a, y in zip(part, ys)]
+                if return_info:
+                    info += [loud.stream_reading(stage.read(s)) for s in slots]
+            finally:
+                for s in slots:
+                    stage.close(s)
+        return (out, info) if return_info else out
+
+    def level(self, audio, loudness=None, gain=None, true_peak=None, limit=None, **options):
+        """level_many of one clip -> the clip as a stream at these settings would have come out."""
+        return self.level_many([audio], loudness, gain, true_peak, limit, **options)[0]
 
     # ------------------------------------------------------------------ pitch and output sample rate: the arbitrary-ratio resampler
     resampler = None

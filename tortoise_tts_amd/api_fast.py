@@ -65,6 +65,7 @@ class _Session:
     rs_slot: Any = None   # stream_sample_rate=: the session's slot on the streaming resampler
     ts_slot: Any = None   # stream_speaking_rate= / stream_pitch=: its slot on the streaming time-stretch
     pitch_slot: Any = None  # stream_pitch=: its slot on the pitch resampler behind the time-stretch
+    level_slot: Any = None  # stream_loudness= / stream_gain=: its slot on the streaming leveler, in front of the rate resampler
 
 
 class TextToSpeech(_Common):
@@ -364,6 +365,7 @@ class TextToSpeech(_Common):
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         stream_rate = rs.stream_options(hf_generate_kwargs)
         stream_voice = tsm.stream_options(hf_generate_kwargs)
+        stream_level = loud.stream_options(hf_generate_kwargs)
         top_k, typical_mass = sampler_kwargs(hf_generate_kwargs)
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
@@ -373,9 +375,10 @@ class TextToSpeech(_Common):
         wav_gen_prev, wav_overlap = None, None
         emitted = 0          # (token, latent) pairs already decoded into an emitted chunk
         threshold = first    # pairs the reference buffers before the next decode (api_fast.py:412)
-        # stream_speaking_rate= / stream_pitch= / stream_sample_rate=: every piece goes through the session's slots of the streaming
-        # time-stretch, the pitch resampler and the rate resampler, in this order; the stream's last piece with flush
-        chain = self._open_chain(stream_voice, stream_rate)
+        # stream_speaking_rate= / stream_pitch= / stream_loudness= / stream_gain= / stream_sample_rate=: every piece goes through the
+        # session's slots of the streaming time-stretch, the pitch resampler, the leveler and the rate resampler, in this order (the
+        # whole-clip chain's: the ceiling holds at 24 kHz); the stream's last piece with flush
+        chain = self._open_chain(stream_voice, stream_rate, stream_level)
         try:
             for codes, done in self.ar.generate_stream(1, max_mel_tokens, chunk, first_chunk=first, temperature=temperature, top_p=top_p,
                                                        repetition_penalty=float(repetition_penalty), top_k=top_k, seed=seed,
@@ -406,6 +409,13 @@ class TextToSpeech(_Common):
     _stream_stage = None
     _stretch_stage = None
     _pitch_stage = None
+    _level_stage = None
+
+    def _stream_lv(self):
+        """The streaming leveler of stream_loudness= / stream_gain= (stages.StreamLevelStage, one slot per session), built on first use."""
+        if self._level_stage is None:
+            self._level_stage = stages.StreamLevelStage(self.max_streams, device=self.device)
+        return self._level_stage
 
     def _stream_rs(self):
         """The streaming resampler of stream_sample_rate= (stages.StreamResampleStage, one slot per session), built on first use."""
@@ -427,35 +437,39 @@ class TextToSpeech(_Common):
             self._pitch_stage = stages.StreamResampleStage(self.max_streams, device=self.device)
         return self._pitch_stage
 
-    def _open_chain(self, stream_voice, stream_rate):
-        """The slots one stream's pieces go through: (time-stretch slot at rq_eff, pitch slot at (pq, 65536), rate slot), None where a
-        stage is not needed - or None when none is.  stream_voice: stretch.stream_options' (rq_eff, pq); stream_rate: Hz.  A rate of
-        exactly 1 is no time-stretch and a ratio of 1 no resampling, as in the whole-clip calls.  An open that fails frees the others."""
-        if stream_voice is None and stream_rate is None:
+    def _open_chain(self, stream_voice, stream_rate, stream_level=None):
+        """The slots one stream's pieces go through: (time-stretch slot at rq_eff, pitch slot at (pq, 65536), leveler slot, rate slot), None
+        where a stage is not needed - or None when none is.  stream_voice: stretch.stream_options' (rq_eff, pq); stream_level:
+        loudness.stream_options' settings; stream_rate: Hz.  A rate of exactly 1 is no time-stretch and a ratio of 1 no resampling, as in
+        the whole-clip calls.  An open that fails frees the others."""
+        if stream_voice is None and stream_rate is None and stream_level is None:
             return None
-        chain = [None, None, None]
+        chain = [None, None, None, None]
         try:
             if stream_voice is not None and stream_voice[0] != E.TSM_RATE_ONE:
                 chain[0] = self._stream_ts().open(stream_voice[0])
             if stream_voice is not None and stream_voice[1] != E.RS_PITCH_ONE:
                 chain[1] = self._stream_pitch().open(stream_voice[1], E.RS_PITCH_ONE)
+            if stream_level is not None:
+                chain[2] = self._stream_lv().open(stream_level)
             if stream_rate is not None:
-                chain[2] = self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
+                chain[3] = self._stream_rs().open(*rs.ratio(rs.SAMPLE_RATE, stream_rate))
         except Exception:
             self._close_chain(tuple(chain))
             raise
         return tuple(chain) if any(c is not None for c in chain) else None
 
     def _close_chain(self, chain):
-        for slot, stage in zip(chain or (), (self._stream_ts, self._stream_pitch, self._stream_rs)):
+        for slot, stage in zip(chain or (), (self._stream_ts, self._stream_pitch, self._stream_lv, self._stream_rs)):
             if slot is not None:
                 stage().close(slot)
 
     def _chain_push(self, items):
         """items = [(chain, piece, flush)] of distinct streams -> what each emits at the end of its chain: ONE push_many per stage for all of
-        them (the time-stretch, then the pitch resampler, then the rate resampler; a stream without a slot on a stage passes it by)."""
+        them (the time-stretch, then the pitch resampler, then the leveler, then the rate resampler; a stream without a slot on a stage passes
+        it by)."""
         pieces = [x for _, x, _ in items]
-        for which, stage in enumerate((self._stream_ts, self._stream_pitch, self._stream_rs)):
+        for which, stage in enumerate((self._stream_ts, self._stream_pitch, self._stream_lv, self._stream_rs)):
             todo = [i for i, (chain, _, _) in enumerate(items) if chain[which] is not None]
             if todo:
                 for i, y in zip(todo, stage().push_many([(items[i][0][which], pieces[i], items[i][2]) for i in todo])):
@@ -464,7 +478,7 @@ class TextToSpeech(_Common):
 
     @staticmethod
     def _chain_of(sess):
-        chain = (sess.ts_slot, sess.pitch_slot, sess.rs_slot)
+        chain = (sess.ts_slot, sess.pitch_slot, sess.level_slot, sess.rs_slot)
         return chain if any(c is not None for c in chain) else None
 
     # ------------------------------------------------------------------ several streams in one decode batch (max_streams > 1)
@@ -489,7 +503,14 @@ class TextToSpeech(_Common):
         (stages.StreamStretchStage) at rate r / 2^(s/12) and, for a pitch, one slot of a second streaming resampler at 2^(s/12), in front
         of the stream_sample_rate slot; every stage is ONE push per round of stream_pieces.  The concatenation is bit for bit the
         whole-clip chain (stretch / shift_pitch, then resample) of the 24 kHz stream; the audio lags by 1407 samples (58.6 ms) until the
-        last piece flushes it, so early pieces may be short or empty.  None, 1.0 and 0: nothing is built, today's bits."""
+        last piece flushes it, so early pieces may be short or empty.  None, 1.0 and 0: nothing is built, today's bits.
+        stream_loudness=T (LUFS, -70 .. -5) or stream_gain=dB, also on tts_stream: the session's pieces through one slot of the streaming
+        leveler (stages.StreamLevelStage) behind the pitch slot and in front of the stream_sample_rate slot - towards T with a
+        slew-limited gain steered by the loudness of what the session has said so far, or at a fixed gain; stream_true_peak= (dBTP,
+        default -1 with a target) keeps a ceiling with the 5 ms look-ahead limiter (the audio lags by 248 samples, 10.3 ms, until the last
+        piece), stream_limit='lookahead' | 'none', stream_level=dict(assume=, boost=, cut=, rise=, fall=) (loudness.STREAM_LEVEL_DEFAULTS).
+        The concatenation is bit for bit level() of the stream without the keywords.  None of them: nothing is built, today's bits.
+        loudness=, true_peak= and limit= stay refused: an integrated loudness needs the whole clip."""
         tsm.refuse_streaming(kwargs, "open_stream")
         tsm.refuse_word_rates(kwargs, "open_stream")
         loud.refuse_streaming(kwargs, "open_stream")
@@ -501,6 +522,7 @@ class TextToSpeech(_Common):
         fastsolver.refuse_streaming(kwargs, "open_stream")
         stream_rate = rs.stream_options(kwargs)  # (validated before a slot is taken)
         stream_voice = tsm.stream_options(kwargs)
+        stream_level = loud.stream_options(kwargs)
         if self.max_streams == 1:
             raise NotImplementedError("open_stream: create the instance with max_streams=2 .. 4")
         if "exp_noise" in kwargs:
@@ -525,7 +547,7 @@ class TextToSpeech(_Common):
         seed = self.deterministic_state(seed=use_deterministic_seed)
         text_tokens, cond = self._prepare(text, voice_samples, conditioning_latents, max_mel_tokens)
         slot = free[0]
-        chain = self._open_chain(stream_voice, stream_rate)  # (before the row is taken: a refusal here leaves no session behind)
+        chain = self._open_chain(stream_voice, stream_rate, stream_level)  # (before the row is taken: a refusal here leaves no session behind)
         try:
             if self.per_session_sampling:
                 self.ar.admit(slot, cond, text_tokens, seed, **dict(zip(("temperature", "top_p", "repetition_penalty", "top_k", "typical_mass"), settings)))
@@ -540,7 +562,7 @@ class TextToSpeech(_Common):
         sess = _Session(self._next_sid, slot, cond, text_tokens, max_mel_tokens, chunk, size, a["overlap_wav_len"], min(first, max_mel_tokens),
                         threshold=first)
         if chain is not None:
-            sess.ts_slot, sess.pitch_slot, sess.rs_slot = chain
+            sess.ts_slot, sess.pitch_slot, sess.level_slot, sess.rs_slot = chain
         self._next_sid += 1
         self._sessions[slot] = sess
         self._session_settings = settings
@@ -560,7 +582,7 @@ class TextToSpeech(_Common):
     def _close_rs(self, sess):
         """Frees every slot of the session's chain."""
         self._close_chain(self._chain_of(sess))
-        sess.ts_slot = sess.pitch_slot = sess.rs_slot = None
+        sess.ts_slot = sess.pitch_slot = sess.level_slot = sess.rs_slot = None
 
     def _resample_due(self, due, vocoded):
         """stream_speaking_rate= / stream_pitch= / stream_sample_rate=: the pieces of this round's sessions that have a chain, all of them
@@ -666,7 +688,9 @@ class TextToSpeech(_Common):
         repetition_penalty, top_k, typical_sampling and typical_mass on an instance with per_session_sampling.  Texts beyond the free
         slots are admitted as earlier sessions end.  stream_sample_rate= (Hz, 8000 .. 96000; one value or a list with one per text,
         None allowed): that text's pieces at another rate than 24 kHz, see open_stream.  stream_speaking_rate= and stream_pitch= (one value
-        or a list with one per text, None allowed): that text's pieces at another speaking rate and pitch, see open_stream."""
+        or a list with one per text, None allowed): that text's pieces at another speaking rate and pitch, see open_stream.
+        stream_loudness=, stream_gain=, stream_true_peak=, stream_limit= and stream_level= (one value or a list with one per text, None
+        allowed): that text's pieces at a level, see open_stream."""
         tsm.refuse_streaming(kwargs, "tts_stream_many")
         tsm.refuse_word_rates(kwargs, "tts_stream_many")
         loud.refuse_streaming(kwargs, "tts_stream_many")
@@ -693,6 +717,13 @@ class TextToSpeech(_Common):
                 per_text[name] = kwargs.pop(name)
         for i in range(len(texts)):  # (every text's rate and pitch are validated together before the first session opens)
             tsm.stream_options({name: per_text[name][i] if name in per_text else kwargs.get(name) for name in ("stream_speaking_rate", "stream_pitch")})
+        for name in loud.STREAM_KEYS:  # (stream_loudness=, stream_gain=, ...: one value or one per text, None allowed)
+            if isinstance(kwargs.get(name), (list, tuple)):
+                if len(kwargs[name]) != len(texts):
+                    raise ValueError(f"tts_stream_many: {len(kwargs[name])} {name} values for {len(texts)} texts")
+                per_text[name] = kwargs.pop(name)
+        for i in range(len(texts)):  # (every text's leveling keywords are validated together before the first session opens)
+            loud.stream_options({name: per_text[name][i] if name in per_text else kwargs.get(name) for name in loud.STREAM_KEYS})
         for name in ("temperature", "top_p", "repetition_penalty", "top_k", "typical_sampling", "typical_mass"):
             if isinstance(kwargs.get(name), (list, tuple)):
                 if not self.per_session_sampling:

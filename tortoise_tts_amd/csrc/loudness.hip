@@ -19,28 +19,18 @@
 //                        fixed order: thread-strided, then a fixed tree), L, the gain, the status.
 //   loud_apply_kernel    item = 2400 samples: y = g x; in LOOKAHEAD mode P, r, the sliding minimum and the Hann smoothing of a tile with its
 //                        halo of 2 Lh + 9 samples all stay in LDS (P is recomputed, not stored: 48 fma per sample).
+// The steps of the arithmetic are loudness_steps.h's, shared with the streaming leveler (loudness_stream.hip).
 #include <math.h>
 #include "runtime.h"
-#include "../../include/tortoise_mi355x_loud.h"
+#include "loudness_steps.h"
 
 namespace tt {
 
-constexpr int kLdH = TT_LOUD_HOP, kLdB = TT_LOUD_BLOCK, kLdS = TT_LOUD_SEGMENT, kLdLh = TT_LOUD_LOOKAHEAD, kLdTaps = TT_LOUD_TAPS;
 constexpr int kLdSegs = 64;                  // segments (threads) of a filter item
 constexpr int kLdItem = kLdSegs * kLdS;      // 9600 samples
 constexpr int kLdTile = 2400;                // samples of a peak / apply item
-constexpr int kLdThreads = 256;
-constexpr int kLdW = 2 * kLdLh + 1;          // 241 window taps
 constexpr int kLdHalo = 2 * kLdLh + 1 + 8;   // 249: r reaches 2 Lh, P one more, the oversampler 8 more
-constexpr int kLdTable = 3 * kLdTaps + kLdW; // phases 1 .. 3, then the window
-static_assert(kLdH % kLdS == 0 && kLdItem == kLdB && kLdTaps == 16, "loudness.hip's item mapping");
-
-struct LoudCoef {
-  double b0, b1, b2, na1, na2;  // shelf (the feedback coefficients negated)
-  double nc1, nc2;              // high-pass feedback, negated; its b is (1, -2, 1)
-  double M[4][4];               // transition of kLdS samples over (shelf y[n-1], y[n-2], high-pass y[n-1], y[n-2])
-  double z_abs;                 // 10^(-6.9309): the absolute gate in the linear domain
-};
+static_assert(kLdItem == kLdB, "loudness.hip's item mapping");
 
 struct LoudBatch {
   const float* audio;
@@ -131,28 +121,14 @@ __global__ __launch_bounds__(kLdSegs) void loud_filter_kernel(LoudBatch b, LoudC
     const int off = t * kLdS, len = min(kLdS, cnt - off);
     if (len > 0) {
       const size_t slot = (size_t)(cl.seg0 + first + t);
-      double x2 = (double)xs[loud_row(off)], x1 = (double)xs[loud_row(off + 1)];
-      double v1 = 0.0, v2 = 0.0, y1 = 0.0, y2 = 0.0, e = 0.0;
+      LoudMem m = {(double)xs[loud_row(off + 1)], (double)xs[loud_row(off)], 0.0, 0.0, 0.0, 0.0};
+      double e = 0.0;
       if (PASS == 1) {
-        v1 = state[4 * slot]; v2 = state[4 * slot + 1]; y1 = state[4 * slot + 2]; y2 = state[4 * slot + 3];
+        m.v1 = state[4 * slot]; m.v2 = state[4 * slot + 1]; m.y1 = state[4 * slot + 2]; m.y2 = state[4 * slot + 3];
       }
-      for (int j = 0; j < len; ++j) {
-        const double x0 = (double)xs[loud_row(off + 2 + j)];
-        double v = k.b0 * x0;  // the five terms in the header's order: the a1 term last, it alone waits for the previous sample
-        v = fma(k.b1, x1, v);
-        v = fma(k.b2, x2, v);
-        v = fma(k.na2, v2, v);
-        v = fma(k.na1, v1, v);
-        double y = v;
-        y = fma(-2.0, v1, y);
-        y = y + v2;
-        y = fma(k.nc2, y2, y);
-        y = fma(k.nc1, y1, y);
-        if (PASS == 1) e = fma(y, y, e);
-        x2 = x1; x1 = x0; v2 = v1; v1 = v; y2 = y1; y1 = y;
-      }
+      loud_segment<PASS>(k, [&](int j) { return (double)xs[loud_row(off + 2 + j)]; }, len, m, e);
       if (PASS == 0) {
-        state[4 * slot] = v1; state[4 * slot + 1] = v2; state[4 * slot + 2] = y1; state[4 * slot + 3] = y2;
+        state[4 * slot] = m.v1; state[4 * slot + 1] = m.v2; state[4 * slot + 2] = m.y1; state[4 * slot + 3] = m.y2;
       } else {
         seg_e[slot] = e;
       }
@@ -183,16 +159,7 @@ __global__ __launch_bounds__(64) void loud_carry_kernel(LoudBatch b, LoudCoef k,
 #pragma unroll
         for (int r = 0; r < 4; ++r) mine[r] = S[r];
       }
-      double nx[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double a = zs[i][r];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a = fma(k.M[r][q], S[q], a);
-        nx[r] = a;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) S[r] = nx[r];
+      loud_carry_step(k, zs[i], S);
     }
     if (s < nseg) {
 #pragma unroll
@@ -200,19 +167,6 @@ __global__ __launch_bounds__(64) void loud_carry_kernel(LoudBatch b, LoudCoef k,
     }
     __syncthreads();
   }
-}
-
-// P[n] from w[0 .. 15] = x[n - 7 .. n + 8]; h = phases 1 .. 3
-__device__ __forceinline__ float loud_peak_at(const float* w, const float* h) {
-  float P = fabsf(w[7]);  // phase 0 is the exact delta
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    float a = 0.f;
-#pragma unroll
-    for (int q = 0; q < kLdTaps; ++q) a = fmaf(h[p * kLdTaps + q], w[q], a);
-    P = fmaxf(P, fabsf(a));
-  }
-  return P;
 }
 
 __global__ __launch_bounds__(kLdThreads) void loud_peak_kernel(LoudBatch b, const float* __restrict__ src, const float* __restrict__ table,
@@ -247,20 +201,6 @@ __global__ __launch_bounds__(kLdThreads) void loud_peak_kernel(LoudBatch b, cons
   }
 }
 
-// a + the values of the other threads, in a fixed tree
-__device__ static inline double loud_sum(double a, double* red) {
-  const int t = threadIdx.x;
-  red[t] = a;
-  __syncthreads();
-  for (int s = kLdThreads / 2; s >= 1; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(kLdThreads) void loud_gate_kernel(LoudBatch b, LoudCoef k, const double* __restrict__ seg_e, int mode,
                                                                double* __restrict__ lufs, const float* __restrict__ true_peak,
                                                                int* __restrict__ blocks_abs, int* __restrict__ blocks_rel,
@@ -280,28 +220,9 @@ __global__ __launch_bounds__(kLdThreads) void loud_gate_kernel(LoudBatch b, Loud
   }
   __threadfence();  // (the hop energies are read back below by other threads of the workgroup)
   __syncthreads();
-  auto z = [&](int j) { return (((q[j] + q[j + 1]) + q[j + 2]) + q[j + 3]) / (double)kLdB; };
-  double sa = 0.0, na = 0.0;
-  for (int j = t; j < nb; j += kLdThreads) {
-    const double zj = z(j);
-    if (zj > k.z_abs) { sa += zj; na += 1.0; }
-  }
-  sa = loud_sum(sa, red);
-  na = loud_sum(na, red);
-  double L = -HUGE_VAL, nr = 0.0;
-  int st = nb == 0 ? TT_LOUD_SHORT : TT_LOUD_SILENT;
-  if (na > 0.0) {
-    const double rel = 0.1 * (sa / na);
-    double sr = 0.0;
-    for (int j = t; j < nb; j += kLdThreads) {
-      const double zj = z(j);
-      if (zj > k.z_abs && zj > rel) { sr += zj; nr += 1.0; }
-    }
-    sr = loud_sum(sr, red);
-    nr = loud_sum(nr, red);
-    L = -0.691 + 10.0 * log10(sr / nr);
-    st = TT_LOUD_OK;
-  }
+  const LoudGates gt = loud_gates(q, nb, k.z_abs, red);
+  const double L = gt.L, na = gt.na, nr = gt.nr;
+  const int st = gt.st;
   if (t != 0) return;
   lufs[c] = L;
   blocks_abs[c] = (int)na;
@@ -310,7 +231,7 @@ __global__ __launch_bounds__(kLdThreads) void loud_gate_kernel(LoudBatch b, Loud
   if (gain) {
     float g = 1.f;
     if (st == TT_LOUD_OK) {
-      g = (float)pow(10.0, ((double)b.target[c] - L) / 20.0);
+      g = loud_gain_of_db((double)b.target[c] - L);
       if (mode == TT_LOUD_SCALE) g = fminf(g, b.ceiling[c] / true_peak[c]);
     }
     gain[c] = g;
@@ -352,25 +273,26 @@ __global__ __launch_bounds__(kLdThreads) void loud_apply_kernel(LoudBatch b, con
     __syncthreads();
     for (int i = t; i < kLdTile + 4 * kLdLh; i += kLdThreads) {
       const int s = t0 - 2 * kLdLh + i;
-      rs[i] = s >= 0 && s < cl.n ? fminf(1.f, ceil_c / (g * fmaxf(Ps[i], Ps[i + 1]))) : 1.f;
+      rs[i] = s >= 0 && s < cl.n ? loud_ratio(ceil_c, g, Ps[i], Ps[i + 1]) : 1.f;
     }
     __syncthreads();
-    for (int i = t; i < kLdTile + 2 * kLdLh; i += kLdThreads) {
-      float m = rs[i];
-      for (int q = 1; q < kLdW; ++q) m = fminf(m, rs[i + q]);
-      ds[i] = 1.f - m;
-    }
+    for (int i = t; i < kLdTile + 2 * kLdLh; i += kLdThreads) ds[i] = loud_slide(rs + i);
     __syncthreads();
     const float* wn = tab + 3 * kLdTaps;
     for (int i = t; i < cnt; i += kLdThreads) {
-      float a = 0.f;
-      for (int q = 0; q < kLdW; ++q) a = fmaf(wn[q], ds[i + q], a);
-      const float s = fminf(rs[i + 2 * kLdLh], 1.f - a);
+      const float s = loud_smooth(wn, ds + i, rs[i + 2 * kLdLh]);
       y[t0 + i] = (g * xs[i + kLdHalo]) * s;
     }
     __syncthreads();
   }
 }
+
+// Phases 1 .. 3 of the oversampler, taps t = -7 .. 8: the header's formula evaluated in fp64 and rounded to f32.  The f32 values are part of
+// the specification, so they are tabulated (tests/test_loudness_cpu.py holds them to the reference's, bit for bit), not left to a libm.
+const float kLoudTaps[3][TT_LOUD_TAPS] = {
+    {-0x1.5e5d38p-11f, 0x1.0bcebcp-8f, -0x1.7339acp-7f, 0x1.873e28p-6f, -0x1.6df07ep-5f, 0x1.4ec604p-4f, -0x1.5aed62p-3f, 0x1.cbc246p-1f, 0x1.2ca176p-2f, -0x1.d2edaap-4f, 0x1.ed2db0p-5f, -0x1.0de388p-5f, 0x1.1370bcp-6f, -0x1.d4dc34p-8f, 0x1.01fc3cp-9f, -0x1.2538c6p-14f},
+    {-0x1.ab6476p-12f, 0x1.0e553ap-8f, -0x1.a54124p-7f, 0x1.d23d36p-6f, -0x1.bd0464p-5f, 0x1.957982p-4f, -0x1.8dd350p-3f, 0x1.42b1c6p-1f, 0x1.42b1c6p-1f, -0x1.8dd350p-3f, 0x1.957982p-4f, -0x1.bd0464p-5f, 0x1.d23d36p-6f, -0x1.a54124p-7f, 0x1.0e553ap-8f, -0x1.ab6476p-12f},
+    {-0x1.2538c6p-14f, 0x1.01fc3cp-9f, -0x1.d4dc34p-8f, 0x1.1370bcp-6f, -0x1.0de388p-5f, 0x1.ed2db0p-5f, -0x1.d2edaap-4f, 0x1.2ca176p-2f, 0x1.cbc246p-1f, -0x1.5aed62p-3f, 0x1.4ec604p-4f, -0x1.6df07ep-5f, 0x1.873e28p-6f, -0x1.7339acp-7f, 0x1.0bcebcp-8f, -0x1.5e5d38p-11f}};
 
 }  // namespace tt
 
@@ -385,55 +307,6 @@ struct tt_loud : EngineHandle {
 };
 
 namespace {
-
-// Phases 1 .. 3 of the oversampler, taps t = -7 .. 8: the header's formula evaluated in fp64 and rounded to f32.  The f32 values are part of
-// the specification, so they are tabulated (tests/test_loudness_cpu.py holds them to the reference's, bit for bit), not left to a libm.
-const float kLoudTaps[3][TT_LOUD_TAPS] = {
-    {-0x1.5e5d38p-11f, 0x1.0bcebcp-8f, -0x1.7339acp-7f, 0x1.873e28p-6f, -0x1.6df07ep-5f, 0x1.4ec604p-4f, -0x1.5aed62p-3f, 0x1.cbc246p-1f, 0x1.2ca176p-2f, -0x1.d2edaap-4f, 0x1.ed2db0p-5f, -0x1.0de388p-5f, 0x1.1370bcp-6f, -0x1.d4dc34p-8f, 0x1.01fc3cp-9f, -0x1.2538c6p-14f},
-    {-0x1.ab6476p-12f, 0x1.0e553ap-8f, -0x1.a54124p-7f, 0x1.d23d36p-6f, -0x1.bd0464p-5f, 0x1.957982p-4f, -0x1.8dd350p-3f, 0x1.42b1c6p-1f, 0x1.42b1c6p-1f, -0x1.8dd350p-3f, 0x1.957982p-4f, -0x1.bd0464p-5f, 0x1.d23d36p-6f, -0x1.a54124p-7f, 0x1.0e553ap-8f, -0x1.ab6476p-12f},
-    {-0x1.2538c6p-14f, 0x1.01fc3cp-9f, -0x1.d4dc34p-8f, 0x1.1370bcp-6f, -0x1.0de388p-5f, 0x1.ed2db0p-5f, -0x1.d2edaap-4f, 0x1.2ca176p-2f, 0x1.cbc246p-1f, -0x1.5aed62p-3f, 0x1.4ec604p-4f, -0x1.6df07ep-5f, 0x1.873e28p-6f, -0x1.7339acp-7f, 0x1.0bcebcp-8f, -0x1.5e5d38p-11f}};
-
-// one K-weighting section's feedback pair (and the shelf's b) for fs = 24000
-void loud_design(LoudCoef* k) {
-  const double fs = (double)TT_LOUD_SAMPLE_RATE;
-  {
-    const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
-    const double K = tan(M_PI * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
-    k->b0 = (Vh + Vb * K / Q + K * K) / a0;
-    k->b1 = 2.0 * (K * K - Vh) / a0;
-    k->b2 = (Vh - Vb * K / Q + K * K) / a0;
-    k->na1 = -(2.0 * (K * K - 1.0) / a0);
-    k->na2 = -((1.0 - K / Q + K * K) / a0);
-  }
-  {
-    const double f0 = 38.13547087602444, Q = 0.5003270373238773;
-    const double K = tan(M_PI * f0 / fs), a0 = 1.0 + K / Q + K * K;
-    k->nc1 = -(2.0 * (K * K - 1.0) / a0);
-    k->nc2 = -((1.0 - K / Q + K * K) / a0);
-  }
-  // M: the recurrence without input on the four unit states, kLdS samples, in extended precision
-  for (int q = 0; q < 4; ++q) {
-    long double v1 = q == 0, v2 = q == 1, y1 = q == 2, y2 = q == 3;
-    for (int j = 0; j < kLdS; ++j) {
-      const long double v = (long double)k->na1 * v1 + (long double)k->na2 * v2;
-      const long double y = v - 2.0L * v1 + v2 + (long double)k->nc1 * y1 + (long double)k->nc2 * y2;
-      v2 = v1; v1 = v; y2 = y1; y1 = y;
-    }
-    k->M[0][q] = (double)v1; k->M[1][q] = (double)v2; k->M[2][q] = (double)y1; k->M[3][q] = (double)y2;
-  }
-  k->z_abs = pow(10.0, (-70.0 + 0.691) / 10.0);
-}
-
-void loud_table(float* tab) {
-  for (int p = 0; p < 3; ++p)
-    for (int q = 0; q < kLdTaps; ++q) tab[p * kLdTaps + q] = kLoudTaps[p][q];
-  double w[kLdW], sum = 0.0;
-  for (int q = 0; q < kLdW; ++q) {
-    w[q] = 0.5 + 0.5 * cos(M_PI * (double)(q - kLdLh) / (double)(kLdLh + 1));
-    sum += w[q];
-  }
-  for (int q = 0; q < kLdW; ++q) tab[3 * kLdTaps + q] = (float)(w[q] / sum);
-}
 
 int loud_run(tt_loud* e, hipStream_t s, const LoudBatch& b, int mode, float* out, double* lufs, float* true_peak, int* blocks_abs, int* blocks_rel,
              double* hop_energy, float* gain, float* out_true_peak, int* status) {

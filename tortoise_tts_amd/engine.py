@@ -483,6 +483,25 @@ _RSS_PROTOS = {
 RSS_ABI_VERSION = 1
 RSS_HIST, RSS_MAX_STREAMS, RSS_BANK_MAX, RSS_AUTO_MAX_Q = 576, 64, 16384, 16  # TT_RSS_HIST, TT_RSS_MAX_STREAMS, TT_RSS_BANK_MAX, TT_RSS_AUTO_MAX_Q
 RSS_AUTO, RSS_TABLE, RSS_BANK = 0, 1, 2
+# include/tortoise_mi355x_lvs.h: the streaming leveler - causal loudness, a slew-limited gain, the look-ahead limiter (its own header and version)
+_fl = C.c_float
+_LVS_PROTOS = {
+    "tt_lvs_abi_version": (_i, []),
+    "tt_lvs_create": (_i, [_i, _i, C.POINTER(vp)]),
+    "tt_lvs_destroy": (None, [vp]),
+    "tt_lvs_open": (_i, [vp, _i, _i, _i, _fl, _fl, _fl, _fl, _fl, _fl, _fl]),
+    "tt_lvs_close": (_i, [vp, _i]),
+    "tt_lvs_state": (_i, [vp, _i, _ip, _ip, _ip, _ip]),
+    "tt_lvs_ready": (_i, [_i, _i, _i, _i]),
+    "tt_lvs_push": (_i, [vp, _i, _ip, _ip, _ip, vp, vp, vp]),
+    "tt_lvs_read": (_i, [vp, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tt_lvs_trace": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
+}
+LVS_ABI_VERSION = 1
+LVS_MAX_STREAMS, LVS_DELAY, LVS_HIST, LVS_TILE = 64, 248, 512, 1024  # TT_LVS_MAX_STREAMS, TT_LVS_DELAY, TT_LVS_HIST, TT_LVS_TILE
+LVS_DEFAULT_HOPS, LVS_MAX_HOPS = 36000, 864000
+LVS_ADAPT, LVS_FIXED = 0, 1
+LVS_NONE, LVS_LOOKAHEAD = 0, 1
 # include/tortoise_mi355x_rsw.h: the resampler along a pitch map, a pitch that changes inside the clip (its own header and version)
 _RSW_PROTOS = {
     "tt_rsw_abi_version": (_i, []),
@@ -668,7 +687,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_F0V_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_LVS_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_F0V_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -710,6 +729,8 @@ def load_library():
         raise EngineError("ABI mismatch: tortoise_mi355x_loud.h is version %d in the library, %d in Python" % (lib.tt_loud_abi_version(), LOUD_ABI_VERSION))
     if lib.tt_rs_abi_version() != RS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rs.h is version %d in the library, %d in Python" % (lib.tt_rs_abi_version(), RS_ABI_VERSION))
+    if lib.tt_lvs_abi_version() != LVS_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_lvs.h is version %d in the library, %d in Python" % (lib.tt_lvs_abi_version(), LVS_ABI_VERSION))
     if lib.tt_rss_abi_version() != RSS_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_rss.h is version %d in the library, %d in Python" % (lib.tt_rss_abi_version(), RSS_ABI_VERSION))
     if lib.tt_rsw_abi_version() != RSW_ABI_VERSION:

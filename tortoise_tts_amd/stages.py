@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from . import engine as E
 from . import formant as fmt
+from . import loudness as loud
 from . import pack
 from . import pitch as f0m
 from . import resample as rs
@@ -905,6 +906,92 @@ class StreamStretchStage(_Handle):
                 offs.append(off[f:f + k])
                 f += k
         return (out, offs) if return_offsets else out
+
+
+class StreamLevelStage(_Handle):
+    """The leveler fed in chunks (csrc/loudness_stream.hip, include/tortoise_mi355x_lvs.h): up to max_streams streams, each with its own
+    settings (loudness.StreamSettings); BS.1770 loudness measured on the prefix heard so far, a slew-limited gain towards a target or a
+    fixed gain, and the look-ahead limiter.  Whatever the chunking, what a stream emits is bit for bit what one flushed push of the whole
+    clip emits, 248 input samples late under the limiter until the flush."""
+
+    api = "tt_lvs"
+
+    def __init__(self, max_streams=16, max_hops=E.LVS_DEFAULT_HOPS, device="cuda"):
+        self.lib = E.init()
+        self.device = torch.device(device)
+        self.max_streams, self.max_hops = int(max_streams), int(max_hops)
+        self.slots = {}  # open slot -> [settings, samples pushed, finished]
+        self._create(self.max_streams, self.max_hops)
+
+    def open(self, settings):
+        """A free slot opened with a loudness.StreamSettings -> its number.  ValueError for settings the device refuses (before a slot is
+        taken), RuntimeError when every slot is taken."""
+        free = [s for s in range(self.max_streams) if s not in self.slots]
+        if not free:
+            raise RuntimeError(f"all {self.max_streams} leveling streams are open")
+        if self.lib.tt_lvs_open(self.h, free[0], *settings.args()):
+            raise ValueError(self.lib.tt_last_error().decode())
+        self.slots[free[0]] = [settings, 0, False]
+        return free[0]
+
+    def close(self, slot=None):
+        """close(slot): the slot is free again (whatever it still held is dropped).  close(): the stage."""
+        if slot is None:
+            self.slots = {}
+            return super().close()
+        if self.slots.pop(slot, None) is not None and self.h:
+            E.check(self.lib.tt_lvs_close(self.h, int(slot)))
+
+    def push_many(self, items):
+        """items = [(slot, chunk f32 [n] (device or host, n >= 0), flush)], distinct open slots -> what each emits (f32 on the stage's
+        device, possibly empty): ONE tt_lvs_push, no synchronisation.  A flushed slot is finished: close() it to free it."""
+        n = len(items)
+        if not 1 <= n <= self.max_streams or len({s for s, _, _ in items}) != n:
+            raise ValueError(f"push_many: {n} chunks for {len({s for s, _, _ in items})} slots (1 .. {self.max_streams} distinct slots)")
+        counts = []
+        for slot, x, flush in items:
+            st = self.slots.get(slot)
+            if st is None or st[2]:
+                raise ValueError(f"push_many: slot {slot} is not open" if st is None else f"push_many: slot {slot} is finished")
+            if x.dim() != 1:
+                raise ValueError(f"push_many: slot {slot}: a chunk of shape {tuple(x.shape)}, expected [samples]")
+            if (st[1] + x.shape[0]) // E.LOUD_HOP > self.max_hops:
+                raise ValueError(f"push_many: slot {slot}: {st[1]} + {x.shape[0]} samples pass the stage's {self.max_hops} hops of 100 ms")
+            counts.append(loud.stream_ready(st[1], x.shape[0], st[0].limit, bool(flush)))
+        dev = self.device
+        audio = torch.cat([x.to(device=dev, dtype=torch.float32) for _, x, _ in items] + [torch.zeros(1, device=dev)])
+        y = torch.empty(sum(counts) + 1, device=dev, dtype=torch.float32)
+        arr = C.c_int * n
+        E.check(self.lib.tt_lvs_push(self.h, n, arr(*[int(s) for s, _, _ in items]), arr(*[int(x.shape[0]) for _, x, _ in items]),
+                                     arr(*[int(bool(f)) for _, _, f in items]), audio.data_ptr(), y.data_ptr(), E.stream_ptr()))
+        out, o = [], 0
+        for (slot, x, flush), c in zip(items, counts):
+            st = self.slots[slot]
+            st[1] += x.shape[0]
+            st[2] = bool(flush)
+            out.append(y[o:o + c])
+            o += c
+        return out
+
+    def read(self, slot):
+        """The slot's latest readings (synchronises): dict(lufs, status, blocks_abs, blocks_rel, gain_db, gain, peak, out_peak, limited,
+        n_in, n_out, hops)."""
+        d, i, f = C.c_double, C.c_int, C.c_float
+        v = dict(lufs=d(), status=i(), blocks_abs=i(), blocks_rel=i(), gain_db=d(), gain=f(), peak=f(), out_peak=f(), limited=i())
+        E.check(self.lib.tt_lvs_read(self.h, int(slot), *[C.byref(a) for a in v.values()], E.stream_ptr()))
+        c = [i(), i(), i(), i()]
+        E.check(self.lib.tt_lvs_state(self.h, int(slot), *[C.byref(a) for a in c]))
+        return dict({k: a.value for k, a in v.items()}, n_in=c[0].value, n_out=c[1].value, hops=c[2].value)
+
+    def trace(self, slot, first_hop=0, count=None):
+        """The per-hop history of the slot (synchronises): dict of numpy arrays q, lufs, gain_db (f64), status, blocks_abs, blocks_rel (i32)."""
+        c = [C.c_int() for _ in range(4)]
+        E.check(self.lib.tt_lvs_state(self.h, int(slot), *[C.byref(a) for a in c]))
+        count = c[2].value - first_hop if count is None else int(count)
+        out = {k: np.zeros(max(count, 0), np.float64) for k in ("q", "lufs", "gain_db")}
+        out.update({k: np.zeros(max(count, 0), np.int32) for k in ("status", "blocks_abs", "blocks_rel")})
+        E.check(self.lib.tt_lvs_trace(self.h, int(slot), int(first_hop), count, *[a.ctypes.data for a in out.values()], E.stream_ptr()))
+        return out
 
 
 class SilenceStage(_ClipStage):
