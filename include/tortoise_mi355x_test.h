@@ -22,12 +22,15 @@ extern "C" {
  *                 (bit-identical results)
  *   TTX_AR_GEMV   a level: autoregressive handles created with max_batch <= 4 (the streaming engine) run the decode step's GEMMs
  *                 2 (default) = GEMV-shaped with the layer norms inside the QKV / c_fc launches (csrc/gemv.hip: five launches per layer),
- *                 1 = GEMV-shaped behind row-norm launches of their own (seven), 0 = on the MFMA tiles.  Read at tt_ar_create. */
+ *                 1 = GEMV-shaped behind row-norm launches of their own (seven), 0 = on the MFMA tiles.  Read at tt_ar_create.
+ *   TTX_NR_SELECT_LONG 0 (default) = the denoiser's noise-floor select keeps a row of up to TT_NR_REG_FRAMES frames in registers, 1 = it
+ *                 re-reads the row every round whatever its length, the form of longer clips (bit-identical results) */
 #define TTX_FLASH32 0
 #define TTX_GEMM_P8 1
 #define TTX_VOC_MFMA 2
 #define TTX_GEMM_SKINNY 3
 #define TTX_AR_GEMV 4
+#define TTX_NR_SELECT_LONG 5
 int ttx_kernel_variant(int which, int v);
 
 /* ============================================================================================
@@ -308,6 +311,15 @@ int tt_op_fmt_run(void* h, const float* wav, const long long* clip_offsets, cons
                   const long long* out_offsets, float* spectrum, float* logmag, float* gains, const long long* stage_offsets, void* stream);
 int tt_op_fmt_synth(void* h, const float* spectrum, const float* gains, const long long* stage_offsets, const int* clip_lengths, int n_clips,
                     float* out, const long long* out_offsets, void* stream);
+
+/* The denoiser staged (csrc/denoise.hip, include/tortoise_mi355x_nr.h; `h` is a tt_nr handle).  tt_op_nr_run is tt_nr_run with three optional
+ * outputs (device f32), clip c's at stage_offsets[c] (host array, element units; the spectrum's at twice that): spectrum [T][2 * bins_pad]
+ * (re, im interleaved), power [bins_pad][T] (transposed, as the select reads it) and gains [T][bins_pad].  The floor is tt_nr_run's own
+ * floor_out.  Nothing is staged for a TT_NR_SHORT clip. */
+struct tt_nr_params;
+int tt_op_nr_run(void* h, const float* wav, const long long* clip_offsets, const int* clip_lengths, const int* noise_first_frame,
+                 const int* noise_frames, const struct tt_nr_params* params, int n_clips, float* out, const long long* out_offsets, float* floor_out,
+                 int* status_out, float* spectrum, float* power, float* gains, const long long* stage_offsets, void* stream);
 
 /* F0 tracker staged (csrc/f0.hip, include/tortoise_mi355x_f0.h; `h` is a tt_f0 handle).  tt_op_f0_track is tt_f0_track with one more output:
  * dprime f64 [frm_off[n_clips]][TT_F0_LAG_MAX + 1], the normalised difference d'(0 .. T) of every frame, sliced by frm_off like lag.

@@ -25,6 +25,7 @@ csrc/classify.hip), with classifier.pth read and packed once per (models_dir, de
 Out of scope (raise, never silently fall back): DeepSpeed flag.
 """
 import inspect
+import math
 import os
 import random
 import time
@@ -35,6 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from . import align
+from . import denoise as nr
 from . import dist as tdist
 from . import engine as E
 from . import stages
@@ -211,6 +213,7 @@ def resolve_stage_dtypes(dtype, half):
     return {k: E.dtype_code(v) for k, v in out.items()}
 
 
+DENOISER_SECONDS = 12  # the clip the denoiser is first built for (voice clips are a few seconds each)
 ORIG_ALIGNER_SECONDS = 30  # the longest clip the aligner of a path without its own clip cap is built for
 LOUDNESS_STAGE_SAMPLES = 16 * 30 * E.LOUD_SAMPLE_RATE  # samples of one call the loudness stage is first built for: sixteen clips of 30 s
 
@@ -1283,6 +1286,73 @@ class _Common:
         self._note(resample_s=self._resample_s)
         return out
 
+    # ------------------------------------------------------------------ noisy voice clips: the spectral-subtraction denoiser
+    denoiser = None
+    denoise_voice_samples = None  # TextToSpeech(denoise_voice_samples=): None | True | dict of denoise_many's options
+
+    def load_denoiser(self, max_samples=0):
+        """The denoiser (stages.DenoiseStage), built on first use for clips of 12 s and rebuilt for a longer one."""
+        return self._clip_stage("denoiser", "DenoiseStage", max_samples, E.NR_MAX_SAMPLES, "denoiser", DENOISER_SECONDS * nr.VOICE_SAMPLE_RATE)
+
+    @torch.no_grad()
+    def denoise_many(self, audios, reduction_db=nr.DEFAULTS["reduction_db"], beta=nr.DEFAULTS["beta"], quantile=nr.DEFAULTS["quantile"],
+                     smooth_frames=nr.DEFAULTS["smooth_frames"], smooth_bins=nr.DEFAULTS["smooth_bins"], noise=None, sample_rate=24000,
+                     return_info=False):
+        """Stationary noise (hiss, room noise) taken out of voice clips by spectral subtraction: audios f32 [n] / [1, n] / [1, 1, n] at any
+        sample rate (any device, n >= 513) -> the clips, each in the shape and on the device it came in (csrc/denoise.hip - DESIGN.md
+        5.38).  Per clip and frequency bin (frames of 1024 samples every 256) the noise power is the `quantile`-quantile of the bin's power
+        over the clip's frames, an exact order statistic, corrected by 1 / (-ln(1 - quantile)), the factor between that quantile and the
+        mean of a Gaussian noise bin; where the power, smoothed over 2 smooth_frames + 1 frames and 2 smooth_bins + 1 bins, exceeds
+        `beta` times that floor the bin keeps the fraction 1 - beta floor / power of its amplitude, everywhere else, and at least,
+        10^(-reduction_db / 20).  noise=(start_s, end_s) - one for all clips or one (or None) per clip, in seconds at `sample_rate`, which
+        is used for nothing else - takes the floor as the mean power over the frames that lie whole inside that stretch (at least 8)
+        instead.  **A clip with digital silence in more than `quantile` of its frames has an auto floor of exactly 0 and comes back as
+        it is: give it a noise= region.**  A clip of fewer than 32 frames (8192 samples) without a region comes back as it is.
+        reduction_db=0 or None calls nothing and returns the clips themselves.  All clips go through ONE device call per 16.
+        return_info=True -> (clips, [dict(status 'ok' / 'short', noise_floor f32 [513], noise_dbfs, mean_attenuation_db)]).
+        **The defaults come from the arithmetic and one synthetic family of vowels in Gaussian noise; nobody has run a real recording or a
+        trained checkpoint through them.**"""
+        audios = self._clips(audios, "denoise")
+        p = nr.params(reduction_db, beta, quantile, smooth_frames, smooth_bins)
+        one = noise is None or (isinstance(noise, (tuple, list)) and len(noise) == 2 and all(isinstance(v, (int, float)) for v in noise))
+        noises = [noise] * len(audios) if one else list(noise)  # (a pair of numbers is one region for all clips)
+        if len(noises) != len(audios):
+            raise ValueError(f"denoise: {len(audios)} clips with {len(noises)} noise regions")
+        for i, a in enumerate(audios):
+            if a.shape[-1] < nr.MIN_SAMPLES:
+                raise ValueError(f"denoise: clip {i} has {a.shape[-1]} samples; the denoiser needs at least {nr.MIN_SAMPLES}")
+        regions = [nr.region_frames(r, a.shape[-1], sample_rate, "denoise", i) for i, (r, a) in enumerate(zip(noises, audios))]
+        if p is None or not audios:
+            return (audios, [None] * len(audios)) if return_info else audios
+        t0 = time.perf_counter()
+        res = self.load_denoiser(max(a.shape[-1] for a in audios)).denoise_many([a.reshape(-1) for a in audios], regions, p)
+        out, info = [], []
+        for a, (y, d) in zip(audios, res):
+            out.append(self._like(a, y))
+            if return_info:
+                e_in, e_out = float(a.reshape(-1).double().pow(2).sum()), float(y.double().pow(2).sum())
+                info.append(dict(status=nr.STATUS[d["status"]], noise_floor=d["floor"], noise_dbfs=nr.noise_dbfs(d["floor"]),
+                                 mean_attenuation_db=10.0 * math.log10(e_in / e_out) if e_in > 0 and e_out > 0 else 0.0))
+        self._denoise_s = time.perf_counter() - t0
+        return (out, info) if return_info else out
+
+    def denoise(self, audio, **options):
+        """denoise_many of one clip -> the clip (with return_info=True: (clip, info))."""
+        res = self.denoise_many([audio], **options)
+        return (res[0][0], res[1][0]) if options.get("return_info") else res[0]
+
+    def _clean_voice_samples(self, voice_samples, denoise, ready=lambda vs: False):
+        """The waveform entries of voice_samples through ONE denoise_many call, before any mel front-end; ready mels and (auto_mel,
+        diffusion_mel) pairs stay as they are.  denoise: the call's keyword, nr.INHERIT for the constructor's denoise_voice_samples."""
+        p = nr.from_option(self.denoise_voice_samples if isinstance(denoise, str) and denoise == nr.INHERIT else denoise)
+        todo = [i for i, vs in enumerate(voice_samples) if torch.is_tensor(vs) and not ready(vs)]
+        if p is None or not todo:
+            return voice_samples
+        out = list(voice_samples)
+        for i, y in zip(todo, self.denoise_many([out[i] for i in todo], sample_rate=nr.VOICE_SAMPLE_RATE, **nr.keywords(p))):
+            out[i] = y
+        return out
+
     # ------------------------------------------------------------------ pauses and silence: speech regions, edge trimming, pause capping
     silencer = None
 
@@ -1403,7 +1473,9 @@ class TextToSpeech(_Common):
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, max_candidates=256, configs=None, max_mel_tokens=500, max_text_tokens=402,
-                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1, mel_front_end="torch", redaction="reference"):
+                 candidate_sharding=True, utterance_batch=1, aligner=None, winner_batch=1, mel_front_end="torch", redaction="reference", denoise_voice_samples=None):
+        nr.from_option(denoise_voice_samples)  # (validated now, used by get_conditioning_latents)
+        self.denoise_voice_samples = denoise_voice_samples
         self.models_dir = models_dir
         self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
         if use_deepspeed:
@@ -1611,14 +1683,16 @@ class TextToSpeech(_Common):
             self._build_stage(name)
 
     # ------------------------------------------------------------------ reference helpers
-    def get_conditioning_latents(self, voice_samples, return_mels=False):
+    def get_conditioning_latents(self, voice_samples, return_mels=False, denoise=nr.INHERIT):
         """api.py:258-299 on the engine: ConditioningEncoder (autoregressive.py:204-228) and contextual_embedder
         (diffusion_decoder.py:186-192, 222-230) run on the device (csrc/cond.hip).  voice_samples is, as in
         the reference, a list of 22.05 kHz waveform tensors (the mel front-end of api.py:271-287 then runs in torch,
         tortoise_tts_amd/audio.py: restated without torchaudio / librosa, pinned through oracle/audio_oracle.py), or a list of ready
-        (auto_mel f32 [1, 80, T_a], diffusion_mel f32 [1, 100, T_d]) pairs, one per clip."""
+        (auto_mel f32 [1, 80, T_a], diffusion_mel f32 [1, 100, T_d]) pairs, one per clip.  denoise=True | dict | None: the waveform
+        entries go through ONE denoise_many call first (its options; the default is the constructor's denoise_voice_samples)."""
         if torch.is_tensor(voice_samples):
             voice_samples = [voice_samples]  # api.py:269-270
+        voice_samples = self._clean_voice_samples(voice_samples, denoise)
         if self.conditioning is None:
             self.conditioning = stages.ConditioningStage(self._sd("autoregressive"), self._sd("diffusion"), self.ar_cfg, self.diff_cfg,
                                                          self.device, self.dtype)

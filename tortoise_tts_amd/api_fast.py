@@ -31,6 +31,7 @@ from typing import Any
 
 import torch
 
+from . import denoise as nr
 from . import engine as E
 from . import stages
 from . import formant as fmt
@@ -79,7 +80,9 @@ class TextToSpeech(_Common):
     def __init__(self, autoregressive_batch_size=None, models_dir=MODELS_DIR, enable_redaction=True, kv_cache=False,
                  use_deepspeed=False, half=False, device=None, tokenizer_vocab_file=None, tokenizer_basic=False, *,
                  state_dicts=None, dtype=None, configs=None, max_mel_tokens=500, max_text_tokens=402, max_streams=1,
-                 per_session_sampling=False, wide_sessions=False, mel_front_end="torch", aligner=None):
+                 per_session_sampling=False, wide_sessions=False, mel_front_end="torch", aligner=None, denoise_voice_samples=None):
+        nr.from_option(denoise_voice_samples)  # (validated now, used by get_conditioning_latents)
+        self.denoise_voice_samples = denoise_voice_samples
         self.models_dir = models_dir
         self._aligner_source = aligner  # align() / tts_with_timings(): the wav2vec2 aligner's (config, state_dict, vocab, tokenizer config) instead of its files
         self.mel_front_end_kind = stages.mel_front_end_kind(mel_front_end)
@@ -141,15 +144,16 @@ class TextToSpeech(_Common):
         return _load_state_dict(self.models_dir, name)
 
     # ------------------------------------------------------------------ conditioning (api_fast.py:230-260)
-    def get_conditioning_latents(self, voice_samples, return_mels=False):
+    def get_conditioning_latents(self, voice_samples, return_mels=False, denoise=nr.INHERIT):
         """Only the autoregressive latent exists on this path (there is no diffusion stage).  voice_samples: 22.05 kHz clips
-        or ready auto mels f32 [1, 80, T] (see tortoise_tts_amd.api.TextToSpeech.get_conditioning_latents)."""
+        or ready auto mels f32 [1, 80, T] (see tortoise_tts_amd.api.TextToSpeech.get_conditioning_latents, also for denoise=)."""
         if torch.is_tensor(voice_samples):
             voice_samples = [voice_samples]
         if self.conditioning is None:
             self.conditioning = stages.ConditioningStage(self._sd("autoregressive"), None, self.ar_cfg, None, self.device, self.dtype)
         def ready(vs):
             return torch.is_tensor(vs) and vs.dim() >= 2 and vs.shape[-2] == 80
+        voice_samples = self._clean_voice_samples(voice_samples, denoise, ready)
 
         mels = []
         device_mels = None
@@ -362,6 +366,7 @@ class TextToSpeech(_Common):
         f0m.refuse_streaming(hf_generate_kwargs, "tts_stream")
         sil.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fmt.refuse_streaming(hf_generate_kwargs, "tts_stream")
+        nr.refuse_streaming(hf_generate_kwargs, "tts_stream")
         fastsolver.refuse_streaming(hf_generate_kwargs, "tts_stream")
         stream_rate = rs.stream_options(hf_generate_kwargs)
         stream_voice = tsm.stream_options(hf_generate_kwargs)
@@ -519,6 +524,7 @@ class TextToSpeech(_Common):
         f0m.refuse_streaming(kwargs, "open_stream")
         sil.refuse_streaming(kwargs, "open_stream")
         fmt.refuse_streaming(kwargs, "open_stream")
+        nr.refuse_streaming(kwargs, "open_stream")
         fastsolver.refuse_streaming(kwargs, "open_stream")
         stream_rate = rs.stream_options(kwargs)  # (validated before a slot is taken)
         stream_voice = tsm.stream_options(kwargs)
@@ -699,6 +705,7 @@ class TextToSpeech(_Common):
         f0m.refuse_streaming(kwargs, "tts_stream_many")
         sil.refuse_streaming(kwargs, "tts_stream_many")
         fmt.refuse_streaming(kwargs, "tts_stream_many")
+        nr.refuse_streaming(kwargs, "tts_stream_many")
         fastsolver.refuse_streaming(kwargs, "tts_stream_many")
         seeds = kwargs.pop("use_deterministic_seed", None)
         if not isinstance(seeds, (list, tuple)):

@@ -19,7 +19,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtortoise_mi355x.so")
 KBENCH_LIB = os.path.join(LIBDIR, "libtortoise_kbench.so")  # experiments only (scripts/kbench.py); never loaded by the product
 SOURCES = ["common.hip", "gemm.hip", "gemm_bf16.hip", "gemm_f16.hip", "gemm_f32.hip", "gemv.hip", "norm.hip", "attention.hip", "decode_attention.hip", "attention_f32.hip", "sampling.hip", "misc.hip", "univnet.hip",
-           "gpt2.hip", "clvp.hip", "cvvp.hip", "align.hip", "ctc_align.hip", "tsm.hip", "tsm_stream.hip", "tsm_warp.hip", "loudness.hip", "loudness_stream.hip", "resample.hip", "resample_stream.hip", "resample_warp.hip", "silence.hip", "f0.hip", "f0_viterbi.hip", "classify.hip", "melfront.hip", "formant.hip", "diffusion.hip", "cond.hip", "hifigan.hip", "vocoder.hip", "capi.hip"]
+           "gpt2.hip", "clvp.hip", "cvvp.hip", "align.hip", "ctc_align.hip", "tsm.hip", "tsm_stream.hip", "tsm_warp.hip", "loudness.hip", "loudness_stream.hip", "resample.hip", "resample_stream.hip", "resample_warp.hip", "silence.hip", "f0.hip", "f0_viterbi.hip", "classify.hip", "melfront.hip", "formant.hip", "denoise.hip", "diffusion.hip", "cond.hip", "hifigan.hip", "vocoder.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-ffp-contract=on",
          "-Werror=extra-tokens", "-Werror=return-type"]  # (a knob inserted as `#endif <rest of the line>` silently drops the rest: round 6 lost a GPU call to one)
 
@@ -43,7 +43,7 @@ def _digest(paths):
 def _headers():
     hs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]
     for name in ("tortoise_mi355x.h", "tortoise_mi355x_test.h", "tortoise_mi355x_align.h", "tortoise_mi355x_classify.h", "tortoise_mi355x_hifi.h",
-                 "tortoise_mi355x_univnet.h", "tortoise_mi355x_mel.h", "tortoise_mi355x_fmt.h", "tortoise_mi355x_ctc.h", "tortoise_mi355x_tsm.h", "tortoise_mi355x_tss.h", "tortoise_mi355x_tsw.h", "tortoise_mi355x_loud.h", "tortoise_mi355x_lvs.h", "tortoise_mi355x_rs.h", "tortoise_mi355x_rss.h", "tortoise_mi355x_rsw.h", "tortoise_mi355x_sil.h", "tortoise_mi355x_f0.h", "tortoise_mi355x_f0v.h", "tortoise_mi355x_solver.h"):
+                 "tortoise_mi355x_univnet.h", "tortoise_mi355x_mel.h", "tortoise_mi355x_fmt.h", "tortoise_mi355x_nr.h", "tortoise_mi355x_ctc.h", "tortoise_mi355x_tsm.h", "tortoise_mi355x_tss.h", "tortoise_mi355x_tsw.h", "tortoise_mi355x_loud.h", "tortoise_mi355x_lvs.h", "tortoise_mi355x_rs.h", "tortoise_mi355x_rss.h", "tortoise_mi355x_rsw.h", "tortoise_mi355x_sil.h", "tortoise_mi355x_f0.h", "tortoise_mi355x_f0v.h", "tortoise_mi355x_solver.h"):
         hs.append(os.path.join(os.path.dirname(HERE), "include", name))
     return hs
 

@@ -4,7 +4,7 @@
 #include "../../include/tortoise_mi355x_test.h"
 
 using namespace tt;
-namespace tt { extern bool g_flash32; extern bool g_voc_mfma; extern bool g_gemm_p8; extern bool g_gemm_skinny; extern int g_ar_gemv; }  // attention.hip, univnet.hip, gemm.hip
+namespace tt { extern bool g_flash32; extern bool g_voc_mfma; extern bool g_gemm_p8; extern bool g_gemm_skinny; extern int g_ar_gemv; extern bool g_nr_select_long; }  // attention.hip, univnet.hip, gemm.hip, gpt2.hip, denoise.hip
 
 extern "C" {
 
@@ -221,7 +221,7 @@ int ttx_kernel_variant(int which, int v) {
     tt::g_ar_gemv = v;
     return prev;
   }
-  bool* sw = which == TTX_FLASH32 ? &tt::g_flash32 : which == TTX_GEMM_P8 ? &tt::g_gemm_p8 : which == TTX_VOC_MFMA ? &tt::g_voc_mfma : which == TTX_GEMM_SKINNY ? &tt::g_gemm_skinny : nullptr;
+  bool* sw = which == TTX_FLASH32 ? &tt::g_flash32 : which == TTX_GEMM_P8 ? &tt::g_gemm_p8 : which == TTX_VOC_MFMA ? &tt::g_voc_mfma : which == TTX_GEMM_SKINNY ? &tt::g_gemm_skinny : which == TTX_NR_SELECT_LONG ? &tt::g_nr_select_long : nullptr;
   TT_REQUIRE(sw != nullptr, "ttx_kernel_variant: unknown kernel family %d", which);
   const int prev = *sw ? 1 : 0;
   *sw = v != 0;

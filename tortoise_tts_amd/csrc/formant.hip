@@ -1,5 +1,7 @@
 // Formant-preserving pitch: cepstral envelope correction (include/tortoise_mi355x_fmt.h).  Five launches, every sum on
-// v_mfma_f32_32x32x2_f32 (exact f32 products: the log of a quiet bin magnifies any operand rounding), built from csrc/stft_steps.h:
+// v_mfma_f32_32x32x2_f32 (exact f32 products: the log of a quiet bin magnifies any operand rounding), built from csrc/stft_steps.h.  The
+// STFT, inverse and overlap-add kernels are the bodies of csrc/stft_kernels.h, shared with csrc/denoise.hip, with this chain's epilogue
+// (the log) and gain (exp) put in:
 //
 //   fmt_stft_kernel      re, im of 32 frames x 64 bins per workgroup (melfront's STFT: virtual frame operand staged once in LDS), written
 //                        interleaved, with the log epilogue L = 0.5 log(re^2 + im^2 + 1e-10) beside them
@@ -13,7 +15,7 @@
 // but k, so every clip's output is bit-identical to running it alone.  Intermediates live in the handle (one slot per clip of a call).
 #include <limits.h>
 #include "runtime.h"
-#include "stft_steps.h"
+#include "stft_kernels.h"
 #include "../../include/tortoise_mi355x_fmt.h"
 #include "../../include/tortoise_mi355x_test.h"
 
@@ -33,33 +35,29 @@ struct FmtClips {  // by value in the kernel arguments: nothing to copy to the d
   int warp[TT_FMT_MAX_CLIPS];
 };
 
+struct FmtLogEpilogue {  // the spectrum interleaved, the log magnitude beside it
+  float* sp;
+  float* lm;
+  int bins_pad;
+  __device__ __forceinline__ void operator()(const f32x16& re, const f32x16& im, int t0, int T, int col, int h) const {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int t = t0 + mfma_row(r, h);
+      if (t < T) {
+        const size_t e = (size_t)t * bins_pad + col;
+        *(float2*)(sp + 2 * e) = make_float2(re[r], im[r]);
+        lm[e] = 0.5f * logf(re[r] * re[r] + im[r] * im[r] + kFmtDelta);
+      }
+    }
+  }
+};
+
 __global__ __launch_bounds__(128) void fmt_stft_kernel(const float* __restrict__ wav, FmtClips clips, const float* __restrict__ basis, int n_fft,
                                                        int hop, int bins_pad, float* __restrict__ spec, float* __restrict__ logmag) {
   extern __shared__ float xs[];
   const int c = blockIdx.y, n = clips.len[c], T = 1 + n / hop;
-  const int t0 = blockIdx.x * kStftTile;
-  if (t0 >= T) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  stft_stage(wav + clips.in_off[c], n, t0, n_fft, hop, xs, tid, 128);
-  __syncthreads();
-  const int b0 = blockIdx.z * kFmtBinsPerBlock + wave * 32;
-  if (b0 >= bins_pad) return;
-  const int i = lane & 31, h = lane >> 5;
-  f32x16 re, im;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { re[r] = 0.f; im[r] = 0.f; }
-  stft_mfma(xs, basis, n_fft, hop, bins_pad, b0, lane, re, im);
-  float* sp = spec + 2 * clips.st_off[c];
-  float* lm = logmag + clips.st_off[c];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int t = t0 + mfma_row(r, h);
-    if (t < T) {
-      const size_t e = (size_t)t * bins_pad + b0 + i;
-      *(float2*)(sp + 2 * e) = make_float2(re[r], im[r]);
-      lm[e] = 0.5f * logf(re[r] * re[r] + im[r] * im[r] + kFmtDelta);
-    }
-  }
+  stft_tile_body(wav + clips.in_off[c], n, T, basis, n_fft, hop, bins_pad, kFmtBinsPerBlock, 128, xs,
+                 FmtLogEpilogue{spec + 2 * clips.st_off[c], logmag + clips.st_off[c], bins_pad});
 }
 
 // cep: [slot][t][64], slot stride cep_clip elements
@@ -108,54 +106,23 @@ __global__ __launch_bounds__(64) void fmt_gain_kernel(const float* __restrict__ 
   }
 }
 
+struct FmtExpGain {  // log gains -> multipliers
+  __device__ __forceinline__ float2 operator()(const float2 g) const { return make_float2(expf(g.x), expf(g.y)); }
+};
+
 // y: [slot][t][n_fft], slot stride y_clip elements
 __global__ __launch_bounds__(64 * kFmtInvWaves) void fmt_inverse_kernel(const float* __restrict__ spec, const float* __restrict__ gains, FmtClips clips,
                                                                         const float* __restrict__ inverse, int n_fft, int hop, int bins_pad,
                                                                         float* __restrict__ y, size_t y_clip) {
   const int c = blockIdx.y, T = 1 + clips.len[c] / hop;
-  const int t0 = blockIdx.x * kStftTile;
-  if (t0 >= T) return;
-  const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-  const int n0 = (blockIdx.z * kFmtInvWaves + (threadIdx.x >> 6)) * 32;
-  if (n0 >= n_fft) return;
-  const size_t row = (size_t)min(t0 + i, T - 1);
-  const float* sp = spec + 2 * clips.st_off[c] + row * 2 * bins_pad + 4 * h;
-  const float* gp = gains + clips.st_off[c] + row * bins_pad + 2 * h;
-  const float* ib = inverse + (size_t)(4 * h) * n_fft + n0 + i;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  for (int k = 0; k < 2 * bins_pad; k += 8) {  // (re, im) of two bins per lane and trip
-    float4 z = *(const float4*)(sp + k);
-    const float2 g = *(const float2*)(gp + k / 2);
-    const float e0 = expf(g.x), e1 = expf(g.y);
-    z.x *= e0; z.y *= e0; z.z *= e1; z.w *= e1;
-    rows_mfma8(z, ib + (size_t)k * n_fft, n_fft, acc);
-  }
-  float* o = y + (size_t)c * y_clip;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int t = t0 + mfma_row(r, h);
-    if (t < T) o[(size_t)t * n_fft + n0 + i] = acc[r];
-  }
+  stft_inverse_body(spec + 2 * clips.st_off[c], gains + clips.st_off[c], T, inverse, n_fft, bins_pad, kFmtInvWaves, y + (size_t)c * y_clip,
+                    FmtExpGain{});
 }
 
 __global__ __launch_bounds__(256) void fmt_ola_kernel(const float* __restrict__ y, size_t y_clip, FmtClips clips, const float* __restrict__ basis,
                                                       int n_fft, int hop, int bins_pad, float* __restrict__ out) {
   const int c = blockIdx.y, n = clips.len[c], T = 1 + n / hop;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int p = j + n_fft / 2;  // position in the padded clip: frame t covers t hop .. t hop + n_fft - 1
-  const int tlo = p >= n_fft ? (p - n_fft) / hop + 1 : 0, thi = min(p / hop, T - 1);
-  const float* yc = y + (size_t)c * y_clip;
-  float num = 0.f, den = 0.f;
-  for (int t = tlo; t <= thi; ++t) {
-    const int k = p - t * hop;
-    const float w = basis[(size_t)k * 2 * bins_pad];  // column 0: window[k] cos(0)
-    num += yc[(size_t)t * n_fft + k];
-    den += w * w;
-  }
-  out[clips.out_off[c] + j] = num / den;
+  stft_ola_body(y + (size_t)c * y_clip, n, T, basis, n_fft, hop, bins_pad, 256, out + clips.out_off[c]);
 }
 
 }  // namespace tt

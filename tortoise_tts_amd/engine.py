@@ -19,7 +19,7 @@ TT_AR_OPT_SESSION_SAMPLING = 7
 TT_AR_OPT_FUSED_QKV_ATTN = 8
 TT_DIFF_OPT_OVERLAP_PREPASS = 1
 TT_DIFF_OPT_FUSED_GN = 2
-TTX_FLASH32, TTX_GEMM_P8, TTX_VOC_MFMA, TTX_GEMM_SKINNY, TTX_AR_GEMV = 0, 1, 2, 3, 4  # ttx_kernel_variant families (include/tortoise_mi355x_test.h)
+TTX_FLASH32, TTX_GEMM_P8, TTX_VOC_MFMA, TTX_GEMM_SKINNY, TTX_AR_GEMV, TTX_NR_SELECT_LONG = 0, 1, 2, 3, 4, 5  # ttx_kernel_variant families (include/tortoise_mi355x_test.h)
 
 
 def dtype_code(name):
@@ -231,6 +231,28 @@ class FmtTables(C.Structure):
 # include/tortoise_mi355x_fmt.h, order == tt_fmt_struct_size(which)
 FMT_STRUCTS = [FmtConfig, FmtTables]
 FMT_ABI_VERSION = 1
+
+# include/tortoise_mi355x_nr.h: TT_NR_MAX_CLIPS, TT_NR_MAX_SAMPLES, TT_NR_MIN_FRAMES, TT_NR_MIN_REGION, TT_NR_QUANTILE_DEN, TT_NR_MAX_SMOOTH, TT_NR_REG_FRAMES
+NR_MAX_CLIPS, NR_MAX_SAMPLES, NR_MIN_FRAMES, NR_MIN_REGION, NR_QUANTILE_DEN, NR_MAX_SMOOTH, NR_REG_FRAMES = 16, 4194304, 32, 8, 10000, 4, 1024
+NR_OK, NR_SHORT, NR_REFUSED = 0, 1, 2  # TT_NR_OK, TT_NR_SHORT, TT_NR_REFUSED
+
+
+class NrConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_fft", "hop", "bins_pad", "max_samples", "max_clips")]
+
+
+class NrTables(C.Structure):
+    _fields_ = [(n, vp) for n in ("basis", "inverse")]
+
+
+class NrParams(C.Structure):
+    _fields_ = [("quantile_num", C.c_int), ("quantile_scale", C.c_float), ("beta", C.c_float), ("g_min", C.c_float), ("smooth_frames", C.c_int),
+                ("smooth_bins", C.c_int)]
+
+
+# include/tortoise_mi355x_nr.h, order == tt_nr_struct_size(which)
+NR_STRUCTS = [NrConfig, NrTables, NrParams]
+NR_ABI_VERSION = 1
 
 class GemmDesc(C.Structure):
     """tt_op_gemm_desc (include/tortoise_mi355x_test.h): every GEMM form of the operator-level test entry tt_op_gemm_ex."""
@@ -582,6 +604,18 @@ _F0V_PROTOS = {
 }
 F0V_ABI_VERSION = 1
 F0V_STATES, F0V_UNVOICED, F0V_TABLE = 8, 7, 481  # TT_F0V_STATES, TT_F0V_UNVOICED, TT_F0V_TABLE
+# include/tortoise_mi355x_nr.h: the spectral-subtraction denoiser of voice clips (its own header and version, same library)
+_NR_PROTOS = {
+    "tt_nr_abi_version": (_i, []),
+    "tt_nr_struct_size": (_sz, [_i]),
+    "tt_nr_create": (_i, [C.POINTER(NrConfig), C.POINTER(NrTables), C.POINTER(vp)]),
+    "tt_nr_destroy": (None, [vp]),
+    "tt_nr_frames": (_i, [vp, _i]),
+    "tt_nr_rank": (_i, [_i, _i]),
+    "tt_nr_region": (_i, [_ll, _ll, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "tt_nr_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(NrParams), _i, vp, C.POINTER(_ll), vp, C.POINTER(_i), vp]),
+}
+
 # include/tortoise_mi355x_fmt.h: formant-preserving pitch, the cepstral envelope correction (its own header and version, same library)
 _FMT_PROTOS = {
     "tt_fmt_abi_version": (_i, []),
@@ -664,6 +698,8 @@ _TEST_PROTOS = {
     "tt_op_cls_head": (_i, [vp, vp, vp, vp, vp, vp]),
     "tt_op_fmt_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp, vp, vp, C.POINTER(_ll), vp]),
     "tt_op_fmt_synth": (_i, [vp, vp, vp, C.POINTER(_ll), C.POINTER(_i), _i, vp, C.POINTER(_ll), vp]),
+    "tt_op_nr_run": (_i, [vp, vp, C.POINTER(_ll), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(NrParams), _i, vp, C.POINTER(_ll), vp, C.POINTER(_i),
+                          vp, vp, vp, C.POINTER(_ll), vp]),
     "tt_op_f0_track": (_i, [vp, _i] + [vp] * 12),
     "tt_op_f0_group": (_i, []),
     "tt_op_f0v_candidates": (_i, [vp, _i] + [vp] * 10),
@@ -687,7 +723,7 @@ def load_library():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_PROTOS.items()) + list(_TEST_PROTOS.items()) + list(_ALIGN_PROTOS.items()) + list(_CLASSIFY_PROTOS.items()) + \
-            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_LVS_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_F0V_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
+            list(_MEL_PROTOS.items()) + list(_CTC_PROTOS.items()) + list(_TSM_PROTOS.items()) + list(_LOUD_PROTOS.items()) + list(_LVS_PROTOS.items()) + list(_RS_PROTOS.items()) + list(_RSS_PROTOS.items()) + list(_RSW_PROTOS.items()) + list(_TSS_PROTOS.items()) + list(_TSW_PROTOS.items()) + list(_SIL_PROTOS.items()) + list(_F0_PROTOS.items()) + list(_F0V_PROTOS.items()) + list(_FMT_PROTOS.items()) + list(_NR_PROTOS.items()) + list(_SOLVER_PROTOS.items()) + list(_HIFI_PROTOS.items()) + list(_UNIVNET_PROTOS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -721,6 +757,12 @@ def load_library():
             raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
     if lib.tt_fmt_abi_version() != FMT_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_fmt.h is version %d in the library, %d in Python" % (lib.tt_fmt_abi_version(), FMT_ABI_VERSION))
+    for i, st in enumerate(NR_STRUCTS):
+        want = lib.tt_nr_struct_size(i)
+        if C.sizeof(st) != want:
+            raise EngineError("ABI mismatch: %s is %d bytes in Python, %d in the library" % (st.__name__, C.sizeof(st), want))
+    if lib.tt_nr_abi_version() != NR_ABI_VERSION:
+        raise EngineError("ABI mismatch: tortoise_mi355x_nr.h is version %d in the library, %d in Python" % (lib.tt_nr_abi_version(), NR_ABI_VERSION))
     if lib.tt_ctc_abi_version() != CTC_ABI_VERSION:
         raise EngineError("ABI mismatch: tortoise_mi355x_ctc.h is version %d in the library, %d in Python" % (lib.tt_ctc_abi_version(), CTC_ABI_VERSION))
     if lib.tt_tsm_abi_version() != TSM_ABI_VERSION:

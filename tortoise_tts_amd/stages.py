@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import engine as E
+from . import denoise as nr
 from . import formant as fmt
 from . import loudness as loud
 from . import pack
@@ -1210,6 +1211,51 @@ class FormantStage(_ClipStage):
         ll, ii = (C.c_longlong * k)(*offs), (C.c_int * k)(*lens)
         E.check(self.lib.tt_fmt_run(self.h, E.ptr(wav), ll, ii, (C.c_int * k)(*idx), k, E.ptr(y), ll, E.stream_ptr()))
         return [y[o:o + n] for o, n in zip(offs, lens)]
+
+
+class DenoiseStage(_ClipStage):
+    """Stationary-noise reduction of voice clips by spectral subtraction (csrc/denoise.hip, include/tortoise_mi355x_nr.h): ragged batches,
+    each clip in auto or region mode, one tt_nr_run call per max_clips clips, every clip's samples and floor bit-identical to running it
+    alone.  Sample-rate agnostic: regions arrive as frames (denoise.region_frames)."""
+
+    api, noun, what, nr = "tt_nr", "denoiser's", "denoise", nr
+    least, least_text = nr.MIN_SAMPLES, f"{nr.MIN_SAMPLES} samples (the frames are centred with reflect padding)"
+
+    def __init__(self, max_samples, max_clips=E.NR_MAX_CLIPS, device="cuda"):
+        super().__init__(max_samples, max_clips, device, extra=None)
+        self.t = {k: v.to(self.device).contiguous() for k, v in nr.tables().items()}
+        c = E.NrConfig()
+        c.n_fft, c.hop, c.bins_pad, c.max_samples, c.max_clips = nr.N_FFT, nr.HOP, nr.BINS_PAD, self.max_samples, self.max_clips
+        tb = E.NrTables()
+        tb.basis, tb.inverse = E.ptr(self.t["basis"]), E.ptr(self.t["inverse"])
+        self._create(C.byref(c), C.byref(tb))
+
+    def denoise_many(self, clips, regions, params):
+        """clips f32 [n] (device or host, n >= 513), one (first frame, frames) each ((0, 0): auto) and one denoise.Params for all -> one
+        (y f32 [n] on the stage's device, dict(status=E.NR_OK / NR_SHORT, floor=f32 [513] on the host)) per clip.  ValueError for a clip
+        the handle does not take or a region outside its clip."""
+        if len(clips) != len(regions):
+            raise ValueError(f"{len(clips)} clips with {len(regions)} noise regions")
+        for i, (x, (first, count)) in enumerate(zip(clips, regions)):
+            self._check_clip(i, x)
+            T = self.nr.frames(x.shape[0])
+            if count and not (count >= E.NR_MIN_REGION and 0 <= first <= T - count):
+                raise ValueError(f"clip {i}: noise region of frames {first} .. {first + count} in a clip of {T} (at least {E.NR_MIN_REGION}, inside the clip)")
+        return self._run(clips, regions, params=params)
+
+    def _group(self, clips, regions, params):
+        k, dev = len(clips), self.device
+        lens = [int(x.shape[0]) for x in clips]
+        offs = self._offsets(lens)
+        wav = self._audio(clips)
+        y = torch.empty(offs[-1] + 1, device=dev, dtype=torch.float32)
+        floor = torch.empty(k, self.nr.BINS_PAD, device=dev, dtype=torch.float32)
+        ll, status = (C.c_longlong * k)(*offs[:k]), (C.c_int * k)()
+        p = self.nr.c_params(params)
+        E.check(self.lib.tt_nr_run(self.h, E.ptr(wav), ll, (C.c_int * k)(*lens), (C.c_int * k)(*[r[0] for r in regions]),
+                                   (C.c_int * k)(*[r[1] for r in regions]), C.byref(p), k, E.ptr(y), ll, E.ptr(floor), status, E.stream_ptr()))
+        fl = floor[:, :self.nr.BINS].cpu()  # (synchronises)
+        return [(y[o:o + n], dict(status=int(status[i]), floor=fl[i].clone())) for i, (o, n) in enumerate(zip(offs, lens))]
 
 
 class LoudnessStage(_ClipStage):
